@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the path_tracer_hip hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
            bench.py --gpus N --steps K --warmup W
 
@@ -12,12 +12,20 @@ flattened and uploaded before the timed region (inputs resident in HBM); the fra
 
 Workload at every N: the configuration BASELINE.json's metric is quoted on -- materialtest.json (the reference's shipped
 scene: three meshes, 80 768 triangles, smooth_coat over rough_conductor, HDRI environment + MIS) at 1280x720, 256 spp,
-uniform sampler, adaptive sampling off (fixed total work => "scaling": "strong").  At N = 1 the same line carries, under
-"extra", BASELINE configs[1] (Cornell box 1280x720 at 256 spp, a flat-list scene without BVH traversal) and materialtest as the reference ships it (Sobol + adaptive, 64 spp in 16-spp passes); `--scene cornell`
-makes that the headline workload instead.  Without the materialtest assets (assets/, copied from the reference's
-data directory by __graft_entry__.build()) the default run FAILS: there is no silent fallback to another workload.
+uniform sampler, adaptive sampling off (fixed total work => "scaling": "strong").  `--scene cornell` makes BASELINE configs[1] the
+headline workload instead.  Without the materialtest assets (assets/, unpacked from tests/golden/scene_data/ by __graft_entry__.build())
+the default run FAILS: there is no silent fallback to another workload.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the traversal kernel BASELINE.json's metric names (the traversal class with the
+A plain run sets up, warms up, times the K steps, writes the last timed step's image if `--dump-outputs DIR` is given and prints ONE JSON
+line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), the workload's config and the image's sanity.
+`--dump-outputs DIR` writes what the timed path computed in its last step, float32: DIR/image_sum.npy (h, w, 3: the framebuffer's radiance
+sums), DIR/sample_count.npy (h, w) and DIR/image_mean.npy (h, w, 3); above 64 MB in all, the same fixed, seeded sample of pixels of each
+(DIR/pixel_index.npy, float64, holds the flat indices y*w + x).
+
+Everything else is measured only under `--full`, as follows.  At N = 1 the line carries, under "extra", BASELINE configs[1] (Cornell box
+1280x720 at 256 spp, a flat-list scene without BVH traversal) and materialtest as the reference ships it (Sobol + adaptive, 64 spp in 16-spp
+passes).  An untimed counting step of the same render feeds the byte model; the timed region records per-launch HIP events and polls the shader
+clock.  `roofline` describes the traversal kernel BASELINE.json's metric names (the traversal class with the
 largest accumulated time; flat-list scenes: their one fused kernel): achieved = algorithmic bytes per launch / average launch duration,
 both from the timed region (HIP events recorded by the shim on the stream the kernels run on; byte model in DESIGN.md section 5).
 `roofline.dominant_class` holds the same for the class with the largest accumulated time of any kind (k_shade on the headline workload),
@@ -122,10 +130,18 @@ def parse_args():
     ap.add_argument("--in-process", action="store_true",
                     help="N > 1 in ONE process (no torch.distributed.run): the host integrator drives N contexts from N host threads (\"devices\": N) and merges "
                          "with tghip_reduce_framebuffers; a step = one complete render through tgh_renderer_render, download of the merged image included")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline figure: the CPU baseline, the secondary workloads under \"extra\", the counting pass "
+                         "and the per-kernel / roofline / walk figures, the rocprofv3 counter passes, the exclusive-launch steps, the shader clock")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the image of the last one to DIR/<name>.npy (float32; see the module docstring)")
     ap.add_argument("--emulate-shards", type=int, default=0,
                     help="development aid: on ONE GPU render and time EVERY one of N tile shards in turn (what the ranks of an N-GPU run do; "
                          "reports max / mean / min over shards and the fixed cost of the framebuffer reduce)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---- algorithmic bytes -------------------------------------------
@@ -388,11 +404,11 @@ class Bench(object):
         for _ in range(warmup):
             step()
         check(lib.tghip_reset_counters(ctx), "tghip_reset_counters")
-        check(lib.tghip_set_option(ctx, b"time_kernels", 0 if a.no_kernel_timing else 1), "tghip_set_option")
+        check(lib.tghip_set_option(ctx, b"time_kernels", 1 if a.full and not a.no_kernel_timing else 0), "tghip_set_option")
         self.fence()
         split[0] = split[1] = 0.0
         # (never in the counter passes' child runs -- they pass --no-clock: a rocm-smi process started under rocprofv3's preloaded tool library takes the run down)
-        poller = ClockPoller().start() if (self.world == 1 and a.clock and a.steps > 0 and shutil.which("rocm-smi") and "ROCPROFILER" not in " ".join(os.environ)
+        poller = ClockPoller().start() if (self.world == 1 and a.full and a.clock and a.steps > 0 and shutil.which("rocm-smi") and "ROCPROFILER" not in " ".join(os.environ)
                                            and "rocprof" not in os.environ.get("LD_PRELOAD", "")) else None
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -439,7 +455,24 @@ class Bench(object):
                 img = (fb_sum/fb_cnt.clamp(min=1).unsqueeze(-1)).cpu().numpy()
             ok = bool(((cnt == spp).all() or a.emulate_shards > 1) and np.isfinite(img).all())
             value = float(w)*h*spp*steps/elapsed*1e-6
-
+            # what the timed path computed in its last step (--dump-outputs), taken before anything below renders again
+            outputs = {"image_sum": merged[0] if merged else fb_sum.cpu().numpy(), "sample_count": cnt, "image_mean": img}
+            config = {"workload": workload, "width": w, "height": h, "spp": spp, "sampler": "uniform (counter-based PCG)",
+                      "adaptive_sampling": False, "max_bounces": int(flat.desc.contents.settings.max_bounces),
+                      "parallelism": "tile-shard x%d%s" % (self.world, (" + framebuffer reduce: " + reduce_note) if self.world > 1 else "")}
+            if not a.full:
+                # a plain run: the headline figure and the sanity of the image it timed, nothing that takes a render of its own
+                out = {"value": round(value, 2), "ms_per_step": round(elapsed/steps*1e3, 3), "config": config, "cpu_baseline": None, "roofline": None,
+                       "setup_s": {"flatten_and_bvh": round(t_flatten, 3), "upload": round(t_upload, 3)},
+                       "result_ok": ok, "image_mean": [round(float(v), 6) for v in img.mean(axis=(0, 1))]}
+                if emulated:
+                    out["emulated_shards"] = emulated
+                if per_rank:
+                    out["per_rank"] = per_rank
+                else:
+                    out["render_ms_per_step"] = round(split[0]/steps*1e3, 3)
+                out["_outputs"] = outputs
+        if self.rank == 0 and a.full:
             # one untimed counting step: exact node / record visit counts of the same (deterministic) render
             check(lib.tghip_set_option(ctx, b"count_traversal", 1), "tghip_set_option")
             check(lib.tghip_reset_counters(ctx), "tghip_reset_counters")
@@ -704,9 +737,7 @@ class Bench(object):
             rays = max(cc["closest_rays"] + cc["shadow_rays"], 1)
             out = {
                 "value": round(value, 2), "ms_per_step": round(elapsed/steps*1e3, 3),
-                "config": {"workload": workload, "width": w, "height": h, "spp": spp, "sampler": "uniform (counter-based PCG)",
-                           "adaptive_sampling": False, "max_bounces": int(flat.desc.contents.settings.max_bounces),
-                           "parallelism": "tile-shard x%d%s" % (self.world, (" + framebuffer reduce: " + reduce_note) if self.world > 1 else "")},
+                "config": config,
                 "cpu_baseline": cpu_baseline(a, scene, path, flat, w, h, spp, self.tmp) if cpu else None,
                 "roofline": ordered_roofline(roofline),
                 "sustained_clock": sustained_clock,
@@ -727,6 +758,7 @@ class Bench(object):
                 out["per_rank"] = per_rank
             else:
                 out["render_ms_per_step"] = round(split[0]/steps*1e3, 3)
+            out["_outputs"] = outputs
         lib.tghip_bind_framebuffer(ctx, None, None)
         if not shared:
             lib.tghip_destroy(ctx)
@@ -743,13 +775,14 @@ def run_in_process(b, a, scene, w, h, spp):
     if tg.device_count() < a.gpus:
         raise SystemExit("bench.py --in-process: %d devices visible, --gpus %d" % (tg.device_count(), a.gpus))
     path, workload = b.make_scene(scene, w, h, spp)
-    secs, ok, img_mean, per_device = [], True, None, None
+    secs, ok, img_mean, per_device, outputs = [], True, None, None, None
     for i in range(a.warmup + a.steps):
         r = tg.Renderer(path, devices=a.gpus)
         t = r.render()
-        mean, _, count = r.image()
+        mean, ssum, count = r.image()
         if i >= a.warmup:
             secs.append(t)
+            outputs = {"image_sum": ssum, "sample_count": count, "image_mean": mean}
             ok = ok and bool((count == spp).all() and np.isfinite(mean).all())
             img_mean = [round(float(v), 6) for v in mean.mean(axis=(0, 1))]
             per_device = [int(r.counters(d).samples) for d in range(a.gpus)]
@@ -760,7 +793,29 @@ def run_in_process(b, a, scene, w, h, spp):
                        "parallelism": "tile-shard x%d in one process: host integrator \"devices\": %d + tghip_reduce_framebuffers (ncclReduce)" % (a.gpus, a.gpus)},
             "roofline": None, "cpu_baseline": None, "result_ok": ok, "image_mean": img_mean,
             "per_rank": {"samples_rendered_by_device": per_device, "render_s_per_step": [round(t, 4) for t in secs],
-                         "note": "one process: the step's wall clock covers every device's shard, the reduce and the download of the merged image"}}
+                         "note": "one process: the step's wall clock covers every device's shard, the reduce and the download of the merged image"},
+            "_outputs": outputs}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, dst):
+    """--dump-outputs: the arrays of the last timed step as dst/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every array keeps the
+    same fixed, seeded sample of pixels (dst/pixel_index.npy: their flat indices y*w + x, float64), so that two builds compare sample for sample."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in outputs.items()}
+    h, w = arrays["sample_count"].shape[:2]
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(dst, exist_ok=True)
+    if total > DUMP_LIMIT_BYTES:
+        per_pixel = total//(h*w)
+        keep = (DUMP_LIMIT_BYTES - (1 << 20))//(per_pixel + 8)
+        idx = np.sort(np.random.default_rng(20240601).choice(h*w, size=keep, replace=False))
+        arrays = {k: v.reshape((h*w,) + v.shape[2:])[idx] for k, v in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dst, k + ".npy"), v)
 
 
 def kernel_class(name):
@@ -793,7 +848,7 @@ def measure_traffic(a, scene, w, h, spp, tmp):
         out = os.path.join(tmp, "pmc_" + counter)
         cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
                "--scene", scene, "--material", a.material, "--res", "%dx%d" % (w, h), "--spp", str(pmc_spp), "--steps", "1", "--warmup", "0",
-               "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
+               "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
         env = dict(os.environ, TMPDIR="/tmp")
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd="/tmp", env=env, timeout=300)
@@ -832,7 +887,7 @@ def measure_counter_all(a, scene, w, h, spp, tmp, counter):
     out = os.path.join(tmp, "pmc_all_" + counter)
     cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
            "--scene", scene, "--material", a.material, "--res", "%dx%d" % (w, h), "--spp", str(spp), "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
     try:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd="/tmp",
                            env=dict(os.environ, TMPDIR="/tmp"), timeout=300)
@@ -866,7 +921,7 @@ def measure_counters_all(a, scene, w, h, spp, tmp, counters, tag):
     out = os.path.join(tmp, "pmc_multi_" + tag)
     cmd = [exe, "--pmc"] + list(counters) + ["--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
            "--scene", scene, "--material", a.material, "--res", "%dx%d" % (w, h), "--spp", str(spp), "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"] + [x for kv in a.opt for x in ("--opt", kv)]
     try:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd="/tmp",
                            env=dict(os.environ, TMPDIR="/tmp"), timeout=300)
@@ -899,7 +954,7 @@ def measure_counter(a, scene, w, h, spp, kernel, tmp, counter):
     out = os.path.join(tmp, "pmc_" + counter)
     cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
            "--scene", scene, "--material", a.material, "--res", "%dx%d" % (w, h), "--spp", str(spp), "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic", "--no-clock"]
     try:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd="/tmp",
                            env=dict(os.environ, TMPDIR="/tmp"), timeout=300)
@@ -985,16 +1040,19 @@ def main():
         scene = a.scene
         if scene in ("materialtest", "mesh1m") and not scenes.have_materialtest():
             # the headline workload is materialtest: a run without its assets is not a measurement of the metric (no silent fallback)
-            raise SystemExit("bench.py: materialtest assets (assets/materialtest) missing -- run __graft_entry__.build() where the "
-                             "reference is mounted, or pass --scene cornell explicitly")
+            raise SystemExit("bench.py: materialtest assets (assets/materialtest) missing -- run __graft_entry__.build() first, "
+                             "or pass --scene cornell explicitly")
         spp = a.spp or (256 if scene in ("cornell", "materialtest") else 32)
         if scene in ("mesh1m", "instances10k") and a.res == "1280x720":
             w, h = 1920, 1080
-        cpu = not a.no_cpu_baseline and b.world == 1
+        cpu = a.full and not a.no_cpu_baseline and b.world == 1
         in_process = a.in_process and a.gpus > 1
         res = run_in_process(b, a, scene, w, h, spp) if in_process else b.run(scene, w, h, spp, a.steps, a.warmup, cpu)
         extra = None
-        if scene == "materialtest" and b.world == 1 and not a.no_extra and not in_process:
+        outputs = res.pop("_outputs", None) if res else None
+        if a.dump_outputs and b.rank == 0:
+            dump_outputs(outputs, a.dump_outputs)
+        if scene == "materialtest" and b.world == 1 and a.full and not a.no_extra and not in_process:
             # BASELINE configs[1] on the same line: a flat-list scene, no traversal kernel (2 steps)
             saved, a.traffic = a.traffic, False
             a.valu_pass = saved                  # (no HBM traffic passes for the extra line, but its VALU-issue roofline)
@@ -1013,8 +1071,8 @@ def main():
             out = {"metric": "Msamples/s (W*H*spp/s), path_tracer render loop", "value": res["value"], "unit": "Msamples/s",
                    "n_gpus": a.gpus if in_process else b.world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": res["ms_per_step"],
                    "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-                   "data": ("the reference's shipped scene data/materialtest/materialtest.json (meshes, HDRI and materials as shipped; copied by build() into "
-                            "assets/), resolution / spp / sampler set by the bench" if scene == "materialtest" else
+                   "data": ("the reference's shipped scene data/materialtest/materialtest.json (meshes, HDRI and materials as shipped; stored in "
+                            "tests/golden/scene_data/, unpacked by build() into assets/), resolution / spp / sampler set by the bench" if scene == "materialtest" else
                             "scene description generated in-tree (tungsten_amd/workloads.py: %s)" % scene) + "; fixed seed 0xBA5EBA11"}
             out.update({k: v for k, v in res.items() if k not in ("value", "ms_per_step")})
             if extra:

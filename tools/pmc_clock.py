@@ -30,7 +30,7 @@ def main():
     out = os.path.join(tmp, "o")
     cmd = [shutil.which("rocprofv3"), "--pmc", "GRBM_GUI_ACTIVE", "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "clk", "--",
            sys.executable, os.path.join(ROOT, "bench.py"), "--scene", a.scene, "--spp", str(a.spp), "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic"] + [x for kv in a.opt for x in ("--opt", kv)]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic"] + [x for kv in a.opt for x in ("--opt", kv)]
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=600)
     files = {os.path.basename(f): os.path.join(d, f) for d, _, fs in os.walk(out) for f in fs if f.endswith(".csv")}
     cc = [v for k, v in files.items() if k.endswith("counter_collection.csv")]

@@ -2,7 +2,7 @@
 
     python tools/pmc_variants.py --out profiles/r5_sq_counters.json [--scene materialtest] [--spp 32] [--opt key=value ...] [--groups sq,ifetch,tcp,sqc]
 
-Each group is one pass of `bench.py --steps 1 --warmup 0` under the profiler (counter collection serialises the dispatches, so every
+Each group is one pass of `bench.py --full --steps 1 --warmup 0` under the profiler (counter collection serialises the dispatches, so every
 launch has the chip to itself: these are exclusive figures, unlike the four-part schedule of a timed run).  Per variant the totals of
 every counter over all its dispatches, the dispatch count, and the derived fractions MI355X_MICROARCH.md "rocprofv3 PMC slots" names:
 SQ_WAIT_ANY (parked on s_waitcnt / barrier) + SQ_WAIT_INST_ANY (issue stall) + SQ_ACTIVE_INST_ANY (issuing) ~= SQ_WAVE_CYCLES."""
@@ -40,7 +40,7 @@ def one_pass(counters, a, tmp, tag):
     out = os.path.join(tmp, "pmc_" + tag)
     cmd = [exe, "--pmc"] + counters + ["--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.join(ROOT, "bench.py"),
            "--scene", a.scene, "--spp", str(a.spp), "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic"] + [x for kv in a.opt for x in ("--opt", kv)]
+           "--full", "--no-cpu-baseline", "--no-extra", "--no-kernel-timing", "--no-traffic"] + [x for kv in a.opt for x in ("--opt", kv)]
     if a.res:
         cmd += ["--res", a.res]
     try:

@@ -1,7 +1,7 @@
 """The benchmark's workloads (BASELINE.json configs[1..4]): scene descriptions in Tungsten's JSON format, written next to their assets.
 Product-side code: bench.py, tools/ and the tests' fixtures (tests/scenes.py re-exports these) build their inputs here.  The Cornell box is
-the committed scenes/cornell-box; materialtest is the reference's shipped data/materialtest (meshes, HDRI: data, copied by
-__graft_entry__.build() into the git-ignored assets/materialtest); mesh1m and instances10k are generated procedurally with fixed seeds."""
+the committed scenes/cornell-box; materialtest is the reference's shipped data/materialtest (meshes, HDRI: data, stored compressed in
+tests/golden/scene_data/ and unpacked by __graft_entry__.build() into the git-ignored assets/materialtest); mesh1m and instances10k are generated procedurally with fixed seeds."""
 import json
 import os
 
