@@ -322,10 +322,11 @@ typedef struct TgHipTexture {
 /* ---- camera (cameras/PinholeCamera.cpp:28-86, Camera.cpp:44-68, ReconstructionFilter) ---- */
 enum { TGHIP_FILTER_DIRAC = 0, TGHIP_FILTER_BOX = 1, TGHIP_FILTER_TABULATED = 2 };
 enum { TGHIP_CAMERA_PINHOLE = 0, TGHIP_CAMERA_THINLENS = 1,     /* cameras/PinholeCamera.cpp, cameras/ThinlensCamera.cpp */
-       TGHIP_CAMERA_EQUIRECTANGULAR = 2, TGHIP_CAMERA_CUBEMAP = 3 };   /* cameras/CubemapCamera.cpp: six 90-degree faces laid out as a cross, a row or a column; inv_xf as for the
-                                                                    equirectangular camera, blade_count = CubemapCamera::ProjectionMode (0 horizontal_cross, 1 vertical_cross, 2 row, 3 column) */                       /* cameras/EquirectangularCamera.cpp: the full sphere around pos, longitude across the image, latitude down it;
-                                                                    inv_xf[0..8] then holds _rot = _transform.extractRotation() row-major (EquirectangularCamera.cpp:129-134) and
-                                                                    inv_xf[9] = 1 / res_y (Camera::_pixelSize.y; pixel_size_x = 1 / res_x as for every camera) */
+       TGHIP_CAMERA_EQUIRECTANGULAR = 2,   /* cameras/EquirectangularCamera.cpp: the full sphere around pos, longitude across the image, latitude down it;
+                                              inv_xf[0..8] then holds _rot = _transform.extractRotation() row-major (EquirectangularCamera.cpp:129-134) and
+                                              inv_xf[9] = 1 / res_y (Camera::_pixelSize.y; pixel_size_x = 1 / res_x as for every camera) */
+       TGHIP_CAMERA_CUBEMAP = 3 };         /* cameras/CubemapCamera.cpp: six 90-degree faces laid out as a cross, a row or a column; inv_xf as for the
+                                              equirectangular camera, blade_count = CubemapCamera::ProjectionMode (0 horizontal_cross, 1 vertical_cross, 2 row, 3 column) */
 enum { TGHIP_APERTURE_DISK = 0, TGHIP_APERTURE_BLADE = 1,       /* textures/DiskTexture.cpp:78-81, textures/BladeTexture.cpp:110-130 */
        TGHIP_APERTURE_BITMAP = 2 };                             /* textures/BitmapTexture.cpp:433-439 with the MAP_UNIFORM distribution (:400-431) */
 typedef struct TgHipCamera {
@@ -564,8 +565,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "cou
                                                                              kernel; images differ only where two triangles of a master answer a ray one rounding
                                                                              apart), "inst_phase_min" / "inst_refill_at" the phase vote's threshold and the refill
                                                                              level of k_trace_closest_instw, "inst_shadow_fast" = 0 shadow rays on
-                                                                             k_trace_shadow_wide<., ., INST>; "shade_lds_pad" bytes of unused LDS per shading
-                                                                             workgroup (an occupancy throttle for experiments) */
+                                                                             k_trace_shadow_wide<., ., INST> */
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out);
 int tghip_reset_counters(tghip_ctx *ctx);
 /* Instrumentation (no reference analogue; bench.py roofline.valu.walk, profiles/r6_lane_util.json): the tallies the counting variants of the

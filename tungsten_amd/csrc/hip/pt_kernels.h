@@ -144,11 +144,7 @@ enum {
 struct PathState {
     char * __restrict__ poolg[PT_POOL_GROUPS];   // base of arrays 8 g .. 8 g + 7
     uint32_t stride;                       // bytes per array
-    // "pool_layout" = 1: slot records instead of arrays -- the eight arrays of a path's state (A_RAY_O .. A_SAMP, 128 bytes)
-    // in ONE cache line per slot, the seven of its shadow-ray block (A_SH_O .. A_SH_P, 112 bytes) in a second one at
-    // rec_shadow, the two auxiliary-output arrays and the three NEE-factor arrays at rec_aux: a sparse queue then touches one line per slot and block
-    // instead of one partially used line per slot and ARRAY
-    uint32_t records, rec_shadow, rec_aux;
+    uint32_t unused_rec[3];                // (no reader or writer: kept so that the kernel-argument offsets, and with them the device code, stay as measured)
     uint32_t * __restrict__ bm;            // queue bitmaps: queue q of workgroup b = words [q*bmStride + b*slots_per_block/32, ...)
     uint32_t bmStride;                     // words per queue
     float4 * __restrict__ partial;         // per work item: radiance sum, count (uint bits)
@@ -169,31 +165,19 @@ struct PathState {
     // walk up where it stopped, in a full wave.  A walk is a pure function of its ray, so hits and visit counts are unchanged.
     // suspend_lanes = 0: off.  Workgroups whose queue is shorter than suspend_min_queue never suspend (the end of a pass).
     uint32_t suspend_lanes, suspend_turns, suspend_min_queue;
-    // The top of the 8-wide BVH -- nodes 0 .. lds_nodes-1 of the breadth-first array: the root, its children, ... -- is copied into LDS by the
-    // DECOUPLED traversal kernels: every ray visits them, and what bounds the walk is the rate at which the CU's vector L1 takes lane
-    // addresses (~1.1 16-byte lane-loads per clock, tools/ubench_chase.hip); ds_read_b128 does not go through it.  wide_depth: stack levels.
-    uint32_t lds_nodes, wide_depth;
+    uint32_t unused_lds_nodes, unused_wide_depth;   // (no reader, like unused_rec above: kept for the kernel-argument offsets)
     uint32_t nee_factors;                  // the shading kernels leave the factors of the NEE terms apart (A_NEE0 .. A_NEE2) for k_trace_shadow<., FORWARD>
     uint32_t walk_base;                    // first of the walk arrays of the pool: +0 grpBase grpMasks triBase triMask, +1 triValid node sp -,
                                            // +2 (shadow slots) partial result.rgb | ray index, +3 tri2Base tri2Mask tri2Valid -,
                                            // +4.. the group stack, two 8-byte entries per array
 };
 
-// PT_POOL_RECORDS_RUNTIME: the record layout of the "pool_layout" experiment (-1 % on k_shade, +6 % on closest-hit: measured and not adopted) as a
-// RUN-TIME option, as rounds 2-4 shipped it -- every slot access then carries the selects between two address computations and the two base
-// pointers (branches and spilled scalars in the refill paths of every kernel).  Without the macro the arrays are the only layout.
-#ifdef PT_POOL_RECORDS_RUNTIME
-#define PT_RECORDS(st) ((st).records != 0u)
-#else
-#define PT_RECORDS(st) false
-#endif
-PT_DEV uint32_t slotOffset(const PathState &st, uint32_t a, uint32_t slot)     // `a` is a literal at every call site: the selects fold
+// (rejected, rounds 2-4: the arrays of a path's state in one 128-byte record per slot -- -1 % on k_shade, +6 % on closest-hit, not adopted; git history has the code)
+PT_DEV uint32_t slotOffset(const PathState &st, uint32_t a, uint32_t slot)     // `a` is a literal at every call site: the mask folds
 {
-    if (PT_RECORDS(st))
-        return a < A_SH_O ? slot*128u + a*16u : a < A_AUX0 ? st.rec_shadow + slot*128u + (a - A_SH_O)*16u : st.rec_aux + slot*80u + (a - A_AUX0)*16u;
     return (a & ((1u << PT_POOL_GROUP_SHIFT) - 1u))*st.stride + slot*16u;
 }
-PT_DEV char *slotBase(const PathState &st, uint32_t a) { return PT_RECORDS(st) ? st.poolg[0] : st.poolg[a >> PT_POOL_GROUP_SHIFT]; }
+PT_DEV char *slotBase(const PathState &st, uint32_t a) { return st.poolg[a >> PT_POOL_GROUP_SHIFT]; }
 // PT_NT_STATE (bit 0: loads, bit 1: stores, bit 2: the work items' partial sums and the samples' luminances too): the 16-byte accesses to the
 // path pool carry the non-temporal hint (global_load / global_store ... nt).  A slot's state is written by one launch and read by the next,
 // megabytes of other slots later; written as ordinary stores it is allocated in L2 on its way out and evicts the records, the attributes
@@ -202,38 +186,25 @@ PT_DEV char *slotBase(const PathState &st, uint32_t a) { return PT_RECORDS(st) ?
 // 16 bytes share their 128-byte line with the neighbouring slots other waves read, and a non-temporal load does not keep the line in L1).
 // Hence 6: stores only.  The values moved are the same either way; 0 gives plain accesses back.
 // WHERE: only the kernels that name NT explicitly -- the wavefront k_shade launches, the decoupled walks' bodies, finishBody / nextPath.
-// Every other kernel (PT_NT_OTHER = 0) stores plainly, and must: with the hint in k_trace_shadow_wide -- one store, a finished slot's
-// radiance, inside the walk's loop -- the two-level shadow walk of instanced scenes lost occluders in 48 % of the pixels of instances10k,
+// Every other kernel (the flat lists, the BVH2 and two-level walks, the sequential wide walks, resolve) stores plainly, and must:
+// with the hint in k_trace_shadow_wide -- one store, a finished slot's radiance, inside the walk's loop -- the two-level shadow walk of instanced scenes lost occluders in 48 % of the pixels of instances10k,
 // differently in every run, and the sequential single-level walk (option decouple = 0) changed its image: the signature of round 3's loop-latch
 // miscompile of that kernel (PT_TURN_JOIN), which the join had cured; without the hint the kernel is exact again
 // (profiles/r5_nt_hazard.txt; tests/test_gpu_parity.py::test_instanced_shadow_walk_agrees_with_the_bvh2_walk and the scheduling test caught it).
-#ifndef PT_NT_STATE
 #define PT_NT_STATE 6
-#endif
-#ifndef PT_SLOT_EXTLOAD
-#define PT_SLOT_EXTLOAD 1     /* the plain loads of the hinted kernels as ONE 16-byte vector load each (0: through float4, which the compiler narrows to
-                                 global_load_dwordx3 where a kernel does not use the last word -- the kernels measured slower, wideRow below) */
-#endif
-#ifndef PT_NT_OTHER
-#define PT_NT_OTHER 0         /* the kernels that do not pass NT explicitly (flat lists, BVH2 and two-level walks, the sequential wide walks, resolve) */
-#endif
-#ifndef PT_NT_TRAV
-#define PT_NT_TRAV PT_NT_STATE   /* (bisecting aid: the hint in the traversal / finish kernels) */
-#endif
-#ifndef PT_NT_TAIL
-#define PT_NT_TAIL 0          /* 1: k_tail's bodies keep the hint too (A/B) */
-#endif
 typedef float    PtF4v __attribute__((ext_vector_type(4)));
 typedef uint32_t PtU4v __attribute__((ext_vector_type(4)));
 // (NT: the PT_NT_STATE bits in force at the call site -- the kernels whose slots are re-read within microseconds, the fused flat-list
-// launches and k_tail, pass 0: there the hint costs 1.3 %, profiles/r5_ab_nt_state.txt)
-// (the plain halves go through float4 / uint4 themselves, as the references of rounds 1-4 did: the same code as then where NT = 0)
+// launches and k_tail, pass 0: there the hint costs 1.3 %, profiles/r5_ab_nt_state.txt and r5_ab_misc_t2_tail.txt)
+// (the plain loads of the hinted kernels are ONE 16-byte vector load each: through float4 the compiler narrows them to global_load_dwordx3
+// where a kernel does not use the last word, and the kernels measured slower, wideRow below; where NT = 0 both halves go through
+// float4 / uint4 themselves, as the references of rounds 1-4 did: the same code as then)
 template<int NT> struct SlotF4Ref {
     PtF4v *p;
     PT_DEV operator float4() const
     {
         if constexpr ((NT & 1) != 0) { const PtF4v v = __builtin_nontemporal_load(p); return make_float4(v.x, v.y, v.z, v.w); }
-        else if constexpr (NT != 0 && PT_SLOT_EXTLOAD) { const PtF4v v = *p; return make_float4(v.x, v.y, v.z, v.w); }
+        else if constexpr (NT != 0) { const PtF4v v = *p; return make_float4(v.x, v.y, v.z, v.w); }
         else return *reinterpret_cast<const float4 *>(p);
     }
     PT_DEV const SlotF4Ref &operator=(float4 v) const
@@ -248,7 +219,7 @@ template<int NT> struct SlotU4Ref {
     PT_DEV operator uint4() const
     {
         if constexpr ((NT & 1) != 0) { const PtU4v v = __builtin_nontemporal_load(p); return make_uint4(v.x, v.y, v.z, v.w); }
-        else if constexpr (NT != 0 && PT_SLOT_EXTLOAD) { const PtU4v v = *p; return make_uint4(v.x, v.y, v.z, v.w); }
+        else if constexpr (NT != 0) { const PtU4v v = *p; return make_uint4(v.x, v.y, v.z, v.w); }
         else return *reinterpret_cast<const uint4 *>(p);
     }
     PT_DEV const SlotU4Ref &operator=(uint4 v) const
@@ -258,12 +229,12 @@ template<int NT> struct SlotU4Ref {
         return *this;
     }
 };
-template<int NT = PT_NT_OTHER>
+template<int NT = 0>
 PT_DEV SlotF4Ref<NT> slotF4(const PathState &st, uint32_t a, uint32_t slot)
 {
     return SlotF4Ref<NT>{reinterpret_cast<PtF4v *>(slotBase(st, a) + (size_t)slotOffset(st, a, slot))};
 }
-template<int NT = PT_NT_OTHER>
+template<int NT = 0>
 PT_DEV SlotU4Ref<NT> slotU4(const PathState &st, uint32_t a, uint32_t slot)
 {
     return SlotU4Ref<NT>{reinterpret_cast<PtU4v *>(slotBase(st, a) + (size_t)slotOffset(st, a, slot))};
@@ -1044,12 +1015,8 @@ PT_DEV int wideNext(WideState &w, uint32_t octInv, uint2 *stack, int stride, uin
     return 2;
 }
 // The node half of wideNext alone (single-level scenes): the next node of the walk in `idx`, false when group and stack are empty.
-// PT_NEXT_NODE_FLAT = 1 (round 5): the same function with two one-instruction divergent regions (the stack's pop and push, LDS accesses) and selects
-// for the rest, instead of three nested branches whose exec-mask bookkeeping and copies were a tenth of the walk's turn.
-#ifndef PT_NEXT_NODE_FLAT
-#define PT_NEXT_NODE_FLAT 1
-#endif
-#if PT_NEXT_NODE_FLAT
+// Two one-instruction divergent regions (the stack's pop and push, LDS accesses) and selects for the rest: written as three nested branches, like
+// wideNext above, the exec-mask bookkeeping and copies were a tenth of the walk's turn (rejected, round 5: DESIGN.md).
 PT_DEV bool wideNextNode(WideState &w, uint32_t octInv, uint2 *stack, int stride, uint32_t &idx)
 {
     const bool need = w.node < 0;                            // the next node comes from the group / the stack
@@ -1070,29 +1037,6 @@ PT_DEV bool wideNextNode(WideState &w, uint32_t octInv, uint2 *stack, int stride
     w.node = -1;
     return !need || have;
 }
-#else
-PT_DEV bool wideNextNode(WideState &w, uint32_t octInv, uint2 *stack, int stride, uint32_t &idx)
-{
-    if (w.node < 0) {
-        if ((w.grpMasks & 0xFFu) == 0u) {
-            if (w.sp == 0)
-                return false;
-            w.sp--;
-            uint2 e = stack[w.sp*stride];
-            w.grpBase = e.x; w.grpMasks = e.y;
-        }
-        uint32_t hits = w.grpMasks & 0xFFu, imask = w.grpMasks >> 8;
-        uint32_t slot = ((uint32_t)__ffs((int)hits) - 1u) ^ octInv;
-        w.node = (int)(w.grpBase + (uint32_t)__popc(imask & ((1u << slot) - 1u)));
-        hits &= hits - 1u;
-        w.grpMasks = (imask << 8) | hits;
-        if (hits) { stack[w.sp*stride] = make_uint2(w.grpBase, w.grpMasks); w.sp++; }
-    }
-    idx = (uint32_t)w.node;
-    w.node = -1;
-    return true;
-}
-#endif
 // nothing left to look at: no record, no node, nothing on the stack
 PT_DEV bool wideWalkOver(const WideState &w) { return w.triMask == 0u && w.tri2Mask == 0u && w.node < 0 && (w.grpMasks & 0xFFu) == 0u && w.sp == 0; }
 // code 4: q1 = the second 16 bytes of node `idx`
@@ -1119,73 +1063,29 @@ PT_DEV void wideEnterInstance(WideState &w, uint2 *stack, int stride, uint32_t r
     w.curInst = (int)recIdx;
 }
 // ---- the node as a lane holds it --------------------------------------------------------------------------------------------------
-// PT_WIDE_HALF = 1 (an experiment of round 5, measured and NOT the product's layout): the shim re-encodes the ABI's 80-byte node
-// (include/tungsten_hip.h: TgHipWideNode) at upload into 128 bytes = one cache line whose 48 child planes are IEEE halfs holding the SAME
-// integers 0 .. 255 -- exactly --, one 16-byte row per axis and side:
-//   [0,16) origin.xyz, exp | imask << 24    [16,32) child_base, rec_base, leaf_valid, 0
-//   [32,48) lo x   [48,64) lo y   [64,80) lo z   [80,96) hi x   [96,112) hi y   [112,128) hi z        (8 halfs per row: slots 0 .. 7)
-// The idea: a wave64 v_cvt_f32_ubyteN costs 3.2 cycles of its SIMD and the v_pk_fma_f32 behind it 3.7 per two planes (tools/ubench_valu.hip,
-// profiles/r5_ubench_valu.txt: only fma / mul / add / and / mov run at 2) -- 5.0 per plane --, while v_fma_mix_f32 reads the half and does
-// the same single-rounding f32 fma in 3.2; and the ray's octant picks the ROW it loads as "near" / "far" per axis by address, where the byte
-// layout needs twelve v_cndmask_b32 on the loaded words: ~85 of ~500 issue cycles per node visit less, every plane distance bit-identical
-// (the whole GPU suite passes on it).  The result: 2.7 % SLOWER on the headline (949 against 975 Msamples/s in one session, closest-hit launches
-// 863 -> 890 us, shadow 827 -> 888; mesh1m 610 -> 600; profiles/r5_ab_half_planes.txt) -- eight 16-byte loads per node instead of five, and
-// 128 VGPRs instead of 115 / 125: the walk is bound as much by what it pulls through the vector L1 as by what it issues.
-#ifndef PT_WIDE_HALF
-#define PT_WIDE_HALF 0
-#endif
+// The ABI's 80-byte node (include/tungsten_hip.h: TgHipWideNode), five 16-byte rows.  (Rejected, round 5: a 128-byte node with the child
+// planes as halfs, one row per axis and side -- fewer VALU cycles per visit, eight loads instead of five, 2.7 % slower: profiles/r5_ab_half_planes.txt.)
 // byte offset of node `idx` behind s.wide
-PT_DEV uint32_t wideNodeOff(const DeviceScene &s, uint32_t idx) { return PT_WIDE_HALF ? idx << 7 : idx*s.wide_stride; }
-#if PT_WIDE_HALF
-#define PT_WIDE_NODE_BYTES 128u
-struct WideNodeRegs { float4 q0, q1, nx, ny, nz, fx, fy, fz; };
-// the 16-byte row at byte `off` behind `base` (uniform: s.wide, or the LDS copy of the top of the tree) -- a 32-bit offset, so that the
-// load is `global_load_dwordx4 v, v_off, s[base]` and a lane holds six row offsets, not six 64-bit pointers
-PT_DEV float4 wideRow(const char *base, uint32_t off) { return *reinterpret_cast<const float4 *>(base + (size_t)off); }
-PT_DEV void wideNodeFetch(WideNodeRegs &n, const char *base, uint32_t off, const WideRay &wr)
-{
-    const uint32_t ox = (wr.octInv & 1u) ? 48u : 0u, oy = (wr.octInv & 2u) ? 48u : 0u, oz = (wr.octInv & 4u) ? 48u : 0u;
-    n.q0 = wideRow(base, off); n.q1 = wideRow(base, off + 16u);
-    n.nx = wideRow(base, off + 32u + ox); n.fx = wideRow(base, off + 80u - ox);
-    n.ny = wideRow(base, off + 48u + oy); n.fy = wideRow(base, off + 96u - oy);
-    n.nz = wideRow(base, off + 64u + oz); n.fz = wideRow(base, off + 112u - oz);
-}
-// (the two-level walks load "a node or a record" through one address: the first three rows are in registers when the kind is known)
-PT_DEV void wideNodeFetchRest(WideNodeRegs &n, const char *base, uint32_t off, const WideRay &wr, float4 q0, float4 q1, float4 q2)
-{
-    const uint32_t ox = (wr.octInv & 1u) ? 48u : 0u, oy = (wr.octInv & 2u) ? 48u : 0u, oz = (wr.octInv & 4u) ? 48u : 0u;
-    const float4 hx = wideRow(base, off + 80u);
-    n.q0 = q0; n.q1 = q1;
-    n.nx = ox ? hx : q2; n.fx = ox ? q2 : hx;
-    n.ny = wideRow(base, off + 48u + oy); n.fy = wideRow(base, off + 96u - oy);
-    n.nz = wideRow(base, off + 64u + oz); n.fz = wideRow(base, off + 112u - oz);
-}
-#else
+PT_DEV uint32_t wideNodeOff(const DeviceScene &s, uint32_t idx) { return idx*s.wide_stride; }
 #define PT_WIDE_NODE_BYTES 80u
 struct WideNodeRegs { float4 q0, q1, q2, q3, q4; };
-// (a 16-byte row is loaded as ONE vector: read through float4 the compiler narrows the row whose last word the walk does not use -- child base,
-// record base, leaf_valid, - -- to a global_load_dwordx3, and the walk built around the 12-byte load is the slower one (pt_math.h: ld4): PT_ROW_X4 = 0 for the A/B)
-#ifndef PT_ROW_X4
-#define PT_ROW_X4 1
-#endif
+// the 16-byte row at byte `off` behind the uniform `base` (s.wide), loaded as ONE vector: read through float4 the compiler narrows the row whose
+// last word the walk does not use -- child base, record base, leaf_valid, - -- to a global_load_dwordx3, and the walk built around the 12-byte
+// load is the slower one (pt_math.h: ld4)
 PT_DEV float4 wideRow(const char *base, uint32_t off)
 {
-#if PT_ROW_X4
     const PtF4v v = *reinterpret_cast<const PtF4v *>(base + (size_t)off);
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4 *>(base + (size_t)off);
-#endif
 }
-PT_DEV void wideNodeFetch(WideNodeRegs &n, const char *base, uint32_t off, const WideRay &)
+PT_DEV void wideNodeFetch(WideNodeRegs &n, const char *base, uint32_t off)
 {
     n.q0 = wideRow(base, off); n.q1 = wideRow(base, off + 16u); n.q2 = wideRow(base, off + 32u); n.q3 = wideRow(base, off + 48u); n.q4 = wideRow(base, off + 64u);
 }
-PT_DEV void wideNodeFetchRest(WideNodeRegs &n, const char *base, uint32_t off, const WideRay &, float4 q0, float4 q1, float4 q2)
+// (the two-level walks load "a node or a record" through one address: the first three rows are in registers when the kind is known)
+PT_DEV void wideNodeFetchRest(WideNodeRegs &n, const char *base, uint32_t off, float4 q0, float4 q1, float4 q2)
 {
     n.q0 = q0; n.q1 = q1; n.q2 = q2; n.q3 = wideRow(base, off + 48u); n.q4 = wideRow(base, off + 64u);
 }
-#endif
 // The node's 80 bytes have arrived: slab-test its eight children against [tmin, tmax], queue the hit ones.  Two children per
 // v_pk_fma_f32; each half is one correctly rounded fma, as in the oracle's scalar fmaf.
 typedef float WideF2 __attribute__((ext_vector_type(2)));
@@ -1198,26 +1098,6 @@ PT_DEV void wideVisit(WideState &w, const WideNodeRegs &nd, f3 o, const WideRay 
     const f3 adjS = spacing*wr.idir;
     const f3 adjO = (xyz(q0) - o)*wr.idir;
     uint32_t hitmask = 0u;
-#if PT_WIDE_HALF
-    typedef _Float16 WideH2 __attribute__((ext_vector_type(2)));
-    // plane distance = fma(q, spacing/d, (origin - o)/d) with q read as a half (v_fma_mix_f32): one rounding, as the oracle's fmaf on float(q)
-    auto plane = [](_Float16 q, float s, float o) { return __builtin_fmaf((float)q, s, o); };
-    const float nxw[4] = {nd.nx.x, nd.nx.y, nd.nx.z, nd.nx.w}, nyw[4] = {nd.ny.x, nd.ny.y, nd.ny.z, nd.ny.w}, nzw[4] = {nd.nz.x, nd.nz.y, nd.nz.z, nd.nz.w};
-    const float fxw[4] = {nd.fx.x, nd.fx.y, nd.fx.z, nd.fx.w}, fyw[4] = {nd.fy.x, nd.fy.y, nd.fy.z, nd.fy.w}, fzw[4] = {nd.fz.x, nd.fz.y, nd.fz.z, nd.fz.w};
-#pragma unroll
-    for (int pr = 0; pr < 4; ++pr) {                // children 2 pr and 2 pr + 1: the two halfs of word pr of every row
-        const WideH2 hnx = __builtin_bit_cast(WideH2, nxw[pr]), hny = __builtin_bit_cast(WideH2, nyw[pr]), hnz = __builtin_bit_cast(WideH2, nzw[pr]);
-        const WideH2 hfx = __builtin_bit_cast(WideH2, fxw[pr]), hfy = __builtin_bit_cast(WideH2, fyw[pr]), hfz = __builtin_bit_cast(WideH2, fzw[pr]);
-        const float tnx0 = plane(hnx.x, adjS.x, adjO.x), tnx1 = plane(hnx.y, adjS.x, adjO.x), tfx0 = plane(hfx.x, adjS.x, adjO.x), tfx1 = plane(hfx.y, adjS.x, adjO.x);
-        const float tny0 = plane(hny.x, adjS.y, adjO.y), tny1 = plane(hny.y, adjS.y, adjO.y), tfy0 = plane(hfy.x, adjS.y, adjO.y), tfy1 = plane(hfy.y, adjS.y, adjO.y);
-        const float tnz0 = plane(hnz.x, adjS.z, adjO.z), tnz1 = plane(hnz.y, adjS.z, adjO.z), tfz0 = plane(hfz.x, adjS.z, adjO.z), tfz1 = plane(hfz.y, adjS.z, adjO.z);
-        float tn0 = fmaxf(fmaxf(tnx0, tny0), fmaxf(tnz0, tmin)), tn1 = fmaxf(fmaxf(tnx1, tny1), fmaxf(tnz1, tmin));
-        float tf0 = fminf(fminf(tfx0, tfy0), fminf(tfz0, tmax)), tf1 = fminf(fminf(tfx1, tfy1), fminf(tfz1, tmax));
-        tf0 *= 1.0000004f; tf1 *= 1.0000004f;
-        hitmask |= (tn0 <= tf0) ? (1u << (2*pr)) : 0u;
-        hitmask |= (tn1 <= tf1) ? (2u << (2*pr)) : 0u;
-    }
-#else
     const float4 q2 = nd.q2, q3 = nd.q3, q4 = nd.q4;
     const WideF2 SX = {adjS.x, adjS.x}, SY = {adjS.y, adjS.y}, SZ = {adjS.z, adjS.z};
     const WideF2 OX = {adjO.x, adjO.x}, OY = {adjO.y, adjO.y}, OZ = {adjO.z, adjO.z};
@@ -1242,7 +1122,6 @@ PT_DEV void wideVisit(WideState &w, const WideNodeRegs &nd, f3 o, const WideRay 
         hitmask |= (tn0 <= tf0) ? (1u << (2*pr)) : 0u;
         hitmask |= (tn1 <= tf1) ? (2u << (2*pr)) : 0u;
     }
-#endif
     const uint32_t imask = ex >> 24;
     // the records of the hit leaf children: bit s -> bits 4 s .. 4 s + 3, masked by the records that exist
     uint32_t x = hitmask & ~imask;
@@ -1304,7 +1183,7 @@ PT_DEV float4 traverseClosestWide(const DeviceScene &s, const RayD &worldRay, ui
             break;
         if (what == 2) {
             WideNodeRegs nd;
-            wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, idx), wr);
+            wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, idx));
             if (COUNT) nodesVisited++;
             wideVisit(w, nd, ray.o, wr, ray.tmin, tmax);
         } else if (what == 1) {

@@ -38,19 +38,12 @@ template<typename T> PT_DEV const T &at32(const T *base, uint32_t idx)
 // A float4 table entry read as ONE 16-byte vector load.  Read through `const float4 &` the compiler drops the words a kernel does not use and
 // issues global_load_dwordx3 / x2 instead.  In isolation the narrow load costs what the wide one costs (tools/ubench_loads.hip), but the kernels
 // built around it are slower -- a three-register destination, the copies behind it, the schedule (measured on the wide nodes' second row: shadow
-// launches -2 %; on the slots: -6.5 %, profiles/r5_ab_x4_loads.txt).  PT_LD4 = 0 gives the narrowed loads back (A/B).
-#ifndef PT_LD4
-#define PT_LD4 1
-#endif
+// launches -2 %; on the slots: -6.5 %, profiles/r5_ab_x4_loads.txt).
 typedef float PtLd4v __attribute__((ext_vector_type(4)));
 PT_DEV float4 ld4(const float4 *base, uint32_t idx)
 {
-#if PT_LD4
     const PtLd4v v = *reinterpret_cast<const PtLd4v *>(reinterpret_cast<const char *>(base) + (size_t)(idx*16u));
     return make_float4(v.x, v.y, v.z, v.w);
-#else
-    return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + (size_t)(idx*16u));
-#endif
 }
 
 struct f3 { float x, y, z; };

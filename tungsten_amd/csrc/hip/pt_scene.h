@@ -97,28 +97,14 @@ struct DeviceScene {
 // One load whatever the format: three floats from the texel's address, a one-channel texture's value taken from the first (the shim leaves
 // 16 readable bytes behind the texel array).  With a branch per format around the load, the four texels of a bilinear lookup were four
 // SEQUENTIAL memory round trips -- each load inside its own divergent region, each followed by s_waitcnt vmcnt(0) -- in every shading variant
-// with bitmap textures; now the four loads are issued back to back (PT_TEXEL_BRANCH = 1 gives the old form back for the A/B).
-#ifndef PT_TEXEL_BRANCH
-#define PT_TEXEL_BRANCH 0
-#endif
-#ifndef PT_TEXEL_STAGES
-#define PT_TEXEL_STAGES 2
-#endif
+// with bitmap textures; now the four loads are issued back to back (the record of both forms: profiles/r5_ab_texel_fetch.txt).
 PT_DEV f3 bitmapTexel(const DeviceScene &s, const TgHipTexture &t, int x, int y)
 {
     const float *tex = s.texels + t.texel_offset;
-#if PT_TEXEL_BRANCH
-    if (t.flags & TGHIP_TEXF_RGB) {
-        const float *p = tex + ((size_t)x + (size_t)y*t.w)*3;
-        return mk3(p[0], p[1], p[2]);
-    }
-    return splat3(tex[(size_t)x + (size_t)y*t.w]);
-#else
     const bool rgb = (t.flags & TGHIP_TEXF_RGB) != 0;
     const float *p = tex + ((size_t)x + (size_t)y*t.w)*(rgb ? 3u : 1u);
     const float a = p[0], b = p[1], c = p[2];
     return mk3(a, rgb ? b : a, rgb ? c : a);
-#endif
 }
 
 // i mod n for n > 0 and any i, result in [0, n): float-reciprocal quotient + fix-up instead of integer division
@@ -159,17 +145,8 @@ PT_DEV f3 textureEval(const DeviceScene &s, int texIdx, float u0, float v0)
         iu0 = min(max(iu0, 0), w - 1); iu1 = min(max(iu1, 0), w - 1);
         iv0 = min(max(iv0, 0), h - 1); iv1 = min(max(iv1, 0), h - 1);
     }
-#if PT_TEXEL_BRANCH
-    if (!linear)
-        return bitmapTexel(s, t, iu0, iv0);
-#else
     // (a nearest-neighbour texture fetches its one texel four times -- one cache line -- instead of branching around three of the loads)
     if (!linear) { iu1 = iu0; iv1 = iv0; }
-#endif
-#if PT_TEXEL_BRANCH
-    f3 x00 = bitmapTexel(s, t, iu0, iv0), x01 = bitmapTexel(s, t, iu1, iv0);
-    f3 x10 = bitmapTexel(s, t, iu0, iv1), x11 = bitmapTexel(s, t, iu1, iv1);
-#else
     f3 x00, x01, x10, x11;
     {
         // the four texels as four 12-byte loads issued back to back and ONE wait: the empty asm below consumes all twelve words, so every load
@@ -180,30 +157,19 @@ PT_DEV f3 textureEval(const DeviceScene &s, int texIdx, float u0, float v0)
         const uint32_t st = rgb ? 3u : 1u;
         const float *p00 = tex + ((size_t)iu0 + (size_t)iv0*t.w)*st, *p01 = tex + ((size_t)iu1 + (size_t)iv0*t.w)*st;
         const float *p10 = tex + ((size_t)iu0 + (size_t)iv1*t.w)*st, *p11 = tex + ((size_t)iu1 + (size_t)iv1*t.w)*st;
-#if PT_TEXEL_STAGES == 2
         // (two stages: the two ROWS first -- two cache lines, two misses in flight --, then each row's neighbour, which is in the line that just
         // arrived; all four at once made the headline 1.3 % slower: the neighbour's request goes to L2 again while its line is still on its way)
         float a0 = p00[0], b0 = p00[1], c0 = p00[2], a2 = p10[0], b2 = p10[1], c2 = p10[2];
         asm volatile("" : "+v"(a0), "+v"(b0), "+v"(c0), "+v"(a2), "+v"(b2), "+v"(c2));
         float a1 = p01[0], b1 = p01[1], c1 = p01[2], a3 = p11[0], b3 = p11[1], c3 = p11[2];
         asm volatile("" : "+v"(a1), "+v"(b1), "+v"(c1), "+v"(a3), "+v"(b3), "+v"(c3));
-#else
-        float a0 = p00[0], b0 = p00[1], c0 = p00[2], a1 = p01[0], b1 = p01[1], c1 = p01[2];
-        float a2 = p10[0], b2 = p10[1], c2 = p10[2], a3 = p11[0], b3 = p11[1], c3 = p11[2];
-        asm volatile("" : "+v"(a0), "+v"(b0), "+v"(c0), "+v"(a1), "+v"(b1), "+v"(c1), "+v"(a2), "+v"(b2), "+v"(c2), "+v"(a3), "+v"(b3), "+v"(c3));
-#endif
         x00 = mk3(a0, rgb ? b0 : a0, rgb ? c0 : a0); x01 = mk3(a1, rgb ? b1 : a1, rgb ? c1 : a1);
         x10 = mk3(a2, rgb ? b2 : a2, rgb ? c2 : a2); x11 = mk3(a3, rgb ? b3 : a3, rgb ? c3 : a3);
     }
-#endif
     f3 r = (x00*(1.0f - u) + x01*u)*(1.0f - v) + (x10*(1.0f - u) + x11*u)*v;
-#if !PT_TEXEL_BRANCH
     // (a select, not a branch: the interpolation is computed either way, so that the compiler cannot sink three of the four loads into it)
     const f3 rs = r*t.scale;
     return mk3(linear ? rs.x : x00.x, linear ? rs.y : x00.y, linear ? rs.z : x00.z);
-#else
-    return r*t.scale;
-#endif
 }
 
 // Distribution2D::warp / pdf (sampling/Distribution2D.hpp:68-83) on the flattened tables
@@ -1456,10 +1422,9 @@ PT_DEV bool embreeBoxVisible(f3 o, f3 d, float tmin, float tmax, f3 lo, f3 hi)
 }
 
 /* Embree MoellerTrumboreIntersector1 (thirdparty/embree/kernels/geometry/triangle_intersector_moeller.h:76-113, finalize() :43-49);
- * Embree's e1 = v0 - v1 = -rec.b, e2 = v2 - v0 = rec.c. */
-#ifndef PT_TRI_BRANCHLESS
-#define PT_TRI_BRANCHLESS 0    /* measured, profiles/r6_ab_lane_cliff.txt: level on the metric's workload, the closest-hit walk of mesh1m 528 -> 537 us */
-#endif
+ * Embree's e1 = v0 - v1 = -rec.b, e2 = v2 - v0 = rec.c.
+ * (rejected, round 6: the test without its two early exits -- level on the metric's workload, mesh1m's closest-hit walk 528 -> 537 us:
+ * profiles/r6_ab_lane_cliff.txt) */
 PT_DEV bool triTest(f3 v0, f3 b, f3 c, const RayD &ray, float tmax, float &t, float &u, float &v)
 {
     f3 e1 = -b, e2 = c;
@@ -1471,31 +1436,13 @@ PT_DEV bool triTest(f3 v0, f3 b, f3 c, const RayD &ray, float tmax, float &t, fl
     float sgn = den < 0.0f ? -1.0f : 1.0f;
     float U = dotEmbree(R, e2)*sgn;
     float V = dotEmbree(R, e1)*sgn;
-#if PT_TRI_BRANCHLESS
-    // Round 6: no early exits.  A wave64 VALU instruction with eight or fewer enabled lanes issues at a QUARTER of the rate (tools/ubench_lanes.hip,
-    // profiles/r6_ubench_lane_masks.txt: 935 G wave-instructions/s with 9 .. 64 lanes enabled, 241 with 1 .. 8, whichever lanes they are), and that is
-    // where the two exits put the rest of the test: of the ~20 lanes of a walk's wave that test a record in a turn, a handful pass the edge
-    // functions and two find a hit (bench.py: roofline.valu.walk), so the distance test and the reciprocal -- some 40 instructions -- ran in nearly
-    // every turn for one to eight lanes, at four times their price.  Every lane with a record computes them now; the values are the same.
-    const bool inside = den != 0.0f && U >= 0.0f && V >= 0.0f && U + V <= absDen;
-    const float T = dotEmbree(Ng, C)*sgn;
-    const bool inRange = T > absDen*ray.tmin && T < absDen*tmax;
-    const float rcpAll = embreeRcp(absDen);
-    t = T*rcpAll; u = U*rcpAll; v = V*rcpAll;
-    return inside && inRange;
-#else
     if (!(den != 0.0f && U >= 0.0f && V >= 0.0f && U + V <= absDen))
         return false;
     float T = dotEmbree(Ng, C)*sgn;
     if (!(T > absDen*ray.tmin && T < absDen*tmax))
         return false;
-#endif
-#ifdef PT_TRI_DIVIDE   /* experiment (profiles/README.md): the exact divisions rounds 1-3 ran here, to price Embree's reciprocal against them */
-    t = T/absDen; u = U/absDen; v = V/absDen;
-#else
     const float rcpAbsDen = embreeRcp(absDen);
     t = T*rcpAbsDen; u = U*rcpAbsDen; v = V*rcpAbsDen;
-#endif
     return true;
 }
 
@@ -1721,14 +1668,6 @@ PT_DEV bool testRecordLoaded(const DeviceScene &s, uint32_t ri, float4 r0, float
     } else {
         ok = false;                                    /* instance records are entered, not tested (traverseClosestInst) */
     }
-#if PT_TRI_BRANCHLESS
-    if (!UNIFORM) {                                    /* (selects, not a region a few lanes enter: triTest above says why) */
-        tmax = ok ? t : tmax;
-        hit = make_float4(ok ? t : hit.x, ok ? u : hit.y, ok ? v : hit.z, ok ? __int_as_float((int)ri) : hit.w);
-        hitMeta = meta;                                /* (read by the callers only behind `ok`) */
-        return ok;
-    }
-#endif
     if (ok) {
         tmax = t;
         hit = make_float4(t, u, v, __int_as_float((int)ri));
@@ -2370,9 +2309,6 @@ PT_DEV int selectMedium(const TgHipObject &o, int current, bool geometricBacksid
  * 3 = mediumMedium (transmittances/{Exponential,Linear,Quadratic,DoubleExponential,Pulse,Erlang}Transmittance.cpp) */
 PT_DEV float transLeafKernel(const TgHipMedium &m, int k, float tau)
 {
-#ifdef PT_EXP_TRANS_ONLY     /* compile-only / A-B diagnostic: what the media kernels cost without the eight non-exponential transmittances */
-    return fmathExp(-tau);
-#endif
     const float p0 = m.trans_p[0], p1 = m.trans_p[1], p2 = m.trans_p[2];
     switch (m.trans_type) {
     case TGHIP_TRANS_LINEAR: {                          /* LinearTransmittance.cpp:32-57 */
@@ -2453,9 +2389,6 @@ PT_DEV float transLeafKernel(const TgHipMedium &m, int k, float tau)
 }
 PT_DEV float transLeafSigmaBar(const TgHipMedium &m)
 {
-#ifdef PT_EXP_TRANS_ONLY
-    return 1.0f;
-#endif
     switch (m.trans_type) {
     case TGHIP_TRANS_LINEAR: return 1.0f/m.trans_p[0];
     case TGHIP_TRANS_QUADRATIC: return 2.0f/m.trans_p[0];
@@ -2505,9 +2438,6 @@ PT_DEV f3 transEval(const TgHipMedium &m, f3 tau, bool startOnSurface, bool endO
 template<uint32_t M>
 PT_DEV float transLeafSample(const TgHipMedium &m, Rng &rng, bool startOnSurface)   /* sampleSurface / sampleMedium */
 {
-#ifdef PT_EXP_TRANS_ONLY
-    return -logfH(1.0f - RNG1D(rng));
-#endif
     const float p0 = m.trans_p[0], p1 = m.trans_p[1], p2 = m.trans_p[2];
     switch (m.trans_type) {
     case TGHIP_TRANS_LINEAR:

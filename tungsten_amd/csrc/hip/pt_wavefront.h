@@ -68,9 +68,6 @@
                             materialtest 968.3 / 969.4 -> 977.8 / 974.5, mesh1m 616.9 / 614.2 -> 622.7 / 621.7 Msamples/s (two libraries alternated
                             twice in one session, profiles/r4_ab_coat_waves.txt); round 3 had measured 3 waves as neutral at 223 VGPRs */
 #endif
-#ifndef PT_TRACE_AHEAD
-#define PT_TRACE_AHEAD 0     /* 1: the one-launch render (FUSE_LOOP) traces a slot's next ray at the end of the turn (shadeBody) -- measured, slower: profiles/r6_ab_trace_ahead.txt */
-#endif
 #ifndef LEAN_WAVES
 #define LEAN_WAVES   2   /* measured: 2 waves/SIMD without scratch beats 3 with 108 B of scratch (kernel is VALU-bound) */
 #endif
@@ -112,7 +109,7 @@ PT_DEV void rngStartSobol(Rng &rng, const DeviceScene &s, const PassParams &pp, 
 
 // EXT: the pass may carry TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS state (checked at run time through pp.flags /
 // pp.rec_count); false compiles those paths out (the specialised shading variants, DESIGN.md "Kernels").
-template<bool CONVERGED = true, bool EXT = true, int NTS = PT_NT_TRAV>
+template<bool CONVERGED = true, bool EXT = true, int NTS = PT_NT_STATE>
 PT_DEV bool nextPath(const DeviceScene &s, const PathState &st, const PassParams &pp, bool finished, bool fresh,
                      uint32_t slot, f3 em, bool black, uint32_t *cursor, bool aborted, uint32_t &finishedCount)
 {
@@ -753,39 +750,16 @@ __global__ __launch_bounds__(512) void k_trace_closest_inst(DeviceScene s, PathS
 // With the join the latch has two predecessors.  Costs nothing: no instruction is emitted.
 #define PT_TURN_JOIN() asm volatile("" ::: "memory")
 // The fetch of a decoupled turn: the lane's record (three rows) and its node (five rows), eight independent loads issued back to back.
-// PT_WALK_FETCH_SAFE = 1 (round 5): every lane loads, from entry 0 where it has nothing to fetch -- no divergent region around the loads.
-// With the loads inside `if (hasRec)` / `if (hasNode)` the closest-hit kernel waited for the record's first row (s_waitcnt vmcnt(2) + three
-// copies out of the region) BEFORE it issued the node's loads: two memory round trips per turn where one was meant.  The through-float4 record
-// reads stay narrowable (pt_math.h: ld4).  PT_LDS_TOP = 1 compiles the top-of-tree-in-LDS experiment of round 3 back in (lds_nodes option).
-#ifndef PT_WALK_FETCH_SAFE
-#define PT_WALK_FETCH_SAFE 1
-#endif
-#ifndef PT_LDS_TOP
-#define PT_LDS_TOP 0
-#endif
-#if PT_WALK_FETCH_SAFE
-#define PT_WALK_FETCH(s, st, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx, wr, topCount, ldsTop) do { \
+// Every lane loads, from entry 0 where it has nothing to fetch -- no divergent region around the loads.  With the loads inside `if (hasRec)` /
+// `if (hasNode)` the closest-hit kernel waited for the record's first row (s_waitcnt vmcnt(2) + three copies out of the region) BEFORE it issued
+// the node's loads: two memory round trips per turn where one was meant (rejected, with the top of the tree in LDS: profiles/r5_ab_walk_fetch.txt).
+// The through-float4 record reads stay narrowable (pt_math.h: ld4).
+#define PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx) do { \
         const uint32_t recAt_ = (hasRec) ? (recIdx)*3u : 0u; \
         const uint32_t nodeAt_ = (hasNode) ? wideNodeOff(s, nodeIdx) : 0u; \
         r0 = at32((s).recs, recAt_); r1 = at32((s).recs, recAt_ + 1u); r2 = at32((s).recs, recAt_ + 2u); \
-        if (PT_LDS_TOP && (hasNode) && (nodeIdx) < (topCount)) wideNodeFetch(nd, ldsTop, nodeAt_, wr); \
-        else wideNodeFetch(nd, reinterpret_cast<const char *>((s).wide), nodeAt_, wr); \
+        wideNodeFetch(nd, reinterpret_cast<const char *>((s).wide), nodeAt_); \
     } while (0)
-#else
-#define PT_WALK_FETCH(s, st, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx, wr, topCount, ldsTop) do { \
-        if (hasRec) { r0 = at32((s).recs, (recIdx)*3u + 0u); r1 = at32((s).recs, (recIdx)*3u + 1u); r2 = at32((s).recs, (recIdx)*3u + 2u); } \
-        if (hasNode) { \
-            if ((nodeIdx) < (topCount)) wideNodeFetch(nd, ldsTop, wideNodeOff(s, nodeIdx), wr); \
-            else                        wideNodeFetch(nd, reinterpret_cast<const char *>((s).wide), wideNodeOff(s, nodeIdx), wr); \
-        } \
-    } while (0)
-#endif
-#ifndef PT_LATE_PUBLISH
-#define PT_LATE_PUBLISH 1     /* the decoupled walks: after the queue ran dry, finished walks publish more than eight at a time (0 for the A/B) */
-#endif
-#ifndef PT_SHADOW_PREP
-#define PT_SHADOW_PREP 1      /* k_trace_shadow_fast: a slot's second ray prepared in the refill block (traceShadowFastBody); 0 for the A/B */
-#endif
 // busy lanes at or below which a wave of the decoupled walks takes new rays from its workgroup's queue (swept in round 5, r5_sweep_final_kernels.txt: 24 / 32 / 40 / 48 / 56 -- 40 is the shadow walk's optimum, the closest-hit walk is level between 40 and 48)
 #ifndef PT_REFILL_AT
 #define PT_REFILL_AT 40
@@ -795,7 +769,7 @@ __global__ __launch_bounds__(512) void k_trace_closest_inst(DeviceScene s, PathS
 // needs about max(nodes, records) turns instead of their sum; a node visited before an earlier node's records have shortened the ray
 // may report a few children more (conservative: hits unchanged, visit counts a little above the sequential walk's).
 // (the kernel's body as a function of the workgroup's LDS objects: k_trace_closest_wide below and the tail kernel, k_tail, run it)
-template<bool COUNT, bool SOLIDS, bool INST, bool DECOUPLED, int NTS = PT_NT_TRAV>
+template<bool COUNT, bool SOLIDS, bool INST, bool DECOUPLED, int NTS = PT_NT_STATE>
 PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, BlockLds &L, uint32_t &fetchNext, int *ldsDyn)
 {
     unsigned short *order = reinterpret_cast<unsigned short *>(ldsDyn);
@@ -804,14 +778,6 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
     BlockCtl &ctl = st.ctl[blockIdx.x];
     if (threadIdx.x == 0) fetchNext = 0;
     const unsigned long long wpStart = COUNT ? wall_clock64() : 0ull;
-    // DECOUPLED: the top of the tree in LDS, behind the stacks (PathState::lds_nodes; queuesBegin's barriers publish the copy)
-    const uint32_t topCount = DECOUPLED ? st.lds_nodes : 0u;
-    const char *ldsTop = reinterpret_cast<const char *>(ldsDyn) + st.slots_per_block*2u + st.wide_depth*blockDim.x*8u;
-    if constexpr (DECOUPLED) {
-        float4 *dst = reinterpret_cast<float4 *>(const_cast<char *>(ldsTop));
-        for (uint32_t i = threadIdx.x; i < topCount*s.wide_stride/16u; i += blockDim.x)
-            dst[i] = s.wide[i];
-    }
     queuesBegin(L, st, ctl, Q_EXTP, 0u, order, Q_EXT);
     const uint32_t n = L.n;
     const uint32_t first = blockIdx.x*st.slots_per_block;
@@ -841,7 +807,7 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
             // (round 6: once the queue is dry the finished walks wait until more than eight of them can publish together, or nothing else is
             // left -- eight or fewer enabled lanes issue VALU instructions at a quarter of the rate, profiles/r6_ubench_lane_masks.txt)
             const unsigned long long pendMask = __ballot(pendingPublish);
-            if (pendMask != 0ull && ((!exhausted && __popcll(busyMask) <= PT_REFILL_AT) || (exhausted && (!PT_LATE_PUBLISH || __popcll(pendMask) > 8 || busyMask == 0ull)))) {
+            if (pendMask != 0ull && ((!exhausted && __popcll(busyMask) <= PT_REFILL_AT) || (exhausted && (__popcll(pendMask) > 8 || busyMask == 0ull)))) {
                 WALK_SECTION(wpPubs, wpPubLanes, pendingPublish);
                 if (pendingPublish) {
                     slotF4<NTS>(st, A_HIT, slot) = hit;
@@ -943,7 +909,7 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
             }
             float4 r0, r1, r2;
             WideNodeRegs nd;
-            PT_WALK_FETCH(s, st, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx, wr, topCount, ldsTop);
+            PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
             WALK_SECTION(wpRecTurns, wpRecLanes, hasRec);
             WALK_SECTION(wpNodeTurns, wpNodeLanes, hasNode);
             if (hasRec) {
@@ -985,7 +951,7 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
             float4 r0, r1, r2;
             WideNodeRegs nd;
             if (hasRec) { r0 = at32(s.recs, recIdx*3u + 0u); r1 = at32(s.recs, recIdx*3u + 1u); r2 = at32(s.recs, recIdx*3u + 2u); }
-            if (hasNode) wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, nodeIdx), wr);
+            if (hasNode) wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, nodeIdx));
             if (hasRec) {
                 if (COUNT) prims++;
                 uint32_t meta;
@@ -1042,7 +1008,7 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
                 float4 q0 = p[0], q1 = p[1], q2 = p[2];
                 if (what == 2) {
                     WideNodeRegs nd;
-                    wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, wr, q0, q1, q2);
+                    wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, q0, q1, q2);
                     if (COUNT) nodes++;
                     wideVisit(w, nd, ray.o, wr, ray.tmin, tmax);
                 } else if (INST && what == 4) {
@@ -1084,17 +1050,16 @@ __global__ WIDE_CLOSEST_BOUNDS void k_trace_closest_wide(DeviceScene s, PathStat
 // vertex and regenerates their slots (finishBody, below), then traces its extension rays, the fresh camera rays among them -- one launch per
 // part and iteration less, and the streaming of the regeneration runs inside the issue-bound walk's launch.  The shim launches the stand-alone
 // k_finish only before a host check (the liveness report) and before k_tail.  Single-level scenes on the decoupled walk.
-// EXT = false: the pass carries none of nextPath's run-time extras (Sobol' sampler, SampleRecords, auxiliary outputs, per-sample output, thin lens, media:
-// pp.flags == 0 -- the metric's passes): the finish in front of the walk is nextPath's lean variant, as in the specialised shading kernels.
-template<int NTS = PT_NT_TRAV, bool EXT = true>
+// (rejected, round 6: the finish of flag-less passes through nextPath's lean variant -- a third fewer instructions, 0.45 % slower: profiles/r6_ab_finish_lean.txt)
+template<int NTS = PT_NT_STATE>
 PT_DEV bool finishBody(const DeviceScene &s, const PathState &st, const PassParams &pp, BlockLds &L, unsigned short *order);
-template<bool COUNT, bool SOLIDS, bool EXT = true>
+template<bool COUNT, bool SOLIDS>
 __global__ WIDE_CLOSEST_BOUNDS void k_finish_trace_closest_wide(DeviceScene s, PathState st, PassParams pp)
 {
     extern __shared__ int ldsDyn[];
     __shared__ BlockLds L;
     __shared__ uint32_t fetchNext;
-    (void)finishBody<PT_NT_TRAV, EXT>(s, st, pp, L, reinterpret_cast<unsigned short *>(ldsDyn));   // (the queue area of the dynamic LDS: slots_per_block entries)
+    (void)finishBody(s, st, pp, L, reinterpret_cast<unsigned short *>(ldsDyn));   // (the queue area of the dynamic LDS: slots_per_block entries)
     __syncthreads();
     traceClosestWideBody<COUNT, SOLIDS, false, true>(s, st, L, fetchNext, ldsDyn);
 }
@@ -1214,7 +1179,7 @@ __global__ __launch_bounds__(512) void k_trace_closest_instw(DeviceScene s, Path
             }
             float4 r0, r1, r2;
             WideNodeRegs nd;
-            PT_WALK_FETCH(s, st, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx, wr, 0u, reinterpret_cast<const char *>(s.wide));
+            PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
             INST_SECTION(2, hasRec);
             INST_SECTION(3, hasNode);
             if (hasRec) {
@@ -1479,7 +1444,7 @@ template<uint32_t M, int FUSE, bool STAGED = false, bool GLOBAL_TABLES = false>
 PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassParams &pp, int cls, BlockLds &L, unsigned char *ldsTables, unsigned short *order)
 {
     // (the fused flat-list launches and k_tail -- STAGED -- re-read their slots within microseconds: no non-temporal hint there, pt_kernels.h)
-    constexpr int SNT = (FUSE != 0 || (STAGED && !PT_NT_TAIL)) ? 0 : PT_NT_STATE;
+    constexpr int SNT = (FUSE != 0 || STAGED) ? 0 : PT_NT_STATE;
     BlockCtl &ctl = st.ctl[blockIdx.x];
     // (CLS_MISS: the escaped paths.  CLS_0_AND_MISS: class 0, then the escaped paths -- one launch of the variant both run; the expanded list
     // keeps the two runs apart, so at most one wave per workgroup mixes surface shading with escaped paths)
@@ -1495,13 +1460,7 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
     const DeviceScene s = (STAGED || GLOBAL_TABLES) ? sg : stageSceneTables(sg, ldsTables);
     const uint32_t first = blockIdx.x*st.slots_per_block;
     const int maxBounces = s.settings.max_bounces, minBounces = s.settings.min_bounces;
-    // PT_EXP_HALF (a compile-only diagnostic, never the product): 1 = the kernel without the continuation sample, 2 = without next-event
-    // estimation -- the register demand of the two halves a split shading stage would consist of (profiles/r5_shade_split_halves.txt)
-#if defined(PT_EXP_HALF) && PT_EXP_HALF == 2
-    const bool nee = false;
-#else
     const bool nee = s.settings.enable_light_sampling != 0;
-#endif
     uint32_t finishedCount = 0, fusedClosest = 0, fusedShadow = 0, fusedPrims = 0, fusedNodes = 0;
     PROF_DECL;
 
@@ -1511,15 +1470,8 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
     // and every wave leaves the loop on its own -- no barrier, no bitmap traffic between the wavefront iterations.
     constexpr bool DIRECT = (FUSE & FUSE_LOOP) != 0;
     uint32_t idle = 0;
-    // Round 6 experiment (PT_TRACE_AHEAD = 1, not the product): the one-launch render traces a slot's NEXT ray -- the continuation, or the camera ray of the
-    // path that takes the slot over -- at the END of the turn, and a continuation that leaves the scene ends its path right there.  Every path's last visit
-    // is a miss (its ray leaves the Cornell box through the open front; no environment to ask): with 3.9 vertices per path a quarter of a turn's lanes hold
-    // such a path, find that out by tracing, and sit out the shading sections -- 47 of 64 lanes at any spp.  With this a visit starts from a stored hit
-    // (53 lanes: the camera rays beside the box still miss) and the render needs 11 % fewer turns -- of 20.8 us instead of 16.2: a walk of the flat list
-    // costs the WAVE its ~4 us whether 48 or 17 lanes need it, and there are two of them per turn now.  Cornell box 2 545 -> 2 290 Msamples/s; images identical
-    // (the GPU suite passes on it).  profiles/r6_ab_trace_ahead.txt.  Only where a miss has nothing else to do: no infinite lights, media, auxiliary outputs.
-    constexpr bool AHEAD = PT_TRACE_AHEAD && DIRECT && (FUSE & FUSE_TRACE) != 0 && (M & (FEAT_INFINITE | FEAT_MEDIA | FEAT_AUX)) == 0u;
-    uint32_t traced = 0;                         // AHEAD: one bit per owned slot whose A_HIT holds the hit of the ray in the slot
+    // (rejected, round 6: tracing a slot's NEXT ray at the end of the turn, so that a visit starts from a stored hit -- 11 % fewer turns, each a quarter
+    // longer, Cornell box 2 545 -> 2 290 Msamples/s: profiles/r6_ab_trace_ahead.txt)
     if (DIRECT) {
         // queuesBegin expanded (and thereby cleared) the extension queues into order[0, L.n): turn that list back into
         // a bitmap of busy slots (in the unused Q_SHADE0 words) each thread can look its own slots up in
@@ -1547,9 +1499,7 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
             local = DIRECT ? i : order[i];
             slot = first + local;
             float4 ro = slotF4<SNT>(st, A_RAY_O, slot), rd = slotF4<SNT>(st, A_RAY_D, slot), hit, thr4 = slotF4<SNT>(st, A_THR, slot);
-            if (AHEAD && ((traced >> turn) & 1u)) {
-                hit = slotF4<SNT>(st, A_HIT, slot);                   // traced at the end of the slot's last visit (class 0 throughout: FUSE_LOOP)
-            } else if (FUSE & FUSE_TRACE) {
+            if (FUSE & FUSE_TRACE) {
                 // TraceableScene::intersect inline: the flat record list, walked uniformly by the wave
                 RayD r0;
                 r0.o = xyz(ro); r0.d = xyz(rd); r0.tmin = ro.w; r0.tmax = rd.w;
@@ -1955,11 +1905,7 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
                     // continuation: bsdf.sample(event, adjoint = false) with all lobes (TraceBase.cpp:546-558)
                     ev.requested = LOBE_ALL;
                     ev.weight = splat3(1.0f); ev.pdf = 1.0f;
-#if defined(PT_EXP_HALF) && PT_EXP_HALF == 1
-                    if (true) {
-#else
                     if (!bsdfSample<M>(s, info.bsdf, ev)) {
-#endif
                         alive = false;
                     } else {
                         wo = toGlobal(frame, ev.wo);
@@ -2030,23 +1976,6 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
             }
             if (survives)
                 slotF4<SNT>(st, A_THR, slot) = mk4(throughput, __uint_as_float(newFlags));
-            if constexpr (AHEAD) {
-                bool haveHit = false;
-                if (survives) {
-                    const float4 h = traverseClosest<true, true, shadeKinds(M)>(sg, ray, nullptr, 0, fusedNodes, fusedPrims);
-                    fusedClosest++;
-                    if (__float_as_int(h.w) < 0) {
-                        // the continuation leaves the scene: what the escaped branch above would do with it at the slot's next visit
-                        survives = false;
-                        finished = true;
-                        black = isnan(sum3(throughput) + sum3(em));
-                    } else {
-                        slotF4<SNT>(st, A_HIT, slot) = h;
-                        haveHit = true;
-                    }
-                }
-                traced = haveHit ? (traced | (1u << turn)) : (traced & ~(1u << turn));
-            }
             PROF(15);
           }
         }
@@ -2063,17 +1992,6 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
         bool regenerated = false;
         if constexpr (FUSE != 0)
             regenerated = nextPath<true, (M & FEAT_QMC) != 0, SNT>(s, st, pp, finished, false, slot, em, black, &L.cursor, aborted, finishedCount);
-        if constexpr (AHEAD) {
-            if (regenerated) {                   // the camera ray nextPath just wrote: traced now, its hit (or miss: the next visit ends the path) stored
-                const float4 ro = slotF4<SNT>(st, A_RAY_O, slot), rd = slotF4<SNT>(st, A_RAY_D, slot);
-                RayD r1;
-                r1.o = xyz(ro); r1.d = xyz(rd); r1.tmin = ro.w; r1.tmax = rd.w;
-                const float4 h = traverseClosest<true, true, shadeKinds(M)>(sg, r1, nullptr, 0, fusedNodes, fusedPrims);
-                fusedClosest++;
-                slotF4<SNT>(st, A_HIT, slot) = h;
-                traced |= 1u << turn;
-            }
-        }
         PROF(7);
         if (DIRECT) {
             if (finished && !regenerated) idle |= 1u << turn;   // the work items ran out: nothing left for this slot
@@ -2641,7 +2559,7 @@ __global__ WIDE_SHADOW_BOUNDS void k_trace_shadow_wide(DeviceScene s, PathState 
                 float4 r0, r1, r2;
             WideNodeRegs nd;
                 if (hasRec) { r0 = at32(s.recs, recIdx*3u + 0u); r1 = at32(s.recs, recIdx*3u + 1u); r2 = at32(s.recs, recIdx*3u + 2u); }
-                if (hasNode) wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, nodeIdx), wr);
+                if (hasNode) wideNodeFetch(nd, reinterpret_cast<const char *>(s.wide), wideNodeOff(s, nodeIdx));
                 bool rayDone = false;
                 if (hasRec) {
                     if (COUNT) prims++;
@@ -2690,7 +2608,7 @@ __global__ WIDE_SHADOW_BOUNDS void k_trace_shadow_wide(DeviceScene s, PathState 
                     float4 q0 = p[0], q1 = p[1], q2 = p[2];
                     if (what == 2) {
                         WideNodeRegs nd;
-                        wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, wr, q0, q1, q2);
+                        wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, q0, q1, q2);
                         if (COUNT) nodes++;
                         // (INST: no far distance for the nodes -- what the reference clips against the ray's farT is the box of an instance's
                         // leaf in ITS tree, tested at the record below; the geometry behind it, and so these boxes, may begin beyond farT)
@@ -2756,7 +2674,7 @@ __global__ WIDE_SHADOW_BOUNDS void k_trace_shadow_wide(DeviceScene s, PathState 
 //     once the queue is dry, in the turn they finish), so their loads fly together and once per refill instead of once per turn;
 //   * the walk is the DECOUPLED one of k_trace_closest_wide: a pending record AND the next node per turn.
 // Same queues, same suspended-walk protocol (Q_HOLD), same results as k_trace_shadow_wide.
-template<bool COUNT, bool SOLIDS, int NTS = PT_NT_TRAV, bool INST = false>
+template<bool COUNT, bool SOLIDS, int NTS = PT_NT_STATE, bool INST = false>
 PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const PassParams &pp, BlockLds &L, uint32_t &fetchNext, int *ldsDyn)
 {
     unsigned short *order = reinterpret_cast<unsigned short *>(ldsDyn);
@@ -2767,14 +2685,6 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
     const unsigned long long wpStart = COUNT ? wall_clock64() : 0ull;
     uint32_t turns = 0, dryTurns = 0;
     const uint32_t appendMask = (1u << Q_FIN) | (!INST && st.suspend_lanes != 0u ? (1u << Q_EXT) | (1u << Q_HOLD) : 0u);
-    // the top of the tree in LDS, behind the stacks (PathState::lds_nodes; queuesBegin's barriers publish the copy)
-    const uint32_t topCount = st.lds_nodes;
-    const char *ldsTop = reinterpret_cast<const char *>(ldsDyn) + st.slots_per_block*2u + st.wide_depth*blockDim.x*8u;
-    {
-        float4 *dst = reinterpret_cast<float4 *>(const_cast<char *>(ldsTop));
-        for (uint32_t i = threadIdx.x; i < topCount*s.wide_stride/16u; i += blockDim.x)
-            dst[i] = s.wide[i];
-    }
     queuesBegin(L, st, ctl, Q_SHADOW, appendMask, order);
     const uint32_t n = L.n;
     const uint32_t first = blockIdx.x*st.slots_per_block;
@@ -2828,7 +2738,6 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
         if (!resume) wideStart(w);
         return true;
     };
-#if PT_SHADOW_PREP
     // Round 6: the slot's SECOND ray is prepared when the slot is fetched, not when its first ray ends.  "On to the second ray" used to run tryRay --
     // the quad test with its division, the three divisions of the reciprocal direction, ~110 instructions -- inside the loop for the two to five
     // lanes whose first ray had just ended, in nearly every turn of the wave; with eight or fewer lanes enabled a VALU instruction issues at a quarter
@@ -2873,25 +2782,12 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
         busy = (done && !second) ? false : busy;
         pendingFinish = (done && !second) ? true : pendingFinish;
     };
-#else
-    // ray r is done: on to the slot's second ray, or the slot is finished (its NEE term is added at the next refill)
-    auto nextRay = [&](bool done) {
-        if (!done) return;
-        if (r == 0) {
-            r = 1;
-            if (tryRay(c1, d1, false))
-                return;
-        }
-        busy = false;
-        pendingFinish = true;
-    };
-#endif
 
     for (;;) {
         unsigned long long busyMask = __ballot(busy);
         const bool refill = !exhausted && __popcll(busyMask) <= PT_REFILL_AT;
         const unsigned long long pendMask = __ballot(pendingFinish);   // (after the queue ran dry: more than eight lanes at a time, traceClosestWideBody)
-        if (pendMask != 0ull && (refill || (exhausted && (!PT_LATE_PUBLISH || __popcll(pendMask) > 8 || busyMask == 0ull)))) {
+        if (pendMask != 0ull && (refill || (exhausted && (__popcll(pendMask) > 8 || busyMask == 0ull)))) {
             WALK_SECTION(wpPubs, wpPubLanes, pendingFinish);
             if (pendingFinish) {
                 // NEE term -> path radiance; paths that ended at this vertex go on the finished list
@@ -2936,13 +2832,8 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
                         slots++;
                         result = splat3(0.0f);
                         r = 0;
-#if PT_SHADOW_PREP
                         prepareSecond(true);
                         nextRay(!tryRay(c0, d0, false));
-#else
-                        if (!tryRay(c0, d0, false))
-                            nextRay(true);
-#endif
                     } else {
                         walkRestore(st, slot, w, stack, stride);
                         if (COUNT) wpResumed++;
@@ -2950,9 +2841,7 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
                         result = xyz(part); r = __float_as_int(part.w);
                         slotW(st, A_SH_O, slot, 3u) = eps;                   // (an ordinary shadow slot again)
                         (void)tryRay(r == 0 ? c0 : c1, r == 0 ? d0 : d1, true);
-#if PT_SHADOW_PREP
                         prepareSecond(false);    // (a resumed first ray: its slot's second ray was counted when the slot was first fetched)
-#endif
                     }
                 }
             }
@@ -3016,7 +2905,7 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
                     float4 q0 = p[0], q1 = p[1], q2 = p[2];
                     if (what == 2) {
                         WideNodeRegs nd;
-                        wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, wr, q0, q1, q2);
+                        wideNodeFetchRest(nd, reinterpret_cast<const char *>(s.wide), off, q0, q1, q2);
                         if (COUNT) nodes++;
                         // (no far distance for the nodes -- what the reference clips against the ray's farT is the box of an instance's leaf in ITS
                         // tree, tested at the record below; the geometry behind it, and so these boxes, may begin beyond farT)
@@ -3064,7 +2953,7 @@ PT_DEV void traceShadowFastBody(const DeviceScene &s, const PathState &st, const
                 hasNode = wideNextNode(w, wr.octInv, stack, stride, nodeIdx);
             float4 r0, r1, r2;
             WideNodeRegs nd;
-            PT_WALK_FETCH(s, st, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx, wr, topCount, ldsTop);
+            PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
             WALK_SECTION(wpRecTurns, wpRecLanes, hasRec);       // (inside `if (busy)`: the ballot covers the lanes that are here)
             WALK_SECTION(wpNodeTurns, wpNodeLanes, hasNode);
             bool rayDone = false;
@@ -3122,13 +3011,13 @@ __global__ WIDE_SHADOW_BOUNDS void k_trace_shadow_fast_inst(DeviceScene s, PathS
     extern __shared__ int ldsDyn[];
     __shared__ BlockLds L;
     __shared__ uint32_t fetchNext;
-    traceShadowFastBody<COUNT, SOLIDS, PT_NT_OTHER, true>(s, st, pp, L, fetchNext, ldsDyn);
+    traceShadowFastBody<COUNT, SOLIDS, 0, true>(s, st, pp, L, fetchNext, ldsDyn);
 }
 
 // Second half of the dynamic-fetch shadow step: finalises the paths that had ended at the vertex whose shadow rays
 // k_trace_shadow_dyn just resolved (Q_FIN), regenerates their slots and reports whether the workgroup has extension
 // rays for the next iteration (returned; BlockCtl::live_slots = how many of its slots still carry a path).
-template<int NTS, bool EXT>
+template<int NTS>
 PT_DEV bool finishBody(const DeviceScene &s, const PathState &st, const PassParams &pp, BlockLds &L, unsigned short *order)
 {
     BlockCtl &ctl = st.ctl[blockIdx.x];
@@ -3151,7 +3040,7 @@ PT_DEV bool finishBody(const DeviceScene &s, const PathState &st, const PassPara
             em = xyz(slotF4<NTS>(st, A_EMI, sl));
             black = FLAG_STATE(__float_as_uint(slotW(st, A_SH_P, sl, 3u))) == ST_TERMINATED_BLACK;
         }
-        bool regenerated = nextPath<true, EXT, NTS>(s, st, pp, fin, false, sl, em, black, &L.cursor, aborted, finishedCount);
+        bool regenerated = nextPath<true, true, NTS>(s, st, pp, fin, false, sl, em, black, &L.cursor, aborted, finishedCount);
         queuePush(regenerated, loc, L, Q_EXTP);
     }
     waveAddStat(&L.samples, finishedCount);
@@ -3209,7 +3098,7 @@ __global__ __launch_bounds__(256) void k_tail(DeviceScene s, PathState st, PassP
     __shared__ __attribute__((aligned(16))) unsigned char ldsTables[PT_LDS_TABLE_BYTES];
     __shared__ unsigned short order[PT_MAX_SLOTS_PER_BLOCK];
     const DeviceScene staged = stageSceneTables(s, ldsTables);   // (for the shading steps; the traversal steps read the scene's big arrays only)
-    constexpr int TNT = PT_NT_TAIL ? PT_NT_STATE : 0;            // (a tail workgroup re-reads what it wrote a few microseconds ago: plain stores)
+    constexpr int TNT = 0;                                       // (a tail workgroup re-reads what it wrote a few microseconds ago: plain stores)
     for (;;) {
         traceClosestWideBody<false, SOLIDS, false, true, TNT>(s, st, L, fetchNext, ldsDyn);
         __syncthreads();

@@ -183,8 +183,6 @@ struct tghip_ctx {
     int classStreamsOpt = 0;              // measured: 735-800 Msamples/s against 825-830 with the classes one after the other on the part's stream
     hipStream_t launchStream = nullptr;   // where the launch helpers put their kernels (stream, or the stream of the part being launched)
     hipEvent_t evPart[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, evMain = nullptr;
-    hipEvent_t evRot[8] = {};             // "rotate_streams": the end of a part's last iteration (the part's next one runs on another stream)
-    bool rotateStreamsOpt = false;        // "rotate_streams" option (runBatch)
     int streamsOpt = 0;                   // "streams": 1 .. 4 parts of the pool on as many streams, 0 = the measured default (four for single-level
                                           // BVH scenes; instanced scenes lose 2.5 % with two)
     hipDeviceProp_t prop;
@@ -215,16 +213,14 @@ struct tghip_ctx {
     bool mediaSimple = false;             // a media scene whose surface BSDFs MASK_MEDIA covers (no instances, no mesh emitters)
     bool mediaLeanOpt = true;             // "media_lean": shade such scenes with k_shade<MASK_MEDIA> instead of <BSDF_MASK_ALL>
     bool foldFinishOpt = true;            // "fold_finish"
-    bool finishLeanOpt = false;           // "finish_lean" = 1: the folded finish of flag-less passes through nextPath's lean variant -- measured SLOWER (profiles/r6_ab_finish_lean.txt), off
     bool topTreeOpt = true;               // "top_tree": 0 = ignore TgHipSceneDesc::top_nodes at the next upload (flat lists walked in record order: faster, not the reference's ties)
     bool mergeMissOpt = true;             // "merge_miss"
     bool tailOpt = true;
     long long tailThreshold = 8192;
-    int shadeLdsPad = 0;                  // "shade_lds_pad": bytes of unused dynamic LDS per k_shade workgroup (an occupancy throttle for experiments: profiles/r6_ab_shade_occupancy.txt)
     bool instShadowFast = true;           // "inst_shadow_fast": instanced scenes' shadow rays on k_trace_shadow_fast_inst (0: k_trace_shadow_wide<., ., INST>)
     bool instShadowJoin = true;           // "inst_shadow_join": 0 = the instanced wide shadow kernel without PT_TURN_JOIN (the miscompiled variant; repro tool only)
     bool failReduce = false;              // "fail_reduce" option (fault injection for the reduce's callers)
-    int wideStride = int(PT_WIDE_NODE_BYTES);   // bytes per device node: 128 (pt_kernels.h: PT_WIDE_HALF); the byte layout also takes 80 ("wide_node_stride" option, at the next upload)
+    int wideStride = int(PT_WIDE_NODE_BYTES);   // bytes per device node: 80 (TgHipWideNode), or 128 -- a cache line each ("wide_node_stride" option, at the next upload)
     uint32_t width = 0, height = 0;
 
     // framebuffer
@@ -239,7 +235,7 @@ struct tghip_ctx {
     TgHipSampleRecord *dRecords = nullptr;   // SampleRecords, ceil(W/4) x ceil(H/4)
     float *lum = nullptr;                 // per-sample luminance of the running pass
     size_t lumCap = 0;
-    std::vector<uint32_t> hostRecLum, hostRecIndex, hostRecCount, hostSorted, hostChunkStart, hostHint;
+    std::vector<uint32_t> hostRecLum, hostRecIndex, hostRecCount, hostSorted, hostChunkStart;
     uint32_t *dSorted = nullptr, *dChunkStart = nullptr, *dHint = nullptr;   // gap-free item enumeration of record passes
     size_t sortedCap = 0, chunkStartCap = 0, hintCap = 0;
     std::vector<uint32_t> hostBucket, hostSortTmp;   // counting sort of the owned records by sample count
@@ -321,12 +317,10 @@ struct tghip_ctx {
     bool fuseFlatOpt = true;              // "fuse_flat": flat-list scenes without forward lobes trace + shadow-test inside k_shade
     // "suspend_lanes" / "suspend_turns" / "suspend_min_queue" (PathState::suspend_*): walk time-slicing of the wide traversal kernels
     int suspendLanes = 12, suspendTurns = 16, suspendMinQueue = 1024;   // (measured, profiles/README.md: materialtest +0.5 %, mesh1m +4 % over none; round 5 on the final kernels, r5_sweep_final_kernels.txt: 12 lanes +0.5 % / +1 % over 16, 8 lanes +0.8 % / -3 %)
-    int ldsNodesOpt = 0;                  // "lds_nodes": nodes of the top of the wide tree kept in LDS by those kernels (9 / 73 / 585 = two / three / four levels; measured: no gain)
     uint32_t numWideNodes = 0;
     int decoupleOpt = 1;                  // "decouple": the wide kernels of single-level scenes test a record AND visit a node per turn (k_trace_closest_wide<.., DECOUPLED>)
     int leafBatch = 1;                    // "leaf_batch" (PathState::leaf_batch)
     int leafBatchBvh2 = 0;                // "leaf_batch_bvh2" (PathState::leaf_batch_bvh2); 0 = leaf_batch, or the measured value for two-level scenes
-    bool poolRecords = false;             // "pool_layout" option: 1 = slot records (PathState::records)
     long long poolPad = 9472;             // bytes between the per-slot arrays of the pool (multiple of 16)
     bool dynamicFetch = true;             // BVH scenes: closest-hit kernel with dynamic ray fetch (k_trace_closest_dyn)
     bool timeKernels = false;             // HIP events around every launch of the wavefront loop (bench.py roofline)
@@ -577,17 +571,9 @@ static size_t dynLdsBytes(const tghip_ctx *ctx, int threads)
 }
 
 // the wide kernels: expanded queue + one 8-byte group entry per tree level and thread
-// nodes of the top of the wide tree the DECOUPLED kernels keep in LDS (PathState::lds_nodes): whole levels of the breadth-first array
-static uint32_t ldsNodeCount(const tghip_ctx *ctx)
-{
-    if (!PT_LDS_TOP || !ctx->decoupleOpt || ctx->haveInstances || ctx->ldsNodesOpt == 0) return 0u;   // (PT_LDS_TOP = 0, the product: the option is accepted and has no effect)
-    const uint32_t n = ctx->scene.wide ? ctx->numWideNodes : 0u;
-    return std::min<uint32_t>(n, uint32_t(ctx->ldsNodesOpt));
-}
 static size_t wideLdsBytes(const tghip_ctx *ctx, int threads)
 {
-    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->wideDepth, 1))*size_t(threads)*sizeof(uint2)
-         + size_t(ldsNodeCount(ctx))*size_t(ctx->wideStride);
+    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->wideDepth, 1))*size_t(threads)*sizeof(uint2);
 }
 
 // k_trace_closest_instw: expanded queue + the BVH2 stack of the scene's tree and the reference's tree over the instances (no master on it) + the
@@ -716,7 +702,7 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     const uint32_t slots = perBlock*grid;
     PathState &p = ctx->pool;
     // the walk arrays behind the A_* ones (suspended walks of the wide kernels, PathState::walk_base): only where they fit the 32-bit offsets
-    uint32_t walkArrays = useWide(ctx) && !ctx->haveInstances && !ctx->poolRecords ? 4u + uint32_t(ctx->wideDepth + 1)/2u : 0u;
+    uint32_t walkArrays = useWide(ctx) && !ctx->haveInstances ? 4u + uint32_t(ctx->wideDepth + 1)/2u : 0u;
     if (ctx->poolSlots >= slots && ctx->poolGrid == grid && (ctx->poolWalkWanted == walkArrays || ctx->poolWalkArrays >= walkArrays)) {
         p.num_slots = slots;
         p.slots_per_block = perBlock;
@@ -737,17 +723,12 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     if (strideBytes*groupArrays >= (1ull << 32)) { ctx->error = "path pool too large for 32-bit slot offsets within an array group"; return TGHIP_E_INVALID; }
     if (A_COUNT + walkArrays > groupArrays*PT_POOL_GROUPS) walkArrays = 0;
     ctx->poolWalkArrays = walkArrays;
-    const uint64_t recordBytes = uint64_t(slots)*336u + 256u;   // the record layout: 128 + 128 + 80 bytes per slot
-    const bool records = ctx->poolRecords && recordBytes < (1ull << 32);
     char *poolBase = nullptr;
-    if ((rc = allocArray(ctx, ctx->poolMem, size_t(std::max<uint64_t>(strideBytes*(A_COUNT + walkArrays), records ? recordBytes : 0)), &poolBase)) != TGHIP_OK) return rc;
+    if ((rc = allocArray(ctx, ctx->poolMem, size_t(strideBytes*(A_COUNT + walkArrays)), &poolBase)) != TGHIP_OK) return rc;
     for (uint32_t g = 0; g < PT_POOL_GROUPS; ++g)
         p.poolg[g] = poolBase + size_t(g)*size_t(groupArrays)*size_t(strideBytes);   // (groups past the last array are never addressed)
     p.walk_base = A_COUNT;
     p.stride = uint32_t(strideBytes);
-    p.records = records ? 1u : 0u;
-    p.rec_shadow = uint32_t(uint64_t(slots)*128u + 128u);
-    p.rec_aux = uint32_t(uint64_t(slots)*256u + 256u);
     POOL_ALLOC(bm, size_t(slots/32)*Q_COUNT);
     p.bmStride = slots/32;
     POOL_ALLOC(ctl, grid); POOL_ALLOC(stats, grid); POOL_ALLOC(live, 4);
@@ -906,7 +887,6 @@ tghip_ctx *tghip_create(int device_ordinal)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evPart[k], hipEventDisableTiming);
     for (int k = 0; k < 8; ++k) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evFork[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evRot[k], hipEventDisableTiming);
         for (int a = 0; a < 2; ++a)
             if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evJoin[k][a], hipEventDisableTiming);
     }
@@ -965,7 +945,6 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->evMain) (void)hipEventDestroy(ctx->evMain);
     for (int k = 0; k < 8; ++k) {
         if (ctx->evFork[k]) (void)hipEventDestroy(ctx->evFork[k]);
-        if (ctx->evRot[k]) (void)hipEventDestroy(ctx->evRot[k]);
         for (int a = 0; a < 2; ++a) {
             if (ctx->evJoin[k][a]) (void)hipEventDestroy(ctx->evJoin[k][a]);
             if (ctx->classStream[k][a]) (void)hipStreamDestroy(ctx->classStream[k][a]);
@@ -1020,7 +999,6 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     }
     else if (k == "inst_simple") ctx->instSimpleOpt = value != 0;
     else if (k == "inst_dyn") { ctx->instDynOpt = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "shade_lds_pad") ctx->shadeLdsPad = int(std::min<long long>(std::max<long long>(value, 0), 120*1024));
     else if (k == "inst_shadow_fast") { ctx->instShadowFast = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
     else if (k == "inst_wide") { ctx->instWideOpt = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
     else if (k == "inst_phase_min") ctx->instPhaseMin = int(std::min<long long>(std::max<long long>(value, 1), 64));
@@ -1038,28 +1016,19 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "tail_family") ctx->tailFamilyOpt = value != 0;
     else if (k == "hoist_quad") { ctx->hoistOpt = value != 0; if (!ctx->hoistOpt) ctx->scene.hoisted_rec = -1; else ctx->scene.hoisted_rec = ctx->hoistedRecScene; }
     else if (k == "merge_miss") ctx->mergeMissOpt = value != 0;
-    else if (k == "rotate_streams") ctx->rotateStreamsOpt = value != 0;
     else if (k == "fold_finish") ctx->foldFinishOpt = value != 0;
-    else if (k == "finish_lean") ctx->finishLeanOpt = value != 0;
     else if (k == "top_tree") ctx->topTreeOpt = value != 0;
     else if (k == "lds_tables") ctx->tablesFit = ctx->tablesFitScene && value != 0;
     else if (k == "env_lds") ctx->scene.env_tex = value != 0 ? ctx->envTexScene : -1;
     else if (k == "media_lean") ctx->mediaLeanOpt = value != 0;
     else if (k == "tail_threshold") ctx->tailThreshold = value;
-    else if (k == "lds_nodes") ctx->ldsNodesOpt = int(std::min<long long>(std::max<long long>(value, 0), 585));
+    else if (k == "lds_nodes") {}   // (accepted, no effect: the top of the wide tree in LDS was measured without gain and is gone, profiles/r5_ab_walk_fetch.txt)
     else if (k == "leaf_batch") ctx->leafBatch = int(std::min<long long>(std::max<long long>(value, 1), 64));
     else if (k == "fuse_flat") ctx->fuseFlatOpt = value != 0;
     else if (k == "run_to_completion") ctx->loopOpt = value != 0;
-    else if (k == "pool_layout") {
-#ifdef PT_POOL_RECORDS_RUNTIME
-        ctx->poolRecords = value != 0; ctx->poolMem.release(); ctx->poolSlots = 0;
-#else
-        if (value != 0) { ctx->error = "pool_layout = 1 needs a build with -DPT_POOL_RECORDS_RUNTIME (the record layout was measured and not adopted)"; return TGHIP_E_UNSUPPORTED; }
-#endif
-    }
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
-        if (value != 128 && (PT_WIDE_HALF || value != 80)) { ctx->error = PT_WIDE_HALF ? "wide_node_stride is 128 (half-plane nodes)" : "wide_node_stride is 80 or 128"; return TGHIP_E_INVALID; }
+        if (value != 128 && value != 80) { ctx->error = "wide_node_stride is 80 or 128"; return TGHIP_E_INVALID; }
         ctx->wideStride = int(value);
     }
     else if (k == "wide_closest") { ctx->wideClosestOpt = value < 0 ? -1 : value != 0; if (ctx->haveScene) chooseThreads(ctx); }
@@ -1169,38 +1138,13 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
             char *p = nullptr;
             HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&p), nodeBytes + recBytes));
             ctx->sceneMem.allocs.push_back(p);
-#if PT_WIDE_HALF
-            static_assert(sizeof(TgHipWideNode) == 80 && offsetof(TgHipWideNode, qlo) == 32 && offsetof(TgHipWideNode, qhi) == 56, "TgHipWideNode layout");
-            // the device's node: the ABI's header, then the 48 child planes as halfs, one 16-byte row per axis and side (pt_kernels.h)
-            {
-                auto half = [](uint32_t q) -> uint16_t {          // the integer q <= 255 as an IEEE half (exact)
-                    if (q == 0u) return uint16_t(0);
-                    const uint32_t e = 31u - uint32_t(__builtin_clz(q));
-                    return uint16_t(((e + 15u) << 10) | ((q << (10u - e)) & 0x3FFu));
-                };
-                std::vector<unsigned char> dev(size_t(sd->num_wide_nodes)*stride, 0);
-                for (uint32_t i = 0; i < sd->num_wide_nodes; ++i) {
-                    const TgHipWideNode &n = sd->wide_nodes[i];
-                    unsigned char *d = dev.data() + size_t(i)*stride;
-                    std::memcpy(d, &n, 32);
-                    uint16_t *rows = reinterpret_cast<uint16_t *>(d + 32);
-                    for (int a = 0; a < 3; ++a)
-                        for (int sl = 0; sl < 8; ++sl) {
-                            rows[a*8 + sl] = half(n.qlo[a][sl]);
-                            rows[24 + a*8 + sl] = half(n.qhi[a][sl]);
-                        }
-                }
-                HIP_TRY(ctx, hipMemcpy(p, dev.data(), dev.size(), hipMemcpyHostToDevice));
-            }
-#else
             HIP_TRY(ctx, hipMemcpy2DAsync(p, stride, sd->wide_nodes, sizeof(TgHipWideNode), sizeof(TgHipWideNode), sd->num_wide_nodes, hipMemcpyHostToDevice, ctx->stream));
-#endif
             HIP_TRY(ctx, hipMemcpyAsync(p + nodeBytes, sd->recs, size_t(sd->num_recs)*sizeof(TgHipPrimRec), hipMemcpyHostToDevice, ctx->stream));
             // The scene's one quad, hoisted out of the decoupled walks (pt_scene.h: DeviceScene::hoisted_rec): a single-level scene of triangles and
             // exactly ONE quad whose wide nodes leave `reserved` zero.  The wide node that holds the quad as a leaf record gets the record's bit of
             // leaf_valid in its `reserved` word -- on the device copy only; the sequential walks (tghip_trace_rays, "decouple" = 0) do not read it.
             s.hoisted_rec = -1; ctx->hoistedRecScene = -1;
-            if (!PT_WIDE_HALF && sd->num_instances == 0) {
+            if (sd->num_instances == 0) {
                 int64_t quad = -1;
                 bool ok = true;
                 for (uint32_t i = 0; i < sd->num_recs && ok; ++i) {
@@ -1568,7 +1512,7 @@ static void launchShadeVariant(tghip_ctx *ctx, int grid, const PathState &st, co
         return;
     }
     hipLaunchKernelGGL((k_shade<M, ((B == MASK_SIMPLE || B == MASK_SIMPLE_INST) ? SIMPLE_WAVES : B == MASK_LEAN ? LEAN_WAVES : B == MASK_COAT ? COAT_WAVES : 2), FUSE>), dim3(grid),
-                       dim3((M == BSDF_MASK_ALL || M == MASK_MEDIA) ? ctx->thrShadeAll : (cls >= 1 && cls < PT_NUM_CLASSES) ? ctx->thrShadeComplex : ctx->thrShadeSimple), size_t(ctx->shadeLdsPad), ctx->launchStream, ctx->scene, st, pp, cls);
+                       dim3((M == BSDF_MASK_ALL || M == MASK_MEDIA) ? ctx->thrShadeAll : (cls >= 1 && cls < PT_NUM_CLASSES) ? ctx->thrShadeComplex : ctx->thrShadeSimple), 0, ctx->launchStream, ctx->scene, st, pp, cls);
 }
 // TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS passes run the FEAT_QMC twin of the variant the scene would use anyway
 template<uint32_t M, int FUSE = 0>
@@ -1667,8 +1611,6 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     st.inst_phase_min = uint32_t(ctx->instPhaseMin);
     st.inst_refill_at = uint32_t(ctx->instRefillAt);
     st.nee_factors = (ctx->haveForward || ctx->haveMeshLight) ? 1u : 0u;   // launchShadow: the closest-hit shadow walk, k_trace_shadow<., FORWARD>
-    st.lds_nodes = ldsNodeCount(ctx);
-    st.wide_depth = uint32_t(std::max(ctx->wideDepth, 1));
     st.suspend_lanes = ctx->poolWalkArrays ? uint32_t(ctx->suspendLanes) : 0u;
     st.suspend_turns = uint32_t(std::max(ctx->suspendTurns, 1));
     st.suspend_min_queue = uint32_t(ctx->suspendMinQueue);
@@ -1707,7 +1649,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     // (materialtest 1280x720x256 / mesh1m 1920x1080x32 on one box: 2 parts 656 / 398 Msamples/s, 4 parts 666 / 412)
     // (instanced scenes: two parts in rounds 2-3; with the walk of the reference's instance tree four are 5 % faster -- profiles/r4_sweep_instances10k.jsonl)
     int parts = ctx->streamsOpt >= 2 ? ctx->streamsOpt : (ctx->streamsOpt == 1 || ctx->shortBatch) ? 1 : (!ctx->haveInstances || ctx->blocksPerCu >= 8) ? 4 : 1;
-    if (fused || flat || st.records || grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
+    if (fused || flat || grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
         parts = 1;
     const bool split = parts > 1;
     PathState stPart[8] = {st, st, st, st, st, st, st, st};
@@ -1745,7 +1687,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     // not see it: the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
     const bool tailEligible = ctx->tailOpt && !ctx->cameraFix && ctx->tablesFit && !flat && !ctx->haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt && !ctx->haveForward &&
                               (ctx->complexMask & TYPES_LATE) == 0 &&
-                              !ctx->haveMeshLight && !ctx->haveMedia && !ctx->auxPass && !ctx->haveCylinder && !count && !st.records &&
+                              !ctx->haveMeshLight && !ctx->haveMedia && !ctx->auxPass && !ctx->haveCylinder && !count &&
                               st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
     const uint64_t tailThreshold = uint64_t(std::max<long long>(ctx->tailThreshold, 0));
     // (k_tail runs 256 threads whatever the depth of the tree: it is used only where a workgroup of it fits a CU -- its static LDS plus
@@ -1794,14 +1736,9 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                     else                 { if (count) CLOSEST_WIDE(true, false, true, false); else CLOSEST_WIDE(false, false, true, false); }
                 } else if (ctx->decoupleOpt && foldFinish) {
                     // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
-#define CLOSEST_FIN(C, S, E) hipLaunchKernelGGL((k_finish_trace_closest_wide<C, S, E>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st, pp)
-                    // ("finish_lean" = 1, an experiment: passes without flags -- uniform sampler, no records, no auxiliary or per-sample output, pinhole, no media: the metric's --
-                    // finish through nextPath's lean variant, 4 220 instead of 6 436 instructions in the kernel; 0.45 % SLOWER on the metric, three alternations: the walk's
-                    // code around it comes out differently.  Off by default; profiles/r6_ab_finish_lean.txt)
-                    const bool leanFinish = ctx->finishLeanOpt && pp.flags == 0u && pp.rec_count == nullptr && !count;
-                    if (leanFinish)           { if (ctx->haveSolids) CLOSEST_FIN(false, true, false); else CLOSEST_FIN(false, false, false); }
-                    else if (ctx->haveSolids) { if (count) CLOSEST_FIN(true, true, true); else CLOSEST_FIN(false, true, true); }
-                    else                      { if (count) CLOSEST_FIN(true, false, true); else CLOSEST_FIN(false, false, true); }
+#define CLOSEST_FIN(C, S) hipLaunchKernelGGL((k_finish_trace_closest_wide<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st, pp)
+                    if (ctx->haveSolids) { if (count) CLOSEST_FIN(true, true); else CLOSEST_FIN(false, true); }
+                    else                 { if (count) CLOSEST_FIN(true, false); else CLOSEST_FIN(false, false); }
 #undef CLOSEST_FIN
                 } else if (ctx->decoupleOpt) {
                     if (ctx->haveSolids) { if (count) CLOSEST_WIDE(true, true, false, true); else CLOSEST_WIDE(false, true, false, true); }
@@ -1874,11 +1811,9 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 hipLaunchKernelGGL(k_finish, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp, iterTag);
         };
         // folded k_finish: the last iteration's finish as a launch of its own -- before the host reads the liveness word, before k_tail
-        int partStream[8] = {0, 1, 2, 3, 4, 5, 6, 7};   // the stream a part's last iteration ran on ("rotate_streams")
-        bool partRan[8] = {false, false, false, false, false, false, false, false};
         auto finishParts = [&](uint32_t tag) {
             for (int k = 0; k < parts; ++k)
-                hipLaunchKernelGGL(k_finish, dim3(grid/parts), dim3(256), 0, split ? streamOf[partStream[k]] : ctx->stream, s, split ? stPart[k] : st, split ? ppPart[k] : pp, tag);
+                hipLaunchKernelGGL(k_finish, dim3(grid/parts), dim3(256), 0, split ? streamOf[k] : ctx->stream, s, split ? stPart[k] : st, split ? ppPart[k] : pp, tag);
         };
     for (;;) {
         evUsed = 0;
@@ -1969,18 +1904,11 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 continue;
             }
             if (split) {
-                // "rotate_streams": part k's iteration i runs on stream (k + i) mod parts.  The hardware queues do not share the chip evenly --
-                // the parts on the queues served later run ~45 % longer launches (profiles/README.md: "by hardware queue") and finish their
-                // share of the work items last --; rotated, every part spends the same time on every queue.
+                // (rejected, round 5: part k's iteration i on stream (k + i) mod parts, so that every part spends the same time on every hardware
+                // queue: profiles/r5_sweep_rotate_streams.jsonl)
                 for (int k = 0; k < parts; ++k) {
-                    const int sIdx = ctx->rotateStreamsOpt ? int((uint32_t(k) + iterTag) % uint32_t(parts)) : k;
-                    ctx->launchStream = streamOf[sIdx];
-                    if (ctx->rotateStreamsOpt) {
-                        if (partRan[k]) (void)hipStreamWaitEvent(ctx->launchStream, ctx->evRot[k], 0);    // the part's previous iteration, on another stream
-                        partStream[k] = sIdx;
-                    }
+                    ctx->launchStream = streamOf[k];
                     launchIteration(stPart[k], ppPart[k], grid/parts, iterTag, true, k);
-                    if (ctx->rotateStreamsOpt) { (void)hipEventRecord(ctx->evRot[k], ctx->launchStream); partRan[k] = true; }
                 }
                 ctx->launchStream = ctx->stream;
             } else {
@@ -2184,7 +2112,7 @@ int tghip_wait(tghip_ctx *ctx)
     if (recordPass) {
         // Gap-free work items for uneven per-record sample counts (PassParams): owned records sorted by descending count,
         // chunk c covers the first chunkStart[c + 1] - chunkStart[c] pixel slots of that order.
-        std::vector<uint32_t> &sorted = ctx->hostSorted, &start = ctx->hostChunkStart, &hint = ctx->hostHint;
+        std::vector<uint32_t> &sorted = ctx->hostSorted, &start = ctx->hostChunkStart;
         const std::vector<uint32_t> &cnt = ctx->hostRecCount;
         sorted.clear();
         for (uint32_t r = 0; r < numRecords; ++r) {
@@ -2221,7 +2149,6 @@ int tghip_wait(tghip_ctx *ctx)
         // (the hint table -- for every 64 items the chunk their first one lies in, 230 k entries for a 16-spp pass at 720p -- is filled by a launch
         // from the chunk starts: building and uploading it here was a third of the host's set-up time between two passes)
         const size_t hintEntries = size_t((recordItems + 63)/64) + 1;
-        (void)hint;
         auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
             if (cap < src.size()) {
                 if (dev) (void)hipFree(dev);
