@@ -561,6 +561,9 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "cou
                                                                              shades as if the small tables did not fit the LDS copy, "env_lds" = 0 samples the
                                                                              environment map through its global tables, "hoist_quad" = 0 leaves a scene's one
                                                                              quad inside the walks, "tail_family" = 0 runs the all-types tail kernel.
+                                                                             "shade_fused" (default 1): single-level scenes with class 0 and one further shading
+                                                                             class shade an iteration in ONE launch (k_shade_fused); 0 = one launch per class, the
+                                                                             same image bit for bit.  TgHipCounters::launches_shade counts every shading launch.
                                                                              Round 6, instanced scenes: "inst_wide" = 0 walks masters through their BVH2 (round 5's
                                                                              kernel; images differ only where two triangles of a master answer a ray one rounding
                                                                              apart), "inst_phase_min" / "inst_refill_at" the phase vote's threshold and the refill

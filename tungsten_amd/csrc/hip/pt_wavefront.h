@@ -1440,11 +1440,21 @@ PT_DEV void auxPostLoop(const DeviceScene &s, f3 dir, bool asked, int bounce, fl
 // extension queues hold work -- the FUSE launches report it)
 // STAGED: sg's small tables are in LDS already (k_tail stages them once for all its iterations)
 // GLOBAL_TABLES: the scene's small tables do not fit the LDS copy (stageSceneTables): read them where they are
-template<uint32_t M, int FUSE, bool STAGED = false, bool GLOBAL_TABLES = false>
-PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassParams &pp, int cls, BlockLds &L, unsigned char *ldsTables, unsigned short *order)
+// PART: the body as one class phase of k_shade_fused (below), which shades two classes' queues in one launch through ONE set of LDS bitmaps.
+//   SHADE_FIRST  begins like a launch of its own (the appended bitmaps start empty) and leaves the write-back to the phase behind it;
+//   SHADE_LAST   keeps what the first phase appended, loads and expands its own input queues, and writes everything back once:
+//                its consumed queues and that of the first phase's class `clsFirst` (empty), the appended queues OR-ed into the global bitmaps.
+#define SHADE_WHOLE 0
+#define SHADE_FIRST 1
+#define SHADE_LAST  2
+template<uint32_t M, int FUSE, bool STAGED = false, bool GLOBAL_TABLES = false, int PART = SHADE_WHOLE>
+PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassParams &pp, int cls, BlockLds &L, unsigned char *ldsTables, unsigned short *order,
+                      int clsFirst = -1)
 {
-    // (the fused flat-list launches and k_tail -- STAGED -- re-read their slots within microseconds: no non-temporal hint there, pt_kernels.h)
-    constexpr int SNT = (FUSE != 0 || STAGED) ? 0 : PT_NT_STATE;
+    static_assert(PART == SHADE_WHOLE || (FUSE == 0 && STAGED), "the class phases of k_shade_fused are wavefront launches over staged tables");
+    // (the fused flat-list launches and k_tail -- STAGED -- re-read their slots within microseconds: no non-temporal hint there, pt_kernels.h;
+    // k_shade_fused's phases touch disjoint slots, each once, as the launches they replace do)
+    constexpr int SNT = (FUSE != 0 || (STAGED && PART == SHADE_WHOLE)) ? 0 : PT_NT_STATE;
     BlockCtl &ctl = st.ctl[blockIdx.x];
     // (CLS_MISS: the escaped paths.  CLS_0_AND_MISS: class 0, then the escaped paths -- one launch of the variant both run; the expanded list
     // keeps the two runs apart, so at most one wave per workgroup mixes surface shading with escaped paths)
@@ -1454,8 +1464,20 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
     // the wavefront launches (FUSE == 0) of the shading classes of one iteration run concurrently (runBatch): each consumes its own
     // queue, touches its own slots, and ORs what it appends into the workgroup's global bitmaps
     constexpr bool CONCURRENT = FUSE == 0;
-    queuesBegin(L, st, ctl, qIn, appendMask, order, qIn2, CONCURRENT);
-    if (CONCURRENT && L.n == 0u)
+    if constexpr (PART == SHADE_LAST) {
+        // (the first phase's queuesBegin left these two bitmaps empty in LDS; no phase pushes to a shading queue, and the barrier also
+        // tells that every wave is through with the first phase's order[] and L.n)
+        const uint32_t W = st.slots_per_block >> 5;
+        for (uint32_t wd = threadIdx.x; wd < W; wd += blockDim.x) {
+            L.bm[qIn][wd] = st.bm[(uint32_t)qIn*st.bmStride + blockIdx.x*W + wd];
+            L.bm[qIn2][wd] = st.bm[(uint32_t)qIn2*st.bmStride + blockIdx.x*W + wd];
+        }
+        __syncthreads();
+        queuesExpand(L, st, qIn, qIn2, order);
+    } else {
+        queuesBegin(L, st, ctl, qIn, appendMask, order, qIn2, CONCURRENT);
+    }
+    if (PART == SHADE_WHOLE && CONCURRENT && L.n == 0u)
         return false;                            // nothing of this class in the workgroup: no bitmap changes, nothing to write back
     const DeviceScene s = (STAGED || GLOBAL_TABLES) ? sg : stageSceneTables(sg, ldsTables);
     const uint32_t first = blockIdx.x*st.slots_per_block;
@@ -2020,6 +2042,14 @@ PT_DEV bool shadeBody(const DeviceScene &sg, const PathState &st, const PassPara
         waveAddStat(&L.shadow_rays, fusedShadow);
         waveAddStat(&L.prims, fusedPrims);
     }
+    if constexpr (PART == SHADE_FIRST)
+        return false;                            // (the phase behind this one writes the bitmaps back)
+    if constexpr (PART == SHADE_LAST) {
+        const uint32_t W = st.slots_per_block >> 5;
+        const uint32_t qFirst = (uint32_t)shadeQueue(clsFirst);
+        for (uint32_t wd = threadIdx.x; wd < W; wd += blockDim.x)
+            st.bm[qFirst*st.bmStride + blockIdx.x*W + wd] = 0u;   // consumed by the first phase
+    }
     const bool anyExt = queuesEnd(L, st, qIn, appendMask, qIn2, CONCURRENT);
     if (FUSE != 0 && threadIdx.x == 0) {         // (the wavefront launches neither regenerate nor finish samples: k_finish does)
         ctl.item_cursor = L.cursor;
@@ -2040,6 +2070,26 @@ __global__ __launch_bounds__(256, W) void k_shade(DeviceScene sg, PathState st, 
     __shared__ __attribute__((aligned(16))) unsigned char ldsTables[GLOBAL_TABLES ? 16u : PT_LDS_TABLE_BYTES];
     __shared__ unsigned short order[PT_MAX_SLOTS_PER_BLOCK];
     (void)shadeBody<M, FUSE, false, GLOBAL_TABLES>(sg, st, pp, cls, L, ldsTables, order);
+}
+// The shading of a whole iteration in one launch, for single-level scenes with class 0 and exactly ONE further class (the shim: shadeFusedPair): every
+// workgroup stages the scene tables once, shades its queue of the further class `clsFurther` with that class's variant MF, then its class-0 queue and
+// its escaped paths with the class-0 variant M0, and writes the queue bitmaps back once.  The two launches this replaces are independent -- disjoint
+// queues of disjoint slots -- but ran one after the other on the part's stream: a second table copy, a second queue prologue and epilogue, and a
+// drain in which the workgroups with a short queue of the first class idle.  Here a workgroup goes on to its next queue as soon as it is through
+// with the first; the one barrier between the phases is the one the shared order[] area needs.  The bodies keep their compile-time masks (the
+// phase is uniform per workgroup), so every slot runs the instructions it ran before.
+// Order: the further class first, always -- it is fixed by the scene, not by queue lengths.  Its BSDFs cost several times class 0's Lambert per
+// slot, so where it is present its phase is the long one, and the cheap class-0 / escaped-path phase fills the drain behind it.
+// W: that of the further class's variant (never more waves per SIMD than either body was built for).
+template<uint32_t MF, uint32_t M0, int W>
+__global__ __launch_bounds__(256, W) void k_shade_fused(DeviceScene sg, PathState st, PassParams pp, int clsFurther)
+{
+    __shared__ BlockLds L;
+    __shared__ __attribute__((aligned(16))) unsigned char ldsTables[PT_LDS_TABLE_BYTES];
+    __shared__ unsigned short order[PT_MAX_SLOTS_PER_BLOCK];
+    const DeviceScene s = stageSceneTables(sg, ldsTables);
+    (void)shadeBody<MF, 0, true, false, SHADE_FIRST>(s, st, pp, clsFurther, L, ldsTables, order);
+    (void)shadeBody<M0, 0, true, false, SHADE_LAST>(s, st, pp, CLS_0_AND_MISS, L, ldsTables, order, clsFurther);
 }
 
 // TraceBase::generalizedShadowRay (TraceBase.cpp:62-125) for the shadow rays queued by k_shade:

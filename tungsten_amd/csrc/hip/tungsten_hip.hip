@@ -50,6 +50,13 @@ extern template __global__ void k_shade<(MASK_FULL | FEAT_QMC), 2, 2>(DeviceScen
 extern template __global__ void k_shade<BSDF_MASK_ALL, 2, 0>(DeviceScene, PathState, PassParams, int);
 extern template __global__ void k_shade<MASK_MEDIA, 2, 0>(DeviceScene, PathState, PassParams, int);   // shade_media.hip
 extern template __global__ void k_shade<BSDF_MASK_ALL, 2, 0, true>(DeviceScene, PathState, PassParams, int);   // shade_global.hip
+// shade_fused.hip: one further class + class 0 and the escaped paths in one launch
+extern template __global__ void k_shade_fused<MASK_COAT, MASK_SIMPLE, COAT_WAVES>(DeviceScene, PathState, PassParams, int);
+extern template __global__ void k_shade_fused<(MASK_COAT | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), COAT_WAVES>(DeviceScene, PathState, PassParams, int);
+extern template __global__ void k_shade_fused<MASK_GLASS, MASK_SIMPLE, 2>(DeviceScene, PathState, PassParams, int);
+extern template __global__ void k_shade_fused<(MASK_GLASS | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), 2>(DeviceScene, PathState, PassParams, int);
+extern template __global__ void k_shade_fused<MASK_PLASTIC, MASK_SIMPLE, 2>(DeviceScene, PathState, PassParams, int);
+extern template __global__ void k_shade_fused<(MASK_PLASTIC | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), 2>(DeviceScene, PathState, PassParams, int);
 // k_tail: tail.hip
 // walk_shadow.hip (compiled without SLP vectorisation)
 extern template __global__ void k_trace_shadow_fast<false, false>(DeviceScene, PathState, PassParams, uint32_t);
@@ -315,6 +322,7 @@ struct tghip_ctx {
     int thrOverride[4] = {0, 0, 0, 0};
     bool loopOpt = true;                  // "run_to_completion": fused flat-list scenes whose materials are all of class 0 render in ONE launch
     bool fuseFlatOpt = true;              // "fuse_flat": flat-list scenes without forward lobes trace + shadow-test inside k_shade
+    bool shadeFusedOpt = true;            // "shade_fused": scenes with class 0 and one further class shade an iteration in ONE launch (k_shade_fused)
     // "suspend_lanes" / "suspend_turns" / "suspend_min_queue" (PathState::suspend_*): walk time-slicing of the wide traversal kernels
     int suspendLanes = 12, suspendTurns = 16, suspendMinQueue = 1024;   // (measured, profiles/README.md: materialtest +0.5 %, mesh1m +4 % over none; round 5 on the final kernels, r5_sweep_final_kernels.txt: 12 lanes +0.5 % / +1 % over 16, 8 lanes +0.8 % / -3 %)
     uint32_t numWideNodes = 0;
@@ -1025,6 +1033,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "lds_nodes") {}   // (accepted, no effect: the top of the wide tree in LDS was measured without gain and is gone, profiles/r5_ab_walk_fetch.txt)
     else if (k == "leaf_batch") ctx->leafBatch = int(std::min<long long>(std::max<long long>(value, 1), 64));
     else if (k == "fuse_flat") ctx->fuseFlatOpt = value != 0;
+    else if (k == "shade_fused") ctx->shadeFusedOpt = value != 0;
     else if (k == "run_to_completion") ctx->loopOpt = value != 0;
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
@@ -1543,6 +1552,30 @@ static void launchComplexClass(tghip_ctx *ctx, int grid, const PathState &st, co
     else                  launchShade<MASK_FULL, FUSE>(ctx, grid, st, pp, cls);
 }
 
+// The further class (1 .. 3) of a scene whose iterations shade in one launch of k_shade_fused, 0 for every other scene: single-level BVH scenes
+// whose tables fit the LDS copy, with class 0 and exactly ONE further class that one of the instantiated pairs covers, on the launch sequence the
+// pairs were built from (class 0 merged with the escaped paths, one stream per part).  Three or more classes, instanced scenes, media, auxiliary
+// outputs, cylinders, mesh emitters, lean scenes and flat lists keep their per-class launches.
+static int shadeFusedPair(const tghip_ctx *ctx)
+{
+    if (!ctx->shadeFusedOpt || isFlat(ctx) || ctx->haveInstances || ctx->haveMedia || ctx->auxPass || ctx->haveCylinder || ctx->haveMeshLight ||
+        ctx->leanScene || !ctx->tablesFit || !ctx->mergeMissOpt || ctx->classStreamsOpt != 0)
+        return 0;
+    int further = 0, n = 0;
+    for (int c = 1; c < PT_NUM_CLASSES; ++c)
+        if (ctx->classPresent[c]) { further = c; ++n; }
+    if (n != 1 || (further == 3 && (ctx->classMask[3] & ~MASK_PLASTIC) != 0))
+        return 0;
+    return further;
+}
+// (the workgroup size of the further class's launches: both phases run at it)
+template<uint32_t MF, int W>
+static void launchShadeFused(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int further)
+{
+    if (pp.flags) hipLaunchKernelGGL((k_shade_fused<(MF | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), W>), dim3(grid), dim3(ctx->thrShadeComplex), 0, ctx->launchStream, ctx->scene, st, pp, further);
+    else          hipLaunchKernelGGL((k_shade_fused<MF, MASK_SIMPLE, W>), dim3(grid), dim3(ctx->thrShadeComplex), 0, ctx->launchStream, ctx->scene, st, pp, further);
+}
+
 // true when the shadow step needs its second half, k_finish (the dynamic-fetch kernel does not regenerate paths itself)
 template<bool COUNT>
 static bool launchShadow(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, uint32_t iterTag)
@@ -1702,6 +1735,14 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     }
     // "fold_finish": k_finish rides in front of the next iteration's closest-hit launch (single-level scenes on the decoupled wide walk)
     const bool foldFinish = ctx->foldFinishOpt && !ctx->cameraFix && !flat && !ctx->haveInstances && wideClosest(ctx) && ctx->decoupleOpt;
+    const int fusedClass = shadeFusedPair(ctx);  // != 0: the iteration's shading is one launch of k_shade_fused
+    // shading launches of an iteration (per part): one for class 0 and the escaped paths (two when "merge_miss" = 0), one per further class
+    int shadeLaunches = 1;
+    if (!fusedClass) {
+        shadeLaunches = (ctx->classStreamsOpt != 0 || !ctx->mergeMissOpt) ? 2 : 1;
+        for (int c = 1; c < PT_NUM_CLASSES; ++c)
+            if (ctx->classPresent[c]) ++shadeLaunches;
+    }
     uint32_t iterTag = 1;                        // k_start publishes tag 1 when it queued anything
     bool first = true;
     int roundIters = checkInterval;              // launches of the wavefront loop between two host checks
@@ -1780,7 +1821,12 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 else launchComplexClass<0>(ctx, grid, st, pp, cls);
             };
             hipStream_t mainStream = ctx->launchStream;
-            if (ctx->classStreamsOpt != 0) {
+            if (fusedClass) {
+                // (class 0, the escaped paths and the scene's one further class in one launch: k_shade_fused, pt_wavefront.h)
+                if (fusedClass == 1)      launchShadeFused<MASK_COAT, COAT_WAVES>(ctx, grid, st, pp, fusedClass);
+                else if (fusedClass == 2) launchShadeFused<MASK_GLASS, 2>(ctx, grid, st, pp, fusedClass);
+                else                      launchShadeFused<MASK_PLASTIC, 2>(ctx, grid, st, pp, fusedClass);
+            } else if (ctx->classStreamsOpt != 0) {
                 hipStream_t *aux = ctx->classStream[part];
                 (void)hipEventRecord(ctx->evFork[part], mainStream);
                 const int nAux = ctx->haveComplex ? 2 : 1;
@@ -1844,7 +1890,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 const int perIter = parts;
                 ctx->counters.launches_trace_closest += roundIters*perIter;
                 ctx->counters.launches_trace_shadow += roundIters*perIter;
-                ctx->counters.launches_shade += roundIters*perIter;
+                ctx->counters.launches_shade += roundIters*perIter*shadeLaunches;   // (one event pair brackets them: ms_shade is their sum)
             }
             if (ctx->hostLive[0] != iterTag)
                 break;                           // the last iteration left every extension queue empty
