@@ -17,7 +17,7 @@ LIBNAME  := $(if $(PROFILE),libtungsten_hip_prof.so,$(if $(VARIANT),libtungsten_
 HOSTSRC  := $(wildcard tungsten_amd/csrc/host/*.cpp)
 HOSTLIB  := $(filter-out tungsten_amd/csrc/host/main.cpp,$(HOSTSRC))
 HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB))
-# the shim + one translation unit per family of k_shade instantiations (they compile in parallel under make -j)
+# the shim + one translation unit per family of k_shade instantiations (they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
 HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h

@@ -521,6 +521,29 @@ int tghip_upload_aux(tghip_ctx *ctx, const TgHipAuxPixel *in, size_t npixels);
 /* the per-sample radiance of the last TGHIP_PASS_SAMPLES pass: nfloats = W*H*(spp_end - spp_begin)*3, laid out
  * [pixel (row-major)][sample - spp_begin][rgb]; samples of pixels the pass's shard does not own are zero */
 int tghip_download_samples(tghip_ctx *ctx, float *rgb, size_t nfloats);
+/* Develops the frame where it lives: the images Integrator::writeBuffers and Camera::saveOutputBuffers put into files (integrators/Integrator.cpp:56-80,
+ * cameras/OutputBuffer.hpp:56-86, 134-189), computed by kernels of their own (csrc/hip/develop.hip) from the framebuffer -- the bound one when one is
+ * bound -- or from the auxiliary output buffers, bit for bit what the host computes from a download (tungsten_host.h: tgh_develop_host_frame / _aux).
+ *   source  TGHIP_DEVELOP_FRAME: mean = sum * (count ? 1 / count : 0); the 8-bit image is max(mean, 0) under one of the operators of
+ *           cameras/Tonemap.hpp:25-48 (powf as glibc computes it), times 255, converted as x86 converts (NaN and everything outside int32
+ *           become INT_MIN, so 0 -- not the 255 a saturating conversion gives), clamped to [0, 255];
+ *           a TGHIP_AUX_* output: part = the combined mean (a nA + b nB)/max(n, 1), the A or B half, or variance/(n max(1, n - 1)); the 8-bit image
+ *           as OutputBuffer::saveLdr makes it: depth divided by the image's largest entry that is not +inf (0 when there is none; a NaN never wins),
+ *           normals mapped from [-1, 1], the variance part and the other outputs as they are, a pixel whose channel average is NaN or infinite
+ *           white, one channel replicated to three; never tone-mapped (`tonemap` is ignored);
+ *   hdr_out 3 floats per pixel for the frame, the output's channel count (3, 1, 3, 3, 1) otherwise; ldr_out 3 bytes per pixel.  Either may be NULL.
+ *           Host memory, or with TGHIP_DEVELOP_DEVICE_POINTERS memory of the context's device (hdr_out 16-byte, ldr_out 4-byte aligned).
+ * Waits for the running pass like the download calls.  TGHIP_E_INVALID: NULL context or description, unknown source / part / operator, npixels != W*H,
+ * an aux source before any aux buffer exists, a part other than the mean of the frame.  TGHIP_E_UNSUPPORTED: the context's "develop_host" option is
+ * set -- the caller develops on the host (the host integrator does; its files are the same bytes either way). */
+enum { TGHIP_TONEMAP_LINEAR = 0, TGHIP_TONEMAP_GAMMA = 1, TGHIP_TONEMAP_REINHARD = 2, TGHIP_TONEMAP_FILMIC = 3, TGHIP_TONEMAP_PBRT = 4 };
+enum { TGHIP_DEVELOP_MEAN = 0, TGHIP_DEVELOP_A = 1, TGHIP_DEVELOP_B = 2, TGHIP_DEVELOP_VARIANCE = 3 };
+#define TGHIP_DEVELOP_FRAME 0xffffffffu       /* source: the framebuffer; otherwise a TGHIP_AUX_* output */
+#define TGHIP_DEVELOP_DEVICE_POINTERS 1u      /* flags: out pointers are device memory (a torch tensor) */
+typedef struct TgHipDevelopDesc { uint32_t source, part, tonemap, flags; } TgHipDevelopDesc;
+int tghip_develop(tghip_ctx *ctx, const TgHipDevelopDesc *desc, float *hdr_out, uint8_t *ldr_out, size_t npixels);
+/* Instrumentation: HIP-event time of the kernels of the context's last tghip_develop, in milliseconds (profiles/r8_develop.txt) */
+int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms);
 /* Multi-GPU framebuffer merge inside one process: ctxs[0..n) are the contexts (one per device, all with the same scene
  * uploaded) that rendered the tile shards 0..n-1 of a frame (TgHipPassDesc.shard_index/shard_count).  Their radiance sums
  * (float32) and sample counts (uint32) are sum-reduced by RCCL (ncclReduce over xGMI, one communicator per device, created at

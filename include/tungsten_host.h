@@ -71,6 +71,19 @@ int  tgh_renderer_records(tgh_renderer *r, TgHostSampleRecord *out, size_t n, ch
  * merged over its devices; all zero when the scene requests none */
 int  tgh_renderer_output_buffers(tgh_renderer *r, TgHipAuxPixel *out, size_t npixels, char *err, size_t errlen);
 
+/* One image of the renderer's output files (include/tungsten_hip.h: tghip_develop, TgHipDevelopDesc) into HOST arrays: developed on the device by a
+ * renderer on one device; by the host functions below over a download by a renderer sharded over several devices, or when the context's
+ * "develop_host" option is set -- the same bytes either way.  hdr_out: 3 floats per pixel for the frame, the output's channel count otherwise;
+ * ldr_out: 3 bytes per pixel; either may be NULL. */
+int  tgh_renderer_develop(tgh_renderer *r, const TgHipDevelopDesc *desc, float *hdr_out, uint8_t *ldr_out, size_t npixels, char *err, size_t errlen);
+/* the scene camera's "tonemap" as TGHIP_TONEMAP_* (-1: a name cameras/Tonemap.hpp does not know) */
+int  tgh_renderer_tonemap(tgh_renderer *r);
+/* The host's own development of a downloaded framebuffer / downloaded auxiliary buffers: the loops of Integrator::writeBuffers (integrators/
+ * Integrator.cpp:56-80) and OutputBuffer::save / saveLdr (cameras/OutputBuffer.hpp:56-86, 146-189) over plain arrays, no device.  What tghip_develop
+ * is held to, bit for bit.  tonemap: TGHIP_TONEMAP_*; output: TGHIP_AUX_*; part: TGHIP_DEVELOP_*.  -1 on an unknown operator / output / part. */
+int  tgh_develop_host_frame(const float *rgb_sum, const uint32_t *count, size_t npixels, uint32_t tonemap, float *hdr_out, uint8_t *ldr_out);
+int  tgh_develop_host_aux(const TgHipAuxPixel *aux, size_t npixels, uint32_t output, uint32_t part, float *hdr_out, uint8_t *ldr_out);
+
 /* The scheduler on its own (no device): tile seeds + generateWork over caller-supplied record statistics. */
 typedef struct tgh_scheduler tgh_scheduler;
 tgh_scheduler *tgh_scheduler_create(uint32_t width, uint32_t height, uint32_t seed);

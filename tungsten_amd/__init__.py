@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import (TgHipCounters, TgHipHit, TgHipPassDesc, TgHipRay, TgHipSceneDesc, TgHostSceneInfo)
+from .capi import (TgHipCounters, TgHipDevelopDesc, TgHipHit, TgHipPassDesc, TgHipRay, TgHipSceneDesc, TgHostSceneInfo)
 
 lib = capi.load_library()
 
@@ -22,6 +22,9 @@ AUX_DTYPE = np.dtype([("a", np.float32, 11), ("b", np.float32, 11), ("variance",
 RECORD_DTYPE = np.dtype([("sample_count", np.uint32), ("next_sample_count", np.uint32), ("sample_index", np.uint32),
                          ("adaptive_weight", np.float32), ("mean", np.float32), ("running_variance", np.float32)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
+TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
+DEVELOP_PART_NAMES = ("mean", "a", "b", "variance")                          # capi.TGHIP_DEVELOP_*
+AUX_OUTPUT_NAMES = ("color", "depth", "normal", "albedo", "visibility")      # capi.TGHIP_AUX_*
 
 
 class TungstenError(RuntimeError):
@@ -199,6 +202,48 @@ class Renderer(object):
 
     def save_outputs(self):
         self._check(lib.tgh_renderer_save_outputs(self._h, self._err, len(self._err)))
+
+    def _develop_desc(self, source, part, tonemap, flags=0):
+        src = capi.TGHIP_DEVELOP_FRAME if source == "frame" else AUX_OUTPUT_NAMES.index(source)
+        if tonemap is None:
+            op = lib.tgh_renderer_tonemap(self._h) if source == "frame" else 0
+            if op < 0:
+                raise TungstenError("the scene camera's tonemap operator is unknown")
+        else:
+            op = TONEMAP_NAMES.index(tonemap)
+        return capi.TgHipDevelopDesc(src, DEVELOP_PART_NAMES.index(part), op, flags)
+
+    def develop(self, source="frame", part="mean", tonemap=None, hdr=False):
+        """One image of the output files, developed on the device (tghip_develop): the 8-bit RGB image uint8 [H, W, 3], or with hdr=True the
+        float image [H, W, channels].  source: "frame" or an auxiliary output ("color", "depth", "normal", "albedo", "visibility"); part:
+        "mean", "a", "b", "variance" (the frame has its mean only); tonemap: "linear", "gamma", "reinhard", "filmic", "pbrt", None = the scene
+        camera's (the frame only: auxiliary outputs are never tone-mapped)."""
+        desc = self._develop_desc(source, part, tonemap)
+        channels = 3 if source == "frame" else capi.TGHIP_AUX_CHANNEL_COUNT[desc.source]
+        out = np.empty((self.height, self.width, channels), np.float32) if hdr else np.empty((self.height, self.width, 3), np.uint8)
+        self._check(lib.tgh_renderer_develop(self._h, C.byref(desc), out.ctypes.data if hdr else None, None if hdr else out.ctypes.data,
+                                             self.width*self.height, self._err, len(self._err)))
+        return out
+
+    def develop_into(self, ldr=None, hdr=None, source="frame", part="mean", tonemap=None, device=0):
+        """The same into torch tensors on the context's device, without a copy through the host: ldr uint8 [H, W, 3], hdr float32 [H, W, channels],
+        both contiguous; either may be None."""
+        desc = self._develop_desc(source, part, tonemap, capi.TGHIP_DEVELOP_DEVICE_POINTERS)
+        channels = 3 if source == "frame" else capi.TGHIP_AUX_CHANNEL_COUNT[desc.source]
+        for name, t, dtype, size in (("ldr", ldr, "torch.uint8", 3), ("hdr", hdr, "torch.float32", channels)):
+            if t is None:
+                continue
+            if str(t.dtype) != dtype:
+                raise TungstenError("develop_into: %s must be %s, not %s" % (name, dtype, t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("develop_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if not t.is_contiguous() or t.numel() != self.width*self.height*size:
+                raise TungstenError("develop_into: %s must be contiguous with %d x %d x %d elements" % (name, self.height, self.width, size))
+        ctx = self.context(device)
+        rc = lib.tghip_develop(ctx, C.byref(desc), hdr.data_ptr() if hdr is not None else None, ldr.data_ptr() if ldr is not None else None,
+                               self.width*self.height)
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
 
     def close(self):
         if self._h:

@@ -101,6 +101,7 @@ class TgHipSceneDesc(C.Structure):
                 ("bounds_lo", f32*3), ("bounds_hi", f32*3)]
 
 
+(TGHIP_OK, TGHIP_E_INVALID, TGHIP_E_NODEVICE, TGHIP_E_HIP, TGHIP_E_NOSCENE, TGHIP_E_ABORTED, TGHIP_E_UNSUPPORTED) = (0, -1, -2, -3, -4, -5, -6)
 TGHIP_PASS_SOBOL, TGHIP_PASS_RECORDS, TGHIP_PASS_AUX, TGHIP_PASS_SAMPLES = 1, 2, 4, 8
 (TGHIP_LIBM_SINF, TGHIP_LIBM_COSF, TGHIP_LIBM_LOGF, TGHIP_LIBM_EXPF, TGHIP_LIBM_SINCOS_SIN, TGHIP_LIBM_SINCOS_COS,
  TGHIP_LIBM_ACOSF, TGHIP_LIBM_ATAN2F, TGHIP_LIBM_POWF, TGHIP_LIBM_CBRTF, TGHIP_LIBM_EMBREE_RCP, TGHIP_LIBM_RCPPS, TGHIP_LIBM_TANF,
@@ -109,6 +110,18 @@ TGHIP_PASS_SOBOL, TGHIP_PASS_RECORDS, TGHIP_PASS_AUX, TGHIP_PASS_SAMPLES = 1, 2,
 
 class TgHipAuxPixel(C.Structure):
     _fields_ = [("a", f32*11), ("b", f32*11), ("variance", f32*11), ("count", u32*5)]
+
+
+(TGHIP_TONEMAP_LINEAR, TGHIP_TONEMAP_GAMMA, TGHIP_TONEMAP_REINHARD, TGHIP_TONEMAP_FILMIC, TGHIP_TONEMAP_PBRT) = range(5)
+TGHIP_DEVELOP_MEAN, TGHIP_DEVELOP_A, TGHIP_DEVELOP_B, TGHIP_DEVELOP_VARIANCE = range(4)
+TGHIP_DEVELOP_FRAME = 0xFFFFFFFF
+TGHIP_DEVELOP_DEVICE_POINTERS = 1
+(TGHIP_AUX_COLOR, TGHIP_AUX_DEPTH, TGHIP_AUX_NORMAL, TGHIP_AUX_ALBEDO, TGHIP_AUX_VISIBILITY) = range(5)
+TGHIP_AUX_CHANNEL_COUNT = (3, 1, 3, 3, 1)
+
+
+class TgHipDevelopDesc(C.Structure):
+    _fields_ = [("source", u32), ("part", u32), ("tonemap", u32), ("flags", u32)]
 
 
 class TgHipPassDesc(C.Structure):
@@ -174,6 +187,8 @@ PROTOTYPES = {
     "tghip_download_aux": (C.c_int, [VP, VP, C.c_size_t]),
     "tghip_upload_aux": (C.c_int, [VP, VP, C.c_size_t]),
     "tghip_download_samples": (C.c_int, [VP, VP, C.c_size_t]),
+    "tghip_develop": (C.c_int, [VP, C.POINTER(TgHipDevelopDesc), VP, VP, C.c_size_t]),
+    "tghip_develop_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_reduce_framebuffers": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, VP, VP, C.c_size_t]),
     "tghip_trace_rays": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
@@ -201,6 +216,10 @@ PROTOTYPES = {
     "tgh_renderer_resume": (C.c_int, [VP, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "tgh_renderer_records": (C.c_int, [VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_renderer_output_buffers": (C.c_int, [VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "tgh_renderer_develop": (C.c_int, [VP, C.POINTER(TgHipDevelopDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "tgh_renderer_tonemap": (C.c_int, [VP]),
+    "tgh_develop_host_frame": (C.c_int, [VP, VP, C.c_size_t, u32, VP, VP]),
+    "tgh_develop_host_aux": (C.c_int, [VP, C.c_size_t, u32, u32, VP, VP]),
     "tgh_scheduler_create": (VP, [u32, u32, u32]),
     "tgh_scheduler_num_tiles": (C.c_size_t, [VP]),
     "tgh_scheduler_num_records": (C.c_size_t, [VP]),

@@ -237,11 +237,12 @@ PT_LIBM_FN bool powInRange(float x, float y)
     const uint32_t ix = f2u(x), iy = f2u(y);
     return ix - 0x00800000u < 0x7f800000u - 0x00800000u && (iy & 0x7fffffffu) < 0x7f800000u && (iy & 0x7fffffffu) != 0u;
 }
-// false when y log2(x) is outside (-126, 126): glibc's overflow / underflow paths, left to the caller's fallback
-PT_LIBM_FN bool powfCore(float x, float y, float &result)
+// false when y log2(x) is outside (-126, 126): glibc's overflow / underflow paths, left to the caller's fallback.
+// ix: the bits of x -- or, for a subnormal x, what e_powf.c makes of them (the bits of x 2^23 with 23 taken off the exponent field, which wraps
+// below zero: develop.hip's tone mapping is the one caller that meets subnormals)
+PT_LIBM_FN bool powfCoreBits(uint32_t ix, float y, float &result)
 {
     const double A0 = 0x1.27616c9496e0bp-2, A1 = -0x1.71969a075c67ap-2, A2 = 0x1.ec70a6ca7baddp-2, A3 = -0x1.7154748bef6c8p-1, A4 = 0x1.71547652ab82bp0;
-    const uint32_t ix = f2u(x);
     const uint32_t tmp = ix - 0x3f330000u;
     const int i = (int)((tmp >> 19) & 15u);
     const uint32_t top = tmp & 0xff800000u;
@@ -273,6 +274,7 @@ PT_LIBM_FN bool powfCore(float x, float y, float &result)
     result = (float)(e*s);
     return true;
 }
+PT_LIBM_FN bool powfCore(float x, float y, float &result) { return powfCoreBits(f2u(x), y, result); }
 
 // ---- cbrtf: s_cbrtf.c -- frexp, a quadratic first guess and one Halley step in double, the cube root of the exponent's remainder from a
 // five-entry table, ldexp.  (Insensitive to contraction: every fused and unfused variant gives glibc's result for every float.)

@@ -2,6 +2,7 @@
 // gfx950 (MI355X) only.  See pt_kernels.h for the execution model and DESIGN.md for the layout.
 #define PT_WAVEFRONT_MAIN
 #include "pt_wavefront.h"
+#include "develop.h"
 
 #include <atomic>
 #include <chrono>
@@ -284,6 +285,14 @@ struct tghip_ctx {
     bool haveSolids = false;              // cube / sphere / disk records: the dynamic-fetch kernels' SOLIDS variants
     TgHipAuxPixel *dAux = nullptr;        // auxiliary output buffers (allocated by the first TGHIP_PASS_AUX pass)
     float *dSamples = nullptr;            // TGHIP_PASS_SAMPLES: per-sample radiance of the last such pass
+    // tghip_develop: where the kernels write when the caller's outputs are host memory (grown on demand), the depth output's maximum, the option
+    // that hands the work back to the caller's host code, the kernels' time
+    float *developHdr = nullptr;
+    uint8_t *developLdr = nullptr;
+    size_t developHdrCap = 0, developLdrCap = 0;
+    uint32_t *developMax = nullptr;
+    bool developHost = false;             // "develop_host"
+    double developMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context
     int rankCount = 0, rankIndex = 0;
     float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
@@ -939,6 +948,9 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->fbCount) (void)hipFree(ctx->fbCount);
     if (ctx->dAux) (void)hipFree(ctx->dAux);
     if (ctx->dSamples) (void)hipFree(ctx->dSamples);
+    if (ctx->developHdr) (void)hipFree(ctx->developHdr);
+    if (ctx->developLdr) (void)hipFree(ctx->developLdr);
+    if (ctx->developMax) (void)hipFree(ctx->developMax);
     if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
     if (ctx->redSum) (void)hipFree(ctx->redSum);
@@ -1034,6 +1046,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "leaf_batch") ctx->leafBatch = int(std::min<long long>(std::max<long long>(value, 1), 64));
     else if (k == "fuse_flat") ctx->fuseFlatOpt = value != 0;
     else if (k == "shade_fused") ctx->shadeFusedOpt = value != 0;
+    else if (k == "develop_host") ctx->developHost = value != 0;   // tghip_develop answers TGHIP_E_UNSUPPORTED: the host integrator then develops a download itself
     else if (k == "run_to_completion") ctx->loopOpt = value != 0;
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
@@ -2445,6 +2458,67 @@ int tghip_download_samples(tghip_ctx *ctx, float *rgb, size_t nfloats)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(rgb, ctx->dSamples, nfloats*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TGHIP_OK;
+}
+
+int tghip_develop(tghip_ctx *ctx, const TgHipDevelopDesc *desc, float *hdr_out, uint8_t *ldr_out, size_t npixels)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_develop: no description"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "tghip_develop before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    const bool frame = desc->source == TGHIP_DEVELOP_FRAME;
+    if (!frame && desc->source >= TGHIP_AUX_OUTPUTS) { ctx->error = "tghip_develop: unknown source"; return TGHIP_E_INVALID; }
+    if (desc->part > TGHIP_DEVELOP_VARIANCE) { ctx->error = "tghip_develop: unknown part"; return TGHIP_E_INVALID; }
+    if (frame && desc->tonemap > TGHIP_TONEMAP_PBRT) { ctx->error = "tghip_develop: unknown tone-mapping operator"; return TGHIP_E_INVALID; }
+    if (frame && desc->part != TGHIP_DEVELOP_MEAN) { ctx->error = "tghip_develop: the framebuffer has no A / B halves and no variance"; return TGHIP_E_INVALID; }
+    if (npixels != size_t(ctx->width)*ctx->height) { ctx->error = "pixel count mismatch"; return TGHIP_E_INVALID; }
+    if (ctx->developHost) { ctx->error = "tghip_develop: the develop_host option is set (the caller develops on the host)"; return TGHIP_E_UNSUPPORTED; }
+    int rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    if (!frame && !ctx->dAux) { ctx->error = "tghip_develop: no auxiliary output buffers yet (no TGHIP_PASS_AUX pass, no tghip_upload_aux)"; return TGHIP_E_INVALID; }
+    const float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
+    const uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    if (frame && ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(cnt)) & 15u)) { ctx->error = "tghip_develop: the bound framebuffer is not 16-byte aligned"; return TGHIP_E_INVALID; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t hdrFloats = npixels*(frame || (desc->source != TGHIP_AUX_DEPTH && desc->source != TGHIP_AUX_VISIBILITY) ? 3 : 1);
+    float *hdr = hdr_out;
+    uint8_t *ldr = ldr_out;
+    if (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) {
+        if ((reinterpret_cast<uintptr_t>(hdr) & 15u) || (reinterpret_cast<uintptr_t>(ldr) & 3u)) { ctx->error = "tghip_develop: device outputs must be aligned (hdr_out to 16 bytes, ldr_out to 4)"; return TGHIP_E_INVALID; }
+    } else {
+        if (hdr_out && ctx->developHdrCap < hdrFloats) {
+            if (ctx->developHdr) (void)hipFree(ctx->developHdr);
+            ctx->developHdr = nullptr; ctx->developHdrCap = 0;
+            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developHdr), hdrFloats*sizeof(float)));
+            ctx->developHdrCap = hdrFloats;
+        }
+        if (ldr_out && ctx->developLdrCap < npixels*3) {
+            if (ctx->developLdr) (void)hipFree(ctx->developLdr);
+            ctx->developLdr = nullptr; ctx->developLdrCap = 0;
+            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developLdr), npixels*3));
+            ctx->developLdrCap = npixels*3;
+        }
+        hdr = hdr_out ? ctx->developHdr : nullptr;
+        ldr = ldr_out ? ctx->developLdr : nullptr;
+    }
+    if (!ctx->developMax) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developMax), 64));
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    if (frame) HIP_TRY(ctx, developLaunchFrame(ctx->stream, sum, cnt, npixels, desc->tonemap, hdr, ldr));
+    else HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux, npixels, desc->source, desc->part, hdr, ldr, ctx->developMax));
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    if (hdr_out && hdr != hdr_out) HIP_TRY(ctx, hipMemcpyAsync(hdr_out, hdr, hdrFloats*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (ldr_out && ldr != ldr_out) HIP_TRY(ctx, hipMemcpyAsync(ldr_out, ldr, npixels*3, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
+    ctx->developMs = ms;
+    return TGHIP_OK;
+}
+
+int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->developMs;
     return TGHIP_OK;
 }
 

@@ -1,4 +1,5 @@
 #include "Integrator.hpp"
+#include "Develop.hpp"
 #include "ImageIO.hpp"
 #include "TraceableScene.hpp"
 
@@ -53,17 +54,15 @@ void Integrator::writeBuffers(const std::string &suffix, bool overwrite)
 {
     const Camera &cam = _scene->cam();
     const RendererSettings &settings = _scene->rendererSettings();
-    const std::vector<float> &hdr = linearImage();
     size_t n = size_t(cam.resX)*cam.resY;
+    std::vector<float> hdr(settings.hdrOutputFile.empty() ? 0 : n*3);
+    std::vector<uint8_t> ldr(settings.outputFile.empty() ? 0 : n*3);
+    if (!hdr.empty() || !ldr.empty()) {
+        TgHipDevelopDesc desc = {TGHIP_DEVELOP_FRAME, TGHIP_DEVELOP_MEAN, ldr.empty() ? 0u : Develop::tonemapIndex(cam.tonemap), 0u};
+        develop(desc, hdr.empty() ? nullptr : hdr.data(), ldr.empty() ? nullptr : ldr.data());
+    }
 
     if (!settings.outputFile.empty()) {
-        std::vector<uint8_t> ldr(n*3);
-        for (size_t i = 0; i < n; ++i) {
-            Vec3f c(std::max(hdr[i*3], 0.0f), std::max(hdr[i*3 + 1], 0.0f), std::max(hdr[i*3 + 2], 0.0f));
-            Vec3f t = ImageIO::tonemap(cam.tonemap, c)*255.0f;
-            for (int k = 0; k < 3; ++k)
-                ldr[i*3 + k] = uint8_t(std::min(std::max(int(t[k]), 0), 255));
-        }
         std::string path = incrementalFilename(settings.outputFile, suffix, overwrite);
         if (path.size() < 4 || path.substr(path.size() - 4) != ".png")
             path += ".png";   // only the PNG writer is in scope
@@ -75,78 +74,33 @@ void Integrator::writeBuffers(const std::string &suffix, bool overwrite)
         saveOutputBuffers();
 }
 
-// OutputBuffer<T>::save for every requested output (cameras/OutputBuffer.hpp:146-189, saveLdr :56-86).  The device keeps
-// every output as A / B halves + Welford sum; what a buffer without two_buffer_variance would hold in _bufferA is the
-// mean of both halves.
+// OutputBuffer<T>::save for every requested output (cameras/OutputBuffer.hpp:146-189): the mean, with two_buffer_variance the two halves, with
+// sample_variance the variance, each as a float and / or an 8-bit file (Develop.hpp has the images' arithmetic)
 void Integrator::saveOutputBuffers()
 {
     const Camera &cam = _scene->cam();
     const int w = int(cam.resX), h = int(cam.resY);
     const size_t n = size_t(w)*h;
-    std::vector<TgHipAuxPixel> aux;
-    currentOutputBuffers(aux);
-    if (aux.size() != n)
-        return;
-    static const int first[5] = {0, 3, 4, 7, 10}, channels[5] = {3, 1, 3, 3, 1};
     auto withTag = [](const std::string &file, const char *tag) {
         size_t dot = file.find_last_of('.');
         return dot == std::string::npos ? file + tag : file.substr(0, dot) + tag + file.substr(dot);
     };
+    std::vector<float> hdr;
+    std::vector<uint8_t> ldr;
     for (const OutputBufferSettings &b : _scene->rendererSettings().outputs) {
-        const int ch0 = first[b.type], nch = channels[b.type];
-        std::vector<float> mean(n*nch), bufA(n*nch), bufB(n*nch), var(n*nch);
-        for (size_t i = 0; i < n; ++i) {
-            const TgHipAuxPixel &p = aux[i];
-            uint32_t cnt = p.count[b.type], cntA = (cnt + 1)/2, cntB = cnt/2;
-            for (int k = 0; k < nch; ++k) {
-                float a = p.a[ch0 + k], bb = p.b[ch0 + k];
-                bufA[i*nch + k] = a; bufB[i*nch + k] = bb;
-                mean[i*nch + k] = (a*float(cntA) + bb*float(cntB))/float(std::max(cnt, 1u));      // operator[] (:134-144)
-                var[i*nch + k] = p.variance[ch0 + k]/float(cnt*std::max(1u, cnt - 1));             // save() (:178-181)
-            }
-        }
-        auto saveHdr = [&](const std::string &file, const std::vector<float> &img) {
-            if (!file.empty()) ImageIO::savePfm(file, img.data(), w, h, nch);
+        const int nch = int(Develop::auxChannels(uint32_t(b.type)));
+        auto save = [&](const char *tag, uint32_t part) {
+            hdr.resize(b.hdrOutputFile.empty() ? 0 : n*nch);
+            ldr.resize(b.ldrOutputFile.empty() ? 0 : n*3);
+            if (hdr.empty() && ldr.empty()) return;
+            TgHipDevelopDesc desc = {uint32_t(b.type), part, 0u, 0u};
+            develop(desc, hdr.empty() ? nullptr : hdr.data(), ldr.empty() ? nullptr : ldr.data());
+            if (!hdr.empty()) ImageIO::savePfm(withTag(b.hdrOutputFile, tag), hdr.data(), w, h, nch);
+            if (!ldr.empty()) ImageIO::savePng(withTag(b.ldrOutputFile, tag), ldr.data(), w, h);
         };
-        auto saveLdr = [&](const std::string &file, const std::vector<float> &img, bool rescale) {   // OutputBuffer::saveLdr
-            if (file.empty()) return;
-            float minimum = 0.0f, maximum = 0.0f;
-            if (b.type == TGHIP_AUX_DEPTH) {
-                for (size_t i = 0; i < n; ++i)
-                    if (img[i] != std::numeric_limits<float>::infinity()) maximum = std::max(maximum, img[i]);
-            } else if (b.type == TGHIP_AUX_NORMAL) {
-                minimum = -1.0f; maximum = 1.0f;
-            } else {
-                rescale = false;
-            }
-            std::vector<uint8_t> ldr(n*3);
-            for (size_t i = 0; i < n; ++i) {
-                bool bad = false;
-                float f[3];
-                for (int k = 0; k < 3; ++k) {
-                    f[k] = img[i*nch + (nch == 3 ? k : 0)];
-                    if (rescale) f[k] = (f[k] - minimum)/(maximum - minimum);
-                }
-                float avg = nch == 3 ? (f[0] + f[1] + f[2])/3.0f : f[0];
-                bad = std::isnan(avg) || std::isinf(avg);
-                for (int k = 0; k < 3; ++k)
-                    ldr[i*3 + k] = bad ? 255 : uint8_t(std::min(std::max(int(f[k]*255.0f), 0), 255));
-            }
-            ImageIO::savePng(file, ldr.data(), w, h);
-        };
-        if (b.twoBufferVariance) {
-            saveHdr(b.hdrOutputFile, mean);
-            if (!b.hdrOutputFile.empty()) { saveHdr(withTag(b.hdrOutputFile, "A"), bufA); saveHdr(withTag(b.hdrOutputFile, "B"), bufB); }
-            saveLdr(b.ldrOutputFile, mean, true);
-            if (!b.ldrOutputFile.empty()) { saveLdr(withTag(b.ldrOutputFile, "A"), bufA, true); saveLdr(withTag(b.ldrOutputFile, "B"), bufB, true); }
-        } else {
-            saveHdr(b.hdrOutputFile, mean);
-            saveLdr(b.ldrOutputFile, mean, true);
-        }
-        if (b.sampleVariance) {
-            if (!b.hdrOutputFile.empty()) saveHdr(withTag(b.hdrOutputFile, "Variance"), var);
-            if (!b.ldrOutputFile.empty()) saveLdr(withTag(b.ldrOutputFile, "Variance"), var, false);
-        }
+        save("", TGHIP_DEVELOP_MEAN);
+        if (b.twoBufferVariance) { save("A", TGHIP_DEVELOP_A); save("B", TGHIP_DEVELOP_B); }
+        if (b.sampleVariance) save("Variance", TGHIP_DEVELOP_VARIANCE);
     }
 }
 
@@ -320,6 +274,9 @@ void PathTraceHipIntegrator::prepareForRender(TraceableScene &scene, uint32_t se
     _sum.assign(size_t(_w)*_h*3, 0.0f);
     _count.assign(size_t(_w)*_h, 0);
     _imageDirty = true;
+    _aux.clear();
+    _auxDirty = true;
+    _auxOnDevice = false;
 
     // PathTraceIntegrator.cpp:187,196-200: the integrator's own sampler, tile dicing, one SampleRecord per 4x4 pixels
     _useSobol = scene.rendererSettings().useSobol;
@@ -377,6 +334,8 @@ void PathTraceHipIntegrator::startRender(std::function<void()> completionCallbac
         check(tghip_render_pass(_ctxs[d], &pass), _ctxs[d], "tghip_render_pass");
     }
     _imageDirty = true;
+    _auxDirty = true;
+    _auxOnDevice = _auxOnDevice || _useAux;
     _worker = std::thread([this, completionCallback]() {
         // one host thread per device drives that device's wavefront loop (tghip_wait blocks until the shard is
         // done; different handles may be driven from different threads, include/tungsten_hip.h)
@@ -503,6 +462,16 @@ void PathTraceHipIntegrator::restoreOutputBuffers(const std::vector<TgHipAuxPixe
                         std::memset(&mine[size_t(x) + size_t(y)*_w], 0, sizeof(TgHipAuxPixel));
         check(tghip_upload_aux(_ctxs[d], mine.data(), mine.size()), _ctxs[d], "tghip_upload_aux");
     }
+    _auxDirty = true;
+    _auxOnDevice = true;
+}
+
+void PathTraceHipIntegrator::fetchOutputBuffers()
+{
+    if (!_auxDirty)
+        return;
+    currentOutputBuffers(_aux);
+    _auxDirty = false;
 }
 
 // The merged framebuffer goes to the first device, the others restart from zero: ownership of a pixel only matters for
@@ -562,6 +531,35 @@ const std::vector<float> &PathTraceHipIntegrator::linearImage()
             _linear[i*3 + k] = _sum[i*3 + k]*inv;
     }
     return _linear;
+}
+
+// A render on one device develops its images where the framebuffer lives (tghip_develop).  Renders sharded over several devices merge on the
+// host, and a context with the "develop_host" option hands the work back (TGHIP_E_UNSUPPORTED): both take the host's own functions over a
+// download -- the same bytes either way (tests/test_gpu_develop.py).
+void PathTraceHipIntegrator::develop(const TgHipDevelopDesc &desc, float *hdr, uint8_t *ldr)
+{
+    waitForCompletion();
+    if (_ctxs.empty())
+        throw std::runtime_error("path_tracer_hip: develop before prepareForRender");
+    const size_t n = size_t(_w)*_h;
+    const bool frame = desc.source == TGHIP_DEVELOP_FRAME;
+    if (_ctxs.size() == 1 && (frame || _auxOnDevice)) {
+        int rc = tghip_develop(_ctxs[0], &desc, hdr, ldr, n);
+        if (rc != TGHIP_E_UNSUPPORTED) {
+            check(rc, _ctxs[0], "tghip_develop");
+            return;
+        }
+    }
+    if ((!frame && desc.source >= TGHIP_AUX_OUTPUTS) || desc.part > TGHIP_DEVELOP_VARIANCE || (frame && desc.part != TGHIP_DEVELOP_MEAN)
+        || (frame && !Develop::tonemapName(desc.tonemap)) || (desc.flags & TGHIP_DEVELOP_DEVICE_POINTERS))
+        throw std::runtime_error("path_tracer_hip: invalid description of an image to develop on the host");
+    if (frame) {
+        fetchFramebuffer();
+        Develop::frame(_sum.data(), _count.data(), n, Develop::tonemapName(desc.tonemap), hdr, ldr);
+    } else {
+        fetchOutputBuffers();
+        Develop::aux(_aux.data(), n, desc.source, desc.part, hdr, ldr);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

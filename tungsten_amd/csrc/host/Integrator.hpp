@@ -60,6 +60,9 @@ public:
 
     // per-pixel mean radiance, row-major, y down (Camera::getLinear, cameras/Camera.hpp:163-172)
     virtual const std::vector<float> &linearImage() = 0;
+    // one image of the output files -- the frame's mean and tone-mapped 8-bit image, or a part of an auxiliary output (include/tungsten_hip.h:
+    // TgHipDevelopDesc) -- as floats and / or 8-bit RGB in host memory; either may be null
+    virtual void develop(const TgHipDevelopDesc &desc, float *hdr, uint8_t *ldr) = 0;
 
     // seed of the per-path sample streams: part of what a resume file must agree on (sceneHash)
     virtual uint32_t samplerSeed() const { return 0; }
@@ -94,9 +97,13 @@ class PathTraceHipIntegrator : public Integrator
     std::vector<uint32_t> _count;
     std::vector<float> _linear;
     bool _imageDirty = true;
+    std::vector<TgHipAuxPixel> _aux;      // host copy of the auxiliary output buffers, for images developed on the host
+    bool _auxDirty = true;
+    bool _auxOnDevice = false;            // a TGHIP_PASS_AUX pass or a resume has put the buffers on the device
 
     void check(int rc, tghip_ctx *ctx, const char *what);
     void fetchFramebuffer();
+    void fetchOutputBuffers();
 
 public:
     PathTraceHipIntegrator();
@@ -109,6 +116,7 @@ public:
     void waitForCompletion() override;
     void abortRender() override;
     const std::vector<float> &linearImage() override;
+    void develop(const TgHipDevelopDesc &desc, float *hdr, uint8_t *ldr) override;
     uint32_t samplerSeed() const override { return _seed; }
     bool supportsResumeRender() const override { return true; }          // PathTraceIntegrator.cpp:215-218
     void saveState(std::ostream &out) override;                           // PathTraceIntegrator.cpp:158-172 (records + samplers)

@@ -1,6 +1,7 @@
 // extern "C" view of the host classes (include/tungsten_host.h).
 #include "../../../include/tungsten_host.h"
 
+#include "Develop.hpp"
 #include "EmbreeTopTree.hpp"
 #include "ImageIO.hpp"
 #include "Integrator.hpp"
@@ -253,6 +254,43 @@ int tgh_renderer_output_buffers(tgh_renderer *r, TgHipAuxPixel *out, size_t npix
         setErr(err, errlen, e.what());
         return -1;
     }
+}
+
+int tgh_renderer_develop(tgh_renderer *r, const TgHipDevelopDesc *desc, float *hdr_out, uint8_t *ldr_out, size_t npixels, char *err, size_t errlen)
+{
+    if (!r || !desc) return -1;
+    try {
+        if (npixels != size_t(r->scene->camera.resX)*r->scene->camera.resY) { setErr(err, errlen, "pixel count mismatch"); return -1; }
+        r->integrator->develop(*desc, hdr_out, ldr_out);
+        return 0;
+    } catch (const std::exception &e) {
+        setErr(err, errlen, e.what());
+        return -1;
+    }
+}
+
+int tgh_renderer_tonemap(tgh_renderer *r)
+{
+    if (!r) return -1;
+    try {
+        return int(Develop::tonemapIndex(r->scene->camera.tonemap));
+    } catch (const std::exception &) {
+        return -1;
+    }
+}
+
+int tgh_develop_host_frame(const float *rgb_sum, const uint32_t *count, size_t npixels, uint32_t tonemap, float *hdr_out, uint8_t *ldr_out)
+{
+    if ((npixels && (!rgb_sum || !count)) || !Develop::tonemapName(tonemap)) return -1;
+    Develop::frame(rgb_sum, count, npixels, Develop::tonemapName(tonemap), hdr_out, ldr_out);
+    return 0;
+}
+
+int tgh_develop_host_aux(const TgHipAuxPixel *aux, size_t npixels, uint32_t output, uint32_t part, float *hdr_out, uint8_t *ldr_out)
+{
+    if ((npixels && !aux) || output >= TGHIP_AUX_OUTPUTS || part > TGHIP_DEVELOP_VARIANCE) return -1;
+    Develop::aux(aux, npixels, output, part, hdr_out, ldr_out);
+    return 0;
 }
 
 tgh_scheduler *tgh_scheduler_create(uint32_t width, uint32_t height, uint32_t seed)
