@@ -17,7 +17,8 @@ LIBNAME  := $(if $(PROFILE),libtungsten_hip_prof.so,$(if $(VARIANT),libtungsten_
 HOSTSRC  := $(wildcard tungsten_amd/csrc/host/*.cpp)
 HOSTLIB  := $(filter-out tungsten_amd/csrc/host/main.cpp,$(HOSTSRC))
 HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB))
-# the shim + one translation unit per family of k_shade instantiations (they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop
+# the shim + one translation unit per family of k_shade instantiations (they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
+# + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
 HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h

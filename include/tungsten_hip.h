@@ -544,6 +544,34 @@ typedef struct TgHipDevelopDesc { uint32_t source, part, tonemap, flags; } TgHip
 int tghip_develop(tghip_ctx *ctx, const TgHipDevelopDesc *desc, float *hdr_out, uint8_t *ldr_out, size_t npixels);
 /* Instrumentation: HIP-event time of the kernels of the context's last tghip_develop, in milliseconds (profiles/r8_develop.txt) */
 int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms);
+/* The denoiser's NL-means filter (denoiser/NlMeans.hpp:95-157: nlMeans with nlMeansWeights :47-93 and denoiser/BoxFilter.hpp) on the device, by
+ * kernels of its own (csrc/hip/denoise.hip): out = the `image` filtered with weights from `guide` and `variance`, patch radius F, search radius R,
+ * distance scale k, the variance times variance_scale -- float32, operation for operation in the reference's order (32 x 32 tiles, offsets dy outer and dx
+ * inner, the box filter's running sums and its in-place slow path in narrow rectangles), so the bits are the reference's and the host's
+ * (tungsten_host.h: tgh_nlmeans_host).  A C-channel image is C independent scalar filters, as nlMeans<Vec3f> and SimdNlMeans' float4 are.
+ *   source  TGHIP_NLMEANS_POINTERS: image / guide / variance / out are height x width pixels of `channels` interleaved floats -- host memory, or with
+ *           TGHIP_DEVELOP_DEVICE_POINTERS memory of the context's device (4-byte aligned); no scene is needed;
+ *           a TGHIP_AUX_* output: image, guide and variance are NULL, and the three planes are the float images tghip_develop gives for that output's
+ *           image_part, guide_part and TGHIP_DEVELOP_VARIANCE, developed on the device into scratch; `channels` is set by the output (3, 1, 3, 3, 1:
+ *           the description's value is ignored) and width x height must be the frame's.  NFOR's feature prefilter of an output is two calls:
+ *           image A with guide B and image B with guide A, F 3, R 5, k 0.5, variance_scale 2.
+ * Non-finite input pixels are outside the contract: what the reference's float-to-int conversion and its min / max make of a NaN is not restated.
+ * Waits for the running pass like tghip_develop.  TGHIP_E_INVALID (tghip_last_error says which): NULL context or description, channels outside
+ * 1..4, F above 8, R above 16, k <= 0, a zero dimension, an unknown source or part, an aux source before an aux buffer exists or with another size
+ * than the frame's, pointers given with an aux source, pointers missing without one. */
+#define TGHIP_NLMEANS_POINTERS 0xffffffffu    /* source: the caller's arrays; otherwise a TGHIP_AUX_* output of the context */
+typedef struct TgHipNlMeansDesc {
+    uint32_t width, height, channels;   /* 1..4, interleaved */
+    uint32_t F, R;                      /* patch and search radius */
+    float    k, variance_scale;
+    uint32_t source;                    /* TGHIP_NLMEANS_POINTERS, or a TGHIP_AUX_* output of the context */
+    uint32_t image_part, guide_part;    /* with an aux source: TGHIP_DEVELOP_MEAN / _A / _B */
+    uint32_t flags;                     /* TGHIP_DEVELOP_DEVICE_POINTERS: all pointers are memory of the context's device */
+} TgHipNlMeansDesc;
+int tghip_nlmeans(tghip_ctx *ctx, const TgHipNlMeansDesc *desc, const float *image, const float *guide, const float *variance, float *out);
+/* Instrumentation: HIP-event time of the kernels of the context's last tghip_nlmeans (the develop kernels of an aux source included), in
+ * milliseconds (profiles/r9_denoise.txt) */
+int tghip_nlmeans_kernel_time(tghip_ctx *ctx, double *ms);
 /* Multi-GPU framebuffer merge inside one process: ctxs[0..n) are the contexts (one per device, all with the same scene
  * uploaded) that rendered the tile shards 0..n-1 of a frame (TgHipPassDesc.shard_index/shard_count).  Their radiance sums
  * (float32) and sample counts (uint32) are sum-reduced by RCCL (ncclReduce over xGMI, one communicator per device, created at

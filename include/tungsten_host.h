@@ -83,6 +83,11 @@ int  tgh_renderer_tonemap(tgh_renderer *r);
  * is held to, bit for bit.  tonemap: TGHIP_TONEMAP_*; output: TGHIP_AUX_*; part: TGHIP_DEVELOP_*.  -1 on an unknown operator / output / part. */
 int  tgh_develop_host_frame(const float *rgb_sum, const uint32_t *count, size_t npixels, uint32_t tonemap, float *hdr_out, uint8_t *ldr_out);
 int  tgh_develop_host_aux(const TgHipAuxPixel *aux, size_t npixels, uint32_t output, uint32_t part, float *hdr_out, uint8_t *ldr_out);
+/* The host's own NL-means filter (include/tungsten_hip.h: tghip_nlmeans, TgHipNlMeansDesc; denoiser/NlMeans.hpp:95-157 restated in
+ * csrc/host/Denoise.cpp) over host arrays of height x width pixels of `channels` interleaved floats, no device: what tghip_nlmeans is held to, bit
+ * for bit, and itself held to results recorded from the reference (tests/golden/nlmeans.npz).  Threaded over the tiles; the bits do not depend on
+ * that.  The description's source must be TGHIP_NLMEANS_POINTERS; its flags are ignored.  -1 on a description tghip_nlmeans would refuse. */
+int  tgh_nlmeans_host(const TgHipNlMeansDesc *desc, const float *image, const float *guide, const float *variance, float *out);
 
 /* The scheduler on its own (no device): tile seeds + generateWork over caller-supplied record statistics. */
 typedef struct tgh_scheduler tgh_scheduler;

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import (TgHipCounters, TgHipDevelopDesc, TgHipHit, TgHipPassDesc, TgHipRay, TgHipSceneDesc, TgHostSceneInfo)
+from .capi import (TgHipCounters, TgHipDevelopDesc, TgHipHit, TgHipNlMeansDesc, TgHipPassDesc, TgHipRay, TgHipSceneDesc, TgHostSceneInfo)
 
 lib = capi.load_library()
 
@@ -244,6 +244,38 @@ class Renderer(object):
                                self.width*self.height)
         if rc != 0:
             raise TungstenError(lib.tghip_last_error(ctx).decode())
+
+    def nlmeans(self, image, guide, variance, F, R, k, variance_scale=1.0, device=0):
+        """The denoiser's NL-means filter on the device (tghip_nlmeans): `image` filtered with weights from `guide` and `variance` -- float32
+        arrays [H, W] or [H, W, C], C = 1..4, all of one shape -- with patch radius F, search radius R and distance scale k; returns the filtered
+        array, bit for bit the reference's nlMeans."""
+        image, guide, variance = (np.ascontiguousarray(a, np.float32) for a in (image, guide, variance))
+        if image.ndim not in (2, 3) or guide.shape != image.shape or variance.shape != image.shape:
+            raise TungstenError("nlmeans: image, guide and variance must be [H, W] or [H, W, C] arrays of one shape")
+        desc = TgHipNlMeansDesc(image.shape[1], image.shape[0], image.shape[2] if image.ndim == 3 else 1, int(F), int(R), float(k),
+                                float(variance_scale), capi.TGHIP_NLMEANS_POINTERS, 0, 0, 0)
+        out = np.empty_like(image)
+        ctx = self.context(device)
+        if lib.tghip_nlmeans(ctx, C.byref(desc), image.ctypes.data, guide.ctypes.data, variance.ctypes.data, out.ctypes.data) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def nlmeans_aux(self, output, image_part, guide_part, F, R, k, variance_scale=1.0, device=0):
+        """The same on the context's auxiliary buffers, nothing but the result leaving the device: the float images develop() gives for `output`'s
+        `image_part` and `guide_part` ("mean", "a", "b") and its variance are the filter's three planes.  Returns [H, W, channels]."""
+        src = AUX_OUTPUT_NAMES.index(output)
+        desc = TgHipNlMeansDesc(self.width, self.height, 0, int(F), int(R), float(k), float(variance_scale), src,
+                                DEVELOP_PART_NAMES.index(image_part), DEVELOP_PART_NAMES.index(guide_part), 0)
+        out = np.empty((self.height, self.width, capi.TGHIP_AUX_CHANNEL_COUNT[src]), np.float32)
+        ctx = self.context(device)
+        if lib.tghip_nlmeans(ctx, C.byref(desc), None, None, None, out.ctypes.data) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def prefilter_features(self, outputs=("depth", "normal", "albedo", "visibility")):
+        """NFOR's feature cross-prefilter (denoiser.cpp: nforDenoiser, section 5.1) on the context's auxiliary buffers: per output the A half
+        filtered with weights from the B half and the B half with weights from A (F 3, R 5, k 0.5, the variance doubled).  {name: (A', B')}."""
+        return {name: (self.nlmeans_aux(name, "a", "b", 3, 5, 0.5, 2.0), self.nlmeans_aux(name, "b", "a", 3, 5, 0.5, 2.0)) for name in outputs}
 
     def close(self):
         if self._h:

@@ -124,6 +124,14 @@ class TgHipDevelopDesc(C.Structure):
     _fields_ = [("source", u32), ("part", u32), ("tonemap", u32), ("flags", u32)]
 
 
+TGHIP_NLMEANS_POINTERS = 0xFFFFFFFF
+
+
+class TgHipNlMeansDesc(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("channels", u32), ("F", u32), ("R", u32), ("k", f32), ("variance_scale", f32),
+                ("source", u32), ("image_part", u32), ("guide_part", u32), ("flags", u32)]
+
+
 class TgHipPassDesc(C.Structure):
     _fields_ = [("spp_begin", u32), ("spp_end", u32), ("seed", u32), ("shard_index", u32), ("shard_count", u32),
                 ("flags", u32),
@@ -189,6 +197,8 @@ PROTOTYPES = {
     "tghip_download_samples": (C.c_int, [VP, VP, C.c_size_t]),
     "tghip_develop": (C.c_int, [VP, C.POINTER(TgHipDevelopDesc), VP, VP, C.c_size_t]),
     "tghip_develop_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_nlmeans": (C.c_int, [VP, C.POINTER(TgHipNlMeansDesc), VP, VP, VP, VP]),
+    "tghip_nlmeans_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_reduce_framebuffers": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, VP, VP, C.c_size_t]),
     "tghip_trace_rays": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
@@ -220,6 +230,7 @@ PROTOTYPES = {
     "tgh_renderer_tonemap": (C.c_int, [VP]),
     "tgh_develop_host_frame": (C.c_int, [VP, VP, C.c_size_t, u32, VP, VP]),
     "tgh_develop_host_aux": (C.c_int, [VP, C.c_size_t, u32, u32, VP, VP]),
+    "tgh_nlmeans_host": (C.c_int, [C.POINTER(TgHipNlMeansDesc), VP, VP, VP, VP]),
     "tgh_scheduler_create": (VP, [u32, u32, u32]),
     "tgh_scheduler_num_tiles": (C.c_size_t, [VP]),
     "tgh_scheduler_num_records": (C.c_size_t, [VP]),

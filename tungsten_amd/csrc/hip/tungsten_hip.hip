@@ -2,6 +2,7 @@
 // gfx950 (MI355X) only.  See pt_kernels.h for the execution model and DESIGN.md for the layout.
 #define PT_WAVEFRONT_MAIN
 #include "pt_wavefront.h"
+#include "denoise.h"
 #include "develop.h"
 
 #include <atomic>
@@ -293,6 +294,12 @@ struct tghip_ctx {
     uint32_t *developMax = nullptr;
     bool developHost = false;             // "develop_host"
     double developMs = 0.0;
+    // tghip_nlmeans: the three input planes and the result on the device when they are not the caller's device memory (grown on demand), the
+    // "nlmeans_batch" option (0: the launcher's choice)
+    float *nlmBuf[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t nlmCap[4] = {0, 0, 0, 0};
+    uint32_t nlmBatch = 0;
+    double nlmMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context
     int rankCount = 0, rankIndex = 0;
     float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
@@ -951,6 +958,7 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->developHdr) (void)hipFree(ctx->developHdr);
     if (ctx->developLdr) (void)hipFree(ctx->developLdr);
     if (ctx->developMax) (void)hipFree(ctx->developMax);
+    for (float *b : ctx->nlmBuf) if (b) (void)hipFree(b);
     if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
     if (ctx->redSum) (void)hipFree(ctx->redSum);
@@ -1047,6 +1055,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "fuse_flat") ctx->fuseFlatOpt = value != 0;
     else if (k == "shade_fused") ctx->shadeFusedOpt = value != 0;
     else if (k == "develop_host") ctx->developHost = value != 0;   // tghip_develop answers TGHIP_E_UNSUPPORTED: the host integrator then develops a download itself
+    else if (k == "nlmeans_batch") ctx->nlmBatch = uint32_t(std::min<long long>(std::max<long long>(value, 0), NLMEANS_MAX_BATCH));   // offsets box-filtered at once by tghip_nlmeans (0: the measured choice, denoise.hip)
     else if (k == "run_to_completion") ctx->loopOpt = value != 0;
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
@@ -2519,6 +2528,80 @@ int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms)
 {
     if (!ctx || !ms) return TGHIP_E_INVALID;
     *ms = ctx->developMs;
+    return TGHIP_OK;
+}
+
+int tghip_nlmeans(tghip_ctx *ctx, const TgHipNlMeansDesc *desc, const float *image, const float *guide, const float *variance, float *out)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_nlmeans: no description"; return TGHIP_E_INVALID; }
+    const bool pointers = desc->source == TGHIP_NLMEANS_POINTERS;
+    if (!pointers && desc->source >= TGHIP_AUX_OUTPUTS) { ctx->error = "tghip_nlmeans: unknown source"; return TGHIP_E_INVALID; }
+    uint32_t channels = desc->channels;
+    if (!pointers) channels = (desc->source == TGHIP_AUX_DEPTH || desc->source == TGHIP_AUX_VISIBILITY) ? 1 : 3;
+    if (channels < 1 || channels > 4) { ctx->error = "tghip_nlmeans: channels must be 1..4"; return TGHIP_E_INVALID; }
+    if (desc->F > NLMEANS_MAX_F) { ctx->error = "tghip_nlmeans: F must be 0..8"; return TGHIP_E_INVALID; }
+    if (desc->R > NLMEANS_MAX_R) { ctx->error = "tghip_nlmeans: R must be 0..16"; return TGHIP_E_INVALID; }
+    if (!(desc->k > 0.0f)) { ctx->error = "tghip_nlmeans: k must be positive"; return TGHIP_E_INVALID; }
+    if (desc->width == 0 || desc->height == 0) { ctx->error = "tghip_nlmeans: the image has no pixels"; return TGHIP_E_INVALID; }
+    if (desc->width > (1u << 20) || desc->height > (1u << 20)) { ctx->error = "tghip_nlmeans: the image is too large"; return TGHIP_E_INVALID; }
+    if (!out) { ctx->error = "tghip_nlmeans: no output array"; return TGHIP_E_INVALID; }
+    if (pointers && (!image || !guide || !variance)) { ctx->error = "tghip_nlmeans: image, guide and variance are needed without an aux source"; return TGHIP_E_INVALID; }
+    if (!pointers && (image || guide || variance)) { ctx->error = "tghip_nlmeans: an aux source takes no image, guide or variance pointers"; return TGHIP_E_INVALID; }
+    if (!pointers && (desc->image_part > TGHIP_DEVELOP_B || desc->guide_part > TGHIP_DEVELOP_B)) { ctx->error = "tghip_nlmeans: image_part and guide_part are the mean or a half"; return TGHIP_E_INVALID; }
+    int rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    if (!pointers && (!ctx->haveScene || !ctx->dAux)) { ctx->error = "tghip_nlmeans: no auxiliary output buffers yet (no TGHIP_PASS_AUX pass, no tghip_upload_aux)"; return TGHIP_E_INVALID; }
+    if (!pointers && (desc->width != uint32_t(ctx->width) || desc->height != uint32_t(ctx->height))) { ctx->error = "tghip_nlmeans: an aux source has the frame's size"; return TGHIP_E_INVALID; }
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    const uintptr_t align = channels == 4 ? 15u : 3u;
+    if (device) {
+        const uintptr_t all = reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(guide) | reinterpret_cast<uintptr_t>(variance) | reinterpret_cast<uintptr_t>(out);
+        if (all & align) { ctx->error = "tghip_nlmeans: device arrays must be aligned (to 16 bytes with four channels, to 4 otherwise)"; return TGHIP_E_INVALID; }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t npixels = size_t(desc->width)*desc->height, nfloats = npixels*channels, nbytes = nfloats*sizeof(float);
+    // scratch planes 0..2: image, guide, variance (uploaded, or developed from the aux buffers); 3: the result of a call with host memory
+    const float *in[3] = {image, guide, variance};
+    float *result = out;
+    for (int b = 0; b < 4; ++b) {
+        const bool needed = b < 3 ? (!pointers || !device) : !device;
+        if (!needed || ctx->nlmCap[b] >= nfloats) continue;
+        if (ctx->nlmBuf[b]) (void)hipFree(ctx->nlmBuf[b]);
+        ctx->nlmBuf[b] = nullptr; ctx->nlmCap[b] = 0;
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->nlmBuf[b]), nbytes));
+        ctx->nlmCap[b] = nfloats;
+    }
+    if (pointers && !device)
+        for (int b = 0; b < 3; ++b) {
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->nlmBuf[b], in[b], nbytes, hipMemcpyHostToDevice, ctx->stream));
+            in[b] = ctx->nlmBuf[b];
+        }
+    if (!device) result = ctx->nlmBuf[3];
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    if (!pointers) {
+        if (!ctx->developMax) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developMax), 64));
+        const uint32_t parts[3] = {desc->image_part, desc->guide_part, TGHIP_DEVELOP_VARIANCE};
+        for (int b = 0; b < 3; ++b) {
+            HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux, npixels, desc->source, parts[b], ctx->nlmBuf[b], nullptr, ctx->developMax));
+            in[b] = ctx->nlmBuf[b];
+        }
+    }
+    HIP_TRY(ctx, nlMeansLaunch(ctx->stream, in[0], in[1], in[2], result, desc->width, desc->height, channels, desc->F, desc->R, desc->k,
+                               desc->variance_scale, ctx->nlmBatch));
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    if (result != out) HIP_TRY(ctx, hipMemcpyAsync(out, result, nbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
+    ctx->nlmMs = ms;
+    return TGHIP_OK;
+}
+
+int tghip_nlmeans_kernel_time(tghip_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->nlmMs;
     return TGHIP_OK;
 }
 

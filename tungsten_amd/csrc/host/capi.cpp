@@ -1,6 +1,7 @@
 // extern "C" view of the host classes (include/tungsten_host.h).
 #include "../../../include/tungsten_host.h"
 
+#include "Denoise.hpp"
 #include "Develop.hpp"
 #include "EmbreeTopTree.hpp"
 #include "ImageIO.hpp"
@@ -290,6 +291,15 @@ int tgh_develop_host_aux(const TgHipAuxPixel *aux, size_t npixels, uint32_t outp
 {
     if ((npixels && !aux) || output >= TGHIP_AUX_OUTPUTS || part > TGHIP_DEVELOP_VARIANCE) return -1;
     Develop::aux(aux, npixels, output, part, hdr_out, ldr_out);
+    return 0;
+}
+
+int tgh_nlmeans_host(const TgHipNlMeansDesc *desc, const float *image, const float *guide, const float *variance, float *out)
+{
+    if (!desc || !image || !guide || !variance || !out || desc->source != TGHIP_NLMEANS_POINTERS) return -1;
+    if (desc->channels < 1 || desc->channels > Denoise::MaxChannels || desc->F > Denoise::MaxF || desc->R > Denoise::MaxR) return -1;
+    if (!(desc->k > 0.0f) || desc->width == 0 || desc->height == 0) return -1;
+    Denoise::nlMeans(image, guide, variance, desc->width, desc->height, desc->channels, int(desc->F), int(desc->R), desc->k, desc->variance_scale, out);
     return 0;
 }
 
