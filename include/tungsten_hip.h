@@ -24,6 +24,8 @@
  *   tghip_get_walk_stats    <- (no reference analogue; lane utilisation of the walks).
  *   tghip_debug_libm        <- std::sin / cos / log / exp / acos / atan2 / pow / cbrt on floats as the reference's path calls them (glibc's sinf ... cbrtf):
  *                              the device's restatements evaluated on the device, for the parity tests.
+ *   tghip_debug_bsdf / tghip_debug_bsdf_info <- Bsdf::eval / pdf / sample (bsdfs/Bsdf.hpp:71-97) of single scatter events: the shading kernels'
+ *                              BSDF code on caller-supplied cases, per shading family, for the parity tests.
  *
  * Ownership: the caller owns every host array (borrowed for the duration of the call; the
  * shim copies with hipMemcpyAsync); the shim owns device memory behind the opaque handle.
@@ -606,6 +608,39 @@ enum { TGHIP_LIBM_SINF = 0, TGHIP_LIBM_COSF = 1, TGHIP_LIBM_LOGF = 2, TGHIP_LIBM
        /* double precision (AtmosphericMedium::inverseOpticalDepth: std::exp / log / erf / sqrt on doubles): x and y then point to n DOUBLES */
        TGHIP_LIBM_EXPD = 13, TGHIP_LIBM_LOGD = 14, TGHIP_LIBM_ERFD = 15, TGHIP_LIBM_SQRTD = 16 };
 int tghip_debug_libm(tghip_ctx *ctx, int fn, const float *x, float *y, size_t n);
+/* Self-test of the device's BSDF code (csrc/hip/pt_scene.h: bsdfEval / bsdfPdf / bsdfSample, the wrappers the shading kernels call) on caller-supplied
+ * cases against the uploaded scene's flattened bsdf table, one thread per case (csrc/hip/debug_units.hip), host pointers.  Per case: eval and pdf of
+ * (wi, wo), then sample(wi) drawing from the counter-based stream started as a path's is with (seed, stream, 0), then ONE further number of that
+ * stream -- so the caller, who can produce the same stream, sees how many numbers the sample consumed.  `variant` selects the instantiation: the
+ * BSDF type / feature mask of one shading family (csrc/hip/pt_wavefront.h), each without the Sobol' sampler.  A type outside the variant's mask folds
+ * away exactly as in that family's shading kernel (black eval, zero pdf, failed sample).  Outputs of a failed sample are unspecified.
+ * TGHIP_E_INVALID (context left usable) for null pointers with n > 0, a bsdf index outside the table, an unknown variant, or no scene; n == 0 succeeds. */
+enum { TGHIP_BSDF_VARIANT_LEAN = 0, TGHIP_BSDF_VARIANT_SIMPLE = 1, TGHIP_BSDF_VARIANT_COAT = 2, TGHIP_BSDF_VARIANT_GLASS = 3,
+       TGHIP_BSDF_VARIANT_PLASTIC = 4, TGHIP_BSDF_VARIANT_MEDIA = 5, TGHIP_BSDF_VARIANT_TAIL = 6, TGHIP_BSDF_VARIANT_FULL = 7,
+       TGHIP_BSDF_VARIANT_ALL = 8, TGHIP_BSDF_VARIANT_COUNT = 9 };
+typedef struct TgHipBsdfCase {
+    int32_t  bsdf;            /* index in the flattened table (TgHipSceneDesc::bsdfs) */
+    uint32_t requested;       /* TGHIP_LOBE_* set */
+    float    wi[3], wo[3];    /* local directions (shading normal = +z) */
+    float    uv[2];
+    uint32_t seed, stream;    /* the sampler: rngStart(seed, stream, 0) */
+    uint32_t variant;         /* TGHIP_BSDF_VARIANT_* */
+    uint32_t reserved;
+} TgHipBsdfCase;
+typedef struct TgHipBsdfResult {
+    float    f[3], pdf;                       /* eval, pdf */
+    uint32_t sample_ok;
+    float    sample_wo[3], sample_weight[3], sample_pdf;
+    uint32_t sampled;                         /* the sampled lobe */
+    float    next;                            /* the stream's next number after the sample returned */
+    uint32_t reserved[2];
+} TgHipBsdfResult;
+int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult *results, size_t n);
+/* What the shading-class rule sees of the uploaded scene's bsdfs (num_bsdfs entries each; any pointer may be NULL): type_mask = the set of bsdf types
+ * inside the material, nested ones included (bit = 1 << TGHIP_BSDF_*; bit 19 when a microfacet bsdf inside uses the Phong distribution; bit 24 when a
+ * texture inside is a bitmap), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
+ * materials into shading classes and picks each class's kernel.  variant_mask (one word): the type / feature mask the variant's kernel is compiled for. */
+int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint32_t *forward, uint32_t *covered, uint32_t *variant_mask);
 int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "count_traversal", "max_slots", ...; "top_tree" = 0 before an upload:
                                                                              TgHipSceneDesc::top_nodes is ignored, flat lists are walked in record order.
                                                                              Instrumentation that never changes an image (tests hold that): "lds_tables" = 0

@@ -4453,6 +4453,12 @@ void oracle_rng_stream(uint32_t seed, uint32_t pixelIndex, uint32_t sampleIndex,
     for (int i = 0; i < n; ++i) out[i] = next1D(&smp);
 }
 
+/* n numbers of each of `count` consecutive streams (seed, first + i, 0): out[count][n] */
+void oracle_rng_streams(uint32_t seed, uint32_t first, uint32_t count, int n, float *out)
+{
+    for (uint32_t i = 0; i < count; ++i) oracle_rng_stream(seed, first + i, 0, n, out + (size_t)i*(size_t)n);
+}
+
 void oracle_camera_ray(const TgHipSceneDesc *s, uint32_t px, uint32_t py, float xi0, float xi1, float *o, float *d)
 {
     /* re-uses traceSample's prologue through a replay sampler */
@@ -4508,6 +4514,27 @@ int oracle_bsdf_sample(const TgHipSceneDesc *s, int bi, const float *wi, const f
     *pdf = e.pdf; *sampledLobe = e.sampled;
     if (consumed) *consumed = smp.replay_pos;
     return ok;
+}
+
+/* oracle_bsdf_eval + oracle_bsdf_sample over n cases (tests/bsdf_cases.py): per case bsdf[i], requested[i], wi / wo (3 floats), uv (2), xi (nxi replay
+ * numbers); out: 14 words per case -- f[3], pdf, sample_ok, s_wo[3], s_weight[3], s_pdf, s_lobe, consumed -- the layout of ref_harness bsdf-cases */
+void oracle_bsdf_cases(const TgHipSceneDesc *s, int n, const int32_t *bsdf, const uint32_t *requested, const float *wi, const float *wo,
+                       const float *uv, const float *xi, int nxi, uint32_t *out)
+{
+    #pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        float v[12];
+        uint32_t lobe = 0;
+        int consumed = 0;
+        oracle_bsdf_eval(s, bsdf[i], wi + 3*(size_t)i, wo + 3*(size_t)i, uv + 2*(size_t)i, requested[i], v, v + 3);
+        int ok = oracle_bsdf_sample(s, bsdf[i], wi + 3*(size_t)i, uv + 2*(size_t)i, requested[i], xi + (size_t)nxi*(size_t)i, nxi, v + 5, v + 8, v + 11,
+                                    &lobe, &consumed);
+        uint32_t *o = out + 14*(size_t)i;
+        memcpy(o, v, sizeof(v));
+        o[4] = ok ? 1u : 0u;
+        o[12] = lobe;
+        o[13] = (uint32_t)consumed;
+    }
 }
 
 /* light sampleDirect for light slot `li` from point p; returns 0 when the sample is rejected */

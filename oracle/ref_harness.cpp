@@ -24,6 +24,8 @@
 //       the sky image the scene's skydome baked (512 x 256 x 3 float32).
 //   ref_harness bounds <scene.json> <out.txt>
 //       bounds() of every finite primitive in scene order: the items' boxes of the reference's top-level Embree geometry.
+//   ref_harness bsdf-cases <scene.json> <cases.bin> <out.bin>
+//       eval / pdf / sample of the scene's bsdfs on caller-supplied cases, raw float32 / uint32 in and out.
 //
 // Nothing here is copied from the reference; it only calls its public classes.
 #include <atomic>
@@ -606,6 +608,60 @@ static int cmdUnits(int argc, char **argv)
     return 0;
 }
 
+// ref_harness bsdf-cases <scene.json> <cases.bin> <out.bin>: the units command's BSDF block on caller-supplied cases, binary in and out (no text
+// round trip: NaN, infinities and every last bit survive).  cases.bin: u32 n, u32 nxi; per case i32 bsdf (index in the scene's own list), u32 requested,
+// f32 wi[3], wo[3], uv[2], xi[nxi] (the numbers the sampler replays).  out.bin: per case f32 f[3], pdf; u32 sample_ok; f32 s_wo[3], s_weight[3], s_pdf;
+// u32 s_lobe, consumed -- 14 words (tools/make_bsdf_golden.py -> tests/golden/bsdf_corners.npz).
+static int cmdBsdfCases(int argc, char **argv)
+{
+    if (argc < 5) return 2;
+    ThreadUtils::startThreads(1);
+    Loaded L;
+    const uint32 seed = 0xBA5EBA11u;
+    if (!loadScene(argv[2], seed, L)) return 1;
+    std::ifstream in(argv[3], std::ios::binary);
+    uint32 header[2] = {0, 0};
+    in.read(reinterpret_cast<char *>(header), sizeof(header));
+    if (!in || header[1] > 64) { std::fprintf(stderr, "ref_harness: bad case file\n"); return 1; }
+    const uint32 n = header[0], nxi = header[1];
+    auto &bsdfs = L.scene->bsdfs();
+    std::vector<uint32> out(size_t(n)*14, 0u);
+    std::vector<float> rec(10 + nxi);
+    for (uint32 c = 0; c < n; ++c) {
+        in.read(reinterpret_cast<char *>(rec.data()), std::streamsize(rec.size()*sizeof(float)));
+        if (!in) { std::fprintf(stderr, "ref_harness: case file ends at case %u\n", c); return 1; }
+        int32 bi; uint32 requested;
+        std::memcpy(&bi, &rec[0], 4); std::memcpy(&requested, &rec[1], 4);
+        if (bi < 0 || size_t(bi) >= bsdfs.size()) { std::fprintf(stderr, "ref_harness: case %u names bsdf %d\n", c, bi); return 1; }
+        Bsdf &bsdf = *bsdfs[size_t(bi)];
+        IntersectionInfo info;
+        info.Ng = info.Ns = Vec3f(0.0f, 0.0f, 1.0f);
+        info.p = Vec3f(0.0f); info.w = Vec3f(0.0f, 0.0f, -1.0f);
+        info.uv = Vec2f(rec[8], rec[9]);
+        info.epsilon = 5e-4f; info.primitive = nullptr; info.bsdf = &bsdf;
+        const Vec3f wi(rec[2], rec[3], rec[4]), wo(rec[5], rec[6], rec[7]);
+        GraftPathSampler s(seed);
+        s.setReplay(std::vector<float>(rec.begin() + 10, rec.end()));
+        TangentFrame frame(info.Ns);
+        SurfaceScatterEvent ev(&info, &s, frame, wi, BsdfLobes(requested), false);
+        ev.wo = wo;
+        const Vec3f f = bsdf.eval(ev, false);
+        const float pdf = bsdf.pdf(ev);
+        SurfaceScatterEvent sv(&info, &s, frame, wi, BsdfLobes(requested), false);
+        const bool ok = bsdf.sample(sv, false);
+        uint32 *o = &out[size_t(c)*14];
+        const float vals[12] = {f.x(), f.y(), f.z(), pdf, 0.0f, sv.wo.x(), sv.wo.y(), sv.wo.z(), sv.weight.x(), sv.weight.y(), sv.weight.z(), sv.pdf};
+        std::memcpy(o, vals, sizeof(vals));
+        o[4] = ok ? 1u : 0u;
+        o[12] = *reinterpret_cast<const uint32 *>(&sv.sampledLobe);
+        o[13] = uint32(s.consumed());
+    }
+    std::ofstream os(argv[4], std::ios::binary);
+    os.write(reinterpret_cast<const char *>(out.data()), std::streamsize(out.size()*4));
+    std::fprintf(stderr, "ref_harness: %u bsdf cases on %zu bsdfs\n", n, bsdfs.size());
+    return os ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {
@@ -623,6 +679,7 @@ int main(int argc, char **argv)
     else if (cmd == "draws") rc = cmdDraws(argc, argv);
     else if (cmd == "sky-image") rc = cmdSkyImage(argc, argv);
     else if (cmd == "bounds") rc = cmdBounds(argc, argv);
+    else if (cmd == "bsdf-cases") rc = cmdBsdfCases(argc, argv);
     if (rc == 2) std::fprintf(stderr, "ref_harness: bad arguments\n");
     return rc;
 }

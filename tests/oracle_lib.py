@@ -162,6 +162,16 @@ def rng_stream(seed, pixel, sample, n):
     return out
 
 
+_lib.oracle_rng_streams.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+
+
+def rng_streams(seed, first, count, n):
+    """[count, n]: the first n numbers of the streams (seed, first + i, 0)."""
+    out = np.empty((count, n), np.float32)
+    _lib.oracle_rng_streams(seed & 0xFFFFFFFF, first, count, n, out.ctypes.data)
+    return out
+
+
 def camera_ray(desc, px, py, xi0, xi1):
     o, d = np.empty(3, np.float32), np.empty(3, np.float32)
     _lib.oracle_camera_ray(desc, px, py, xi0, xi1, o.ctypes.data, d.ctypes.data)
@@ -183,6 +193,23 @@ def bsdf_sample(desc, bsdf, wi, uv, requested, xi):
     ok = _lib.oracle_bsdf_sample(desc, bsdf, wi.ctypes.data, uv.ctypes.data, requested & 0xFFFFFFFF, xi.ctypes.data, len(xi),
                                  wo.ctypes.data, weight.ctypes.data, C.byref(pdf), C.byref(lobe), C.byref(consumed))
     return bool(ok), wo, weight, pdf.value, lobe.value, consumed.value
+
+
+_lib.oracle_bsdf_cases.argtypes = [DESC_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+
+
+def bsdf_cases(desc, bsdf, requested, wi, wo, uv, xi):
+    """bsdf_eval + bsdf_sample over n cases at once: [n, 14] uint32 words -- f[3], pdf, sample_ok, s_wo[3], s_weight[3], s_pdf, s_lobe, consumed
+    (the floats as bit patterns) -- the layout the reference harness writes for the same cases."""
+    bsdf = np.ascontiguousarray(bsdf, np.int32)
+    requested = np.ascontiguousarray(requested, np.uint32)
+    wi, wo, uv, xi = [np.ascontiguousarray(v, np.float32) for v in (wi, wo, uv, xi)]
+    n = bsdf.size
+    assert wi.shape == (n, 3) and wo.shape == (n, 3) and uv.shape == (n, 2) and xi.shape[0] == n and requested.shape == (n,)
+    out = np.zeros((n, 14), np.uint32)
+    _lib.oracle_bsdf_cases(desc, n, bsdf.ctypes.data, requested.ctypes.data, wi.ctypes.data, wo.ctypes.data, uv.ctypes.data, xi.ctypes.data,
+                           xi.shape[1], out.ctypes.data)
+    return out
 
 
 def light_sample(desc, light, p, xi0, xi1):

@@ -973,3 +973,127 @@ def _crowd(scene):
 
 GOLDEN_CASES["cornell_crowd"] = (cornell, dict(resolution=(48, 27), spp=8, edit=_crowd))
 GOLDEN_CASES["cornell_crowd_sobol"] = (cornell, dict(resolution=(48, 27), spp=8, edit=_crowd, renderer=_SOBOL))
+
+
+# ---- BSDF corners: every bsdf type with plain parameters, then parameters at and beyond the edges of what the code clamps and divides by ----
+_DISTRIBUTIONS = ("beckmann", "ggx", "phong")
+_CORNER_ROUGHNESS = (0.001, 0.01, 0.05, 1.0, 2.0)        # below, at and above the lower clamp (0.01), at and above the upper (1.0)
+_CORNER_IOR = (1.0, 1.0001, 0.75, 2.5)
+_K0 = {"eta": [0.2, 0.92, 1.1], "k": [0.0, 0.0, 0.0]}
+
+
+def bsdf_corner_list():
+    """The named bsdfs of scenes.bsdf_corners, in scene order.  Nested bsdfs are named ones defined earlier in the list (an INLINE nested
+    bsdf of the reference is never prepared for rendering, see ZOO above)."""
+    def checker(on, off, res=8):
+        return {"type": "checker", "on_color": on, "off_color": off, "res_u": res, "res_v": res}
+    out = []
+
+    def add(name, **kw):
+        out.append(dict(kw, name=name))
+    # every type once, with plain parameters
+    add("plain_lambert", type="lambert", albedo=[0.6, 0.5, 0.4])
+    add("plain_null", type="null", albedo=1)
+    add("plain_forward", type="forward", albedo=1)
+    add("plain_mirror", type="mirror", albedo=[0.9, 0.9, 0.95])
+    add("plain_rough_conductor", type="rough_conductor", distribution="ggx", roughness=0.2, albedo=1, **_CU)
+    add("plain_conductor", type="conductor", albedo=[0.95, 0.9, 0.8], **_CU)
+    add("plain_smooth_coat", type="smooth_coat", ior=1.4, thickness=2.0, sigma_a=[0.3, 0.1, 0.05], albedo=1, substrate="plain_rough_conductor")
+    add("plain_dielectric", type="dielectric", ior=1.5, albedo=1)
+    add("plain_rough_dielectric", type="rough_dielectric", ior=1.45, distribution="beckmann", roughness=0.15, albedo=1)
+    add("plain_plastic", type="plastic", ior=1.5, thickness=1.0, sigma_a=[0.2, 0.4, 0.1], albedo=[0.3, 0.5, 0.7])
+    add("plain_rough_plastic", type="rough_plastic", ior=1.6, thickness=0.5, sigma_a=0.3, distribution="ggx", roughness=0.25, albedo=[0.6, 0.3, 0.2])
+    add("plain_mixed", type="mixed", ratio=0.4, albedo=1, bsdf0="plain_lambert", bsdf1="plain_mirror")
+    add("plain_transparency", type="transparency", alpha=0.6, albedo=1, base="plain_lambert")
+    add("plain_diffuse_transmission", type="diffuse_transmission", albedo=[0.8, 0.7, 0.5])
+    add("plain_phong", type="phong", exponent=40.0, diffuse_ratio=0.3, albedo=[0.14, 0.45, 0.091])
+    add("plain_thinsheet", type="thinsheet", ior=1.5, thickness=0.4, sigma_a=[0.3, 0.1, 0.6], enable_interference=True, albedo=1)
+    add("plain_oren_nayar", type="oren_nayar", roughness=0.6, albedo=[0.63, 0.065, 0.05])
+    add("plain_rough_coat", type="rough_coat", ior=1.4, thickness=1.0, sigma_a=[0.2, 0.1, 0.3], distribution="ggx", roughness=0.2, albedo=1,
+        substrate="plain_lambert")
+    # the microfacet clamps, every distribution
+    for dist in _DISTRIBUTIONS:
+        for r in _CORNER_ROUGHNESS:
+            add("rc_%s_%g" % (dist, r), type="rough_conductor", distribution=dist, roughness=r, albedo=1, **_CU)
+            add("rd_%s_%g" % (dist, r), type="rough_dielectric", distribution=dist, roughness=r, ior=1.5, albedo=1)
+    add("rc_checker_low", type="rough_conductor", distribution="ggx", roughness=checker(0.005, 0.02), albedo=1, **_CU)
+    add("rd_checker_high", type="rough_dielectric", distribution="beckmann", roughness=checker(0.9, 1.5), ior=1.5, albedo=1)
+    for r in (0.001, 1.0):
+        add("rp_%g" % r, type="rough_plastic", ior=1.5, thickness=1.0, sigma_a=[0.2, 0.4, 0.1], distribution="ggx", roughness=r, albedo=[0.3, 0.5, 0.7])
+        add("rcoat_%g" % r, type="rough_coat", ior=1.4, thickness=1.0, sigma_a=[0.2, 0.1, 0.3], distribution="beckmann", roughness=r, albedo=1,
+            substrate="plain_lambert")
+    add("rp_phong", type="rough_plastic", ior=1.5, thickness=1.0, sigma_a=0.2, distribution="phong", roughness=0.2, albedo=[0.3, 0.5, 0.7])
+    add("rcoat_phong", type="rough_coat", ior=1.4, thickness=1.0, sigma_a=0.2, distribution="phong", roughness=0.2, albedo=1, substrate="plain_rough_conductor")
+    add("on_0", type="oren_nayar", roughness=0.0, albedo=[0.63, 0.065, 0.05])
+    add("on_1", type="oren_nayar", roughness=1.0, albedo=[0.63, 0.065, 0.05])
+    add("phong_e1", type="phong", exponent=1.0, diffuse_ratio=0.3, albedo=[0.5, 0.4, 0.3])
+    add("phong_e10000", type="phong", exponent=1e4, diffuse_ratio=0.3, albedo=[0.5, 0.4, 0.3])
+    add("phong_d0", type="phong", exponent=20.0, diffuse_ratio=0.0, albedo=[0.5, 0.4, 0.3])
+    add("phong_d1", type="phong", exponent=20.0, diffuse_ratio=1.0, albedo=[0.5, 0.4, 0.3])
+    # ior at one, a hair above, below one, and large
+    for ior in _CORNER_IOR:
+        add("dielectric_ior%g" % ior, type="dielectric", ior=ior, albedo=1)
+        add("rd_ior%g" % ior, type="rough_dielectric", ior=ior, distribution="ggx", roughness=0.2, albedo=1)
+        add("plastic_ior%g" % ior, type="plastic", ior=ior, thickness=1.0, sigma_a=[0.2, 0.4, 0.1], albedo=[0.3, 0.5, 0.7])
+        add("thinsheet_ior%g" % ior, type="thinsheet", ior=ior, thickness=0.4, sigma_a=[0.3, 0.1, 0.6], albedo=1)
+        add("coat_ior%g" % ior, type="smooth_coat", ior=ior, thickness=1.0, sigma_a=[0.3, 0.1, 0.05], albedo=1, substrate="plain_rough_conductor")
+    add("dielectric_norefr", type="dielectric", ior=1.33, enable_refraction=False, albedo=1)
+    add("rd_norefr", type="rough_dielectric", ior=1.7, distribution="ggx", roughness=0.3, enable_refraction=False, albedo=1)
+    # conductors: explicit eta / k with k = 0 next to the named material
+    add("conductor_k0", type="conductor", albedo=1, **_K0)
+    add("conductor_au", type="conductor", albedo=1, material="Au")
+    add("rc_k0", type="rough_conductor", distribution="ggx", roughness=0.2, albedo=1, **_K0)
+    add("rc_au", type="rough_conductor", distribution="ggx", roughness=0.2, albedo=1, material="Au")
+    # layers: no thickness, no absorption, nearly opaque
+    for tag, kw in (("thick0", dict(thickness=0.0, sigma_a=[0.2, 0.4, 0.1])), ("sigma0", dict(thickness=1.0, sigma_a=0.0)), ("sigma100", dict(thickness=1.0, sigma_a=100.0))):
+        add("plastic_" + tag, type="plastic", ior=1.5, albedo=[0.3, 0.5, 0.7], **kw)
+        add("coat_" + tag, type="smooth_coat", ior=1.4, albedo=1, substrate="plain_rough_conductor", **kw)
+        add("rcoat_" + tag, type="rough_coat", ior=1.4, distribution="ggx", roughness=0.2, albedo=1, substrate="plain_lambert", **kw)
+    add("thinsheet_if_thick0", type="thinsheet", ior=1.5, thickness=0.0, sigma_a=[0.3, 0.1, 0.6], enable_interference=True, albedo=1)
+    add("thinsheet_if_checker", type="thinsheet", ior=1.5, thickness=checker(0.8, 0.2), sigma_a=[0.3, 0.1, 0.6], enable_interference=True, albedo=1)
+    add("thinsheet_sigma0", type="thinsheet", ior=1.5, thickness=0.5, sigma_a=0.0, enable_interference=False, albedo=1)
+    # mixtures and cut-outs at their ends
+    for tag, v in (("0", 0.0), ("1", 1.0), ("checker", checker(0.9, 0.1))):
+        add("mixed_" + tag, type="mixed", ratio=v, albedo=1, bsdf0="plain_rough_conductor", bsdf1="plain_lambert")
+        add("transparency_" + tag, type="transparency", alpha=v, albedo=1, base="plain_lambert")
+    # the deepest nesting the upload accepts (three levels); one branch of each ends in a dielectric
+    add("inner_mixed_glass", type="mixed", ratio=0.3, albedo=1, bsdf0="plain_dielectric", bsdf1="plain_lambert")
+    add("inner_cut_glass", type="transparency", alpha=0.7, albedo=1, base="plain_rough_dielectric")
+    add("inner_coat", type="smooth_coat", ior=1.4, thickness=0.5, sigma_a=[0.3, 0.1, 0.05], albedo=1, substrate="plain_lambert")
+    add("deep_coat_mixed_glass", type="smooth_coat", ior=1.5, thickness=1.0, sigma_a=[0.1, 0.2, 0.3], albedo=1, substrate="inner_mixed_glass")
+    add("deep_cut_mixed_glass", type="transparency", alpha=checker(0.8, 0.3), albedo=1, base="inner_mixed_glass")
+    add("deep_mixed_coat_cut", type="mixed", ratio=0.6, albedo=1, bsdf0="inner_coat", bsdf1="inner_cut_glass")
+    add("deep_rcoat_mixed_glass", type="rough_coat", ior=1.3, thickness=0.5, sigma_a=0.1, distribution="ggx", roughness=0.3, albedo=1, substrate="inner_mixed_glass")
+    # bitmap textures: an interpolated albedo and a nearest-neighbour scalar roughness
+    add("tex_albedo", type="lambert", albedo={"type": "bitmap", "file": "corner_albedo.png", "interpolate": True})
+    add("tex_roughness", type="rough_conductor", distribution="beckmann", albedo=1,
+        roughness={"type": "bitmap", "file": "corner_rough.png", "gamma_correct": False, "interpolate": False}, **_CU)
+    return out
+
+
+CORNER_TEXTURE_SIZE = (8, 4)     # width, height of the two bitmaps (the case generator puts uv on their texel boundaries)
+
+
+def bsdf_corners(tmpdir, **kw):
+    """The Cornell box with the bsdfs of bsdf_corner_list() appended to its list (none of them on a primitive: the loaders keep every
+    named bsdf): the scene of the per-call BSDF comparisons (tests/bsdf_cases.py)."""
+    import numpy as np
+    tmpdir = str(tmpdir)
+    w, h = CORNER_TEXTURE_SIZE
+    y, x = np.mgrid[0:h, 0:w]
+    write_png(os.path.join(tmpdir, "corner_albedo.png"), np.stack([(x*37 + 11) % 256, (y*71 + x*5) % 256, (255 - x*29 - y*13) % 256], axis=-1), 2, filters=(0,))
+    rough = (x + y*w)*8 % 256        # roughness = value/255: 0 (below the lower clamp), 8/255 ... and 1 in the last column
+    rough[:, -1] = 255
+    write_png(os.path.join(tmpdir, "corner_rough.png"), np.stack([rough]*3, axis=-1), 2, filters=(0,))
+
+    def edit(scene):
+        scene["bsdfs"] += bsdf_corner_list()
+    user = kw.pop("edit", None)
+
+    def both(scene):
+        edit(scene)
+        if user:
+            user(scene)
+    kw.setdefault("resolution", (32, 18))
+    kw.setdefault("spp", 2)
+    return cornell(tmpdir, name=kw.pop("name", "bsdf_corners.json"), edit=both, **kw)

@@ -43,7 +43,8 @@ def test_product_library_does_not_link_the_oracle():
 
 def test_ctypes_layout_matches_the_headers(tmp_path):
     structs = ["TgHipBvhNode", "TgHipWideNode", "TgHipPrimRec", "TgHipTriAttr", "TgHipObject", "TgHipBsdf", "TgHipTexture", "TgHipMedium", "TgHipCamera",
-               "TgHipSettings", "TgHipSceneDesc", "TgHipPassDesc", "TgHipAuxPixel", "TgHipCounters", "TgHipRay", "TgHipHit", "TgHostSceneInfo"]
+               "TgHipSettings", "TgHipSceneDesc", "TgHipPassDesc", "TgHipAuxPixel", "TgHipCounters", "TgHipRay", "TgHipHit", "TgHostSceneInfo",
+               "TgHipBsdfCase", "TgHipBsdfResult"]
     src = '#include <stdio.h>\n#include "tungsten_host.h"\nint main(void){\n'
     for s in structs:
         src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (s, s)
@@ -61,12 +62,39 @@ def test_ctypes_layout_matches_the_headers(tmp_path):
     assert C.sizeof(capi.TgHipRay) == 32 and C.sizeof(capi.TgHipHit) == 16
 
 
+def test_ctypes_layout_of_the_bsdf_cases(tmp_path):
+    """TgHipBsdfCase / TgHipBsdfResult (tghip_debug_bsdf): every field of the ctypes mirror and of the numpy record type at the C offset."""
+    fields = {"TgHipBsdfCase": ["bsdf", "requested", "wi", "wo", "uv", "seed", "stream", "variant", "reserved"],
+              "TgHipBsdfResult": ["f", "pdf", "sample_ok", "sample_wo", "sample_weight", "sample_pdf", "sampled", "next", "reserved"]}
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tungsten_hip.h"\nint main(void){\n'
+    for s, names in fields.items():
+        src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (s, s)
+        for n in names:
+            src += 'printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (s, n, s, n)
+    src += 'printf("variants %d\\n", (int)TGHIP_BSDF_VARIANT_COUNT);\nreturn 0;}\n'
+    c = tmp_path/"bsdf.c"
+    c.write_text(src)
+    exe = str(tmp_path/"bsdf")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe])
+    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
+    for s, names in fields.items():
+        ct, dt = getattr(capi, s), {"TgHipBsdfCase": tg.BSDF_CASE_DTYPE, "TgHipBsdfResult": tg.BSDF_RESULT_DTYPE}[s]
+        assert int(got[s]) == C.sizeof(ct) == dt.itemsize, s
+        assert [f[0] for f in ct._fields_] == names == list(dt.names)
+        for n in names:
+            assert int(got["%s.%s" % (s, n)]) == getattr(ct, n).offset == dt.fields[n][1], (s, n)
+    assert C.sizeof(capi.TgHipBsdfCase) == 56 and C.sizeof(capi.TgHipBsdfResult) == 64
+    assert int(got["variants"]) == capi.TGHIP_BSDF_VARIANT_COUNT == len(capi.TGHIP_BSDF_VARIANT_NAMES)
+
+
 def test_error_paths_without_arguments():
     lib = tg.lib
     assert lib.tghip_upload_scene(None, None) == -1
     assert lib.tghip_render_pass(None, None) == -1
     assert lib.tghip_wait(None) == -1
     assert lib.tghip_set_option(None, b"x", 1) == -1
+    assert lib.tghip_debug_bsdf(None, None, None, 0) == -1
+    assert lib.tghip_debug_bsdf_info(None, 0, None, None, None, None) == -1
     lib.tghip_destroy(None)   # no-op
     with pytest.raises(tg.TungstenError):
         tg.FlattenedScene("/nonexistent/scene.json")

@@ -21,6 +21,12 @@ lib = capi.load_library()
 AUX_DTYPE = np.dtype([("a", np.float32, 11), ("b", np.float32, 11), ("variance", np.float32, 11), ("count", np.uint32, 5)])
 RECORD_DTYPE = np.dtype([("sample_count", np.uint32), ("next_sample_count", np.uint32), ("sample_index", np.uint32),
                          ("adaptive_weight", np.float32), ("mean", np.float32), ("running_variance", np.float32)])
+# capi.TgHipBsdfCase / TgHipBsdfResult as numpy record types (Renderer.debug_bsdf)
+BSDF_CASE_DTYPE = np.dtype([("bsdf", np.int32), ("requested", np.uint32), ("wi", np.float32, 3), ("wo", np.float32, 3), ("uv", np.float32, 2),
+                            ("seed", np.uint32), ("stream", np.uint32), ("variant", np.uint32), ("reserved", np.uint32)])
+BSDF_RESULT_DTYPE = np.dtype([("f", np.float32, 3), ("pdf", np.float32), ("sample_ok", np.uint32), ("sample_wo", np.float32, 3),
+                              ("sample_weight", np.float32, 3), ("sample_pdf", np.float32), ("sampled", np.uint32), ("next", np.float32),
+                              ("reserved", np.uint32, 2)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 DEVELOP_PART_NAMES = ("mean", "a", "b", "variance")                          # capi.TGHIP_DEVELOP_*
@@ -152,6 +158,27 @@ class Renderer(object):
         if rc != 0:
             raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
         return y
+
+    def debug_bsdf(self, cases, device=0):
+        """The shading kernels' BSDF code on caller-supplied cases (tghip_debug_bsdf): `cases` an array of BSDF_CASE_DTYPE, the result an
+        array of BSDF_RESULT_DTYPE of the same length."""
+        cases = np.ascontiguousarray(cases, BSDF_CASE_DTYPE).reshape(-1)
+        out = np.zeros(cases.size, BSDF_RESULT_DTYPE)
+        rc = lib.tghip_debug_bsdf(self.context(device), cases.ctypes.data if cases.size else None, out.ctypes.data if cases.size else None, cases.size)
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        return out
+
+    def debug_bsdf_info(self, variant=capi.TGHIP_BSDF_VARIANT_ALL, device=0):
+        """(type_mask, forward, covered) per bsdf of the flattened table, as the shading-class rule sees them, and the mask the variant's kernel is
+        compiled for (tghip_debug_bsdf_info)."""
+        n = int(self.info.num_bsdfs)
+        tm, fwd, cov = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        mask = C.c_uint32(0)
+        rc = lib.tghip_debug_bsdf_info(self.context(device), int(variant), tm.ctypes.data, fwd.ctypes.data, cov.ctypes.data, C.addressof(mask))
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        return tm, fwd.astype(bool), cov.astype(bool), int(mask.value)
 
     def trace_samples(self, spp_begin, spp_end, seed=DEFAULT_SEED, tile_seeds=None, device=0):
         """One TGHIP_PASS_SAMPLES pass on the device (into a cleared framebuffer): the radiance of every individual sample,

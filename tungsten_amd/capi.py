@@ -132,6 +132,21 @@ class TgHipNlMeansDesc(C.Structure):
                 ("source", u32), ("image_part", u32), ("guide_part", u32), ("flags", u32)]
 
 
+(TGHIP_BSDF_VARIANT_LEAN, TGHIP_BSDF_VARIANT_SIMPLE, TGHIP_BSDF_VARIANT_COAT, TGHIP_BSDF_VARIANT_GLASS, TGHIP_BSDF_VARIANT_PLASTIC,
+ TGHIP_BSDF_VARIANT_MEDIA, TGHIP_BSDF_VARIANT_TAIL, TGHIP_BSDF_VARIANT_FULL, TGHIP_BSDF_VARIANT_ALL, TGHIP_BSDF_VARIANT_COUNT) = range(10)
+TGHIP_BSDF_VARIANT_NAMES = ("lean", "simple", "coat", "glass", "plastic", "media", "tail", "full", "all")
+
+
+class TgHipBsdfCase(C.Structure):
+    _fields_ = [("bsdf", i32), ("requested", u32), ("wi", f32*3), ("wo", f32*3), ("uv", f32*2), ("seed", u32), ("stream", u32),
+                ("variant", u32), ("reserved", u32)]
+
+
+class TgHipBsdfResult(C.Structure):
+    _fields_ = [("f", f32*3), ("pdf", f32), ("sample_ok", u32), ("sample_wo", f32*3), ("sample_weight", f32*3), ("sample_pdf", f32),
+                ("sampled", u32), ("next", f32), ("reserved", u32*2)]
+
+
 class TgHipPassDesc(C.Structure):
     _fields_ = [("spp_begin", u32), ("spp_end", u32), ("seed", u32), ("shard_index", u32), ("shard_count", u32),
                 ("flags", u32),
@@ -202,6 +217,8 @@ PROTOTYPES = {
     "tghip_reduce_framebuffers": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, VP, VP, C.c_size_t]),
     "tghip_trace_rays": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
+    "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
+    "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
     "tghip_set_option": (C.c_int, [VP, C.c_char_p, C.c_longlong]),
     "tghip_get_counters": (C.c_int, [VP, C.POINTER(TgHipCounters)]),
     "tghip_reset_counters": (C.c_int, [VP]),

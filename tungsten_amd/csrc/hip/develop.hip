@@ -42,8 +42,7 @@ __device__ __forceinline__ float developPowf(float x, float y)
             return ptlibm::u2f(0x7fc00000u);              // finite x < 0
         ix = (ptlibm::f2u(x*0x1p23f) & 0x7fffffffu) - (23u << 23);   // subnormal: normalised, the exponent below zero
     }
-    float r;
-    return ptlibm::powfCoreBits(ix, y, r) ? r : powf(x, y);
+    return ptlibm::powfCoreBits(ix, y);
 }
 
 // ImageIO::tonemap (cameras/Tonemap.hpp:25-48), one channel

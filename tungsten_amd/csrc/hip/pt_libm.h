@@ -237,10 +237,10 @@ PT_LIBM_FN bool powInRange(float x, float y)
     const uint32_t ix = f2u(x), iy = f2u(y);
     return ix - 0x00800000u < 0x7f800000u - 0x00800000u && (iy & 0x7fffffffu) < 0x7f800000u && (iy & 0x7fffffffu) != 0u;
 }
-// false when y log2(x) is outside (-126, 126): glibc's overflow / underflow paths, left to the caller's fallback.
+// x^y for a positive normal x and a finite non-zero y (powInRange), glibc's overflow / underflow paths (y log2(x) outside (-126, 126)) included.
 // ix: the bits of x -- or, for a subnormal x, what e_powf.c makes of them (the bits of x 2^23 with 23 taken off the exponent field, which wraps
 // below zero: develop.hip's tone mapping is the one caller that meets subnormals)
-PT_LIBM_FN bool powfCoreBits(uint32_t ix, float y, float &result)
+PT_LIBM_FN float powfCoreBits(uint32_t ix, float y)
 {
     const double A0 = 0x1.27616c9496e0bp-2, A1 = -0x1.71969a075c67ap-2, A2 = 0x1.ec70a6ca7baddp-2, A3 = -0x1.7154748bef6c8p-1, A4 = 0x1.71547652ab82bp0;
     const uint32_t tmp = ix - 0x3f330000u;
@@ -259,8 +259,16 @@ PT_LIBM_FN bool powfCoreBits(uint32_t ix, float y, float &result)
     q = __builtin_fma(p, r2, q);
     yy = __builtin_fma(yy, r4, q);                                 // log2(x)
     const double ylogx = (double)y*yy;
-    if (((d2u(ylogx) >> 47) & 0xffffu) >= (d2u(126.0) >> 47))
-        return false;
+    if (((d2u(ylogx) >> 47) & 0xffffu) >= (d2u(126.0) >> 47)) {
+        // |y log2(x)| >= 126, e_powf.c's range checks in round-to-nearest (the base is positive here: no sign to carry): overflow to infinity,
+        // underflow to zero, and between -150 and -149 what __math_may_uflowf's 0x1.4p-75f * 0x1.4p-75f rounds to, the smallest subnormal;
+        // everything else -- subnormal results included -- goes through the same exp2 below, rounded once by the conversion to float.
+        // (Left to the device's own powf, Phong's pow(cos, exponent) with a subnormal result came out two ulps off glibc's:
+        // tests/test_gpu_bsdf_units.py.)
+        if (ylogx > 0x1.fffffffd1d571p+6) return u2f(0x7f800000u);
+        if (ylogx <= -150.0) return 0.0f;
+        if (ylogx < -149.0) return u2f(1u);
+    }
     const double C0 = 0x1.c6af84b912394p-5, C1 = 0x1.ebfce50fac4f3p-3, C2 = 0x1.62e42ff0c52d6p-1, Shift = 0x1.8p+52/32.0;
     double kd = ylogx + Shift;
     const uint64_t ki = d2u(kd);
@@ -271,10 +279,9 @@ PT_LIBM_FN bool powfCoreBits(uint32_t ix, float y, float &result)
     const double rr2 = rr*rr;
     double e = __builtin_fma(C2, rr, 1.0);
     e = __builtin_fma(zz, rr2, e);
-    result = (float)(e*s);
-    return true;
+    return (float)(e*s);
 }
-PT_LIBM_FN bool powfCore(float x, float y, float &result) { return powfCoreBits(f2u(x), y, result); }
+PT_LIBM_FN float powfCore(float x, float y) { return powfCoreBits(f2u(x), y); }
 
 // ---- cbrtf: s_cbrtf.c -- frexp, a quadratic first guess and one Halley step in double, the cube root of the exponent's remainder from a
 // five-entry table, ldexp.  (Insensitive to contraction: every fused and unfused variant gives glibc's result for every float.)

@@ -120,7 +120,7 @@ PT_DEV float expfH(float x) { return ptlibm::expfAll(x); }
 // core covers positive normal x, finite non-zero y and results that are normal floats -- every call site's operands (Davis transmittances:
 // base >= 1, optical depths) --; outside that (zero / subnormal / negative base, overflow, underflow: exact or saturating results) ocml's.
 PT_DEV float atan2fH(float y, float x) { return ptlibm::atan2fCore(y, x); }
-PT_DEV float powfH(float x, float y) { float r; return (ptlibm::powInRange(x, y) && ptlibm::powfCore(x, y, r)) ? r : powf(x, y); }
+PT_DEV float powfH(float x, float y) { return ptlibm::powInRange(x, y) ? ptlibm::powfCore(x, y) : powf(x, y); }
 PT_DEV float cbrtfH(float x) { return ptlibm::cbrtfCore(x); }
 PT_DEV float tanfH(float x) { return ptlibm::tanfCore(x); }      // |x| < 120 (OrenNayarBsdf: angles in [0, pi/2])
 

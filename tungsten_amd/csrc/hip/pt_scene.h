@@ -1160,7 +1160,8 @@ struct BsdfOps {
             if (e.wi.z <= 0.0f || e.wo.z <= 0.0f) return 0.0f;
             return cosineHemispherePdf(e.wo);
         case TGHIP_BSDF_MIRROR: case TGHIP_BSDF_CONDUCTOR:
-            if (!(M & (BSDF_BIT(TGHIP_BSDF_MIRROR) | BSDF_BIT(TGHIP_BSDF_CONDUCTOR)))) return 0.0f;
+            // (each type behind its own bit: MASK_GLASS and MASK_MEDIA hold the mirror without the conductor, and a conductor must be black there)
+            if (!(M & (b.type == TGHIP_BSDF_MIRROR ? BSDF_BIT(TGHIP_BSDF_MIRROR) : BSDF_BIT(TGHIP_BSDF_CONDUCTOR)))) return 0.0f;
             return ((e.requested & TGHIP_LOBE_SPECULAR_R) && checkReflectionConstraint(e.wi, e.wo)) ? 1.0f : 0.0f;
         case TGHIP_BSDF_ROUGH_CONDUCTOR: {                     /* RoughConductorBsdf.cpp:127-143 */
             if (!(M & (BSDF_BIT(TGHIP_BSDF_ROUGH_CONDUCTOR)))) return 0.0f;

@@ -2,6 +2,7 @@
 // gfx950 (MI355X) only.  See pt_kernels.h for the execution model and DESIGN.md for the layout.
 #define PT_WAVEFRONT_MAIN
 #include "pt_wavefront.h"
+#include "debug_units.h"
 #include "denoise.h"
 #include "develop.h"
 
@@ -280,6 +281,8 @@ struct tghip_ctx {
     bool classPresent[PT_NUM_CLASSES] = {false, false, false, false};   // shading classes (pt_kernels.h: PT_NUM_CLASSES) that occur among the records
     uint32_t classMask[PT_NUM_CLASSES] = {0, 0, 0, 0};                  // ... and the BSDF types inside each
     bool haveForward = false;             // some BSDF has a forward lobe (shadow rays attenuate instead of stop)
+    std::vector<uint32_t> bsdfTypes;      // per bsdf of the uploaded scene: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap (tghip_debug_bsdf_info)
+    std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
     bool cameraFix = false;               // equirectangular camera: k_camera_rays rewrites the fresh camera rays before they are traced
@@ -427,6 +430,44 @@ static uint32_t bsdfTypeMask(const TgHipSceneDesc *s, int bi, int depth)
     if (b.type == TGHIP_BSDF_MIXED)
         m |= bsdfTypeMask(s, b.sub0, depth + 1) | bsdfTypeMask(s, b.sub1, depth + 1);
     return m;
+}
+
+// May shading family `variant` (TGHIP_BSDF_VARIANT_*) be given a material with type set `tm` (bsdfTypeMask) and forward lobe `fwd`?  The one
+// statement of the rules the upload and the launch plan apply to type sets (they call it on a material's set or on the union over a class / the scene):
+// the shading classes 0 / 1 / 2 (SIMPLE / COAT / GLASS) take materials without a forward lobe whose types their mask covers, in that order; what is left
+// is class 3, shaded by PLASTIC when all of it fits that mask and by FULL / ALL otherwise; MEDIA takes a media scene whose surface types it covers; TAIL
+// finishes scenes without forward lobes and without the five late types.  LEAN is the exception: the product picks it per SCENE (tghip_upload_scene's
+// `lean`: no bitmap texture anywhere, one quad light, quads and cubes only), so for LEAN this is tghip_debug_bsdf_info's per-material reading of that
+// rule -- SIMPLE's types and no bitmap inside the material (FEAT_BITMAP in tm, set for that entry only) -- and not a site the product calls.
+static bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
+{
+    switch (variant) {
+    case TGHIP_BSDF_VARIANT_LEAN:    return !fwd && (tm & ~MASK_LEAN) == 0;
+    case TGHIP_BSDF_VARIANT_SIMPLE:  return !fwd && (tm & ~MASK_SIMPLE) == 0;
+    case TGHIP_BSDF_VARIANT_COAT:    return !fwd && (tm & ~MASK_COAT) == 0;
+    case TGHIP_BSDF_VARIANT_GLASS:   return !fwd && (tm & ~MASK_GLASS) == 0;
+    case TGHIP_BSDF_VARIANT_PLASTIC: return (tm & ~MASK_PLASTIC) == 0;
+    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0;   // (bits 0 .. 18: the BSDF types)
+    case TGHIP_BSDF_VARIANT_TAIL:    return !fwd && (tm & ~MASK_TAIL) == 0;
+    case TGHIP_BSDF_VARIANT_FULL:    return (tm & ~MASK_FULL) == 0;
+    case TGHIP_BSDF_VARIANT_ALL:     return true;
+    default: return false;
+    }
+}
+
+// does a texture inside bsdf `bi` (nested ones included) hold a bitmap?
+static bool bsdfUsesBitmap(const TgHipSceneDesc *s, int bi, int depth)
+{
+    if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return false;
+    const TgHipBsdf &b = s->bsdfs[bi];
+    const int32_t tex[3] = {b.albedo, b.roughness, b.tex1};
+    for (int32_t t : tex)
+        if (t >= 0 && uint32_t(t) < s->num_textures && s->textures[t].type == TGHIP_TEX_BITMAP) return true;
+    if (b.type == TGHIP_BSDF_SMOOTH_COAT || b.type == TGHIP_BSDF_ROUGH_COAT || b.type == TGHIP_BSDF_TRANSPARENCY)
+        return bsdfUsesBitmap(s, b.sub0, depth + 1);
+    if (b.type == TGHIP_BSDF_MIXED)
+        return bsdfUsesBitmap(s, b.sub0, depth + 1) || bsdfUsesBitmap(s, b.sub1, depth + 1);
+    return false;
 }
 
 // Depth of the subtree under `root` (also validates child references).  `level`: 0 = the scene's tree (leaves: non-instance records and
@@ -820,7 +861,7 @@ static void chooseThreads(tghip_ctx *ctx)
     if (ctx->haveMeshLight || inst) ctx->thrShadeSimple = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
     else ctx->thrShadeSimple = ctx->leanScene ? pickThreads(ctx, k_shade<MASK_LEAN, LEAN_WAVES, 0>, 256, 0) : pickThreads(ctx, k_shade<MASK_SIMPLE, SIMPLE_WAVES, 0>, 256, 0);
     // (one workgroup size for the launches of classes 1 .. 3: that of the largest variant among them)
-    if (ctx->haveMeshLight || inst || (ctx->classPresent[3] && (ctx->classMask[3] & ~MASK_PLASTIC) != 0))
+    if (ctx->haveMeshLight || inst || (ctx->classPresent[3] && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false)))
                                                     ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
     else if (ctx->classPresent[3])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_PLASTIC, 2, 0>, 256, 0);
     else if (ctx->classPresent[2])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_GLASS, 2, 0>, 256, 0);
@@ -1382,6 +1423,12 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
             typeMask[i] = bsdfTypeMask(sd, int(i), 0);
             if (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ctx->haveForward = true;
         }
+        ctx->bsdfTypes.assign(sd->num_bsdfs, 0u);
+        ctx->bsdfForward.assign(sd->num_bsdfs, 0);
+        for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
+            ctx->bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u);
+            ctx->bsdfForward[i] = (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ? 1 : 0;
+        }
         for (uint32_t i = 0; i < sd->num_recs; ++i) {
             uint32_t meta = sd->recs[i].meta;
             if (TGHIP_REC_KIND(meta) == TGHIP_REC_INSTANCE || TGHIP_REC_KIND(meta) == TGHIP_REC_INSTANCE_SET)
@@ -1393,7 +1440,8 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
             // the smallest family that covers every type inside the material (nested ones included); forward lobes -> "everything else"
             const uint32_t tm = typeMask[size_t(bi)];
             const bool fwd = (sd->bsdfs[bi].lobes & TGHIP_LOBE_FORWARD) != 0;
-            const int c = (!fwd && (tm & ~MASK_SIMPLE) == 0) ? 0 : (!fwd && (tm & ~MASK_COAT) == 0) ? 1 : (!fwd && (tm & ~MASK_GLASS) == 0) ? 2 : 3;
+            const int c = familyCovers(TGHIP_BSDF_VARIANT_SIMPLE, tm, fwd) ? 0 : familyCovers(TGHIP_BSDF_VARIANT_COAT, tm, fwd) ? 1 :
+                          familyCovers(TGHIP_BSDF_VARIANT_GLASS, tm, fwd) ? 2 : 3;
             recClass[i] = uint8_t(c);
             ctx->classPresent[c] = true;
             ctx->classMask[c] |= tm;
@@ -1402,7 +1450,7 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
         {
             uint32_t allTypes = 0;
             for (int c = 0; c < PT_NUM_CLASSES; ++c) allTypes |= ctx->classMask[c];
-            ctx->mediaSimple = ctx->haveMedia && !ctx->haveInstances && (allTypes & ~MASK_MEDIA & 0x7FFFFu) == 0;   // (bits 0 .. 18: the BSDF types)
+            ctx->mediaSimple = ctx->haveMedia && !ctx->haveInstances && familyCovers(TGHIP_BSDF_VARIANT_MEDIA, allTypes, false);
         }
         bool lean = sd->num_infinite_lights == 0 && sd->num_lights <= 1;
         for (uint32_t i = 0; i < sd->num_textures && lean; ++i) lean = sd->textures[i].type != TGHIP_TEX_BITMAP;
@@ -1558,7 +1606,7 @@ static void launchShade(tghip_ctx *ctx, int grid, const PathState &st, const Pas
 template<int FUSE>
 static void launchComplexClass(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int cls)
 {
-    const bool plasticOnly = (ctx->classMask[3] & ~MASK_PLASTIC) == 0;
+    const bool plasticOnly = familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false);
     if constexpr (FUSE == 0) {
         if (ctx->haveInstances) {
             if (cls == 1)                     launchShade<MASK_COAT_INST>(ctx, grid, st, pp, cls);
@@ -1586,7 +1634,7 @@ static int shadeFusedPair(const tghip_ctx *ctx)
     int further = 0, n = 0;
     for (int c = 1; c < PT_NUM_CLASSES; ++c)
         if (ctx->classPresent[c]) { further = c; ++n; }
-    if (n != 1 || (further == 3 && (ctx->classMask[3] & ~MASK_PLASTIC) != 0))
+    if (n != 1 || (further == 3 && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false)))
         return 0;
     return further;
 }
@@ -1740,8 +1788,8 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     }
     // k_tail runs the wide single-level kernels' bodies: scenes those kernels render, passes without visit counts (per-launch timing does
     // not see it: the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
-    const bool tailEligible = ctx->tailOpt && !ctx->cameraFix && ctx->tablesFit && !flat && !ctx->haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt && !ctx->haveForward &&
-                              (ctx->complexMask & TYPES_LATE) == 0 &&
+    const bool tailEligible = ctx->tailOpt && !ctx->cameraFix && ctx->tablesFit && !flat && !ctx->haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt &&
+                              familyCovers(TGHIP_BSDF_VARIANT_TAIL, ctx->complexMask, ctx->haveForward) &&
                               !ctx->haveMeshLight && !ctx->haveMedia && !ctx->auxPass && !ctx->haveCylinder && !count &&
                               st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
     const uint64_t tailThreshold = uint64_t(std::max<long long>(ctx->tailThreshold, 0));
@@ -2766,6 +2814,50 @@ int tghip_debug_libm(tghip_ctx *ctx, int fn, const float *x, float *y, size_t n)
     (void)hipFree(dx);
     if (dy) (void)hipFree(dy);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    return TGHIP_OK;
+}
+
+// the BSDF wrappers exactly as the shading kernels call them, per shading family (debug_units.hip)
+int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult *results, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (n == 0) return TGHIP_OK;
+    if (!cases || !results || n > 0x3FFFFFFFu) { ctx->error = "invalid bsdf self-test arguments"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "bsdf self-test without an uploaded scene"; return TGHIP_E_INVALID; }
+    uint32_t variants = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (cases[i].bsdf < 0 || uint32_t(cases[i].bsdf) >= ctx->scene.num_bsdfs) { ctx->error = "bsdf self-test: bsdf index outside the scene's table"; return TGHIP_E_INVALID; }
+        if (cases[i].variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "bsdf self-test: unknown variant"; return TGHIP_E_INVALID; }
+        variants |= 1u << cases[i].variant;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TgHipBsdfCase *dc = nullptr;
+    TgHipBsdfResult *dr = nullptr;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dc), n*sizeof(TgHipBsdfCase)));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dr), n*sizeof(TgHipBsdfResult));
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, cases, n*sizeof(TgHipBsdfCase), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dr, 0, n*sizeof(TgHipBsdfResult), ctx->stream);
+    if (e == hipSuccess) e = debugBsdfLaunch(ctx->stream, ctx->scene, dc, dr, uint32_t(n), variants);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dr, n*sizeof(TgHipBsdfResult), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dc);
+    if (dr) (void)hipFree(dr);
+    if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    return TGHIP_OK;
+}
+
+int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint32_t *forward, uint32_t *covered, uint32_t *variant_mask)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!ctx->haveScene) { ctx->error = "bsdf self-test without an uploaded scene"; return TGHIP_E_INVALID; }
+    if (variant < 0 || variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "bsdf self-test: unknown variant"; return TGHIP_E_INVALID; }
+    if (variant_mask) *variant_mask = debugBsdfVariantMask(uint32_t(variant));
+    for (size_t i = 0; i < ctx->bsdfTypes.size(); ++i) {
+        if (type_mask) type_mask[i] = ctx->bsdfTypes[i];
+        if (forward) forward[i] = ctx->bsdfForward[i];
+        if (covered) covered[i] = familyCovers(uint32_t(variant), ctx->bsdfTypes[i], ctx->bsdfForward[i] != 0) ? 1u : 0u;
+    }
     return TGHIP_OK;
 }
 
