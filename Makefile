@@ -56,6 +56,8 @@ $(OBJDIR)/tail.o: HIPFLAGS := $(if $(HIPOPT),$(HIPFLAGS),$(subst -O3,$(TAILOPT),
 WALKOPT ?= -Os
 SHADOWOPT ?= -O1
 $(OBJDIR)/tungsten_hip.o: HIPFLAGS := $(if $(HIPOPT),$(HIPFLAGS),$(subst -O3,$(WALKOPT),$(HIPFLAGS)))
+# (walk_shadow_tex.hip: the shim's closest-hit shadow walk once more, for scenes with `disk` / `blade` textures -- built like the shim's)
+$(OBJDIR)/walk_shadow_tex.o: HIPFLAGS := $(if $(HIPOPT),$(HIPFLAGS),$(subst -O3,$(WALKOPT),$(HIPFLAGS)))
 $(OBJDIR)/walk_shadow.o: HIPFLAGS := $(if $(HIPOPT),$(HIPFLAGS),$(subst -O3,$(SHADOWOPT),$(HIPFLAGS)))
 
 $(OBJDIR)/%.o: tungsten_amd/csrc/hip/%.hip $(HIPHDR)

@@ -300,7 +300,14 @@ typedef struct TgHipMedium {
 enum { TGHIP_MEDIUM_HOMOGENEOUS = 0, TGHIP_MEDIUM_EXPONENTIAL = 1, TGHIP_MEDIUM_ATMOSPHERE = 2 };
 
 /* ---- textures ------------------------------------------------------------------------- */
-enum { TGHIP_TEX_CONSTANT = 0, TGHIP_TEX_CHECKER = 1, TGHIP_TEX_BITMAP = 2 };
+/* textures/TextureFactory.cpp:11-18.  An `ies` texture (textures/IesTexture.cpp) is a scalar bitmap the host bakes at load: it arrives as TGHIP_TEX_BITMAP.
+ * TGHIP_TEX_DISK  (textures/DiskTexture.cpp):  value = _value; every other field unused.
+ * TGHIP_TEX_BLADE (textures/BladeTexture.cpp): value = _value and, in fields the type does not otherwise use, what BladeTexture::init (:22-31) leaves:
+ *     res_u = _numBlades          scale = _angle
+ *     on_color[0] = _bladeAngle   on_color[1] = _area        on_color[2] = 1.0f/_area (the pdf inside the polygon)
+ *     off_color[0], [1] = _baseNormal                        off_color[2], pad = _baseEdge
+ * Both are evaluated by the all-features shading family only (a scene that holds one is shaded by it throughout). */
+enum { TGHIP_TEX_CONSTANT = 0, TGHIP_TEX_CHECKER = 1, TGHIP_TEX_BITMAP = 2, TGHIP_TEX_DISK = 3, TGHIP_TEX_BLADE = 4 };
 #define TGHIP_TEXF_LINEAR 1u
 #define TGHIP_TEXF_CLAMP  2u
 #define TGHIP_TEXF_RGB    4u
@@ -638,7 +645,8 @@ typedef struct TgHipBsdfResult {
 int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult *results, size_t n);
 /* What the shading-class rule sees of the uploaded scene's bsdfs (num_bsdfs entries each; any pointer may be NULL): type_mask = the set of bsdf types
  * inside the material, nested ones included (bit = 1 << TGHIP_BSDF_*; bit 19 when a microfacet bsdf inside uses the Phong distribution; bit 24 when a
- * texture inside is a bitmap), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
+ * texture inside is a bitmap; bits 20 - 23 together when the scene holds a `disk` or `blade` texture anywhere -- such a scene is shaded by the all-features
+ * family throughout, so TGHIP_BSDF_VARIANT_ALL alone covers its entries), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
  * materials into shading classes and picks each class's kernel.  variant_mask (one word): the type / feature mask the variant's kernel is compiled for. */
 int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint32_t *forward, uint32_t *covered, uint32_t *variant_mask);
 int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "count_traversal", "max_slots", ...; "top_tree" = 0 before an upload:

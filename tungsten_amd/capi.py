@@ -53,6 +53,11 @@ class TgHipTexture(C.Structure):
                 ("avg", f32*3), ("pad", f32), ("texel_offset", i64), ("dist_offset", i64)]
 
 
+# TgHipTexture.type (an `ies` texture is baked by the host and arrives as TGHIP_TEX_BITMAP)
+(TGHIP_TEX_CONSTANT, TGHIP_TEX_CHECKER, TGHIP_TEX_BITMAP, TGHIP_TEX_DISK, TGHIP_TEX_BLADE) = range(5)
+(TGHIP_TEXF_LINEAR, TGHIP_TEXF_CLAMP, TGHIP_TEXF_RGB, TGHIP_TEXF_VALID) = (1, 2, 4, 8)    # TgHipTexture.flags
+
+
 class TgHipMedium(C.Structure):
     _fields_ = [("sigma_a", f32*3), ("sigma_s", f32*3), ("sigma_t", f32*3), ("absorption_only", i32), ("max_bounce", i32),
                 ("phase_type", i32), ("phase_g", f32), ("trans_type", i32), ("trans_p", f32*3),

@@ -88,6 +88,14 @@ struct DeviceScene {
 #define FEAT_PHONG      (1u << 19)   /* microfacet BSDFs with the Phong distribution (pow(double, double)): only in the MASK_FULL / BSDF_MASK_ALL variants */
 #define FEAT_BUMP       (1u << 20)   /* bump-mapped shading frames (Primitive::setupTangentFrame, TgHipBsdf::bump1): only in the BSDF_MASK_ALL variant */
 #define MASK_FULL       (BSDF_MASK_ALL & ~(FEAT_QMC | FEAT_MEDIA | FEAT_AUX | FEAT_CYLINDER | FEAT_BUMP))
+// The marker of the all-features family: the four feature bits that only BSDF_MASK_ALL (and its FEAT_QMC twin, which it is itself) carries together.
+// Code for the procedural `disk` and `blade` textures (TGHIP_TEX_DISK / TGHIP_TEX_BLADE) is compiled only where all four are set -- the mask has no
+// bit left for a FEAT_ of their own, and a scene that holds one is shaded by that family throughout (tungsten_hip.hip: haveProcTex).  The closest-hit
+// shadow walk of scenes WITHOUT such a texture instantiates its BSDF code with MASK_ALL_NO_PROCTEX: no function it calls looks at FEAT_AUX, so
+// its instructions are those of BSDF_MASK_ALL before these textures existed.
+#define FEAT_FAMILY_ALL (FEAT_MEDIA | FEAT_AUX | FEAT_CYLINDER | FEAT_BUMP)
+#define HAS_PROCTEX(M)  ((((M) & FEAT_FAMILY_ALL)) == FEAT_FAMILY_ALL)
+#define MASK_ALL_NO_PROCTEX (BSDF_MASK_ALL & ~FEAT_AUX)
 // next1D of the path's sampler inside code templated on M
 #define RNG1D(r) rngNext1DT<(M & FEAT_QMC) != 0>(r)
 
@@ -117,6 +125,66 @@ PT_DEV int wrapIndex(int i, int n)
     return r;
 }
 
+// DiskTexture::operator[] / pdf (textures/DiskTexture.cpp:51-54, 75-78): is uv inside the circle of diameter one around (0.5, 0.5)?
+PT_DEV bool diskTexInside(float u, float v)
+{
+    const float du = u - 0.5f, dv = v - 0.5f;
+    return du*du + dv*dv < 0.25f;
+}
+// (real calls, not inlined: arc tangent, sine and cosine would otherwise be copied into every texture lookup of the all-features family and
+// push its BSDF code over the inliner's limits -- scenes without these textures then pay a compare and a branch per lookup, nothing more)
+#define PT_TEX_CALL __device__ __attribute__((noinline))
+// BladeTexture::operator[] / pdf (textures/BladeTexture.cpp:73-87, 125-138): is uv inside the regular polygon?  The point is turned into the
+// sector of the first blade and tested against that blade's edge (_baseNormal = (nx, ny)); (0, 0) -- the uv of a primitive that has none --
+// counts as inside.  angle = _angle, bladeAngle = _bladeAngle.
+PT_TEX_CALL bool bladeTexInside(float angle, float bladeAngle, float nx, float ny, float u, float v)
+{
+    if (u + v == 0.0f)
+        return true;
+    const float gx = u*2.0f - 1.0f, gy = v*2.0f - 1.0f;
+    float phi = atan2fH(gy, gx) - angle;
+    phi = -(floorf(phi/bladeAngle)*bladeAngle + angle);
+    float sinPhi, cosPhi;
+    sincosfH(phi, sinPhi, cosPhi);
+    const float lx = gx*cosPhi - gy*sinPhi, ly = gy*cosPhi + gx*sinPhi;
+    return !(nx*(lx - 1.0f) + ny*(ly - 0.0f) > 0.0f);
+}
+// the blade's parameters where the flattened texture carries them (tungsten_hip.h): scale = _angle, on_color[0] = _bladeAngle, off_color[0], [1] = _baseNormal
+PT_DEV bool bladeTexInside(const TgHipTexture &t, float u, float v) { return bladeTexInside(t.scale, t.on_color[0], t.off_color[0], t.off_color[1], u, v); }
+// Texture::sample(MAP_SPHERICAL, xi) of the two (the jacobian is ignored: DiskTexture.cpp:70-73, BladeTexture.cpp:103-123); blades = 0: the disk.
+// (ex, ey) = _baseEdge.
+PT_TEX_CALL float2 procTexSample(int blades, float angle, float bladeAngle, float ex, float ey, float xi0, float xi1)
+{
+    if (blades == 0) {
+        float phi = xi0*PT_TWO_PI, r = sqrtf(xi1);                     // SampleWarp::uniformDisk (SampleWarp.hpp:64-69)
+        float sinPhi, cosPhi;
+        sincosfH(phi, sinPhi, cosPhi);
+        return make_float2(cosPhi*r*0.5f + 0.5f, sinPhi*r*0.5f + 0.5f);
+    }
+    float bu = xi0*(float)blades;
+    int blade = (int)bu;
+    bu -= (float)blade;
+    float phi = angle + (float)blade*bladeAngle;
+    float sinPhi, cosPhi;
+    sincosfH(phi, sinPhi, cosPhi);
+    float uSqrt = sqrtf(bu);
+    float alpha = 1.0f - uSqrt, beta = (1.0f - xi1)*uSqrt;
+    float lx = (1.0f + ex)*beta + (1.0f - alpha - beta), ly = ey*beta;
+    return make_float2((lx*cosPhi - ly*sinPhi)*0.5f + 0.5f, (ly*cosPhi + lx*sinPhi)*0.5f + 0.5f);
+}
+PT_DEV void procTexSample(const TgHipTexture &t, float xi0, float xi1, float &u, float &v)
+{
+    const float2 uv = procTexSample(t.type == TGHIP_TEX_DISK ? 0 : t.res_u, t.scale, t.on_color[0], t.off_color[2], t.pad, xi0, xi1);
+    u = uv.x; v = uv.y;
+}
+// Texture::pdf(MAP_SPHERICAL, uv): uniformDiskPdf()*4 inside the disk, 1/_area inside the polygon (t.on_color[2]), 0 outside
+PT_DEV float procTexPdf(const TgHipTexture &t, float u, float v)
+{
+    if (t.type == TGHIP_TEX_DISK)
+        return diskTexInside(u, v) ? PT_INV_PI*4.0f : 0.0f;
+    return bladeTexInside(t, u, v) ? t.on_color[2] : 0.0f;
+}
+
 template<uint32_t M>
 PT_DEV f3 textureEval(const DeviceScene &s, int texIdx, float u0, float v0)
 {
@@ -126,6 +194,12 @@ PT_DEV f3 textureEval(const DeviceScene &s, int texIdx, float u0, float v0)
     if (t.type == TGHIP_TEX_CHECKER) {
         int ui = (int)(u0*(float)t.res_u), vi = (int)(v0*(float)t.res_v);
         return ((ui ^ vi) & 1) ? ld3(t.on_color) : ld3(t.off_color);
+    }
+    if constexpr (HAS_PROCTEX(M)) {
+        if (t.type == TGHIP_TEX_DISK)
+            return diskTexInside(u0, v0) ? ld3(t.value) : splat3(0.0f);
+        if (t.type == TGHIP_TEX_BLADE)
+            return bladeTexInside(t, u0, v0) ? ld3(t.value) : splat3(0.0f);
     }
     if (!(M & FEAT_BITMAP))
         return splat3(0.0f);
@@ -1838,7 +1912,7 @@ PT_DEV void intersectionInfo(const DeviceScene &s, const RayD &ray, float4 hit, 
 }
 
 // BitmapTexture::derivatives (textures/BitmapTexture.cpp:359-398) of a scalar bitmap (bump maps are requested as scalars, Bsdf.cpp:24):
-// central differences of the four texels around the lookup, interpolated; constant and checker textures have none
+// central differences of the four texels around the lookup, interpolated; constant, checker, disk and blade textures have none
 PT_DEV void textureDerivatives(const DeviceScene &s, int texIdx, float u0, float v0, float &du, float &dv)
 {
     const TgHipTexture &t = s.textures[texIdx];
@@ -2010,6 +2084,10 @@ PT_DEV float lightDirectPdf(const DeviceScene &s, int objIdx, f3 w, f3 p, const 
     if (o.type == TGHIP_OBJ_POINT)                             /* Point::directPdf (Point.cpp:117-121) */
         return lengthSq(p - ld3(o.pos));
     const TgHipTexture &t = s.textures[o.emission];
+    if constexpr (HAS_PROCTEX(M)) {
+        if (t.type == TGHIP_TEX_DISK || t.type == TGHIP_TEX_BLADE)     /* the texture's own pdf (InfiniteSphere.cpp:223-228) */
+            return PT_INV_PI*PT_INV_TWO_PI*procTexPdf(t, lh.u, lh.v)/lh.sinTheta;
+    }
     if (!(M & FEAT_BITMAP) || t.type != TGHIP_TEX_BITMAP)
         return PT_INV_FOUR_PI;
     // (u, v, sinTheta) = infDirectionToUV(o, w): lightIntersect computed exactly that for this direction (InfiniteSphere::directPdf,
@@ -2181,6 +2259,15 @@ PT_DEV bool lightSampleDirect(const DeviceScene &s, int objIdx, f3 p, Rng &rng, 
     const TgHipTexture &t = s.textures[o.emission];
     float xi0 = RNG1D(rng), xi1 = RNG1D(rng);
     dist = PT_INF;
+    if constexpr (HAS_PROCTEX(M)) {
+        if (t.type == TGHIP_TEX_DISK || t.type == TGHIP_TEX_BLADE) {   /* the texture's own sample / pdf (InfiniteSphere.cpp:168-174) */
+            float u, v, sinTheta;
+            procTexSample(t, xi0, xi1, u, v);
+            d = infUvToDirection(o, u, v, sinTheta);
+            pdf = PT_INV_PI*PT_INV_TWO_PI*procTexPdf(t, u, v)/sinTheta;
+            return pdf != 0.0f;
+        }
+    }
     if (!(M & FEAT_BITMAP) || t.type != TGHIP_TEX_BITMAP) {
         d = uniformSphere(xi0, xi1);
         pdf = PT_INV_FOUR_PI;

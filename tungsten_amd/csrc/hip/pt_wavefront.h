@@ -2096,7 +2096,10 @@ __global__ __launch_bounds__(256, W) void k_shade_fused(DeviceScene sg, PathStat
 // a closest-hit query up to the light; unoccluded iff nothing is hit or the closest hit is the
 // light itself (endCap); surfaces with a forward lobe attenuate and the ray continues (FORWARD variant only:
 // scenes without a forward-lobe BSDF run the lean variant).
-template<bool COUNT, bool FORWARD, bool FLAT, int INST = 0>
+// MS: the mask the walk's BSDF, texture and emitter code is instantiated with -- MASK_ALL_NO_PROCTEX (pt_scene.h) for every scene without a `disk` or
+// `blade` texture, BSDF_MASK_ALL for those with one: a `transparency` surface whose alpha is such a texture is evaluated HERE when a shadow ray
+// crosses it (explicit instantiations: walk_shadow_tex.hip).
+template<bool COUNT, bool FORWARD, bool FLAT, int INST = 0, uint32_t MS = MASK_ALL_NO_PROCTEX>
 __global__ __launch_bounds__(512) void k_trace_shadow(DeviceScene s, PathState st, PassParams pp, uint32_t iterTag)
 {
     extern __shared__ int ldsStack[];
@@ -2171,16 +2174,22 @@ __global__ __launch_bounds__(512) void k_trace_shadow(DeviceScene s, PathState s
                         const f3 bh = mk3(fmaxf(fmaxf(b.x, p1.x), fmaxf(p2.x, p3.x)), fmaxf(fmaxf(b.y, p1.y), fmaxf(p2.y, p3.y)), fmaxf(fmaxf(b.z, p1.z), fmaxf(p2.z, p3.z)));
                         found = embreeBoxVisible(ray.o, ray.d, ray.tmin, ray.tmax, bl, bh);
                     }
-                    if (medium >= 0)                             // TraceBase.cpp:103-112: ray.farT() is the hit distance when anything was hit
+                    // The reference multiplies a see-through surface's transparency into the throughput BEFORE the segment's medium transmittance
+                    // (TraceBase.cpp:97, 104-112).  The walk of scenes with a `disk` / `blade` texture keeps that order (REF_ORDER); the others multiply the
+                    // medium's first, as they always did -- the same bits wherever the transparency is 1 (a `forward` boundary) or there is no medium, which
+                    // is every such golden; a fractional alpha inside a medium can differ in the last bit there.
+                    constexpr bool REF_ORDER = HAS_PROCTEX(MS);
+                    const bool passesOn = ri >= 0 && hitObject != endCap;
+                    if (medium >= 0 && !(REF_ORDER && passesOn))  // TraceBase.cpp:103-112: ray.farT() is the hit distance when anything was hit
                         transmittance = transmittance*mediumTransmittance(s, medium, ray.o, ray.d, found ? hit.x : ray.tmax, startsOnSurface, true);
                     if (ri < 0 || hitObject == endCap) {
                         if (bounce < s.settings.min_bounces) transmittance = splat3(0.0f);
                         if (meshLight) {
                             // attenuatedEmission on a mesh light (TraceBase.cpp:144-174, TriangleMesh.cpp:344-355,469-473,493-496)
                             Info li;
-                            intersectionInfo<BSDF_MASK_ALL>(s, ray, hit, li);
+                            intersectionInfo<MS>(s, ray, hit, li);
                             const TgHipObject &lo = s.objects[endCap];
-                            f3 e = lightEvalDirect<BSDF_MASK_ALL>(s, endCap, li.u, li.v, li.backSide);
+                            f3 e = lightEvalDirect<MS>(s, endCap, li.u, li.v, li.backSide);
                             float total = travelled + hit.x;
                             if (r == 0) {
                                 if (total*(1.0f + 1e-3f) < sd.w) { e = splat3(0.0f); visValid = false; }   // a nearer part of the mesh than the sampled point
@@ -2193,7 +2202,7 @@ __global__ __launch_bounds__(512) void k_trace_shadow(DeviceScene s, PathState s
                         break;
                     }
                     Info info;
-                    intersectionInfo<BSDF_MASK_ALL>(s, ray, hit, info, hitInst);
+                    intersectionInfo<MS>(s, ray, hit, info, hitInst);
                     const uint32_t lobes = s.bsdfs[info.bsdf].lobes;
                     if (!(lobes & TGHIP_LOBE_FORWARD)) { transmittance = splat3(0.0f); break; }
                     Frame frame = frameFromNormal(info.Ns);
@@ -2205,9 +2214,11 @@ __global__ __launch_bounds__(512) void k_trace_shadow(DeviceScene s, PathState s
                     Event fe;
                     fe.wi = toLocal(frame, -ray.d); fe.wo = -fe.wi;
                     fe.requested = TGHIP_LOBE_FORWARD; fe.u = info.u; fe.v = info.v; fe.rng = nullptr;
-                    f3 transparency = bsdfEval<FORWARD ? BSDF_MASK_ALL : 0u>(s, info.bsdf, fe);
+                    f3 transparency = bsdfEval<FORWARD ? MS : 0u>(s, info.bsdf, fe);
                     if (isZero(transparency)) { transmittance = splat3(0.0f); break; }
                     transmittance = transmittance*transparency;
+                    if (REF_ORDER && medium >= 0)
+                        transmittance = transmittance*mediumTransmittance(s, medium, ray.o, ray.d, hit.x, startsOnSurface, true);
                     bounce++;
                     if (bounce >= s.settings.max_bounces) { transmittance = splat3(0.0f); break; }
                     if (s.num_media)                             // :115-116

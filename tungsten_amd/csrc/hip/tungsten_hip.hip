@@ -70,6 +70,15 @@ extern template __global__ void k_trace_shadow_fast_inst<false, false>(DeviceSce
 extern template __global__ void k_trace_shadow_fast_inst<false, true>(DeviceScene, PathState, PassParams, uint32_t);
 extern template __global__ void k_trace_shadow_fast_inst<true, false>(DeviceScene, PathState, PassParams, uint32_t);
 extern template __global__ void k_trace_shadow_fast_inst<true, true>(DeviceScene, PathState, PassParams, uint32_t);
+// walk_shadow_tex.hip: the closest-hit shadow walk of scenes that hold a `disk` or `blade` texture
+extern template __global__ void k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<true, true, false, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<true, true, true, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<true, true, false, 1, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
+extern template __global__ void k_trace_shadow<true, true, false, 2, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
 extern template __global__ void k_tail<MASK_TAIL, false>(DeviceScene, PathState, PassParams, uint32_t);
 extern template __global__ void k_tail<MASK_TAIL, true>(DeviceScene, PathState, PassParams, uint32_t);
 extern template __global__ void k_tail<(MASK_TAIL | FEAT_QMC), false>(DeviceScene, PathState, PassParams, uint32_t);
@@ -281,7 +290,7 @@ struct tghip_ctx {
     bool classPresent[PT_NUM_CLASSES] = {false, false, false, false};   // shading classes (pt_kernels.h: PT_NUM_CLASSES) that occur among the records
     uint32_t classMask[PT_NUM_CLASSES] = {0, 0, 0, 0};                  // ... and the BSDF types inside each
     bool haveForward = false;             // some BSDF has a forward lobe (shadow rays attenuate instead of stop)
-    std::vector<uint32_t> bsdfTypes;      // per bsdf of the uploaded scene: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap (tghip_debug_bsdf_info)
+    std::vector<uint32_t> bsdfTypes;      // per bsdf of the uploaded scene: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when the scene holds a disk / blade texture (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
@@ -318,6 +327,8 @@ struct tghip_ctx {
     int thrShadeAll = 256;                // workgroup size of k_shade<BSDF_MASK_ALL> (media scenes, TGHIP_PASS_AUX passes)
     bool haveCylinder = false;            // cylinder primitives -- or a bump-mapped bsdf (TgHipBsdf::bump1): BSDF_MASK_ALL shading (the only FEAT_CYLINDER /
                                           // FEAT_BUMP variant), never fused
+    bool haveProcTex = false;             // a `disk` or `blade` texture (TGHIP_TEX_DISK / _BLADE): evaluated by the all-features family only -- sets haveCylinder (BSDF_MASK_ALL
+                                          // shading, never fused, no k_tail) and sends a closest-hit shadow walk to k_trace_shadow<., true, ., ., BSDF_MASK_ALL>
     bool haveMedia = false;               // participating media: BSDF_MASK_ALL shading (the only FEAT_MEDIA variant), closest-hit shadow walk, never fused
     bool haveInstances = false;           // instance records: two-level traversal kernels (INST), MASK_FULL shading, never the flat list
     bool hoistOpt = true;                 // "hoist_quad": the scene's one quad tested before the decoupled walks instead of inside them (at the next upload)
@@ -447,7 +458,7 @@ static bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
     case TGHIP_BSDF_VARIANT_COAT:    return !fwd && (tm & ~MASK_COAT) == 0;
     case TGHIP_BSDF_VARIANT_GLASS:   return !fwd && (tm & ~MASK_GLASS) == 0;
     case TGHIP_BSDF_VARIANT_PLASTIC: return (tm & ~MASK_PLASTIC) == 0;
-    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0;   // (bits 0 .. 18: the BSDF types)
+    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0 && !HAS_PROCTEX(tm);   // (bits 0 .. 18: the BSDF types; tghip_debug_bsdf_info's marker of a disk / blade scene)
     case TGHIP_BSDF_VARIANT_TAIL:    return !fwd && (tm & ~MASK_TAIL) == 0;
     case TGHIP_BSDF_VARIANT_FULL:    return (tm & ~MASK_FULL) == 0;
     case TGHIP_BSDF_VARIANT_ALL:     return true;
@@ -850,6 +861,9 @@ static void chooseThreads(tghip_ctx *ctx)
         ctx->thrShadow = ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false>, 256, 3);
     else if (!flat && !ctx->haveForward && !ctx->haveMeshLight && dyn)
         ctx->thrShadow = ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_dyn<false, true>, 256, 2) : pickThreads(ctx, k_trace_shadow_dyn<false, false>, 256, 2);   // measured: 192 / 256 / 320 / 384 threads = 525 / 462 / 633 / 619 us per launch
+    else if (ctx->haveProcTex && (ctx->haveForward || ctx->haveMeshLight))
+        ctx->thrShadow = inst ? (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>, 512, 1))
+                              : flat ? pickThreads(ctx, k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>, 512, 1);
     else if (inst)
         ctx->thrShadow = (ctx->haveForward || ctx->haveMeshLight)
                        ? (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2>, 512, 1))
@@ -1167,6 +1181,12 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
             if (sd->num_inst_prims && !sd->inst_prims) return bad("scene with instances without inst_prims");
         }
     }
+    for (uint32_t i = 0; i < sd->num_textures; ++i) {
+        const TgHipTexture &t = sd->textures[i];
+        if (t.type < TGHIP_TEX_CONSTANT || t.type > TGHIP_TEX_BLADE) { ctx->error = "unknown texture type"; return TGHIP_E_UNSUPPORTED; }
+        // a blade's sampling picks one of res_u sectors and its lookups divide by the sector's angle
+        if (t.type == TGHIP_TEX_BLADE && (t.res_u < 1 || !(t.on_color[0] > 0.0f))) { ctx->error = "blade texture without blades"; return TGHIP_E_INVALID; }
+    }
     int depth = bvhDepthOf(sd, &ctx->bvhMasterDepth);
     if (depth < 0 || depth > TGHIP_MAX_BVH_DEPTH) { ctx->error = "malformed or too deep BVH"; return TGHIP_E_INVALID; }
     for (uint32_t i = 0; i < sd->num_bsdfs; ++i)
@@ -1279,6 +1299,10 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
         if (sd->bsdfs[i].bump1 < 0 || uint32_t(sd->bsdfs[i].bump1) > sd->num_textures) { ctx->error = "bsdf bump map index out of range"; return TGHIP_E_INVALID; }
         if (sd->bsdfs[i].bump1 > 0) ctx->haveCylinder = true;      // (shaded by the same one variant)
     }
+    ctx->haveProcTex = false;
+    for (uint32_t i = 0; i < sd->num_textures; ++i)
+        if (sd->textures[i].type == TGHIP_TEX_DISK || sd->textures[i].type == TGHIP_TEX_BLADE) ctx->haveProcTex = true;
+    if (ctx->haveProcTex) ctx->haveCylinder = true;                // (that variant again: the only one that evaluates them, pt_scene.h HAS_PROCTEX)
     if (ctx->haveMedia) {
         if (!sd->media || sd->num_media > PT_MAX_MEDIA) { ctx->error = "more than 126 media are not supported"; return TGHIP_E_UNSUPPORTED; }
         if (sd->num_objects >= (1u << 16)) { ctx->error = "media scenes support at most 65535 primitives"; return TGHIP_E_UNSUPPORTED; }
@@ -1426,7 +1450,9 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
         ctx->bsdfTypes.assign(sd->num_bsdfs, 0u);
         ctx->bsdfForward.assign(sd->num_bsdfs, 0);
         for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
-            ctx->bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u);
+            // (FEAT_FAMILY_ALL: the scene holds a `disk` or `blade` texture, so every material of it is shaded by the all-features family -- no other
+            // family covers the entry)
+            ctx->bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u) | (ctx->haveProcTex ? FEAT_FAMILY_ALL : 0u);
             ctx->bsdfForward[i] = (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ? 1 : 0;
         }
         for (uint32_t i = 0; i < sd->num_recs; ++i) {
@@ -1654,6 +1680,14 @@ static bool launchShadow(tghip_ctx *ctx, int grid, const PathState &st, const Pa
     const bool flat = isFlat(ctx);
     const bool closestWalk = ctx->haveForward || ctx->haveMeshLight;   // shadow rays are closest-hit walks, not any-hit queries
     const bool wideShadow = wideShadowRays(ctx) && !closestWalk && !ctx->auxPass;
+    if (ctx->haveProcTex && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels)
+#define SHADOW_TEX(FLAT, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, true, FLAT, I, BSDF_MASK_ALL>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
+        if (ctx->haveInstances) { if (ctx->haveSolids) SHADOW_TEX(false, 1); else SHADOW_TEX(false, 2); }
+        else if (flat) SHADOW_TEX(true, 0);
+        else           SHADOW_TEX(false, 0);
+#undef SHADOW_TEX
+        return false;
+    }
     if (ctx->haveInstances && !wideShadow) {
 #define SHADOW_INST(FWD, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, FWD, false, I>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
         if (closestWalk) { if (ctx->haveSolids) SHADOW_INST(true, 1); else SHADOW_INST(true, 2); }

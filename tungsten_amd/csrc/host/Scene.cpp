@@ -2,6 +2,9 @@
 #include "SkyModel.hpp"
 #include "ImageIO.hpp"
 
+#include <algorithm>
+#include <cctype>
+#include <cstdlib>
 #include <thread>
 #include <cstdio>
 #include <cstring>
@@ -117,6 +120,8 @@ Vec3f Texture::average() const
     switch (type) {
     case Constant: return value;
     case Checker:  return (onColor + offColor)*0.5f;          // CheckerTexture.cpp:49-52
+    case Disk:     return PI*0.25f*value;                     // DiskTexture.cpp:36-39
+    case Blade:    return bladeArea*value;                    // BladeTexture.cpp:58-61
     default:       return scale*texAvg;                       // BitmapTexture.cpp:283-286
     }
 }
@@ -124,7 +129,7 @@ Vec3f Texture::average() const
 Vec3f Texture::maximum() const
 {
     switch (type) {
-    case Constant: return value;
+    case Constant: case Disk: case Blade: return value;
     case Checker:  return vmax(onColor, offColor);
     default:       return scale*texMax;
     }
@@ -133,10 +138,219 @@ Vec3f Texture::maximum() const
 void Texture::scaleValues(float f)
 {
     switch (type) {
-    case Constant: value = value*f; break;
+    case Constant: case Disk: case Blade: value = value*f; break;   // DiskTexture.cpp:80-83, BladeTexture.cpp:140-143
     case Checker:  onColor = onColor*f; offColor = offColor*f; break;
     default:       scale *= f; break;
     }
+}
+
+// BladeTexture::init (textures/BladeTexture.cpp:22-31), float for float
+void Texture::initBlade()
+{
+    bladeAngle = TWO_PI/blades;
+    float sinAngle = std::sin(bladeAngle*0.5f);
+    float cosAngle = std::cos(bladeAngle*0.5f);
+    bladeArea = 0.25f*0.5f*blades*std::sin(bladeAngle);
+    const float k = std::sin(PI/blades);                       // _baseEdge = Vec2f(-sinAngle, cosAngle)*2.0f*sin(pi/n)
+    bladeEdge[0] = -sinAngle*2.0f*k;
+    bladeEdge[1] = cosAngle*2.0f*k;
+    bladeNormal[0] = cosAngle;
+    bladeNormal[1] = sinAngle;
+}
+
+// The text of an IES file as IesTexture::loadResources reads it through an istringstream: operator>> skips white space, takes the longest
+// prefix that is a number and rounds it correctly (strtof / strtol here); the first extraction that finds no number fails the stream, and
+// every later one then leaves nothing (zero here).
+namespace {
+struct IesReader
+{
+    const std::string &s;
+    size_t p = 0;
+    bool ok = true;
+    explicit IesReader(const std::string &text) : s(text) {}
+    bool getline(std::string &line)
+    {
+        if (!ok || p >= s.size()) { ok = false; return false; }
+        size_t e = s.find('\n', p);
+        if (e == std::string::npos) { line = s.substr(p); p = s.size(); }
+        else { line = s.substr(p, e - p); p = e + 1; }
+        return true;
+    }
+    void skipWs() { while (p < s.size() && std::isspace(static_cast<unsigned char>(s[p]))) ++p; }
+    int readInt()
+    {
+        if (!ok) return 0;
+        skipWs();
+        const char *b = s.c_str() + p;
+        char *e = nullptr;
+        long v = std::strtol(b, &e, 10);
+        if (e == b) { ok = false; return 0; }
+        p += size_t(e - b);
+        return int(v);
+    }
+    float readRawFloat()
+    {
+        if (!ok) return 0.0f;
+        skipWs();
+        const char *b = s.c_str() + p;
+        char *e = nullptr;
+        float v = std::strtof(b, &e);
+        if (e == b) { ok = false; return 0.0f; }
+        p += size_t(e - b);
+        return v;
+    }
+    // readFloat (IesTexture.cpp:78-87): a comma DIRECTLY at the read position is dropped (peek() skips no white space)
+    float readFloat()
+    {
+        if (ok && p < s.size() && s[p] == ',') ++p;
+        return readRawFloat();
+    }
+};
+}
+
+// IesTexture::loadResources (textures/IesTexture.cpp:89-214) restated: header, angle lists, candelas, wrapHorzAngles (:45-73), then per texel the
+// two lower_bound searches and the bilinear mix of the four candelas around it, divided by the maximum at the end.  A file that cannot be read
+// (or that holds no angles) gives texels of INV_TWO_PI.  The constructor chain IesTexture() -> BitmapTexture() leaves _valid FALSE and nothing
+// sets it afterwards, so the reference looks an IES bake up without interpolation and without _scale (BitmapTexture.cpp:302, 325-330) whatever
+// _linear says: `valid` stays false here too.
+void Texture::bakeIes(const std::string &file)
+{
+    type = Bitmap;
+    rgb = false; linear = true; clamp = false; valid = false;
+    const int res = iesResolution;
+    if (res <= 0 || res > 8192)
+        throw std::runtime_error("IES texture: resolution out of range");
+    w = res*2; h = res;
+    texels.assign(size_t(w)*h, 0.0f);
+
+    std::string data;
+    {
+        std::ifstream in(file.c_str(), std::ios::binary);
+        if (in && !file.empty()) {
+            std::stringstream ss;
+            ss << in.rdbuf();
+            data = ss.str();
+        }
+    }
+    std::vector<float> vertAngles, horzAngles, candelas;
+    int photometricType = 0, verticalCount = 0;
+    IesReader in(data);
+    std::string line;
+    while (in.getline(line)) {
+        if (line.find("TILT=") == std::string::npos)
+            continue;
+        if (line.find("TILT=INCLUDE") != std::string::npos) {   // skip TILT data
+            in.getline(line);
+            int numAngles = in.readInt();
+            for (int i = 0; i < numAngles*2; ++i)
+                in.readRawFloat();
+        }
+        in.readInt();                       // numLamps
+        in.readRawFloat();                  // lumensPerLamp
+        in.readRawFloat();                  // candelaMultiplier (not applied: the bake is normalised)
+        verticalCount = in.readInt();
+        int horizontalCount = in.readInt();
+        photometricType = in.readInt();
+        in.readInt();                       // unitType
+        for (int i = 0; i < 6; ++i)         // width, height, length, ballast, future, watts
+            in.readRawFloat();
+        // (a header that is not one: no angles, which gives the fall-back below instead of lists of a size read from garbage)
+        if (!in.ok || verticalCount < 0 || horizontalCount < 0 || verticalCount > (1 << 12) || horizontalCount > (1 << 12))
+            verticalCount = horizontalCount = 0;
+        for (int i = 0; i < verticalCount; ++i)
+            vertAngles.push_back(in.readFloat());
+        for (int i = 0; i < horizontalCount; ++i)
+            horzAngles.push_back(in.readFloat());
+        for (int i = 0; i < verticalCount*horizontalCount; ++i)
+            candelas.push_back(in.readFloat());
+        break;
+    }
+
+    std::vector<int> horzIndex, vertIndex;
+    for (size_t i = 0; i < horzAngles.size(); ++i) horzIndex.push_back(int(i));
+    for (size_t i = 0; i < vertAngles.size(); ++i) vertIndex.push_back(int(i));
+
+    if (photometricType == 1 && !horzAngles.empty()) {         // wrapHorzAngles
+        if (horzAngles.back() == 0.0f) {
+            horzAngles.clear(); horzAngles.push_back(0.0f); horzAngles.push_back(360.0f);
+            horzIndex.clear(); horzIndex.push_back(0); horzIndex.push_back(0);
+        }
+        if (horzAngles.back() == 90.0f) {
+            int numEntries = int(horzAngles.size());
+            for (int i = numEntries - 2; i >= 0; --i) {
+                horzAngles.push_back(180.0f - horzAngles[size_t(i)]);
+                horzIndex.push_back(horzIndex[size_t(i)]);
+            }
+            horzAngles.back() = 180.0f;
+        }
+        if (horzAngles.back() == 180.0f) {
+            int numEntries = int(horzAngles.size());
+            for (int i = numEntries - 2; i >= 0; --i) {
+                horzAngles.push_back(360.0f - horzAngles[size_t(i)]);
+                horzIndex.push_back(horzIndex[size_t(i)]);
+            }
+            horzAngles.back() = 360.0f;
+        }
+    }
+
+    if (horzAngles.empty() || vertAngles.empty()) {
+        for (float &t : texels) t = INV_TWO_PI;
+        finishBitmap();
+        return;
+    }
+
+    float maxValue = 0.0f;
+    for (int y = 0; y < res; ++y) {
+        for (int x = 0; x < res*2; ++x) {
+            float u = (x + 0.5f)/(res*2);
+            float v = (y + 0.5f)/res;
+            float horz = u*360.0f;
+            float vert = (1.0f - v)*180.0f;
+            if (photometricType != 1) {
+                if (horz > 180.0f) horz -= 360.0f;
+                if (vert > 90.0f) vert -= 180.0f;
+            }
+            int row0 = -1, row1 = -1, col0 = -1, col1 = -1;
+            if (photometricType == 1 || (horz >= horzAngles.front() && horz <= horzAngles.back())) {
+                auto top = std::lower_bound(horzAngles.begin(), horzAngles.end(), horz);
+                if (top == horzAngles.end())
+                    top = std::lower_bound(horzAngles.begin(), horzAngles.end(), horz - 360.0f);
+                if (top != horzAngles.end()) {
+                    row1 = int(top - horzAngles.begin());
+                    row0 = top == horzAngles.begin() ? int(horzIndex.size()) - 1 : int(top - 1 - horzAngles.begin());
+                }
+            }
+            if (vert >= vertAngles.front() && vert <= vertAngles.back()) {
+                auto top = std::lower_bound(vertAngles.begin(), vertAngles.end(), vert);
+                if (top != vertAngles.end()) {
+                    col1 = int(top - vertAngles.begin());
+                    col0 = top == vertAngles.begin() ? col1 : int(top - 1 - vertAngles.begin());
+                }
+            }
+            float value = 0.0f;
+            if (row0 != -1 && row1 != -1 && col0 != -1 && col1 != -1) {
+                float horz0 = horzAngles[size_t(row0)], horz1 = horzAngles[size_t(row1)];
+                float vert0 = vertAngles[size_t(col0)], vert1 = vertAngles[size_t(col1)];
+                if (horz0 > horz1)
+                    horz0 -= 360.0f;
+                auto candela = [&](int row, int col) -> float {
+                    size_t i = size_t(horzIndex[size_t(row)])*size_t(verticalCount) + size_t(vertIndex[size_t(col)]);
+                    return i < candelas.size() ? candelas[i] : 0.0f;
+                };
+                float c00 = candela(row0, col0), c01 = candela(row0, col1);
+                float c10 = candela(row1, col0), c11 = candela(row1, col1);
+                float fu = horz0 == horz1 ? 0.0f : (horz - horz0)/(horz1 - horz0);
+                float fv = vert0 == vert1 ? 0.0f : (vert - vert0)/(vert1 - vert0);
+                value = (c00*(1.0f - fu) + c10*fu)*(1.0f - fv)
+                      + (c01*(1.0f - fu) + c11*fu)*fv;
+            }
+            texels[size_t(x) + size_t(y)*size_t(res)*2] = value;
+            maxValue = std::max(maxValue, value);
+        }
+    }
+    if (maxValue != 0.0f)
+        for (float &t : texels) t /= maxValue;
+    finishBitmap();
 }
 
 void Texture::loadBitmap(const std::string &file)
@@ -500,6 +714,26 @@ std::shared_ptr<Texture> Scene::fetchTexture(const JsonValue &v, bool rgb, bool 
             v.getField("clamp", t->clamp);
             v.getField("scale", t->scale);
             return cached(t);
+        } else if (type == "disk") {                               // DiskTexture::fromJson (textures/DiskTexture.cpp:18-21)
+            t->type = Texture::Disk;
+            getVec3(v, "value", t->value);
+        } else if (type == "blade") {                              // BladeTexture::fromJson (textures/BladeTexture.cpp:33-41)
+            t->type = Texture::Blade;
+            v.getField("blades", t->blades);
+            v.getField("angle", t->bladeOffset);
+            getVec3(v, "value", t->value);
+            if (t->blades < 1)
+                throw JsonLoadException("a blade texture needs at least one blade");
+            t->initBlade();
+        } else if (type == "ies") {                                // IesTexture::fromJson (textures/IesTexture.cpp:27-32): no other key is read
+            t->type = Texture::Bitmap;
+            t->ies = true;
+            t->rgb = false;
+            std::string file;
+            if (v.getField("file", file))
+                t->path = _srcDir.empty() ? file : _srcDir + "/" + file;
+            v.getField("resolution", t->iesResolution);
+            _iesTextures.push_back(t);
         } else {
             throw JsonLoadException("Texture type '" + type + "' is outside the path_tracer_hip hot-path scope");
         }
@@ -1407,6 +1641,9 @@ void Scene::loadResources()
     for (auto &kv : _textureCache)
         if (!kv.second->valid)
             kv.second->loadBitmap(kv.second->path);
+    for (auto &t : _iesTextures)
+        if (t->texels.empty())
+            t->bakeIes(t->path);
 }
 
 std::unique_ptr<Scene> Scene::load(const std::string &jsonPath)

@@ -22,9 +22,18 @@ namespace tungsten_amd {
 // ---- textures (src/core/textures) ---------------------------------------------------
 struct Texture
 {
-    enum Type { Constant = 0, Checker = 1, Bitmap = 2 };
+    enum Type { Constant = 0, Checker = 1, Bitmap = 2, Disk = 3, Blade = 4 };   // (an `ies` texture is a Bitmap whose texels bakeIes() wrote)
     Type type = Constant;
-    Vec3f value = Vec3f(1.0f);                 // ConstantTexture
+    Vec3f value = Vec3f(1.0f);                 // ConstantTexture; DiskTexture / BladeTexture: _value
+    // BladeTexture (textures/BladeTexture.cpp:14-31): _numBlades, _angle and what init() derives from them
+    int blades = 6;
+    float bladeOffset = 0.5f*PI/6, bladeAngle = 0.0f, bladeArea = 0.0f;
+    float bladeEdge[2] = {0.0f, 0.0f}, bladeNormal[2] = {0.0f, 0.0f};
+    void initBlade();
+    // IesTexture (textures/IesTexture.cpp): the profile baked into 2 resolution x resolution scalar texels
+    bool ies = false;
+    int iesResolution = 256;
+    void bakeIes(const std::string &file);     // IesTexture::loadResources + BitmapTexture::init
     Vec3f onColor = Vec3f(0.8f), offColor = Vec3f(0.2f); // CheckerTexture.cpp:11-30
     int resU = 20, resV = 20;
     // BitmapTexture: float texels (.hdr), or 8-bit ones (.png) converted once to the floats the reference's lookups produce
@@ -230,6 +239,7 @@ class Scene
     friend struct Camera;                      // (a thin-lens camera's bitmap aperture goes through fetchTexture)
     std::string _srcDir;
     mutable std::vector<std::pair<std::string, std::shared_ptr<Texture>>> _textureCache;
+    mutable std::vector<std::shared_ptr<Texture>> _iesTextures;   // (TextureCache serves bitmaps only: every `ies` texture is baked on its own)
 
     // autoAlpha: TexelConversion::REQUEST_AUTO (TransparencyBsdf's "alpha"): the alpha channel where the decoder reports one -- for a .png
     // always (io/ImageIO.cpp:386-407 decodes to RGBA and reports 4 channels) --, else the average

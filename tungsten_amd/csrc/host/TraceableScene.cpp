@@ -371,6 +371,20 @@ void TraceableScene::flatten()
             d.texel_offset = int64_t(_texels.size());
             _texels.insert(_texels.end(), t->texels.begin(), t->texels.end());
         }
+        if (t->type == Texture::Disk || t->type == Texture::Blade) {
+            // only `value` speaks for a disk; a blade's parameters travel in the fields it does not otherwise use (tungsten_hip.h)
+            std::memset(d.on_color, 0, sizeof(d.on_color));
+            std::memset(d.off_color, 0, sizeof(d.off_color));
+            d.res_u = d.res_v = 0;
+            d.scale = 0.0f;
+        }
+        if (t->type == Texture::Blade) {
+            d.res_u = t->blades;
+            d.scale = t->bladeOffset;
+            d.on_color[0] = t->bladeAngle; d.on_color[1] = t->bladeArea; d.on_color[2] = 1.0f/t->bladeArea;
+            d.off_color[0] = t->bladeNormal[0]; d.off_color[1] = t->bladeNormal[1];
+            d.off_color[2] = t->bladeEdge[0]; d.pad = t->bladeEdge[1];
+        }
         int32_t idx = int32_t(_textures.size());
         _textures.push_back(d);
         texIndex[t.get()] = idx;
