@@ -21,7 +21,8 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
-HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h
+# (the shim reads what csrc/host/SceneCheck.cpp decided about a scene: SceneTraits)
+HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp
 # -ffp-contract=off: no FMA contraction, so device arithmetic rounds like the CPU reference/oracle
 # (DESIGN.md "Numerics"); TG_FAST=1 allows contraction.
 FPFLAGS  := $(if $(TG_FAST),-ffp-contract=fast,-ffp-contract=off)
@@ -36,7 +37,8 @@ HIPFLAGS := --offload-arch=$(ARCH) $(if $(HIPOPT),$(HIPOPT),-O3) -std=c++17 -fPI
 
 all: $(LIBDIR)/$(LIBNAME) $(if $(PROFILE)$(VARIANT),,$(LIBDIR)/tungsten_hip oracle/liboracle.so oracle/libm_host.so)
 
-$(OBJDIR)/host_%.o: tungsten_amd/csrc/host/%.cpp $(wildcard tungsten_amd/csrc/host/*.hpp) include/tungsten_hip.h include/tungsten_host.h
+# (pt_variants.h: the kernel variants' type / feature masks, which SceneCheck.cpp sorts materials by)
+$(OBJDIR)/host_%.o: tungsten_amd/csrc/host/%.cpp $(wildcard tungsten_amd/csrc/host/*.hpp) include/tungsten_hip.h include/tungsten_host.h tungsten_amd/csrc/hip/pt_variants.h
 	@mkdir -p $(OBJDIR)
 	g++ $(HOSTFLAGS) -c $< -o $@
 

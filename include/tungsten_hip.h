@@ -202,8 +202,8 @@ typedef struct TgHipTriAttr {
 enum { TGHIP_OBJ_MESH = 0, TGHIP_OBJ_QUAD = 1, TGHIP_OBJ_CUBE = 2, TGHIP_OBJ_SPHERE = 3,
        TGHIP_OBJ_INFINITE_SPHERE = 4, TGHIP_OBJ_INSTANCES = 5, TGHIP_OBJ_DISK = 6,
        TGHIP_OBJ_INFINITE_SPHERE_CAP = 7,     /* sun-like emitter: normal = _capDir, scale[0] = _cosCapAngle, edge0/edge1 = _capFrame tangent/bitangent (InfiniteSphereCap.cpp:233-249) */
-       TGHIP_OBJ_POINT = 8,
-       TGHIP_OBJ_CYLINDER = 9 };              /* primitives/Cylinder.cpp:305-319: pos = _pos, rot = _rot, normal = _axis, scale = {_radius, _halfHeight, _capped ? 1 : 0} */                 /* Dirac point light (primitives/Point.cpp): pos = _pos, scale = _power as Point.cpp:186 leaves it; never hit, sampled without random numbers */
+       TGHIP_OBJ_POINT = 8,                   /* Dirac point light (primitives/Point.cpp): pos = _pos, scale = _power as Point.cpp:186 leaves it; never hit, sampled without random numbers */
+       TGHIP_OBJ_CYLINDER = 9 };              /* primitives/Cylinder.cpp:305-319: pos = _pos, rot = _rot, normal = _axis, scale = {_radius, _halfHeight, _capped ? 1 : 0} */
 #define TGHIP_OBJF_SMOOTH   1u   /* mesh "smooth": Ns interpolated (TriangleMesh.cpp:344-355) */
 #define TGHIP_OBJF_SAMPLE   2u   /* infinite_sphere "sample" (InfiniteSphere.cpp:117-122)      */
 #define TGHIP_OBJF_SKYDOME  4u   /* a TGHIP_OBJ_INFINITE_SPHERE that is the `skydome` primitive (primitives/Skydome.cpp): its emission is the
@@ -508,6 +508,9 @@ void        tghip_destroy(tghip_ctx *ctx);
 const char *tghip_last_error(tghip_ctx *ctx);      /* ctx may be NULL: last create error */
 int         tghip_device_count(void);
 
+/* A description that is refused (TGHIP_E_INVALID / TGHIP_E_UNSUPPORTED: malformed, or outside what the device code supports) leaves the context exactly as it
+ * was: the scene uploaded before stays uploaded and renders on.  Every such refusal is decided on the host before the device is touched, by the check
+ * tgh_scene_check (tungsten_host.h) runs on its own. */
 int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *scene);
 int tghip_render_pass(tghip_ctx *ctx, const TgHipPassDesc *pass);   /* asynchronous */
 int tghip_wait(tghip_ctx *ctx);

@@ -169,6 +169,21 @@ int tgh_top_tree_for_scene(const TgHipObject *objects, uint32_t num_objects, con
  * a record kind (TGHIP_REC_*) whose bounds are not restated. */
 int tgh_leaf_bounds(const TgHipObject *object, uint32_t kind, float lo[3], float hi[3]);
 
+/* What tghip_upload_scene decides about a description before it touches the device (csrc/host/SceneCheck.cpp), on its own, no device: TGHIP_OK, or the
+ * upload's refusal -- its code (TGHIP_E_INVALID / TGHIP_E_UNSUPPORTED) and in `err` its message -- under the default options.  `out` (may be NULL)
+ * receives the facts the launch code branches on: flags (0 / 1), the stack depths of the BVH2 and the wide BVH walks and their parts inside a master,
+ * the shading classes present among the records and the BSDF types inside each, the quad hoisted out of the wide walks and the environment map
+ * whose marginal tables ride in LDS (-1: none). */
+typedef struct TgHostSceneTraits {
+    int32_t  have_media, have_instances, have_mesh_light, have_forward, have_solids, all_features_shading, have_proc_tex;
+    int32_t  lean_scene, media_simple, thinlens, camera_fix, have_complex, top_tree, tables_fit;
+    int32_t  bvh_depth, bvh_master_depth, wide_depth, wide_master_depth;
+    int32_t  class_present[4];
+    uint32_t class_mask[4], complex_mask;
+    int32_t  hoisted_rec, env_tex;
+} TgHostSceneTraits;
+int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may be NULL */, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

@@ -192,6 +192,13 @@ class TgHostSceneInfo(C.Structure):
                 ("adaptive_sampling", i32), ("stratified_sampler", i32), ("current_spp", u32)]
 
 
+class TgHostSceneTraits(C.Structure):
+    _fields_ = [(n, i32) for n in ("have_media", "have_instances", "have_mesh_light", "have_forward", "have_solids", "all_features_shading", "have_proc_tex",
+                                   "lean_scene", "media_simple", "thinlens", "camera_fix", "have_complex", "top_tree", "tables_fit",
+                                   "bvh_depth", "bvh_master_depth", "wide_depth", "wide_master_depth")] + \
+               [("class_present", i32*4), ("class_mask", u32*4), ("complex_mask", u32), ("hoisted_rec", i32), ("env_tex", i32)]
+
+
 # every symbol the two headers declare: name -> (restype, argtypes)
 VP = C.c_void_p
 TGHIP_COMM_ID_BYTES = 128
@@ -279,6 +286,7 @@ PROTOTYPES = {
     "tgh_top_tree_build": (C.c_int, [VP, C.c_uint32, VP, C.c_uint32]),
     "tgh_top_tree_for_scene": (C.c_int, [VP, C.c_uint32, VP, C.c_uint32, VP, C.c_uint32]),
     "tgh_leaf_bounds": (C.c_int, [VP, C.c_uint32, VP, VP]),
+    "tgh_scene_check": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(TgHostSceneTraits), C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

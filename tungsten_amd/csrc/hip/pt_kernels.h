@@ -47,15 +47,10 @@ enum { ST_DONE = 0, ST_ACTIVE = 1, ST_TERMINATED = 2, ST_TERMINATED_BLACK = 3 };
 #define FLAG_MEDIUM_BOUNCE(f)  (((f) >> 19) & 0xFFu)
 #define FLAG_MEDIUM_BITS(medium, mbounce) ((((uint32_t)((medium) + 1)) & 0x7Fu) << 9 | (((uint32_t)(mbounce)) & 0xFFu) << 19)
 #define FLAG_AUX_RECORDED      (1u << 27)   /* TGHIP_PASS_AUX: recordedOutputValues (PathTracer.cpp:46) */
-#define PT_MAX_MEDIA 126u
 // shadow-ray tag of a media scene: light object (16 bits) | medium the ray starts in + 1 (8 bits) | bounce (8 bits)
 #define SHADOW_TAG_MEDIA(light, medium, bounce) ((uint32_t)(light) | ((uint32_t)((medium) + 1) << 16) | ((uint32_t)(bounce) << 24))
 
-// Shading classes ("sort by material"): the class of a record's BSDF says which k_shade variant shades a hit on it -- 0: Lambert / null
-// (MASK_SIMPLE), 1: the conductor family (MASK_COAT: rough conductor, conductor, mirror, smooth coat over those), 2: the dielectric
-// family (MASK_GLASS: dielectric, rough dielectric), 3: everything else (plastics, mixed, transparency, forward: MASK_PLASTIC when that
-// covers them, else every type); CLS_MISS: the path's ray left the scene.  One queue and one launch per class that occurs in the scene.
-#define PT_NUM_CLASSES 4
+// the shading classes (pt_variants.h: PT_NUM_CLASSES) as queue indices; CLS_MISS: the path's ray left the scene
 #define CLS_MISS 4
 #define CLS_0_AND_MISS 5   /* a k_shade launch that consumes the queue of class 0 and, behind it, the escaped paths' (same shading variant) */
 #ifndef PT_ITEM_GROUP
@@ -316,35 +311,7 @@ PT_DEV void auxAdd3(TgHipAuxPixel &px, int output, int ch0, int n, float c0, flo
 
 PT_DEV uint32_t laneId() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
-// ---- small scene tables in LDS --------------------------------------------------------------------
-// The shading kernels chase object -> bsdf -> texture -> light records per lane.  Those tables are tiny, but the
-// vector L1 is flushed continuously by the streaming path state, so every dependent lookup pays L2 latency.
-// Each workgroup copies them into LDS once and the lookups become LDS reads (the big arrays -- records, attributes,
-// texels, CDFs -- stay in global memory).
-// Round 5: the copy is UNCONDITIONAL.  With the run-time fallback "too large: keep the global tables" every table pointer was a select
-// of an LDS and a global address, so the compiler could not infer the address space and every lookup became a flat_load -- 315 of them in
-// the class-0 variant, each behind an `s_waitcnt vmcnt(0) lgkmcnt(0)` that also drains every global load in flight (235 such waits).
-// Whether the tables fit is decided by the host at upload (tungsten_hip.hip: tablesFit, the same arithmetic as below); scenes whose
-// tables do not fit shade with the GLOBAL_TABLES instantiation of the all-features variant, which does not stage at all.  The sampled
-// environment map's marginal tables come along when env_tex >= 0 (the host clears env_tex when they do not fit next to the rest).
-#define PT_LDS_TABLE_BYTES 12288u
-struct SceneTableLayout { uint32_t offBsdf, offTex, offLights, offEnv, offEnvG, total; };
-__host__ __device__ inline SceneTableLayout sceneTableLayout(uint32_t numObjects, uint32_t numBsdfs, uint32_t numTextures, uint32_t numLights, uint32_t numInfinite, int envH)
-{
-    SceneTableLayout l;
-    const uint32_t szObj = numObjects*(uint32_t)sizeof(TgHipObject), szBsdf = numBsdfs*(uint32_t)sizeof(TgHipBsdf), szTex = numTextures*(uint32_t)sizeof(TgHipTexture);
-    const uint32_t szLights = (numLights + numInfinite)*(uint32_t)sizeof(int32_t);
-    l.offBsdf = (szObj + 15u) & ~15u;
-    l.offTex = (l.offBsdf + szBsdf + 15u) & ~15u;
-    l.offLights = (l.offTex + szTex + 15u) & ~15u;
-    // the marginal tables of the sampled environment map (mpdf[h] mcdf[h + 1], then its 513-entry guide): the head of the
-    // envmap-sampling chain becomes LDS reads
-    l.offEnv = (l.offLights + szLights + 15u) & ~15u;
-    const uint32_t szEnvF = envH > 0 ? (2u*(uint32_t)envH + 1u)*4u : 0u, szEnvG = envH > 0 ? (PT_GUIDE_MARGINAL + 1u)*2u : 0u;
-    l.offEnvG = (l.offEnv + szEnvF + 3u) & ~3u;
-    l.total = envH > 0 ? ((l.offEnvG + szEnvG + 3u) & ~3u) : l.offLights + szLights;
-    return l;
-}
+// ---- small scene tables in LDS: the layout both sides compute is pt_variants.h's sceneTableLayout ----
 PT_DEV DeviceScene stageSceneTables(const DeviceScene &s, unsigned char *lds)
 {
     const bool env = s.env_tex >= 0;

@@ -10,6 +10,7 @@
 #include "pt_math.h"
 #include "pt_erfinv_table.h"
 #include "../../../include/tungsten_hip.h"
+#include "pt_variants.h"
 
 struct DeviceScene {
     const float4 * __restrict__ nodes;        // 4 x float4 per TgHipBvhNode
@@ -59,43 +60,13 @@ struct DeviceScene {
     TgHipSettings settings;
 };
 
-#define PT_MAX_BSDF_DEPTH 3
-
 #define LOBE_ALL              (TGHIP_LOBE_GLOSSY_R | TGHIP_LOBE_GLOSSY_T | TGHIP_LOBE_DIFFUSE_R | TGHIP_LOBE_DIFFUSE_T | \
                                TGHIP_LOBE_SPECULAR_R | TGHIP_LOBE_SPECULAR_T | TGHIP_LOBE_ANISOTROPIC)
 #define LOBE_SPECULAR         (TGHIP_LOBE_SPECULAR_R | TGHIP_LOBE_SPECULAR_T)
 #define LOBE_TRANSMISSIVE     (TGHIP_LOBE_GLOSSY_T | TGHIP_LOBE_DIFFUSE_T | TGHIP_LOBE_SPECULAR_T)
 #define LOBE_ALL_BUT_SPECULAR (~(uint32_t)(LOBE_SPECULAR | TGHIP_LOBE_FORWARD))
 
-// M is the compile-time set of BSDF types (bit = 1 << TGHIP_BSDF_*) a kernel variant has to handle: cases
-// outside M fold away, which is what keeps the Lambert-only shading kernel small (DESIGN.md "Kernels").
-#define BSDF_BIT(t) (1u << (t))
-#define BSDF_MASK_ALL 0xFFFFFFFFu
-// The upper bits of M say which scene FEATURES a shading-kernel variant has to handle (all set in BSDF_MASK_ALL);
-// code for absent features folds away like BSDF types do.
-#define FEAT_BITMAP     (1u << 24)   /* bitmap textures (incl. environment maps)                      */
-#define FEAT_INFINITE   (1u << 25)   /* infinite-sphere emitters                                       */
-#define FEAT_MULTILIGHT (1u << 26)   /* more than one sampled light (TraceBase::chooseLight's pdf loop) */
-#define FEAT_TRIANGLES  (1u << 27)   /* triangle records (attribute gather, smooth normals)            */
-#define FEAT_SOLIDS     (1u << 28)   /* sphere records; sphere / cube emitters as sampled lights       */
-#define FEAT_ALL        (FEAT_BITMAP | FEAT_INFINITE | FEAT_MULTILIGHT | FEAT_TRIANGLES | FEAT_SOLIDS)
-#define FEAT_MESHLIGHT  (1u << 29)   /* triangle-mesh emitters as sampled lights: only in the MASK_FULL / BSDF_MASK_ALL variants */
-#define FEAT_QMC        (1u << 30)   /* TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS passes: every variant has a twin with this bit (launchShade) */
-#define FEAT_INSTANCES  (1u << 31)   /* hits reached through an instance record (primitives/Instance.cpp): only in MASK_FULL / BSDF_MASK_ALL */
-#define FEAT_MEDIA      (1u << 23)   /* participating media (media/HomogeneousMedium.cpp): only in the BSDF_MASK_ALL variant */
-#define FEAT_AUX        (1u << 22)   /* TGHIP_PASS_AUX passes (auxiliary output buffers): only in the BSDF_MASK_ALL variant */
-#define FEAT_CYLINDER   (1u << 21)   /* cylinder primitives / emitters (primitives/Cylinder.cpp): only in the BSDF_MASK_ALL variant */
-#define FEAT_PHONG      (1u << 19)   /* microfacet BSDFs with the Phong distribution (pow(double, double)): only in the MASK_FULL / BSDF_MASK_ALL variants */
-#define FEAT_BUMP       (1u << 20)   /* bump-mapped shading frames (Primitive::setupTangentFrame, TgHipBsdf::bump1): only in the BSDF_MASK_ALL variant */
-#define MASK_FULL       (BSDF_MASK_ALL & ~(FEAT_QMC | FEAT_MEDIA | FEAT_AUX | FEAT_CYLINDER | FEAT_BUMP))
-// The marker of the all-features family: the four feature bits that only BSDF_MASK_ALL (and its FEAT_QMC twin, which it is itself) carries together.
-// Code for the procedural `disk` and `blade` textures (TGHIP_TEX_DISK / TGHIP_TEX_BLADE) is compiled only where all four are set -- the mask has no
-// bit left for a FEAT_ of their own, and a scene that holds one is shaded by that family throughout (tungsten_hip.hip: haveProcTex).  The closest-hit
-// shadow walk of scenes WITHOUT such a texture instantiates its BSDF code with MASK_ALL_NO_PROCTEX: no function it calls looks at FEAT_AUX, so
-// its instructions are those of BSDF_MASK_ALL before these textures existed.
-#define FEAT_FAMILY_ALL (FEAT_MEDIA | FEAT_AUX | FEAT_CYLINDER | FEAT_BUMP)
-#define HAS_PROCTEX(M)  ((((M) & FEAT_FAMILY_ALL)) == FEAT_FAMILY_ALL)
-#define MASK_ALL_NO_PROCTEX (BSDF_MASK_ALL & ~FEAT_AUX)
+// (the BSDF type / feature masks M of the kernel variants: pt_variants.h)
 // next1D of the path's sampler inside code templated on M
 #define RNG1D(r) rngNext1DT<(M & FEAT_QMC) != 0>(r)
 
@@ -270,12 +241,7 @@ PT_DEV float bitmapPdf(const DeviceScene &s, int texIdx, const TgHipTexture &t, 
     const float *pdf = s.dist + t.dist_offset + t.h + t.h + 1;
     return pdf[(size_t)row*t.w + column]*mpdfR*t.w*t.h;
 }
-// Guide tables (built by the shim at upload) make the two CDF inversions of Distribution2D::warp short dependent
-// chains instead of 9- and 10-step binary searches over L2-resident arrays: for a CDF a[0..n] and B buckets,
-// g[b] = upper_bound(a, b/B), so for x in [b/B, (b+1)/B) the answer lies in [g[b], g[b+1]].  B is a power of two
-// (x*B is exact), and the final search inside the window is the same upper_bound, so the result is identical.
-#define PT_GUIDE_MARGINAL 512
-#define PT_GUIDE_ROW      256
+// (guide tables: PT_GUIDE_MARGINAL / PT_GUIDE_ROW, pt_variants.h)
 PT_DEV int upperBoundGuided(const float *a, const uint16_t *g, int buckets, float x)
 {
     int b = min((int)(x*(float)buckets), buckets - 1);

@@ -55,11 +55,7 @@
             atomicAdd(&wk_[20], (unsigned long long)hi_); atomicAdd(&wk_[21], (unsigned long long)ra_); \
         } } while (0)
 
-// BSDF type sets of the shading-kernel variants (pt_scene.h BsdfOps<D, M>)
-#define TYPES_SIMPLE (BSDF_BIT(TGHIP_BSDF_LAMBERT) | BSDF_BIT(TGHIP_BSDF_NULL) | BSDF_BIT(TGHIP_BSDF_ERROR))
-#define MASK_SIMPLE  (TYPES_SIMPLE | FEAT_ALL)
-#define MASK_LEAN    TYPES_SIMPLE        /* analytic primitives, constant/checker textures, one area light (Cornell box) */
-#define MASK_SIMPLE_INST (MASK_SIMPLE | FEAT_INSTANCES)   /* classes 0 and 2 of scenes with instance records (no mesh emitters) */
+// waves per SIMD the shading-kernel variants are bounded for (their BSDF type sets: pt_variants.h)
 #ifndef SIMPLE_WAVES
 #define SIMPLE_WAVES 3   /* measured: 4 waves/SIMD (128 VGPRs, spills) is 10 % slower on materialtest's k_shade */
 #endif
@@ -71,23 +67,6 @@
 #ifndef LEAN_WAVES
 #define LEAN_WAVES   2   /* measured: 2 waves/SIMD without scratch beats 3 with 108 B of scratch (kernel is VALU-bound) */
 #endif
-#define MASK_COAT    (MASK_SIMPLE | BSDF_BIT(TGHIP_BSDF_ROUGH_CONDUCTOR) | BSDF_BIT(TGHIP_BSDF_SMOOTH_COAT) | \
-                      BSDF_BIT(TGHIP_BSDF_MIRROR) | BSDF_BIT(TGHIP_BSDF_CONDUCTOR))
-#define MASK_GLASS   (MASK_SIMPLE | BSDF_BIT(TGHIP_BSDF_DIELECTRIC) | BSDF_BIT(TGHIP_BSDF_ROUGH_DIELECTRIC) | \
-                      BSDF_BIT(TGHIP_BSDF_MIRROR))
-#define MASK_PLASTIC (MASK_SIMPLE | BSDF_BIT(TGHIP_BSDF_PLASTIC) | BSDF_BIT(TGHIP_BSDF_ROUGH_PLASTIC))
-/* media scenes whose surfaces are Lambert / null / forward / (smooth) dielectric / mirror -- every media scene the reference ships and the
-   fog / smoke goldens: 216 VGPRs without scratch where BSDF_MASK_ALL spills 292 registers to 848 B of scratch.  (Always the FEAT_QMC twin:
-   media passes carry PT_PASS_MEDIA in their flags.) */
-#define MASK_MEDIA   (MASK_SIMPLE | FEAT_MEDIA | FEAT_QMC | BSDF_BIT(TGHIP_BSDF_FORWARD) | BSDF_BIT(TGHIP_BSDF_DIELECTRIC) | BSDF_BIT(TGHIP_BSDF_MIRROR))
-/* the five types added last (ABI 9): only the full variants shade them; scenes that use one keep the loop to the end (no k_tail) */
-#define TYPES_LATE   (BSDF_BIT(TGHIP_BSDF_DIFFUSE_TRANSMISSION) | BSDF_BIT(TGHIP_BSDF_PHONG) | BSDF_BIT(TGHIP_BSDF_THINSHEET) | \
-                      BSDF_BIT(TGHIP_BSDF_OREN_NAYAR) | BSDF_BIT(TGHIP_BSDF_ROUGH_COAT))
-#define MASK_TAIL    (MASK_FULL & ~(FEAT_INSTANCES | FEAT_MESHLIGHT | TYPES_LATE))   /* k_tail: the 14 BSDF types of rounds 1-3, single-level scenes without mesh emitters */
-/* the class variants of scenes with instance records (no mesh emitters): hits reached through an instance (FEAT_INSTANCES) */
-#define MASK_COAT_INST    (MASK_COAT | FEAT_INSTANCES)
-#define MASK_GLASS_INST   (MASK_GLASS | FEAT_INSTANCES)
-#define MASK_PLASTIC_INST (MASK_PLASTIC | FEAT_INSTANCES)
 
 // Finalises the finished sample of every lane with `finished` set (OutputBuffer::addSample semantics,
 // cameras/OutputBuffer.hpp:104-107: NaN/Inf samples are dropped without counting; PathTracer.cpp:119-122,

@@ -5,6 +5,7 @@
 #include "debug_units.h"
 #include "denoise.h"
 #include "develop.h"
+#include "../host/SceneCheck.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -211,8 +212,7 @@ struct tghip_ctx {
     bool haveScene = false;
     DeviceBuffers sceneMem;
     DeviceScene scene;
-    int bvhDepth = 0;
-    int wideDepth = 0;                    // levels of the 8-wide BVH (0: the scene has none, the kernels walk the BVH2)
+    SceneTraits sc;                       // what checkScene decided about it (csrc/host/SceneCheck.hpp): the facts the launch code branches on, the derived tables
     bool wideOpt = true;                  // "wide_bvh" option: use it when the scene carries one
     // "wide_closest" / "wide_shadow": which kernels walk the wide BVH when the scene has one.  -1 = the measured default:
     // both, except that closest-hit rays of instanced scenes stay on the two-level BVH2 kernel (instances10k 1080p, one MI355X:
@@ -222,15 +222,12 @@ struct tghip_ctx {
     int instWideOpt = 1;                  // "inst_wide": ... with the masters' subtrees walked through the wide BVH (k_trace_closest_instw); 0 = the BVH2 walk of round 5
     int instPhaseMin = 24;                // "inst_phase_min" / "inst_refill_at" (PathState::inst_*)
     int instRefillAt = 48;
-    int bvhMasterDepth = 0;               // instanced scenes: the part of bvhDepth that is the deepest master's BVH2 subtree, and the wide walk's levels inside a master
-    int wideMasterDepth = 0;
     int wideClosestOpt = -1, wideShadowOpt = -1;
     // "tail_kernel" / "tail_threshold": once a host check finds at most tail_threshold paths alive in the pool, the rest of the batch runs in
     // k_tail (one launch per part: every workgroup iterates over its own slots until they are done).  The kernel is built for latency, not
     // throughput (one shading variant for every class, one wave per SIMD): measured, Msamples/s for thresholds off / 2 Ki / 8 Ki / 32 Ki / 128 Ki:
     // mesh1m 605 / 625 / 611 / 575 / 514, materialtest 963 / 966 / 964 / 968 / 966, materialtest as shipped 573 / 611 / 630 / 623 / 625
-    bool mediaSimple = false;             // a media scene whose surface BSDFs MASK_MEDIA covers (no instances, no mesh emitters)
-    bool mediaLeanOpt = true;             // "media_lean": shade such scenes with k_shade<MASK_MEDIA> instead of <BSDF_MASK_ALL>
+    bool mediaLeanOpt = true;             // "media_lean": shade media scenes whose surface BSDFs MASK_MEDIA covers (sc.mediaSimple) with k_shade<MASK_MEDIA> instead of <BSDF_MASK_ALL>
     bool foldFinishOpt = true;            // "fold_finish"
     bool topTreeOpt = true;               // "top_tree": 0 = ignore TgHipSceneDesc::top_nodes at the next upload (flat lists walked in record order: faster, not the reference's ties)
     bool mergeMissOpt = true;             // "merge_miss"
@@ -285,17 +282,6 @@ struct tghip_ctx {
     float4 *partial = nullptr;
 
     // shading classes of the uploaded scene (rec_class) and the kernel variants chosen for them
-    bool haveComplex = false;             // some primitive record uses a BSDF of class 1, 2 or 3
-    uint32_t complexMask = 0;             // union of the BSDF types inside those materials
-    bool classPresent[PT_NUM_CLASSES] = {false, false, false, false};   // shading classes (pt_kernels.h: PT_NUM_CLASSES) that occur among the records
-    uint32_t classMask[PT_NUM_CLASSES] = {0, 0, 0, 0};                  // ... and the BSDF types inside each
-    bool haveForward = false;             // some BSDF has a forward lobe (shadow rays attenuate instead of stop)
-    std::vector<uint32_t> bsdfTypes;      // per bsdf of the uploaded scene: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when the scene holds a disk / blade texture (tghip_debug_bsdf_info)
-    std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
-    bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
-    bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
-    bool cameraFix = false;               // equirectangular camera: k_camera_rays rewrites the fresh camera rays before they are traced
-    bool haveSolids = false;              // cube / sphere / disk records: the dynamic-fetch kernels' SOLIDS variants
     TgHipAuxPixel *dAux = nullptr;        // auxiliary output buffers (allocated by the first TGHIP_PASS_AUX pass)
     float *dSamples = nullptr;            // TGHIP_PASS_SAMPLES: per-sample radiance of the last such pass
     // tghip_develop: where the kernels write when the caller's outputs are host memory (grown on demand), the depth output's maximum, the option
@@ -325,19 +311,10 @@ struct tghip_ctx {
     size_t samplesCap = 0, samplesFloats = 0;
     bool auxPass = false;                 // the pass being rendered keeps them: BSDF_MASK_ALL shading, no fused / dynamic-fetch shadow kernels
     int thrShadeAll = 256;                // workgroup size of k_shade<BSDF_MASK_ALL> (media scenes, TGHIP_PASS_AUX passes)
-    bool haveCylinder = false;            // cylinder primitives -- or a bump-mapped bsdf (TgHipBsdf::bump1): BSDF_MASK_ALL shading (the only FEAT_CYLINDER /
-                                          // FEAT_BUMP variant), never fused
-    bool haveProcTex = false;             // a `disk` or `blade` texture (TGHIP_TEX_DISK / _BLADE): evaluated by the all-features family only -- sets haveCylinder (BSDF_MASK_ALL
-                                          // shading, never fused, no k_tail) and sends a closest-hit shadow walk to k_trace_shadow<., true, ., ., BSDF_MASK_ALL>
-    bool haveMedia = false;               // participating media: BSDF_MASK_ALL shading (the only FEAT_MEDIA variant), closest-hit shadow walk, never fused
-    bool haveInstances = false;           // instance records: two-level traversal kernels (INST), MASK_FULL shading, never the flat list
     bool hoistOpt = true;                 // "hoist_quad": the scene's one quad tested before the decoupled walks instead of inside them (at the next upload)
     bool tailFamilyOpt = true;            // "tail_family": k_tail<MASK_COAT> for scenes without class-2 / class-3 materials and without solids
-    bool tablesFit = true;                // objects + bsdfs + textures + light lists fit the shading workgroups' LDS copy (pt_kernels.h: stageSceneTables)
-    bool tablesFitScene = true;           // ... as decided at upload; "lds_tables" = 0 shades as if they did not (the GLOBAL_TABLES variant: tests)
-    int hoistedRecScene = -1;             // DeviceScene::hoisted_rec as decided at upload ("hoist_quad" switches it at run time: the skip word stays in the node)
-    int envTexScene = -1;                 // the sampled environment map whose marginal tables ride in LDS; "env_lds" = 0 samples it through its global tables
-    bool leanScene = false;               // no bitmap texture, no infinite light, <= 1 sampled light, no triangles: k_shade<MASK_LEAN>
+    bool tablesFit = true;                // sc.tablesFit, or false under "lds_tables" = 0: shade as if the small tables did not fit the LDS copy (the GLOBAL_TABLES variant: tests).
+                                          // Likewise scene.hoisted_rec and scene.env_tex are sc.hoisted.record / sc.env_tex unless "hoist_quad" / "env_lds" = 0 say -1
     bool countTraversal = false;
     int checkInterval = 0;                // "check_interval": wavefront iterations between host-side liveness checks; 0 = 16 for batches that refill
                                           // the pool several times (every check drains all streams: materialtest 825 / 835 / 845 Msamples/s for
@@ -415,204 +392,9 @@ static int allocArray(tghip_ctx *ctx, DeviceBuffers &mem, size_t count, T **dst)
     return TGHIP_OK;
 }
 
-static int bsdfDepth(const TgHipSceneDesc *s, int bi, int depth)
-{
-    if (bi < 0 || depth > 16) return depth;
-    const TgHipBsdf &b = s->bsdfs[bi];
-    int d = depth + 1;
-    if (b.type == TGHIP_BSDF_SMOOTH_COAT || b.type == TGHIP_BSDF_ROUGH_COAT || b.type == TGHIP_BSDF_TRANSPARENCY)
-        return bsdfDepth(s, b.sub0, d);
-    if (b.type == TGHIP_BSDF_MIXED)
-        return std::max(bsdfDepth(s, b.sub0, d), bsdfDepth(s, b.sub1, d));
-    return d;
-}
-
-// set of BSDF types (bit = 1 << type) in the subtree of bsdf `bi`
-static uint32_t bsdfTypeMask(const TgHipSceneDesc *s, int bi, int depth)
-{
-    if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return 0;
-    const TgHipBsdf &b = s->bsdfs[bi];
-    uint32_t m = 1u << uint32_t(b.type);
-    if ((b.type == TGHIP_BSDF_ROUGH_CONDUCTOR || b.type == TGHIP_BSDF_ROUGH_DIELECTRIC || b.type == TGHIP_BSDF_ROUGH_PLASTIC || b.type == TGHIP_BSDF_ROUGH_COAT) &&
-        b.distribution == TGHIP_DIST_PHONG)
-        m |= FEAT_PHONG;                     // outside every family mask: such a material is shaded by the full variant (pt_scene.h: mfDist)
-    if (b.type == TGHIP_BSDF_SMOOTH_COAT || b.type == TGHIP_BSDF_ROUGH_COAT || b.type == TGHIP_BSDF_TRANSPARENCY)
-        m |= bsdfTypeMask(s, b.sub0, depth + 1);
-    if (b.type == TGHIP_BSDF_MIXED)
-        m |= bsdfTypeMask(s, b.sub0, depth + 1) | bsdfTypeMask(s, b.sub1, depth + 1);
-    return m;
-}
-
-// May shading family `variant` (TGHIP_BSDF_VARIANT_*) be given a material with type set `tm` (bsdfTypeMask) and forward lobe `fwd`?  The one
-// statement of the rules the upload and the launch plan apply to type sets (they call it on a material's set or on the union over a class / the scene):
-// the shading classes 0 / 1 / 2 (SIMPLE / COAT / GLASS) take materials without a forward lobe whose types their mask covers, in that order; what is left
-// is class 3, shaded by PLASTIC when all of it fits that mask and by FULL / ALL otherwise; MEDIA takes a media scene whose surface types it covers; TAIL
-// finishes scenes without forward lobes and without the five late types.  LEAN is the exception: the product picks it per SCENE (tghip_upload_scene's
-// `lean`: no bitmap texture anywhere, one quad light, quads and cubes only), so for LEAN this is tghip_debug_bsdf_info's per-material reading of that
-// rule -- SIMPLE's types and no bitmap inside the material (FEAT_BITMAP in tm, set for that entry only) -- and not a site the product calls.
-static bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
-{
-    switch (variant) {
-    case TGHIP_BSDF_VARIANT_LEAN:    return !fwd && (tm & ~MASK_LEAN) == 0;
-    case TGHIP_BSDF_VARIANT_SIMPLE:  return !fwd && (tm & ~MASK_SIMPLE) == 0;
-    case TGHIP_BSDF_VARIANT_COAT:    return !fwd && (tm & ~MASK_COAT) == 0;
-    case TGHIP_BSDF_VARIANT_GLASS:   return !fwd && (tm & ~MASK_GLASS) == 0;
-    case TGHIP_BSDF_VARIANT_PLASTIC: return (tm & ~MASK_PLASTIC) == 0;
-    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0 && !HAS_PROCTEX(tm);   // (bits 0 .. 18: the BSDF types; tghip_debug_bsdf_info's marker of a disk / blade scene)
-    case TGHIP_BSDF_VARIANT_TAIL:    return !fwd && (tm & ~MASK_TAIL) == 0;
-    case TGHIP_BSDF_VARIANT_FULL:    return (tm & ~MASK_FULL) == 0;
-    case TGHIP_BSDF_VARIANT_ALL:     return true;
-    default: return false;
-    }
-}
-
-// does a texture inside bsdf `bi` (nested ones included) hold a bitmap?
-static bool bsdfUsesBitmap(const TgHipSceneDesc *s, int bi, int depth)
-{
-    if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return false;
-    const TgHipBsdf &b = s->bsdfs[bi];
-    const int32_t tex[3] = {b.albedo, b.roughness, b.tex1};
-    for (int32_t t : tex)
-        if (t >= 0 && uint32_t(t) < s->num_textures && s->textures[t].type == TGHIP_TEX_BITMAP) return true;
-    if (b.type == TGHIP_BSDF_SMOOTH_COAT || b.type == TGHIP_BSDF_ROUGH_COAT || b.type == TGHIP_BSDF_TRANSPARENCY)
-        return bsdfUsesBitmap(s, b.sub0, depth + 1);
-    if (b.type == TGHIP_BSDF_MIXED)
-        return bsdfUsesBitmap(s, b.sub0, depth + 1) || bsdfUsesBitmap(s, b.sub1, depth + 1);
-    return false;
-}
-
-// Depth of the subtree under `root` (also validates child references).  `level`: 0 = the scene's tree (leaves: non-instance records and
-// instance-set records, which are collected in `found`), 1 = the reference's tree behind a set record (leaves: one or two slots of
-// inst_prims; the instance records behind them are collected in `found`), 2 = a master's subtree (triangles and the like only).
-static int subtreeDepth(const TgHipSceneDesc *s, int32_t root, size_t &visited, int level, std::vector<uint32_t> *found)
-{
-    std::vector<std::pair<int32_t, int>> stack;
-    stack.emplace_back(root, 1);
-    int depth = 0;
-    while (!stack.empty()) {
-        auto cur = stack.back();
-        stack.pop_back();
-        if (cur.first < 0) {
-            uint32_t first = TGHIP_LEAF_FIRST(cur.first), count = TGHIP_LEAF_COUNT(cur.first);
-            if (level == 1) {
-                if (count < 1 || count > 2 || first + count > s->num_inst_prims) return -1;
-                for (uint32_t k = first; k < first + count; ++k) {
-                    const uint32_t ri = s->inst_prims[k];
-                    if (ri >= s->num_top_recs || TGHIP_REC_KIND(s->recs[ri].meta) != TGHIP_REC_INSTANCE) return -1;
-                    found->push_back(ri);
-                }
-                continue;
-            }
-            if (first + count > s->num_recs) return -1;
-            for (uint32_t i = first; i < first + count; ++i) {
-                const uint32_t kind = TGHIP_REC_KIND(s->recs[i].meta);
-                if (kind == TGHIP_REC_INSTANCE) return -1;           // instance records are reached through their set's tree only
-                if (kind == TGHIP_REC_INSTANCE_SET) {
-                    if (level != 0 || count != 1) return -1;
-                    found->push_back(i);
-                }
-            }
-            continue;
-        }
-        if (uint32_t(cur.first) >= s->num_nodes || ++visited > s->num_nodes) return -1;
-        depth = std::max(depth, cur.second);
-        stack.emplace_back(s->nodes[cur.first].child0, cur.second + 1);
-        stack.emplace_back(s->nodes[cur.first].child1, cur.second + 1);
-    }
-    return depth;
-}
-
-// Stack words the BVH2 traversal needs: the scene's tree; with `instances` primitives, above it the reference's tree over the instances
-// and the deepest master subtree (pt_kernels.h: instanceSetIntersect).
-static int bvhDepthOf(const TgHipSceneDesc *s, int *masterDepthOut = nullptr)
-{
-    if (masterDepthOut) *masterDepthOut = 0;
-    size_t visited = 0;
-    std::vector<uint32_t> sets;
-    int depth = subtreeDepth(s, 0, visited, 0, &sets);
-    if (depth < 0 || (sets.empty() != (s->num_instances == 0))) return -1;
-    if (sets.empty()) return depth;
-    if (!s->inst_prims || !s->inst_leaf_boxes) return -1;
-    std::vector<uint32_t> inst;
-    int ref = 0;
-    for (uint32_t set : sets) {
-        int32_t root;
-        std::memcpy(&root, &s->recs[set].c[0], 4);
-        if (root == 0) return -1;
-        int d = subtreeDepth(s, root, visited, 1, &inst);
-        if (d < 0) return -1;
-        ref = std::max(ref, d);
-    }
-    if (inst.size() != s->num_instances) return -1;
-    std::vector<uint32_t> roots;
-    for (uint32_t i : inst) {
-        uint32_t root, leaf;
-        std::memcpy(&root, &s->recs[i].c[0], 4);
-        std::memcpy(&leaf, &s->recs[i].c[1], 4);
-        if (root == 0 || root >= s->num_nodes || leaf >= s->num_inst_prims) return -1;
-        roots.push_back(root);
-    }
-    std::sort(roots.begin(), roots.end());
-    roots.erase(std::unique(roots.begin(), roots.end()), roots.end());
-    int master = 0;
-    for (uint32_t root : roots) {
-        int d = subtreeDepth(s, int32_t(root), visited, 2, nullptr);
-        if (d < 0) return -1;
-        master = std::max(master, d);
-    }
-    if (masterDepthOut) *masterDepthOut = master;
-    return depth + ref + master + 3;
-}
-
-// Validates the wide BVH -- the top-level tree from node 0 and, with instances, the masters' subtrees behind it (roots in the
-// instance records): children behind their parent, every node in one tree, record runs inside the record array -- and returns
-// the stack depth the walk needs (-1 when malformed).
-static int wideDepthOf(const TgHipSceneDesc *s, int *masterDepthOut = nullptr)
-{
-    if (masterDepthOut) *masterDepthOut = 0;
-    const uint32_t n = s->num_wide_nodes;
-    std::vector<uint8_t> depth(n, 0);
-    depth[0] = 1;
-    uint32_t firstMaster = n;
-    for (uint32_t i = 0; i < s->num_recs && s->num_instances; ++i) {
-        if (TGHIP_REC_KIND(s->recs[i].meta) != TGHIP_REC_INSTANCE) continue;
-        uint32_t root;
-        std::memcpy(&root, &s->recs[i].c[2], 4);
-        if (root == 0 || root >= n) return -1;
-        depth[root] = 1;
-        firstMaster = std::min(firstMaster, root);
-    }
-    int topDepth = 1, masterDepth = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const TgHipWideNode &w = s->wide_nodes[i];
-        if (depth[i] == 0) return -1;                        // unreachable node: not a forest in breadth-first order
-        const uint32_t kids = uint32_t(__builtin_popcount(w.imask));
-        if (kids && (w.child_base <= i || uint64_t(w.child_base) + kids > n)) return -1;
-        if (kids && i < firstMaster && w.child_base + kids > firstMaster) return -1;   // the top level does not reach into a master
-        for (uint32_t k = 0; k < kids; ++k) {
-            if (depth[w.child_base + k] != 0) return -1;     // two parents
-            depth[w.child_base + k] = uint8_t(depth[i] + 1);
-        }
-        if (i < firstMaster) topDepth = std::max(topDepth, int(depth[i]) + (kids ? 1 : 0));
-        else masterDepth = std::max(masterDepth, int(depth[i]) + (kids ? 1 : 0));
-        if (topDepth > TGHIP_MAX_WIDE_DEPTH || masterDepth > TGHIP_MAX_WIDE_DEPTH) return -1;
-        for (int sl = 0; sl < 8; ++sl) {
-            const uint32_t bits = (w.leaf_valid >> (4*sl)) & 15u;
-            if ((bits & (bits + 1u)) != 0u || (bits && (w.imask & (1u << sl)))) return -1;   // records 0 .. count-1 of a leaf slot
-        }
-        const uint32_t recLimit = i < firstMaster ? (s->num_top_recs ? s->num_top_recs : s->num_recs) : s->num_recs;
-        if (w.leaf_valid && uint64_t(w.rec_base) + uint32_t(__builtin_popcount(w.leaf_valid)) > recLimit) return -1;
-        for (int a = 0; a < 3; ++a)
-            if (w.exp[a] == 0 || w.exp[a] == 255) return -1;
-    }
-    const int total = s->num_instances ? topDepth + masterDepth + 3 : topDepth;   // + what entering an instance parks on the stack
-    if (masterDepthOut) *masterDepthOut = masterDepth;
-    return total > TGHIP_MAX_WIDE_DEPTH ? -1 : total;
-}
-
-static bool isFlat(const tghip_ctx *ctx) { return ctx->scene.num_recs <= TGHIP_FLAT_MAX_RECS && !ctx->haveInstances; }
+static bool isFlat(const tghip_ctx *ctx) { return ctx->scene.num_recs <= TGHIP_FLAT_MAX_RECS && !ctx->sc.haveInstances; }
 // the single-level traversal kernels walk the 8-wide BVH when the scene carries one
-static bool useWide(const tghip_ctx *ctx) { return ctx->wideDepth > 0 && ctx->wideOpt && ctx->dynamicFetch && !isFlat(ctx); }
+static bool useWide(const tghip_ctx *ctx) { return ctx->sc.wideDepth > 0 && ctx->wideOpt && ctx->dynamicFetch && !isFlat(ctx); }
 
 
 static bool wideClosest(const tghip_ctx *ctx);
@@ -623,7 +405,7 @@ static bool wideShadowRays(const tghip_ctx *ctx);
 // the smaller workgroups that then fit are not faster).
 static uint32_t slotCap(const tghip_ctx *ctx)
 {
-    const bool allWide = !isFlat(ctx) && !ctx->haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && !ctx->haveForward && !ctx->haveMeshLight;
+    const bool allWide = !isFlat(ctx) && !ctx->sc.haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && !ctx->sc.haveForward && !ctx->sc.haveMeshLight;
     uint32_t cap = allWide ? PT_MAX_SLOTS_PER_BLOCK : 2048u;      // (BlockLdsSmall in the other traversal kernels)
     if (ctx->slotsPerBlockOpt > 0)
         cap = std::min<uint32_t>(cap, uint32_t(ctx->slotsPerBlockOpt));
@@ -636,32 +418,32 @@ static uint32_t slotCap(const tghip_ctx *ctx)
 static size_t traceLdsBytes(const tghip_ctx *ctx, int threads)
 {
     const bool flat = isFlat(ctx);
-    size_t stack = flat ? 0 : size_t(std::max(ctx->bvhDepth, 1))*size_t(threads)*sizeof(int);
+    size_t stack = flat ? 0 : size_t(std::max(ctx->sc.bvhDepth, 1))*size_t(threads)*sizeof(int);
     return std::max<size_t>(stack, size_t(slotCap(ctx))*sizeof(unsigned short));
 }
 
 // dynamic-fetch traversal kernels keep the expanded queue next to the stacks
 static size_t dynLdsBytes(const tghip_ctx *ctx, int threads)
 {
-    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->bvhDepth, 1))*size_t(threads)*sizeof(int);
+    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->sc.bvhDepth, 1))*size_t(threads)*sizeof(int);
 }
 
 // the wide kernels: expanded queue + one 8-byte group entry per tree level and thread
 static size_t wideLdsBytes(const tghip_ctx *ctx, int threads)
 {
-    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->wideDepth, 1))*size_t(threads)*sizeof(uint2);
+    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->sc.wideDepth, 1))*size_t(threads)*sizeof(uint2);
 }
 
 // k_trace_closest_instw: expanded queue + the BVH2 stack of the scene's tree and the reference's tree over the instances (no master on it) + the
 // masters' group stack (8-byte entries, 8-byte aligned)
-static int instTreeDepth(const tghip_ctx *ctx) { return std::max(ctx->bvhDepth - ctx->bvhMasterDepth, 1); }
+static int instTreeDepth(const tghip_ctx *ctx) { return std::max(ctx->sc.bvhDepth - ctx->sc.bvhMasterDepth, 1); }
 static size_t instWideLdsBytes(const tghip_ctx *ctx, int threads)
 {
     const size_t ints = ((size_t(slotCap(ctx)) >> 1) + size_t(instTreeDepth(ctx))*size_t(threads) + 1u) & ~size_t(1);
-    return ints*sizeof(int) + size_t(std::max(ctx->wideMasterDepth, 1))*size_t(threads)*sizeof(uint2);
+    return ints*sizeof(int) + size_t(std::max(ctx->sc.wideMasterDepth, 1))*size_t(threads)*sizeof(uint2);
 }
-static bool instWide(const tghip_ctx *ctx) { return ctx->haveInstances && ctx->instWideOpt && ctx->wideDepth > 0 && ctx->wideMasterDepth > 0 && ctx->wideOpt; }
-static bool wideClosest(const tghip_ctx *ctx) { return useWide(ctx) && (ctx->wideClosestOpt < 0 ? !ctx->haveInstances : ctx->wideClosestOpt != 0); }
+static bool instWide(const tghip_ctx *ctx) { return ctx->sc.haveInstances && ctx->instWideOpt && ctx->sc.wideDepth > 0 && ctx->sc.wideMasterDepth > 0 && ctx->wideOpt; }
+static bool wideClosest(const tghip_ctx *ctx) { return useWide(ctx) && (ctx->wideClosestOpt < 0 ? !ctx->sc.haveInstances : ctx->wideClosestOpt != 0); }
 static bool wideShadowRays(const tghip_ctx *ctx) { return useWide(ctx) && ctx->wideShadowOpt != 0; }
 
 static int launchGrid(const tghip_ctx *ctx) { return ctx->prop.multiProcessorCount*std::max(ctx->blocksPerCu, 1)*std::max(ctx->gridRounds, 1); }
@@ -772,13 +554,13 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     const uint32_t grid = uint32_t(launchGrid(ctx));
     uint32_t perBlock = (wantSlots + grid - 1)/grid;
     uint32_t cap = slotCap(ctx);
-    if (isFlat(ctx) || ctx->haveInstances)
+    if (isFlat(ctx) || ctx->sc.haveInstances)
         cap = std::min<uint32_t>(cap, 16u*uint32_t(std::min(ctx->thrClosest, ctx->thrShadow))/64u*64u);   // OrderRegs
     perBlock = std::min<uint32_t>(cap, std::max<uint32_t>(64u, (perBlock + 63u)/64u*64u));
     const uint32_t slots = perBlock*grid;
     PathState &p = ctx->pool;
     // the walk arrays behind the A_* ones (suspended walks of the wide kernels, PathState::walk_base): only where they fit the 32-bit offsets
-    uint32_t walkArrays = useWide(ctx) && !ctx->haveInstances ? 4u + uint32_t(ctx->wideDepth + 1)/2u : 0u;
+    uint32_t walkArrays = useWide(ctx) && !ctx->sc.haveInstances ? 4u + uint32_t(ctx->sc.wideDepth + 1)/2u : 0u;
     if (ctx->poolSlots >= slots && ctx->poolGrid == grid && (ctx->poolWalkWanted == walkArrays || ctx->poolWalkArrays >= walkArrays)) {
         p.num_slots = slots;
         p.slots_per_block = perBlock;
@@ -833,65 +615,65 @@ static void chooseThreads(tghip_ctx *ctx)
     // from the same sweep).  Instanced scenes with the dynamic-fetch closest-hit kernel: two parts, 8 per CU (instances10k: 141 -> 153
     // Msamples/s; with the static-fetch kernel parts lost: 127 against 114-120).
     const bool oneStream = ctx->streamsOpt == 1 || (ctx->streamsOpt == 0 && ctx->shortBatch);   // (shortBatch: tghip_render_pass)
-    const bool pairedInst = !flat && ctx->haveInstances && !oneStream && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt && wideShadowRays(ctx) &&
-                            !ctx->haveForward && !ctx->haveMeshLight;
-    const bool paired = (!flat && !ctx->haveInstances && !oneStream && wideClosest(ctx) && wideShadowRays(ctx)) || pairedInst;
+    const bool pairedInst = !flat && ctx->sc.haveInstances && !oneStream && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt && wideShadowRays(ctx) &&
+                            !ctx->sc.haveForward && !ctx->sc.haveMeshLight;
+    const bool paired = (!flat && !ctx->sc.haveInstances && !oneStream && wideClosest(ctx) && wideShadowRays(ctx)) || pairedInst;
     ctx->blocksPerCu = ctx->blocksPerCuOpt > 0 ? ctx->blocksPerCuOpt : ((flat || paired) ? 8 : 4);
     if (flat && ctx->blocksPerCuOpt == 0) {
         ctx->thrClosest = ctx->thrShadow = ctx->thrShadeSimple = ctx->thrShadeComplex = 256;
     } else {
-    const bool inst = ctx->haveInstances;
+    const bool inst = ctx->sc.haveInstances;
     const bool dyn = ctx->dynamicFetch && !inst;               // (the two-level dynamic-fetch kernel is chosen by instDynOpt below)
     const bool wide = useWide(ctx);
     const bool wideC = wideClosest(ctx), wideS = wideShadowRays(ctx);
     // (wide closest-hit kernel, materialtest 1280x720x256 / mesh1m, one MI355X: 128 / 192 / 256 / 320 threads = 505 / 433 / 394 / 469 us per
     // launch, but the shading launches behind it run 6 % faster after 192 than after 256: 579 / 571 / 552 Msamples/s for 192 / 256 / 320)
-    ctx->thrClosest = wideC && inst ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false, true>, 192, 3))
-                    : wideC ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false>, 192, 3))
+    ctx->thrClosest = wideC && inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false, true>, 192, 3))
+                    : wideC ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false>, 192, 3))
                     : flat ? pickThreads(ctx, k_trace_closest<false, true>, 512, 1)
-                    : (inst && ctx->dynamicFetch && ctx->instDynOpt && instWide(ctx)) ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest_instw<false, true>, 320, 4) : pickThreads(ctx, k_trace_closest_instw<false, false>, 320, 4))
-                    : (inst && ctx->dynamicFetch && ctx->instDynOpt) ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest_inst<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_inst<false, false>, 320, 2))
-                    : inst ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest<false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_closest<false, false, 2>, 512, 1))
-                    : dyn ? (ctx->haveSolids ? pickThreads(ctx, k_trace_closest_dyn<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_dyn<false, false>, 320, 2))   // 20 waves/CU measured best (profiles/README.md)
+                    : (inst && ctx->dynamicFetch && ctx->instDynOpt && instWide(ctx)) ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_instw<false, true>, 320, 4) : pickThreads(ctx, k_trace_closest_instw<false, false>, 320, 4))
+                    : (inst && ctx->dynamicFetch && ctx->instDynOpt) ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_inst<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_inst<false, false>, 320, 2))
+                    : inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest<false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_closest<false, false, 2>, 512, 1))
+                    : dyn ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_dyn<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_dyn<false, false>, 320, 2))   // 20 waves/CU measured best (profiles/README.md)
                                         : pickThreads(ctx, k_trace_closest<false, false>, 512, 1);
-    if (wideS && inst && !ctx->haveForward && !ctx->haveMeshLight)
-        ctx->thrShadow = ctx->instShadowFast ? (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_fast_inst<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_fast_inst<false, false>, 256, 3))
-                                             : (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false, true>, 256, 3));
-    else if (wideS && !ctx->haveForward && !ctx->haveMeshLight)
-        ctx->thrShadow = ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false>, 256, 3);
-    else if (!flat && !ctx->haveForward && !ctx->haveMeshLight && dyn)
-        ctx->thrShadow = ctx->haveSolids ? pickThreads(ctx, k_trace_shadow_dyn<false, true>, 256, 2) : pickThreads(ctx, k_trace_shadow_dyn<false, false>, 256, 2);   // measured: 192 / 256 / 320 / 384 threads = 525 / 462 / 633 / 619 us per launch
-    else if (ctx->haveProcTex && (ctx->haveForward || ctx->haveMeshLight))
-        ctx->thrShadow = inst ? (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>, 512, 1))
+    if (wideS && inst && !ctx->sc.haveForward && !ctx->sc.haveMeshLight)
+        ctx->thrShadow = ctx->instShadowFast ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_fast_inst<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_fast_inst<false, false>, 256, 3))
+                                             : (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false, true>, 256, 3));
+    else if (wideS && !ctx->sc.haveForward && !ctx->sc.haveMeshLight)
+        ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false>, 256, 3);
+    else if (!flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && dyn)
+        ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_dyn<false, true>, 256, 2) : pickThreads(ctx, k_trace_shadow_dyn<false, false>, 256, 2);   // measured: 192 / 256 / 320 / 384 threads = 525 / 462 / 633 / 619 us per launch
+    else if (ctx->sc.haveProcTex && (ctx->sc.haveForward || ctx->sc.haveMeshLight))
+        ctx->thrShadow = inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>, 512, 1))
                               : flat ? pickThreads(ctx, k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>, 512, 1);
     else if (inst)
-        ctx->thrShadow = (ctx->haveForward || ctx->haveMeshLight)
-                       ? (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2>, 512, 1))
-                       : (ctx->haveSolids ? pickThreads(ctx, k_trace_shadow<false, false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, false, false, 2>, 512, 1));
-    else if (ctx->haveForward || ctx->haveMeshLight)
+        ctx->thrShadow = (ctx->sc.haveForward || ctx->sc.haveMeshLight)
+                       ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2>, 512, 1))
+                       : (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, false, false, 2>, 512, 1));
+    else if (ctx->sc.haveForward || ctx->sc.haveMeshLight)
         ctx->thrShadow = flat ? pickThreads(ctx, k_trace_shadow<false, true, true>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false>, 512, 1);
     else
         ctx->thrShadow = flat ? pickThreads(ctx, k_trace_shadow<false, false, true>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, false, false>, 512, 1);
-    if (ctx->haveMeshLight || inst) ctx->thrShadeSimple = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
-    else ctx->thrShadeSimple = ctx->leanScene ? pickThreads(ctx, k_shade<MASK_LEAN, LEAN_WAVES, 0>, 256, 0) : pickThreads(ctx, k_shade<MASK_SIMPLE, SIMPLE_WAVES, 0>, 256, 0);
+    if (ctx->sc.haveMeshLight || inst) ctx->thrShadeSimple = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
+    else ctx->thrShadeSimple = ctx->sc.leanScene ? pickThreads(ctx, k_shade<MASK_LEAN, LEAN_WAVES, 0>, 256, 0) : pickThreads(ctx, k_shade<MASK_SIMPLE, SIMPLE_WAVES, 0>, 256, 0);
     // (one workgroup size for the launches of classes 1 .. 3: that of the largest variant among them)
-    if (ctx->haveMeshLight || inst || (ctx->classPresent[3] && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false)))
+    if (ctx->sc.haveMeshLight || inst || (ctx->sc.classPresent[3] && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false)))
                                                     ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
-    else if (ctx->classPresent[3])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_PLASTIC, 2, 0>, 256, 0);
-    else if (ctx->classPresent[2])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_GLASS, 2, 0>, 256, 0);
+    else if (ctx->sc.classPresent[3])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_PLASTIC, 2, 0>, 256, 0);
+    else if (ctx->sc.classPresent[2])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_GLASS, 2, 0>, 256, 0);
     else                                            ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_COAT, COAT_WAVES, 0>, 256, 0);
-    if (ctx->haveMedia) ctx->thrShadeSimple = ctx->thrShadeComplex = pickThreads(ctx, k_shade<BSDF_MASK_ALL, 2, 0>, 256, 0);
+    if (ctx->sc.haveMedia) ctx->thrShadeSimple = ctx->thrShadeComplex = pickThreads(ctx, k_shade<BSDF_MASK_ALL, 2, 0>, 256, 0);
     if (paired && ctx->blocksPerCuOpt == 0) {
         // (closest / shadow / shade simple / shade complex, Msamples/s: 256/256/128/128 657, 192/256/128/128 634, 128/256/128/128 623,
         //  320/256/128/128 556, 256/320/128/128 549, 256/256/256/128 646, 256/256/128/64 623; 4 per CU with 192/256/192/128: 608)
         ctx->thrClosest = pairedInst ? 192 : 256;
-        if (!ctx->haveForward && !ctx->haveMeshLight) ctx->thrShadow = 256;
+        if (!ctx->sc.haveForward && !ctx->sc.haveMeshLight) ctx->thrShadow = 256;
         ctx->thrShadeSimple = ctx->thrShadeComplex = 128;
         // (round 5, the same sweep at today's kernels, three rounds A B C in one session, profiles/r5_sweep_shade_threads.jsonl: materialtest
         // 128/128 965, 192/192 967, 256/256 979 Msamples/s -- k_shade's 26 KB of LDS per workgroup then serve four waves instead of two --, but
         // mesh1m 604 -> 597, materialtest with a rough dielectric 453 -> 451 / 431, with a dielectric 480 -> 480: 256 threads only for what it
         // was measured to help, a small tree with the conductor family as its only other shading class)
-        if (!pairedInst && ctx->numWideNodes <= 32768u && ctx->classPresent[1] && !ctx->classPresent[2] && !ctx->classPresent[3])
+        if (!pairedInst && ctx->numWideNodes <= 32768u && ctx->sc.classPresent[1] && !ctx->sc.classPresent[2] && !ctx->sc.classPresent[3])
             ctx->thrShadeSimple = ctx->thrShadeComplex = 256;
     }
     }
@@ -901,7 +683,7 @@ static void chooseThreads(tghip_ctx *ctx)
         if (ctx->thrOverride[i] >= 64) *dst[i] = std::min(ctx->thrOverride[i]/64*64, i < 2 ? 512 : 256);
     if (std::getenv("TGHIP_VERBOSE"))
         std::fprintf(stderr, "[tghip] grid %d x threads closest %d shadow %d shade %d/%d (flat %d, forward %d, complex mask 0x%x)\n",
-                     launchGrid(ctx), ctx->thrClosest, ctx->thrShadow, ctx->thrShadeSimple, ctx->thrShadeComplex, int(flat), int(ctx->haveForward), ctx->complexMask);
+                     launchGrid(ctx), ctx->thrClosest, ctx->thrShadow, ctx->thrShadeSimple, ctx->thrShadeComplex, int(flat), int(ctx->sc.haveForward), ctx->sc.complexMask);
 }
 
 extern "C" {
@@ -1097,12 +879,12 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "fail_reduce") ctx->failReduce = value != 0;   // fault injection: tghip_reduce_framebuffers with this context as a rank fails (the hosts' fallbacks are tested with it)
     else if (k == "tail_kernel") ctx->tailOpt = value != 0;
     else if (k == "tail_family") ctx->tailFamilyOpt = value != 0;
-    else if (k == "hoist_quad") { ctx->hoistOpt = value != 0; if (!ctx->hoistOpt) ctx->scene.hoisted_rec = -1; else ctx->scene.hoisted_rec = ctx->hoistedRecScene; }
+    else if (k == "hoist_quad") { ctx->hoistOpt = value != 0; if (!ctx->hoistOpt) ctx->scene.hoisted_rec = -1; else ctx->scene.hoisted_rec = ctx->sc.hoisted.record; }
     else if (k == "merge_miss") ctx->mergeMissOpt = value != 0;
     else if (k == "fold_finish") ctx->foldFinishOpt = value != 0;
     else if (k == "top_tree") ctx->topTreeOpt = value != 0;
-    else if (k == "lds_tables") ctx->tablesFit = ctx->tablesFitScene && value != 0;
-    else if (k == "env_lds") ctx->scene.env_tex = value != 0 ? ctx->envTexScene : -1;
+    else if (k == "lds_tables") ctx->tablesFit = ctx->sc.tablesFit && value != 0;
+    else if (k == "env_lds") ctx->scene.env_tex = value != 0 ? ctx->sc.env_tex : -1;
     else if (k == "media_lean") ctx->mediaLeanOpt = value != 0;
     else if (k == "tail_threshold") ctx->tailThreshold = value;
     else if (k == "lds_nodes") {}   // (accepted, no effect: the top of the wide tree in LDS was measured without gain and is gone, profiles/r5_ab_walk_fetch.txt)
@@ -1133,149 +915,54 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
 {
     if (!ctx || !sd) return TGHIP_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (sd->abi_version != TGHIP_ABI_VERSION) { ctx->error = "scene description ABI version mismatch"; return TGHIP_E_INVALID; }
-    if (sd->num_nodes == 0 || !sd->nodes) { ctx->error = "scene has no BVH"; return TGHIP_E_INVALID; }
-    if (sd->camera.res_x <= 0 || sd->camera.res_y <= 0) { ctx->error = "invalid camera resolution"; return TGHIP_E_INVALID; }
-    if (sd->num_lights > 16) { ctx->error = "more than 16 sampled lights are not supported"; return TGHIP_E_UNSUPPORTED; }
-    if (sd->num_objects >= (1u << 24)) { ctx->error = "too many objects"; return TGHIP_E_UNSUPPORTED; }
-    if (sd->num_recs >= (1u << 26) || sd->num_nodes >= (1u << 26)) {   // 64-B attribute / node records behind 32-bit byte offsets (at32)
-        ctx->error = "more than 2^26 primitive records or BVH nodes are not supported";
-        return TGHIP_E_UNSUPPORTED;
-    }
-    // every index the shim (or a kernel) dereferences on the caller's word: refuse a malformed description instead of
-    // reading out of bounds
-    {
-        auto bad = [&](const char *what) { ctx->error = std::string("malformed scene description: ") + what; return TGHIP_E_INVALID; };
-        if ((sd->num_recs && (!sd->recs || !sd->tri_attrs)) || (sd->num_objects && !sd->objects) || (sd->num_bsdfs && !sd->bsdfs) ||
-            (sd->num_textures && !sd->textures) || (sd->num_lights && !sd->lights) || (sd->num_infinite_lights && !sd->infinite_lights))
-            return bad("a non-empty array is NULL");
-        for (uint32_t i = 0; i < sd->num_lights; ++i)
-            if (sd->lights[i] < 0 || uint32_t(sd->lights[i]) >= sd->num_objects) return bad("lights[] entry out of range");
-        for (uint32_t i = 0; i < sd->num_infinite_lights; ++i)
-            if (sd->infinite_lights[i] < 0 || uint32_t(sd->infinite_lights[i]) >= sd->num_objects) return bad("infinite_lights[] entry out of range");
-        for (uint32_t i = 0; i < sd->num_recs; ++i) {
-            const uint32_t kind = TGHIP_REC_KIND(sd->recs[i].meta);
-            if (kind > TGHIP_REC_INSTANCE_SET) return bad("unknown primitive record kind");
-            if (TGHIP_REC_OBJECT(sd->recs[i].meta) >= sd->num_objects) return bad("primitive record refers to an object out of range");
-        }
-        for (uint32_t i = 0; i < sd->num_objects; ++i) {
-            const TgHipObject &o = sd->objects[i];
-            if (o.bsdf < -1 || o.bsdf >= int32_t(sd->num_bsdfs)) return bad("object bsdf out of range");
-            if (o.emission < -1 || o.emission >= int32_t(sd->num_textures)) return bad("object emission texture out of range");
-            if (o.light < -1 || o.light >= int32_t(sd->num_lights)) return bad("object light index out of range");
-            if (o.int_medium < -1 || o.ext_medium < -1 || o.int_medium >= int32_t(sd->num_media) || o.ext_medium >= int32_t(sd->num_media))
-                return bad("primitive medium out of range");
-        }
-        for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
-            const TgHipBsdf &b = sd->bsdfs[i];
-            const int32_t nt = int32_t(sd->num_textures), nb = int32_t(sd->num_bsdfs);
-            if (b.albedo < -1 || b.albedo >= nt || b.roughness < -1 || b.roughness >= nt || b.tex1 < -1 || b.tex1 >= nt)
-                return bad("bsdf texture out of range");
-            if (b.sub0 < -1 || b.sub0 >= nb || b.sub1 < -1 || b.sub1 >= nb) return bad("nested bsdf out of range");
-        }
-        if (sd->camera.medium < -1 || sd->camera.medium >= int32_t(sd->num_media)) return bad("camera medium out of range");
-        // instanced scenes: bvhDepthOf (level 1) and the tight-box upload index recs[] / inst_tight_boxes[] by num_top_recs
-        if (sd->num_instances != 0) {
-            if (sd->num_top_recs == 0 || sd->num_top_recs > sd->num_recs) return bad("num_top_recs out of range for a scene with instances");
-            if (!sd->inst_tight_boxes) return bad("scene with instances without inst_tight_boxes");
-            if (sd->num_inst_prims && !sd->inst_prims) return bad("scene with instances without inst_prims");
-        }
-    }
-    for (uint32_t i = 0; i < sd->num_textures; ++i) {
-        const TgHipTexture &t = sd->textures[i];
-        if (t.type < TGHIP_TEX_CONSTANT || t.type > TGHIP_TEX_BLADE) { ctx->error = "unknown texture type"; return TGHIP_E_UNSUPPORTED; }
-        // a blade's sampling picks one of res_u sectors and its lookups divide by the sector's angle
-        if (t.type == TGHIP_TEX_BLADE && (t.res_u < 1 || !(t.on_color[0] > 0.0f))) { ctx->error = "blade texture without blades"; return TGHIP_E_INVALID; }
-    }
-    int depth = bvhDepthOf(sd, &ctx->bvhMasterDepth);
-    if (depth < 0 || depth > TGHIP_MAX_BVH_DEPTH) { ctx->error = "malformed or too deep BVH"; return TGHIP_E_INVALID; }
-    for (uint32_t i = 0; i < sd->num_bsdfs; ++i)
-        if (bsdfDepth(sd, int(i), 0) > PT_MAX_BSDF_DEPTH) { ctx->error = "BSDF nesting deeper than 3 is not supported"; return TGHIP_E_UNSUPPORTED; }
-    for (uint32_t i = 0; i < sd->num_lights; ++i) {
-        int t = sd->objects[sd->lights[i]].type;
-        if (t == TGHIP_OBJ_MESH) {
-            const TgHipObject &lo = sd->objects[sd->lights[i]];
-            if (lo.first_light_tri < 0 || lo.num_light_tris <= 0 || !sd->light_tris ||
-                uint64_t(lo.first_light_tri) + uint64_t(lo.num_light_tris)*10u + 1u > sd->num_light_tri_floats) {
-                ctx->error = "sampled mesh emitter without a valid light_tris block";
-                return TGHIP_E_INVALID;
-            }
-        } else if (t != TGHIP_OBJ_QUAD && t != TGHIP_OBJ_INFINITE_SPHERE && t != TGHIP_OBJ_CUBE && t != TGHIP_OBJ_SPHERE && t != TGHIP_OBJ_DISK && t != TGHIP_OBJ_INFINITE_SPHERE_CAP && t != TGHIP_OBJ_POINT && t != TGHIP_OBJ_CYLINDER) {
-            ctx->error = "unknown emitter type";
-            return TGHIP_E_UNSUPPORTED;
-        }
-    }
+    // everything that can refuse the description, and everything derived from it, before the context is touched (csrc/host/SceneCheck.cpp)
+    SceneCheckOptions opt;
+    opt.top_tree = ctx->topTreeOpt;
+    opt.wide_node_stride = uint32_t(ctx->wideStride);
+    SceneTraits traits;
+    int rc = checkScene(sd, opt, traits, ctx->error);
+    if (rc != TGHIP_OK) return rc;
 
     if (ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->sceneMem.release();
     ctx->haveScene = false;
+    ctx->sc = std::move(traits);   // (its tables are copied from below: they live until the next upload, which waits for the stream first)
+    const SceneTraits &sc = ctx->sc;
     DeviceScene &s = ctx->scene;
     std::memset(&s, 0, sizeof(s));
-    int rc;
     const TgHipBvhNode *dn; const TgHipPrimRec *dr; const TgHipTriAttr *da;
     if ((rc = uploadArray(ctx, ctx->sceneMem, sd->nodes, sd->num_nodes, &dn)) != TGHIP_OK) return rc;
-    ctx->wideDepth = 0;
-    ctx->wideMasterDepth = 0;
     ctx->numWideNodes = 0;
-    s.hoisted_rec = -1; ctx->hoistedRecScene = -1;
-    if (sd->wide_nodes && sd->num_wide_nodes) {
+    if (sc.wideDepth > 0) {
         // the wide nodes and the primitive records share ONE allocation, so that a lane of the wide kernels addresses
         // "a node or a record" with one base pointer and one 32-bit offset
-        const int wd = wideDepthOf(sd, &ctx->wideMasterDepth);
-        if (wd < 0) { ctx->error = "malformed wide BVH"; return TGHIP_E_INVALID; }
         const size_t stride = size_t(ctx->wideStride);
         const size_t nodeBytes = (size_t(sd->num_wide_nodes)*stride + 127u) & ~size_t(127);
         const size_t recBytes = std::max<size_t>(sd->num_recs, 1)*sizeof(TgHipPrimRec);
-        if (nodeBytes + recBytes < (1ull << 32)) {
-            char *p = nullptr;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&p), nodeBytes + recBytes));
-            ctx->sceneMem.allocs.push_back(p);
-            HIP_TRY(ctx, hipMemcpy2DAsync(p, stride, sd->wide_nodes, sizeof(TgHipWideNode), sizeof(TgHipWideNode), sd->num_wide_nodes, hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(p + nodeBytes, sd->recs, size_t(sd->num_recs)*sizeof(TgHipPrimRec), hipMemcpyHostToDevice, ctx->stream));
-            // The scene's one quad, hoisted out of the decoupled walks (pt_scene.h: DeviceScene::hoisted_rec): a single-level scene of triangles and
-            // exactly ONE quad whose wide nodes leave `reserved` zero.  The wide node that holds the quad as a leaf record gets the record's bit of
-            // leaf_valid in its `reserved` word -- on the device copy only; the sequential walks (tghip_trace_rays, "decouple" = 0) do not read it.
-            s.hoisted_rec = -1; ctx->hoistedRecScene = -1;
-            if (sd->num_instances == 0) {
-                int64_t quad = -1;
-                bool ok = true;
-                for (uint32_t i = 0; i < sd->num_recs && ok; ++i) {
-                    const uint32_t kind = TGHIP_REC_KIND(sd->recs[i].meta);
-                    if (kind == TGHIP_REC_QUAD) { ok = quad < 0; quad = i; }
-                    else if (kind != TGHIP_REC_TRIANGLE) ok = false;
-                }
-                int64_t node = -1;
-                uint32_t bit = 0;
-                for (uint32_t i = 0; i < sd->num_wide_nodes && ok && quad >= 0; ++i) {
-                    const TgHipWideNode &n = sd->wide_nodes[i];
-                    if (n.reserved != 0u) ok = false;
-                    uint32_t rank = 0;
-                    for (uint32_t b = 0; b < 32u; ++b)
-                        if ((n.leaf_valid >> b) & 1u) {
-                            if (int64_t(n.rec_base) + rank == quad) { ok = ok && node < 0; node = i; bit = b; }
-                            ++rank;
-                        }
-                }
-                if (ok && quad >= 0 && node >= 0) {
-                    const uint32_t word = 1u << bit;
-                    // (on ctx->stream, behind the 2-D copy of the nodes queued above: that stream is non-blocking, so a copy on the null stream would
-                    // not wait for it and could be overwritten by it -- the quad would then be tested before AND inside every walk; `word` is on
-                    // the stack, so the copy is waited for here)
-                    HIP_TRY(ctx, hipMemcpyAsync(p + size_t(node)*stride + offsetof(TgHipWideNode, reserved), &word, sizeof(word), hipMemcpyHostToDevice, ctx->stream));
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    s.hoisted_rec = ctx->hoistOpt ? int32_t(quad) : -1;
-                    ctx->hoistedRecScene = int32_t(quad);
-                }
-            }
-            s.wide = reinterpret_cast<const float4 *>(p);
-            s.recs_offset = uint32_t(nodeBytes);
-            s.wide_stride = uint32_t(stride);
-            dr = reinterpret_cast<const TgHipPrimRec *>(p + nodeBytes);
-            ctx->wideDepth = wd;
-            ctx->numWideNodes = sd->num_wide_nodes;
+        char *p = nullptr;
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&p), nodeBytes + recBytes));
+        ctx->sceneMem.allocs.push_back(p);
+        HIP_TRY(ctx, hipMemcpy2DAsync(p, stride, sd->wide_nodes, sizeof(TgHipWideNode), sizeof(TgHipWideNode), sd->num_wide_nodes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(p + nodeBytes, sd->recs, size_t(sd->num_recs)*sizeof(TgHipPrimRec), hipMemcpyHostToDevice, ctx->stream));
+        if (sc.hoisted.record >= 0) {
+            // the hoisted quad's bit in the `reserved` word of the wide node that holds it (SceneTraits::hoisted) -- on the device copy only; the
+            // sequential walks (tghip_trace_rays, "decouple" = 0) do not read it.
+            // (on ctx->stream, behind the 2-D copy of the nodes queued above: that stream is non-blocking, so a copy on the null stream would
+            // not wait for it and could be overwritten by it -- the quad would then be tested before AND inside every walk; `word` is on
+            // the stack, so the copy is waited for here)
+            const uint32_t word = 1u << sc.hoisted.bit;
+            HIP_TRY(ctx, hipMemcpyAsync(p + size_t(sc.hoisted.node)*stride + offsetof(TgHipWideNode, reserved), &word, sizeof(word), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
+        s.wide = reinterpret_cast<const float4 *>(p);
+        s.recs_offset = uint32_t(nodeBytes);
+        s.wide_stride = uint32_t(stride);
+        dr = reinterpret_cast<const TgHipPrimRec *>(p + nodeBytes);
+        ctx->numWideNodes = sd->num_wide_nodes;
+    } else if ((rc = uploadArray(ctx, ctx->sceneMem, sd->recs, sd->num_recs, &dr)) != TGHIP_OK) {
+        return rc;
     }
-    if (!ctx->wideDepth && (rc = uploadArray(ctx, ctx->sceneMem, sd->recs, sd->num_recs, &dr)) != TGHIP_OK) return rc;
+    s.hoisted_rec = ctx->hoistOpt ? sc.hoisted.record : -1;
     if ((rc = uploadArray(ctx, ctx->sceneMem, sd->tri_attrs, sd->num_recs, &da)) != TGHIP_OK) return rc;
     s.nodes = reinterpret_cast<const float4 *>(dn);
     s.recs = reinterpret_cast<const float4 *>(dr);
@@ -1289,270 +976,39 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
     if ((rc = uploadArray(ctx, ctx->sceneMem, sd->texels, sd->num_texel_floats, &s.texels, 16)) != TGHIP_OK) return rc;
     if ((rc = uploadArray(ctx, ctx->sceneMem, sd->dist, sd->num_dist_floats, &s.dist)) != TGHIP_OK) return rc;
     if ((rc = uploadArray(ctx, ctx->sceneMem, sd->light_tris, sd->num_light_tri_floats, &s.light_tris)) != TGHIP_OK) return rc;
-    ctx->haveMeshLight = false;
-    ctx->haveInstances = sd->num_instances > 0;
-    ctx->haveMedia = sd->num_media > 0;
-    ctx->haveCylinder = false;
-    for (uint32_t i = 0; i < sd->num_objects; ++i)
-        if (sd->objects[i].type == TGHIP_OBJ_CYLINDER) ctx->haveCylinder = true;
-    for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
-        if (sd->bsdfs[i].bump1 < 0 || uint32_t(sd->bsdfs[i].bump1) > sd->num_textures) { ctx->error = "bsdf bump map index out of range"; return TGHIP_E_INVALID; }
-        if (sd->bsdfs[i].bump1 > 0) ctx->haveCylinder = true;      // (shaded by the same one variant)
-    }
-    ctx->haveProcTex = false;
-    for (uint32_t i = 0; i < sd->num_textures; ++i)
-        if (sd->textures[i].type == TGHIP_TEX_DISK || sd->textures[i].type == TGHIP_TEX_BLADE) ctx->haveProcTex = true;
-    if (ctx->haveProcTex) ctx->haveCylinder = true;                // (that variant again: the only one that evaluates them, pt_scene.h HAS_PROCTEX)
-    if (ctx->haveMedia) {
-        if (!sd->media || sd->num_media > PT_MAX_MEDIA) { ctx->error = "more than 126 media are not supported"; return TGHIP_E_UNSUPPORTED; }
-        if (sd->num_objects >= (1u << 16)) { ctx->error = "media scenes support at most 65535 primitives"; return TGHIP_E_UNSUPPORTED; }
-        if (sd->camera.medium >= int32_t(sd->num_media)) { ctx->error = "camera medium out of range"; return TGHIP_E_INVALID; }
-        for (uint32_t i = 0; i < sd->num_objects; ++i)
-            if (sd->objects[i].int_medium >= int32_t(sd->num_media) || sd->objects[i].ext_medium >= int32_t(sd->num_media)) {
-                ctx->error = "primitive medium out of range";
-                return TGHIP_E_INVALID;
-            }
-        for (uint32_t i = 0; i < sd->num_media; ++i) {
-            if (sd->media[i].phase_type < TGHIP_PHASE_ISOTROPIC || sd->media[i].phase_type > TGHIP_PHASE_RAYLEIGH) {
-                ctx->error = "unknown phase function";
-                return TGHIP_E_UNSUPPORTED;
-            }
-            if (sd->media[i].medium_type < TGHIP_MEDIUM_HOMOGENEOUS || sd->media[i].medium_type > TGHIP_MEDIUM_ATMOSPHERE) {
-                ctx->error = "unknown medium type"; return TGHIP_E_UNSUPPORTED;
-            }
-            if (sd->media[i].medium_type != TGHIP_MEDIUM_HOMOGENEOUS && sd->media[i].trans_type != TGHIP_TRANS_EXPONENTIAL) {
-                ctx->error = "an exponential or atmospheric medium with a non-exponential transmittance is not supported"; return TGHIP_E_UNSUPPORTED;
-            }
-            if (sd->media[i].medium_type == TGHIP_MEDIUM_ATMOSPHERE && !(sd->media[i].falloff_scale > 0.0f && sd->media[i].falloff_dir[0] > 0.0f)) {
-                ctx->error = "an atmospheric medium needs a positive falloff scale and radius"; return TGHIP_E_INVALID;
-            }
-            if (sd->media[i].trans_type < TGHIP_TRANS_EXPONENTIAL || sd->media[i].trans_type > TGHIP_TRANS_INTERPOLATED) {
-                ctx->error = "unknown transmittance";
-                return TGHIP_E_UNSUPPORTED;
-            }
-            if (sd->media[i].trans_type == TGHIP_TRANS_INTERPOLATED &&
-                (i + 2 >= sd->num_media || sd->media[i + 1].trans_type == TGHIP_TRANS_INTERPOLATED || sd->media[i + 2].trans_type == TGHIP_TRANS_INTERPOLATED)) {
-                ctx->error = "an interpolated transmittance needs its two (non-interpolated) operands in the media entries behind it";
-                return TGHIP_E_INVALID;
-            }
-        }
-    }
-    ctx->thinlens = sd->camera.type == TGHIP_CAMERA_THINLENS;
-    // the equirectangular camera's rays are written by a launch of their own in front of every closest-hit launch (k_camera_rays): the kernels that
-    // generate a camera ray and trace it in one go -- the folded finish, the flat lists' fused launches, k_tail -- are not used for such scenes
-    ctx->cameraFix = sd->camera.type == TGHIP_CAMERA_EQUIRECTANGULAR || sd->camera.type == TGHIP_CAMERA_CUBEMAP;
-    if (sd->camera.type == TGHIP_CAMERA_CUBEMAP && (sd->camera.blade_count < 0 || sd->camera.blade_count > 3)) { ctx->error = "unknown cubemap projection mode"; return TGHIP_E_INVALID; }
-    if (sd->camera.type < TGHIP_CAMERA_PINHOLE || sd->camera.type > TGHIP_CAMERA_CUBEMAP) { ctx->error = "unknown camera type"; return TGHIP_E_UNSUPPORTED; }
-    if (sd->camera.type == TGHIP_CAMERA_THINLENS && sd->camera.aperture_type == TGHIP_APERTURE_BITMAP) {
-        // the aperture's Distribution2D: marginalPdf[h] marginalCdf[h + 1] pdf[w h] cdf[(w + 1) h] inside dist[]
-        const uint64_t aw = uint64_t(std::max(sd->camera.aperture_w, 0)), ah = uint64_t(std::max(sd->camera.aperture_h, 0));
-        if (aw == 0 || ah == 0 || !sd->dist || uint64_t(sd->camera.aperture_dist) + ah + ah + 1 + aw*ah + (aw + 1)*ah > sd->num_dist_floats) {
-            ctx->error = "the bitmap aperture's distribution lies outside dist[]";
-            return TGHIP_E_INVALID;
-        }
-        // a table that cannot be inverted (an all-black aperture: 0/0 in the marginal CDF) would send every lens sample outside it
-        const float *mcdf = sd->dist + sd->camera.aperture_dist + ah;
-        bool usable = mcdf[0] == 0.0f && mcdf[ah] > 0.0f;
-        for (uint64_t i = 0; usable && i < ah; ++i)
-            usable = std::isfinite(mcdf[i + 1]) && mcdf[i + 1] >= mcdf[i];
-        if (!usable) {
-            ctx->error = "the bitmap aperture's distribution is not a CDF (zero total weight or non-finite entries)";
-            return TGHIP_E_INVALID;
-        }
-    } else if (sd->camera.type == TGHIP_CAMERA_THINLENS && sd->camera.aperture_type != TGHIP_APERTURE_DISK && sd->camera.aperture_type != TGHIP_APERTURE_BLADE) {
-        ctx->error = "unknown aperture type";
-        return TGHIP_E_UNSUPPORTED;
-    }
-    for (uint32_t i = 0; i < sd->num_lights; ++i)
-        if (sd->objects[sd->lights[i]].type == TGHIP_OBJ_MESH) ctx->haveMeshLight = true;
-    // CDF guide tables for the samplable bitmaps (pt_scene.h: upperBoundGuided)
-    {
-        std::vector<uint16_t> guide;
-        std::vector<int32_t> texGuide(std::max<uint32_t>(sd->num_textures, 1u), -1);
-        auto build = [&](const float *a, int n, int buckets) {   // g[b] = upper_bound(a[0..n], b/buckets)
-            int idx = 0;
-            for (int b = 0; b <= buckets; ++b) {
-                float x = float(b)/float(buckets);
-                while (idx <= n && a[idx] <= x) ++idx;
-                guide.push_back(uint16_t(std::min(idx, n + 1)));
-            }
-        };
-        for (uint32_t i = 0; i < sd->num_textures; ++i) {
-            const TgHipTexture &t = sd->textures[i];
-            if (t.type != TGHIP_TEX_BITMAP || t.dist_offset < 0 || t.w <= 0 || t.h <= 0 || t.w >= 65535 || t.h >= 65535)
-                continue;
-            if (guide.size() + size_t(PT_GUIDE_MARGINAL + 1) + size_t(t.h)*(PT_GUIDE_ROW + 1) >= (1u << 31))
-                continue;
-            texGuide[i] = int32_t(guide.size());
-            const float *mpdf = sd->dist + t.dist_offset;
-            const float *mcdf = mpdf + t.h;
-            const float *cdf = mcdf + (t.h + 1) + size_t(t.w)*t.h;
-            build(mcdf, t.h, PT_GUIDE_MARGINAL);
-            for (int y = 0; y < t.h; ++y)
-                build(cdf + size_t(y)*(t.w + 1), t.w, PT_GUIDE_ROW);
-        }
-        if (guide.empty()) guide.push_back(0);
-        if ((rc = uploadArray(ctx, ctx->sceneMem, guide.data(), guide.size(), &s.guide)) != TGHIP_OK) return rc;
-        if ((rc = uploadArray(ctx, ctx->sceneMem, texGuide.data(), texGuide.size(), &s.tex_guide)) != TGHIP_OK) return rc;
-        // the conditional tables of those bitmaps once more as interleaved (cdf, pdf) pairs (pt_scene.h: upperBoundGuidedPairs)
-        std::vector<float2> rows;
-        std::vector<int32_t> texRows(std::max<uint32_t>(sd->num_textures, 1u), -1);
-        for (uint32_t i = 0; i < sd->num_textures; ++i) {
-            const TgHipTexture &t = sd->textures[i];
-            if (texGuide[i] < 0 || rows.size() + size_t(t.w + 1)*size_t(t.h) >= (1u << 28))
-                continue;
-            texRows[i] = int32_t(rows.size());
-            const float *pdf = sd->dist + t.dist_offset + t.h + (t.h + 1);
-            const float *cdf = pdf + size_t(t.w)*t.h;
-            for (int y = 0; y < t.h; ++y)
-                for (int x = 0; x <= t.w; ++x)
-                    rows.push_back(make_float2(cdf[size_t(y)*(t.w + 1) + x], x < t.w ? pdf[size_t(y)*t.w + x] : 0.0f));
-        }
-        if (rows.empty()) rows.push_back(make_float2(0.0f, 0.0f));
-        if ((rc = uploadArray(ctx, ctx->sceneMem, rows.data(), rows.size(), &s.rows)) != TGHIP_OK) return rc;
-        if ((rc = uploadArray(ctx, ctx->sceneMem, texRows.data(), texRows.size(), &s.tex_rows)) != TGHIP_OK) return rc;
-        // the marginal tables of the first sampled environment map, for the shading kernels' LDS copy (stageSceneTables)
-        s.env_tex = -1; s.env_h = 0; s.env_marginal = nullptr; s.env_guide = nullptr;
-        std::vector<uint16_t> envGuide;
-        for (uint32_t li = 0; li < sd->num_lights && s.env_tex < 0; ++li) {
-            const TgHipObject &o = sd->objects[sd->lights[li]];
-            if (o.type != TGHIP_OBJ_INFINITE_SPHERE || o.emission < 0 || texGuide[size_t(o.emission)] < 0) continue;
-            const TgHipTexture &t = sd->textures[o.emission];
-            s.env_tex = o.emission;
-            s.env_h = t.h;
-            s.env_marginal = s.dist + t.dist_offset;          // mpdf[h] mcdf[h + 1] (device pointer arithmetic only)
-            envGuide.assign(guide.begin() + texGuide[size_t(o.emission)], guide.begin() + texGuide[size_t(o.emission)] + PT_GUIDE_MARGINAL + 1);
-            envGuide.push_back(0);                            // padded to whole 32-bit words
-        }
-        // do the small tables fit the shading workgroups' LDS copy (pt_kernels.h: stageSceneTables)?  Without the environment map's marginal
-        // tables they must, or the scene shades with the GLOBAL_TABLES variant; the marginal tables come along only when there is room
-        ctx->tablesFit = sceneTableLayout(sd->num_objects, sd->num_bsdfs, sd->num_textures, sd->num_lights, sd->num_infinite_lights, 0).total <= PT_LDS_TABLE_BYTES;
-        if (s.env_tex >= 0 && sceneTableLayout(sd->num_objects, sd->num_bsdfs, sd->num_textures, sd->num_lights, sd->num_infinite_lights, s.env_h).total > PT_LDS_TABLE_BYTES) {
-            s.env_tex = -1; s.env_h = 0; s.env_marginal = nullptr;      // (sampled through the texture's own tables in global memory, like any other bitmap)
-            envGuide.clear();
-        }
-        ctx->tablesFitScene = ctx->tablesFit;
-        ctx->envTexScene = s.env_tex;
-        if (envGuide.empty()) envGuide.assign(2, 0);
-        if ((rc = uploadArray(ctx, ctx->sceneMem, envGuide.data(), envGuide.size(), &s.env_guide)) != TGHIP_OK) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the vectors go out of scope
-    }
-    // shading classes ("sort by material", pt_kernels.h: PT_NUM_CLASSES): 0 = BSDFs made of lambert / null only, 1 = conductor family, 2 = dielectric family, 3 = the rest
-    {
-        std::vector<uint32_t> typeMask(sd->num_bsdfs, 0u);
-        std::vector<uint8_t> recClass(std::max<uint32_t>(sd->num_recs, 1u), 0);
-        ctx->haveComplex = false; ctx->complexMask = 0; ctx->haveForward = false; ctx->haveSolids = false;
-        for (int c = 0; c < PT_NUM_CLASSES; ++c) { ctx->classPresent[c] = false; ctx->classMask[c] = 0; }
-        for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
-            typeMask[i] = bsdfTypeMask(sd, int(i), 0);
-            if (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ctx->haveForward = true;
-        }
-        ctx->bsdfTypes.assign(sd->num_bsdfs, 0u);
-        ctx->bsdfForward.assign(sd->num_bsdfs, 0);
-        for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
-            // (FEAT_FAMILY_ALL: the scene holds a `disk` or `blade` texture, so every material of it is shaded by the all-features family -- no other
-            // family covers the entry)
-            ctx->bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u) | (ctx->haveProcTex ? FEAT_FAMILY_ALL : 0u);
-            ctx->bsdfForward[i] = (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ? 1 : 0;
-        }
-        for (uint32_t i = 0; i < sd->num_recs; ++i) {
-            uint32_t meta = sd->recs[i].meta;
-            if (TGHIP_REC_KIND(meta) == TGHIP_REC_INSTANCE || TGHIP_REC_KIND(meta) == TGHIP_REC_INSTANCE_SET)
-                continue;                    // never a hit record itself: hits are the master's triangles
-            if (TGHIP_REC_KIND(meta) > TGHIP_REC_CYLINDER) { ctx->error = "unknown primitive record kind"; return TGHIP_E_INVALID; }
-            if (TGHIP_REC_KIND(meta) != TGHIP_REC_TRIANGLE && TGHIP_REC_KIND(meta) != TGHIP_REC_QUAD) ctx->haveSolids = true;
-            int bi = TGHIP_REC_KIND(meta) == TGHIP_REC_TRIANGLE ? sd->tri_attrs[i].bsdf : sd->objects[TGHIP_REC_OBJECT(meta)].bsdf;
-            if (bi < 0 || uint32_t(bi) >= sd->num_bsdfs) { ctx->error = "primitive record without a valid bsdf"; return TGHIP_E_INVALID; }
-            // the smallest family that covers every type inside the material (nested ones included); forward lobes -> "everything else"
-            const uint32_t tm = typeMask[size_t(bi)];
-            const bool fwd = (sd->bsdfs[bi].lobes & TGHIP_LOBE_FORWARD) != 0;
-            const int c = familyCovers(TGHIP_BSDF_VARIANT_SIMPLE, tm, fwd) ? 0 : familyCovers(TGHIP_BSDF_VARIANT_COAT, tm, fwd) ? 1 :
-                          familyCovers(TGHIP_BSDF_VARIANT_GLASS, tm, fwd) ? 2 : 3;
-            recClass[i] = uint8_t(c);
-            ctx->classPresent[c] = true;
-            ctx->classMask[c] |= tm;
-            if (c != 0) { ctx->haveComplex = true; ctx->complexMask |= tm; }
-        }
-        {
-            uint32_t allTypes = 0;
-            for (int c = 0; c < PT_NUM_CLASSES; ++c) allTypes |= ctx->classMask[c];
-            ctx->mediaSimple = ctx->haveMedia && !ctx->haveInstances && familyCovers(TGHIP_BSDF_VARIANT_MEDIA, allTypes, false);
-        }
-        bool lean = sd->num_infinite_lights == 0 && sd->num_lights <= 1;
-        for (uint32_t i = 0; i < sd->num_textures && lean; ++i) lean = sd->textures[i].type != TGHIP_TEX_BITMAP;
-        for (uint32_t i = 0; i < sd->num_recs && lean; ++i)
-            lean = TGHIP_REC_KIND(sd->recs[i].meta) == TGHIP_REC_QUAD || TGHIP_REC_KIND(sd->recs[i].meta) == TGHIP_REC_CUBE;
-        for (uint32_t i = 0; i < sd->num_lights && lean; ++i) lean = sd->objects[sd->lights[i]].type == TGHIP_OBJ_QUAD;
-        ctx->leanScene = lean;
-        if ((rc = uploadArray(ctx, ctx->sceneMem, recClass.data(), recClass.size(), &s.rec_class)) != TGHIP_OK) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // recClass goes out of scope
-    }
+    // the tables derived from the description (SceneTraits)
+    if ((rc = uploadArray(ctx, ctx->sceneMem, sc.guide.data(), sc.guide.size(), &s.guide)) != TGHIP_OK) return rc;
+    if ((rc = uploadArray(ctx, ctx->sceneMem, sc.texGuide.data(), sc.texGuide.size(), &s.tex_guide)) != TGHIP_OK) return rc;
+    if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float2 *>(sc.rows.data()), sc.rows.size()/2, &s.rows)) != TGHIP_OK) return rc;
+    if ((rc = uploadArray(ctx, ctx->sceneMem, sc.texRows.data(), sc.texRows.size(), &s.tex_rows)) != TGHIP_OK) return rc;
+    s.env_tex = sc.env_tex; s.env_h = sc.env_h;
+    s.env_marginal = sc.env_tex >= 0 ? s.dist + sd->textures[sc.env_tex].dist_offset : nullptr;   // mpdf[h] mcdf[h + 1] (device pointer arithmetic only)
+    if ((rc = uploadArray(ctx, ctx->sceneMem, sc.envGuide.data(), sc.envGuide.size(), &s.env_guide)) != TGHIP_OK) return rc;
+    ctx->tablesFit = sc.tablesFit;
+    if ((rc = uploadArray(ctx, ctx->sceneMem, sc.recClass.data(), sc.recClass.size(), &s.rec_class)) != TGHIP_OK) return rc;
     s.num_nodes = sd->num_nodes; s.num_recs = sd->num_recs; s.num_objects = sd->num_objects;
     s.num_lights = sd->num_lights; s.num_infinite_lights = sd->num_infinite_lights;
     s.num_bsdfs = sd->num_bsdfs; s.num_textures = sd->num_textures;
     s.num_instances = sd->num_instances;
-    s.inst_prims = nullptr; s.inst_leaf_boxes = nullptr; s.inst_tight_boxes = nullptr;
     if (sd->num_instances) {
         if ((rc = uploadArray(ctx, ctx->sceneMem, sd->inst_prims, size_t(sd->num_inst_prims), &s.inst_prims)) != TGHIP_OK) return rc;
         const float4 *boxes = nullptr;
         if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float4 *>(sd->inst_leaf_boxes), size_t(sd->num_inst_prims)*2, &boxes)) != TGHIP_OK) return rc;
         s.inst_leaf_boxes = boxes;
-        if (!sd->inst_tight_boxes) { ctx->error = "scene with instances without inst_tight_boxes"; return TGHIP_E_INVALID; }
         const float4 *tight = nullptr;
         if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float4 *>(sd->inst_tight_boxes), size_t(sd->num_top_recs)*2, &tight)) != TGHIP_OK) return rc;
         s.inst_tight_boxes = tight;
     }
-    s.top_nodes = nullptr;
-    s.flat_boxes = nullptr;
-    if (sd->top_nodes && sd->num_top_nodes && ctx->topTreeOpt) {
-        // the reference's top-level Embree tree (TgHipTopNode): flat lists only, every record exactly one leaf, children behind their parents
-        // (preorder: no cycles), no deeper than the walk's stack allows (pt_kernels.h: flatOrderedWalk)
-        const uint32_t nn = sd->num_top_nodes;
-        bool ok = sd->num_recs >= 2 && sd->num_recs <= TGHIP_FLAT_MAX_RECS && !sd->num_instances && nn < sd->num_recs;
-        std::vector<float4> boxes(size_t(sd->num_recs)*2);
-        std::vector<int> leafOf(sd->num_recs, 0), depth(nn, 0), parents(nn, 0);
-        if (ok) depth[0] = 1;
-        for (uint32_t n = 0; n < nn && ok; ++n) {
-            ok = depth[n] >= 1 && depth[n] <= TGHIP_TOP_MAX_DEPTH && (n == 0 || parents[n] == 1);
-            for (int i = 0; i < 4 && ok; ++i) {
-                const int32_t c = sd->top_nodes[n].child[i];
-                if (c == TGHIP_TOP_EMPTY) continue;
-                if (c >= 0) {
-                    ok = uint32_t(c) > n && uint32_t(c) < nn;
-                    if (ok) { depth[c] = depth[n] + 1; parents[c]++; }
-                } else {
-                    const uint32_t r = uint32_t(~c);
-                    ok = r < sd->num_recs && leafOf[r]++ == 0;
-                    if (ok) {
-                        const TgHipTopNode &t = sd->top_nodes[n];
-                        boxes[2*r] = make_float4(t.lower[i][0], t.lower[i][1], t.lower[i][2], 0.0f);
-                        boxes[2*r + 1] = make_float4(t.upper[i][0], t.upper[i][1], t.upper[i][2], 0.0f);
-                    }
-                }
-            }
-        }
-        for (uint32_t r = 0; r < sd->num_recs && ok; ++r) {
-            const uint32_t kind = TGHIP_REC_KIND(sd->recs[r].meta);
-            ok = leafOf[r] == 1 && (kind == TGHIP_REC_QUAD || kind == TGHIP_REC_CUBE || kind == TGHIP_REC_SPHERE || kind == TGHIP_REC_DISK || kind == TGHIP_REC_CYLINDER);
-        }
-        if (!ok) { ctx->error = "top_nodes: not the tree of a flat list (every record one leaf, preorder, depth <= TGHIP_TOP_MAX_DEPTH)"; return TGHIP_E_INVALID; }
+    if (sc.topTree) {
         static_assert(sizeof(TgHipTopNode) == 28*sizeof(float), "TgHipTopNode layout");
-        if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float *>(sd->top_nodes), size_t(nn)*28, &s.top_nodes)) != TGHIP_OK) return rc;
-        if ((rc = uploadArray(ctx, ctx->sceneMem, boxes.data(), boxes.size(), &s.flat_boxes)) != TGHIP_OK) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // boxes goes out of scope
+        if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float *>(sd->top_nodes), size_t(sd->num_top_nodes)*28, &s.top_nodes)) != TGHIP_OK) return rc;
+        if ((rc = uploadArray(ctx, ctx->sceneMem, reinterpret_cast<const float4 *>(sc.flatBoxes.data()), sc.flatBoxes.size()/4, &s.flat_boxes)) != TGHIP_OK) return rc;
     }
-    s.media = nullptr;
     s.num_media = sd->num_media;
     if (sd->num_media && (rc = uploadArray(ctx, ctx->sceneMem, sd->media, size_t(sd->num_media), &s.media)) != TGHIP_OK) return rc;
-    if (ctx->haveMedia) ctx->haveForward = true;   // shadow rays pick up transmittance segment by segment: the closest-hit walk
     if ((rc = uploadArray(ctx, ctx->sceneMem, &sd->camera, 1, &s.camera)) != TGHIP_OK) return rc;
-    s.sobol = nullptr;
-    if (sd->sobol_matrices) {
-        if (sd->num_sobol_words != uint64_t(TGHIP_SOBOL_DIMS)*TGHIP_SOBOL_BITS) { ctx->error = "sobol_matrices must hold 1024 x 52 words"; return TGHIP_E_INVALID; }
-        if ((rc = uploadArray(ctx, ctx->sceneMem, sd->sobol_matrices, size_t(sd->num_sobol_words), &s.sobol)) != TGHIP_OK) return rc;
-    }
+    if (sd->sobol_matrices && (rc = uploadArray(ctx, ctx->sceneMem, sd->sobol_matrices, size_t(sd->num_sobol_words), &s.sobol)) != TGHIP_OK) return rc;
     s.settings = sd->settings;
-    ctx->bvhDepth = depth;
 
     // framebuffer
     if (ctx->width != uint32_t(sd->camera.res_x) || ctx->height != uint32_t(sd->camera.res_y) || !ctx->fbSum) {
@@ -1632,9 +1088,9 @@ static void launchShade(tghip_ctx *ctx, int grid, const PathState &st, const Pas
 template<int FUSE>
 static void launchComplexClass(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int cls)
 {
-    const bool plasticOnly = familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false);
+    const bool plasticOnly = familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false);
     if constexpr (FUSE == 0) {
-        if (ctx->haveInstances) {
+        if (ctx->sc.haveInstances) {
             if (cls == 1)                     launchShade<MASK_COAT_INST>(ctx, grid, st, pp, cls);
             else if (cls == 2)                launchShade<MASK_GLASS_INST>(ctx, grid, st, pp, cls);
             else if (plasticOnly)             launchShade<MASK_PLASTIC_INST>(ctx, grid, st, pp, cls);
@@ -1654,13 +1110,13 @@ static void launchComplexClass(tghip_ctx *ctx, int grid, const PathState &st, co
 // outputs, cylinders, mesh emitters, lean scenes and flat lists keep their per-class launches.
 static int shadeFusedPair(const tghip_ctx *ctx)
 {
-    if (!ctx->shadeFusedOpt || isFlat(ctx) || ctx->haveInstances || ctx->haveMedia || ctx->auxPass || ctx->haveCylinder || ctx->haveMeshLight ||
-        ctx->leanScene || !ctx->tablesFit || !ctx->mergeMissOpt || ctx->classStreamsOpt != 0)
+    if (!ctx->shadeFusedOpt || isFlat(ctx) || ctx->sc.haveInstances || ctx->sc.haveMedia || ctx->auxPass || ctx->sc.allFeaturesShading || ctx->sc.haveMeshLight ||
+        ctx->sc.leanScene || !ctx->tablesFit || !ctx->mergeMissOpt || ctx->classStreamsOpt != 0)
         return 0;
     int further = 0, n = 0;
     for (int c = 1; c < PT_NUM_CLASSES; ++c)
-        if (ctx->classPresent[c]) { further = c; ++n; }
-    if (n != 1 || (further == 3 && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->classMask[3], false)))
+        if (ctx->sc.classPresent[c]) { further = c; ++n; }
+    if (n != 1 || (further == 3 && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false)))
         return 0;
     return further;
 }
@@ -1678,49 +1134,49 @@ static bool launchShadow(tghip_ctx *ctx, int grid, const PathState &st, const Pa
 {
     const size_t ldsBytes = traceLdsBytes(ctx, ctx->thrShadow);
     const bool flat = isFlat(ctx);
-    const bool closestWalk = ctx->haveForward || ctx->haveMeshLight;   // shadow rays are closest-hit walks, not any-hit queries
+    const bool closestWalk = ctx->sc.haveForward || ctx->sc.haveMeshLight;   // shadow rays are closest-hit walks, not any-hit queries
     const bool wideShadow = wideShadowRays(ctx) && !closestWalk && !ctx->auxPass;
-    if (ctx->haveProcTex && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels)
+    if (ctx->sc.haveProcTex && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels)
 #define SHADOW_TEX(FLAT, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, true, FLAT, I, BSDF_MASK_ALL>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (ctx->haveInstances) { if (ctx->haveSolids) SHADOW_TEX(false, 1); else SHADOW_TEX(false, 2); }
+        if (ctx->sc.haveInstances) { if (ctx->sc.haveSolids) SHADOW_TEX(false, 1); else SHADOW_TEX(false, 2); }
         else if (flat) SHADOW_TEX(true, 0);
         else           SHADOW_TEX(false, 0);
 #undef SHADOW_TEX
         return false;
     }
-    if (ctx->haveInstances && !wideShadow) {
+    if (ctx->sc.haveInstances && !wideShadow) {
 #define SHADOW_INST(FWD, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, FWD, false, I>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (closestWalk) { if (ctx->haveSolids) SHADOW_INST(true, 1); else SHADOW_INST(true, 2); }
-        else             { if (ctx->haveSolids) SHADOW_INST(false, 1); else SHADOW_INST(false, 2); }
+        if (closestWalk) { if (ctx->sc.haveSolids) SHADOW_INST(true, 1); else SHADOW_INST(true, 2); }
+        else             { if (ctx->sc.haveSolids) SHADOW_INST(false, 1); else SHADOW_INST(false, 2); }
 #undef SHADOW_INST
         return false;
     }
     if (wideShadow) {
         const size_t lds = wideLdsBytes(ctx, ctx->thrShadow);
 #define SHADOW_WIDE(S, I) hipLaunchKernelGGL((k_trace_shadow_wide<COUNT, S, I>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (ctx->haveInstances) {
+        if (ctx->sc.haveInstances) {
             // (rounds 2 and 3 launched the counting variant here: the non-counting one lost occluders inside instances.  The cause is the
             // loop latch the backend generates for the turn without PT_TURN_JOIN, pt_wavefront.h; "inst_shadow_join" = 0 launches that
             // variant for tools/repro_latch_miscompile.py)
-            if (!ctx->instShadowJoin && !ctx->haveSolids && !COUNT)
+            if (!ctx->instShadowJoin && !ctx->sc.haveSolids && !COUNT)
                 hipLaunchKernelGGL((k_trace_shadow_wide<false, false, true, false>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
             else if (ctx->instShadowFast) {      // round 6: the two-level walk inside the fast kernel's slot handling
-                if (ctx->haveSolids) hipLaunchKernelGGL((k_trace_shadow_fast_inst<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
+                if (ctx->sc.haveSolids) hipLaunchKernelGGL((k_trace_shadow_fast_inst<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
                 else                 hipLaunchKernelGGL((k_trace_shadow_fast_inst<COUNT, false>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
             }
-            else if (ctx->haveSolids) SHADOW_WIDE(true, true); else SHADOW_WIDE(false, true);
+            else if (ctx->sc.haveSolids) SHADOW_WIDE(true, true); else SHADOW_WIDE(false, true);
         }
         else if (ctx->decoupleOpt) {
 #define SHADOW_WIDE_D(S) hipLaunchKernelGGL((k_trace_shadow_fast<COUNT, S>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag)
-            if (ctx->haveSolids) SHADOW_WIDE_D(true); else SHADOW_WIDE_D(false);
+            if (ctx->sc.haveSolids) SHADOW_WIDE_D(true); else SHADOW_WIDE_D(false);
 #undef SHADOW_WIDE_D
         }
-        else                    { if (ctx->haveSolids) SHADOW_WIDE(true, false); else SHADOW_WIDE(false, false); }
+        else                    { if (ctx->sc.haveSolids) SHADOW_WIDE(true, false); else SHADOW_WIDE(false, false); }
 #undef SHADOW_WIDE
         return true;
     }
     if (!flat && !closestWalk && ctx->dynamicFetch && !ctx->auxPass) {   // (the dynamic-fetch kernel does not report transmittances)
-        if (ctx->haveSolids) hipLaunchKernelGGL((k_trace_shadow_dyn<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), dynLdsBytes(ctx, ctx->thrShadow), ctx->launchStream,
+        if (ctx->sc.haveSolids) hipLaunchKernelGGL((k_trace_shadow_dyn<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), dynLdsBytes(ctx, ctx->thrShadow), ctx->launchStream,
                                                 ctx->scene, st, pp, iterTag);
         else                 hipLaunchKernelGGL((k_trace_shadow_dyn<COUNT, false>), dim3(grid), dim3(ctx->thrShadow), dynLdsBytes(ctx, ctx->thrShadow), ctx->launchStream,
                                                 ctx->scene, st, pp, iterTag);
@@ -1747,17 +1203,17 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     st.inst_tree_depth = uint32_t(instTreeDepth(ctx));
     st.inst_phase_min = uint32_t(ctx->instPhaseMin);
     st.inst_refill_at = uint32_t(ctx->instRefillAt);
-    st.nee_factors = (ctx->haveForward || ctx->haveMeshLight) ? 1u : 0u;   // launchShadow: the closest-hit shadow walk, k_trace_shadow<., FORWARD>
+    st.nee_factors = (ctx->sc.haveForward || ctx->sc.haveMeshLight) ? 1u : 0u;   // launchShadow: the closest-hit shadow walk, k_trace_shadow<., FORWARD>
     st.suspend_lanes = ctx->poolWalkArrays ? uint32_t(ctx->suspendLanes) : 0u;
     st.suspend_turns = uint32_t(std::max(ctx->suspendTurns, 1));
     st.suspend_min_queue = uint32_t(ctx->suspendMinQueue);
-    st.leaf_batch_bvh2 = uint32_t(ctx->leafBatchBvh2 > 0 ? ctx->leafBatchBvh2 : ctx->haveInstances ? 16 : ctx->leafBatch);
+    st.leaf_batch_bvh2 = uint32_t(ctx->leafBatchBvh2 > 0 ? ctx->leafBatchBvh2 : ctx->sc.haveInstances ? 16 : ctx->leafBatch);
     const DeviceScene &s = ctx->scene;
     const int grid = int(ctx->poolGrid);
     const bool count = ctx->countTraversal;
     const bool flat = isFlat(ctx);
-    const bool fused = flat && !ctx->haveForward && !ctx->haveMeshLight && ctx->fuseFlatOpt && !ctx->auxPass && !ctx->haveCylinder && ctx->tablesFit && !ctx->cameraFix;
-    const bool runToCompletion = fused && !ctx->haveComplex && ctx->loopOpt;   // one launch renders the whole batch
+    const bool fused = flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit && !ctx->sc.cameraFix;
+    const bool runToCompletion = fused && !ctx->sc.haveComplex && ctx->loopOpt;   // one launch renders the whole batch
     const size_t ldsBytes = traceLdsBytes(ctx, ctx->thrClosest);
 
     // optional per-launch timing: one event pair per kernel launch of a check interval, read back at the
@@ -1785,7 +1241,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     // overlaps the other parts' kernels
     // (materialtest 1280x720x256 / mesh1m 1920x1080x32 on one box: 2 parts 656 / 398 Msamples/s, 4 parts 666 / 412)
     // (instanced scenes: two parts in rounds 2-3; with the walk of the reference's instance tree four are 5 % faster -- profiles/r4_sweep_instances10k.jsonl)
-    int parts = ctx->streamsOpt >= 2 ? ctx->streamsOpt : (ctx->streamsOpt == 1 || ctx->shortBatch) ? 1 : (!ctx->haveInstances || ctx->blocksPerCu >= 8) ? 4 : 1;
+    int parts = ctx->streamsOpt >= 2 ? ctx->streamsOpt : (ctx->streamsOpt == 1 || ctx->shortBatch) ? 1 : (!ctx->sc.haveInstances || ctx->blocksPerCu >= 8) ? 4 : 1;
     if (fused || flat || grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
         parts = 1;
     const bool split = parts > 1;
@@ -1822,9 +1278,9 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     }
     // k_tail runs the wide single-level kernels' bodies: scenes those kernels render, passes without visit counts (per-launch timing does
     // not see it: the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
-    const bool tailEligible = ctx->tailOpt && !ctx->cameraFix && ctx->tablesFit && !flat && !ctx->haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt &&
-                              familyCovers(TGHIP_BSDF_VARIANT_TAIL, ctx->complexMask, ctx->haveForward) &&
-                              !ctx->haveMeshLight && !ctx->haveMedia && !ctx->auxPass && !ctx->haveCylinder && !count &&
+    const bool tailEligible = ctx->tailOpt && !ctx->sc.cameraFix && ctx->tablesFit && !flat && !ctx->sc.haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt &&
+                              familyCovers(TGHIP_BSDF_VARIANT_TAIL, ctx->sc.complexMask, ctx->sc.haveForward) &&
+                              !ctx->sc.haveMeshLight && !ctx->sc.haveMedia && !ctx->auxPass && !ctx->sc.allFeaturesShading && !count &&
                               st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
     const uint64_t tailThreshold = uint64_t(std::max<long long>(ctx->tailThreshold, 0));
     // (k_tail runs 256 threads whatever the depth of the tree: it is used only where a workgroup of it fits a CU -- its static LDS plus
@@ -1833,19 +1289,19 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     if (tailEligible) {
         int nb = 0;
         // (the conductor-family tail, tailCoat below, needs no more than the all-types one)
-        const void *fn = pp.flags ? (ctx->haveSolids ? reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), true>) : reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), false>))
-                                  : (ctx->haveSolids ? reinterpret_cast<const void *>(k_tail<MASK_TAIL, true>) : reinterpret_cast<const void *>(k_tail<MASK_TAIL, false>));
+        const void *fn = pp.flags ? (ctx->sc.haveSolids ? reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), true>) : reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), false>))
+                                  : (ctx->sc.haveSolids ? reinterpret_cast<const void *>(k_tail<MASK_TAIL, true>) : reinterpret_cast<const void *>(k_tail<MASK_TAIL, false>));
         tailFits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, wideLdsBytes(ctx, 256)) == hipSuccess && nb >= 1;
     }
     // "fold_finish": k_finish rides in front of the next iteration's closest-hit launch (single-level scenes on the decoupled wide walk)
-    const bool foldFinish = ctx->foldFinishOpt && !ctx->cameraFix && !flat && !ctx->haveInstances && wideClosest(ctx) && ctx->decoupleOpt;
+    const bool foldFinish = ctx->foldFinishOpt && !ctx->sc.cameraFix && !flat && !ctx->sc.haveInstances && wideClosest(ctx) && ctx->decoupleOpt;
     const int fusedClass = shadeFusedPair(ctx);  // != 0: the iteration's shading is one launch of k_shade_fused
     // shading launches of an iteration (per part): one for class 0 and the escaped paths (two when "merge_miss" = 0), one per further class
     int shadeLaunches = 1;
     if (!fusedClass) {
         shadeLaunches = (ctx->classStreamsOpt != 0 || !ctx->mergeMissOpt) ? 2 : 1;
         for (int c = 1; c < PT_NUM_CLASSES; ++c)
-            if (ctx->classPresent[c]) ++shadeLaunches;
+            if (ctx->sc.classPresent[c]) ++shadeLaunches;
     }
     uint32_t iterTag = 1;                        // k_start publishes tag 1 when it queued anything
     bool first = true;
@@ -1853,43 +1309,43 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
         // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
         auto launchIteration = [&](const PathState &st, const PassParams &pp, int grid, uint32_t iterTag, bool timed, int part) {
             auto tic = [&]() { if (timed) ticMain(); };
-            if (ctx->cameraFix)                  // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
+            if (ctx->sc.cameraFix)                  // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
                 hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp);
             tic();
             if (flat) {
                 if (count) hipLaunchKernelGGL((k_trace_closest<true, true>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
                 else       hipLaunchKernelGGL((k_trace_closest<false, true>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
-            } else if (ctx->haveInstances && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt) {
+            } else if (ctx->sc.haveInstances && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt) {
                 // the three-level walk with dynamic ray fetch
                 const bool iw = instWide(ctx);               // the masters through the wide BVH (round 6)
                 const size_t ldsDyn = iw ? instWideLdsBytes(ctx, ctx->thrClosest) : dynLdsBytes(ctx, ctx->thrClosest);
 #define CLOSEST_DYN_INST(C, S) do { if (iw) hipLaunchKernelGGL((k_trace_closest_instw<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st); \
                                     else hipLaunchKernelGGL((k_trace_closest_inst<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st); } while (0)
-                if (ctx->haveSolids) { if (count) CLOSEST_DYN_INST(true, true); else CLOSEST_DYN_INST(false, true); }
+                if (ctx->sc.haveSolids) { if (count) CLOSEST_DYN_INST(true, true); else CLOSEST_DYN_INST(false, true); }
                 else                 { if (count) CLOSEST_DYN_INST(true, false); else CLOSEST_DYN_INST(false, false); }
 #undef CLOSEST_DYN_INST
-            } else if (ctx->haveInstances && !wideClosest(ctx)) {
+            } else if (ctx->sc.haveInstances && !wideClosest(ctx)) {
 #define CLOSEST_INST(C, I) hipLaunchKernelGGL((k_trace_closest<C, false, I>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st)
-                if (ctx->haveSolids) { if (count) CLOSEST_INST(true, 1); else CLOSEST_INST(false, 1); }
+                if (ctx->sc.haveSolids) { if (count) CLOSEST_INST(true, 1); else CLOSEST_INST(false, 1); }
                 else                 { if (count) CLOSEST_INST(true, 2); else CLOSEST_INST(false, 2); }
 #undef CLOSEST_INST
             } else if (wideClosest(ctx)) {
                 const size_t ldsWide = wideLdsBytes(ctx, ctx->thrClosest);
 #define CLOSEST_WIDE(C, S, I, D) hipLaunchKernelGGL((k_trace_closest_wide<C, S, I, D>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st)
-                if (ctx->haveInstances) {
-                    if (ctx->haveSolids) { if (count) CLOSEST_WIDE(true, true, true, false); else CLOSEST_WIDE(false, true, true, false); }
+                if (ctx->sc.haveInstances) {
+                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, true, false); else CLOSEST_WIDE(false, true, true, false); }
                     else                 { if (count) CLOSEST_WIDE(true, false, true, false); else CLOSEST_WIDE(false, false, true, false); }
                 } else if (ctx->decoupleOpt && foldFinish) {
                     // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
 #define CLOSEST_FIN(C, S) hipLaunchKernelGGL((k_finish_trace_closest_wide<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st, pp)
-                    if (ctx->haveSolids) { if (count) CLOSEST_FIN(true, true); else CLOSEST_FIN(false, true); }
+                    if (ctx->sc.haveSolids) { if (count) CLOSEST_FIN(true, true); else CLOSEST_FIN(false, true); }
                     else                 { if (count) CLOSEST_FIN(true, false); else CLOSEST_FIN(false, false); }
 #undef CLOSEST_FIN
                 } else if (ctx->decoupleOpt) {
-                    if (ctx->haveSolids) { if (count) CLOSEST_WIDE(true, true, false, true); else CLOSEST_WIDE(false, true, false, true); }
+                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, false, true); else CLOSEST_WIDE(false, true, false, true); }
                     else                 { if (count) CLOSEST_WIDE(true, false, false, true); else CLOSEST_WIDE(false, false, false, true); }
                 } else {
-                    if (ctx->haveSolids) { if (count) CLOSEST_WIDE(true, true, false, false); else CLOSEST_WIDE(false, true, false, false); }
+                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, false, false); else CLOSEST_WIDE(false, true, false, false); }
                     else                 { if (count) CLOSEST_WIDE(true, false, false, false); else CLOSEST_WIDE(false, false, false, false); }
                 }
 #undef CLOSEST_WIDE
@@ -1897,7 +1353,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 if (ctx->dynamicFetch) {
                     const size_t ldsDyn = dynLdsBytes(ctx, ctx->thrClosest);
 #define CLOSEST_DYN(C, S) hipLaunchKernelGGL((k_trace_closest_dyn<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st)
-                    if (ctx->haveSolids) { if (count) CLOSEST_DYN(true, true); else CLOSEST_DYN(false, true); }
+                    if (ctx->sc.haveSolids) { if (count) CLOSEST_DYN(true, true); else CLOSEST_DYN(false, true); }
                     else                 { if (count) CLOSEST_DYN(true, false); else CLOSEST_DYN(false, false); }
 #undef CLOSEST_DYN
                 } else {
@@ -1912,14 +1368,14 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
             // for 2 to 24 hardware queues): with four parts in flight the chip is not short of independent launches.
             auto shadeClass = [&](int cls) {
                 const bool simple = cls == 0 || cls == CLS_MISS || cls == CLS_0_AND_MISS;
-                if (ctx->mediaSimple && ctx->mediaLeanOpt && !ctx->auxPass && !ctx->haveCylinder && !ctx->haveMeshLight)
+                if (ctx->sc.mediaSimple && ctx->mediaLeanOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && !ctx->sc.haveMeshLight)
                     launchShadeVariant<MASK_MEDIA, 0>(ctx, grid, st, pp, cls);                      // media scenes with simple surfaces: no scratch
-                else if (ctx->haveMedia || ctx->auxPass || ctx->haveCylinder) launchShadeVariant<BSDF_MASK_ALL, 0>(ctx, grid, st, pp, cls);   // the one variant with FEAT_MEDIA / FEAT_AUX / FEAT_CYLINDER
-                else if (ctx->haveMeshLight) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);   // the only variant with mesh-emitter sampling (every BSDF type)
-                else if (ctx->haveInstances && simple && ctx->instSimpleOpt) launchShade<MASK_SIMPLE_INST>(ctx, grid, st, pp, cls);   // Lambert / escaped paths of instanced scenes
-                else if (ctx->haveInstances && (simple || !ctx->instSimpleOpt)) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);
+                else if (ctx->sc.haveMedia || ctx->auxPass || ctx->sc.allFeaturesShading) launchShadeVariant<BSDF_MASK_ALL, 0>(ctx, grid, st, pp, cls);   // the one variant with FEAT_MEDIA / FEAT_AUX / FEAT_CYLINDER
+                else if (ctx->sc.haveMeshLight) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);   // the only variant with mesh-emitter sampling (every BSDF type)
+                else if (ctx->sc.haveInstances && simple && ctx->instSimpleOpt) launchShade<MASK_SIMPLE_INST>(ctx, grid, st, pp, cls);   // Lambert / escaped paths of instanced scenes
+                else if (ctx->sc.haveInstances && (simple || !ctx->instSimpleOpt)) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);
                 else if (simple) {               // the escaped paths run the class-0 variant: its surface code never runs there, so the launch is short
-                    if (ctx->leanScene) launchShade<MASK_LEAN>(ctx, grid, st, pp, cls);
+                    if (ctx->sc.leanScene) launchShade<MASK_LEAN>(ctx, grid, st, pp, cls);
                     else                launchShade<MASK_SIMPLE>(ctx, grid, st, pp, cls);
                 }
                 else launchComplexClass<0>(ctx, grid, st, pp, cls);
@@ -1933,7 +1389,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
             } else if (ctx->classStreamsOpt != 0) {
                 hipStream_t *aux = ctx->classStream[part];
                 (void)hipEventRecord(ctx->evFork[part], mainStream);
-                const int nAux = ctx->haveComplex ? 2 : 1;
+                const int nAux = ctx->sc.haveComplex ? 2 : 1;
                 for (int a = 0; a < nAux; ++a) {
                     (void)hipStreamWaitEvent(aux[a], ctx->evFork[part], 0);
                     ctx->launchStream = aux[a];
@@ -1941,9 +1397,9 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                     (void)hipEventRecord(ctx->evJoin[part][a], aux[a]);
                 }
                 ctx->launchStream = mainStream;
-                if (!ctx->haveComplex) shadeClass(0);             // the longest launches stay on the part's own stream
+                if (!ctx->sc.haveComplex) shadeClass(0);             // the longest launches stay on the part's own stream
                 for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->classPresent[c]) shadeClass(c);
+                    if (ctx->sc.classPresent[c]) shadeClass(c);
                 for (int a = 0; a < nAux; ++a)
                     (void)hipStreamWaitEvent(mainStream, ctx->evJoin[part][a], 0);
             } else {
@@ -1951,7 +1407,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 if (ctx->mergeMissOpt) shadeClass(CLS_0_AND_MISS);
                 else { shadeClass(CLS_MISS); shadeClass(0); }
                 for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->classPresent[c]) shadeClass(c);
+                    if (ctx->sc.classPresent[c]) shadeClass(c);
             }
             tic(); tic();
             const bool finish = count ? launchShadow<true>(ctx, grid, st, pp, iterTag) : launchShadow<false>(ctx, grid, st, pp, iterTag);
@@ -2003,7 +1459,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 const size_t ldsTail = wideLdsBytes(ctx, 256);
                 uint32_t classes = 1u;
                 for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->classPresent[c]) classes |= 1u << c;
+                    if (ctx->sc.classPresent[c]) classes |= 1u << c;
                 for (int k = 0; k < parts; ++k) {
                     const PathState &sp = split ? stPart[k] : st;
                     const PassParams &ppk = split ? ppPart[k] : pp;
@@ -2012,10 +1468,10 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                     else if (split) HIP_TRY(ctx, hipEventRecord(ctx->evMain, ctx->stream));
 #define TAIL_LAUNCH(M, S) hipLaunchKernelGGL((k_tail<M, S>), dim3(grid/parts), dim3(256), ldsTail, stream, s, sp, ppk, classes)
                     // scenes of Lambert / null and conductor-family materials only (the metric's): the narrower instantiation, "tail_family" = 0 for the A/B
-                    const bool tailCoat = ctx->tailFamilyOpt && !ctx->haveSolids && !ctx->classPresent[2] && !ctx->classPresent[3];
+                    const bool tailCoat = ctx->tailFamilyOpt && !ctx->sc.haveSolids && !ctx->sc.classPresent[2] && !ctx->sc.classPresent[3];
                     if (tailCoat) { if (pp.flags) TAIL_LAUNCH((MASK_COAT | FEAT_QMC), false); else TAIL_LAUNCH(MASK_COAT, false); }
-                    else if (pp.flags) { if (ctx->haveSolids) TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), true); else TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), false); }
-                    else          { if (ctx->haveSolids) TAIL_LAUNCH(MASK_TAIL, true); else TAIL_LAUNCH(MASK_TAIL, false); }
+                    else if (pp.flags) { if (ctx->sc.haveSolids) TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), true); else TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), false); }
+                    else          { if (ctx->sc.haveSolids) TAIL_LAUNCH(MASK_TAIL, true); else TAIL_LAUNCH(MASK_TAIL, false); }
 #undef TAIL_LAUNCH
                 }
                 for (int k = 1; k < parts; ++k) {
@@ -2042,13 +1498,13 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 ppi.iter_tag = iterTag;
                 tic(); tic(); tic();
                 if (runToCompletion) {
-                    if (ctx->leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW | FUSE_LOOP>(ctx, grid, st, ppi, 0);
+                    if (ctx->sc.leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW | FUSE_LOOP>(ctx, grid, st, ppi, 0);
                     else                launchShade<MASK_SIMPLE, FUSE_TRACE | FUSE_SHADOW | FUSE_LOOP>(ctx, grid, st, ppi, 0);
                 }
-                else if (ctx->leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW>(ctx, grid, st, ppi, 0);
+                else if (ctx->sc.leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW>(ctx, grid, st, ppi, 0);
                 else                     launchShade<MASK_SIMPLE, FUSE_TRACE | FUSE_SHADOW>(ctx, grid, st, ppi, 0);
                 for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->classPresent[c]) launchComplexClass<FUSE_SHADOW>(ctx, grid, st, ppi, c);
+                    if (ctx->sc.classPresent[c]) launchComplexClass<FUSE_SHADOW>(ctx, grid, st, ppi, c);
                 tic(); tic(); tic();
                 ctx->counters.iterations++;
                 continue;
@@ -2165,7 +1621,7 @@ int tghip_wait(tghip_ctx *ctx)
     PassParams base{};
     base.shard_skew = shardSkew;
     base.owned_tiles = shardCount > 1 ? ctx->dOwnedTiles : nullptr;
-    base.flags = pass.flags | (ctx->thinlens ? PT_PASS_THINLENS : 0u) | (ctx->haveMedia ? PT_PASS_MEDIA : 0u);
+    base.flags = pass.flags | (ctx->sc.thinlens ? PT_PASS_THINLENS : 0u) | (ctx->sc.haveMedia ? PT_PASS_MEDIA : 0u);
     base.variance_w = (w + 3)/4;
     if (pass.flags & TGHIP_PASS_SOBOL) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dTileSeeds, pass.tile_seeds, size_t(numTiles)*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -2370,7 +1826,7 @@ int tghip_wait(tghip_ctx *ctx)
         // the run-to-completion kernel (runBatch) gives every thread its own slots for the whole launch: one slot per
         // thread keeps the whole path state (112 B x 0.5 M slots) inside the Infinity Cache -- measured +5 % over four
         const bool flat = isFlat(ctx);
-        const bool loop = flat && !ctx->haveForward && !ctx->haveMeshLight && ctx->fuseFlatOpt && !ctx->cameraFix && !ctx->haveComplex && ctx->loopOpt && !ctx->auxPass && !ctx->haveCylinder && ctx->tablesFit;
+        const bool loop = flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->sc.cameraFix && !ctx->sc.haveComplex && ctx->loopOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit;
         if (loop && !ctx->maxSlotsSet)
             wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->thrShadeSimple));
     }
@@ -2887,10 +2343,10 @@ int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint
     if (!ctx->haveScene) { ctx->error = "bsdf self-test without an uploaded scene"; return TGHIP_E_INVALID; }
     if (variant < 0 || variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "bsdf self-test: unknown variant"; return TGHIP_E_INVALID; }
     if (variant_mask) *variant_mask = debugBsdfVariantMask(uint32_t(variant));
-    for (size_t i = 0; i < ctx->bsdfTypes.size(); ++i) {
-        if (type_mask) type_mask[i] = ctx->bsdfTypes[i];
-        if (forward) forward[i] = ctx->bsdfForward[i];
-        if (covered) covered[i] = familyCovers(uint32_t(variant), ctx->bsdfTypes[i], ctx->bsdfForward[i] != 0) ? 1u : 0u;
+    for (size_t i = 0; i < ctx->sc.bsdfTypes.size(); ++i) {
+        if (type_mask) type_mask[i] = ctx->sc.bsdfTypes[i];
+        if (forward) forward[i] = ctx->sc.bsdfForward[i];
+        if (covered) covered[i] = familyCovers(uint32_t(variant), ctx->sc.bsdfTypes[i], ctx->sc.bsdfForward[i] != 0) ? 1u : 0u;
     }
     return TGHIP_OK;
 }
@@ -2991,14 +2447,14 @@ int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_
         const bool flat = isFlat(ctx);
 #define RAYS_LAUNCH(C, F) hipLaunchKernelGGL((k_trace_rays<C, F>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats)
         // (closest hits of a scene with `instances` primitives are a matter of the reference's visiting order: the BVH2 walk, never the wide one)
-        if (useWide(ctx) && !ctx->haveInstances) {
-            const size_t ldsWide = size_t(std::max(ctx->wideDepth, 1))*256u*sizeof(uint2);
+        if (useWide(ctx) && !ctx->sc.haveInstances) {
+            const size_t ldsWide = size_t(std::max(ctx->sc.wideDepth, 1))*256u*sizeof(uint2);
 #define RAYS_WIDE(C, I) hipLaunchKernelGGL((k_trace_rays<C, false, I, true>), dim3(grid), dim3(256), ldsWide, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats)
-            if (ctx->haveInstances) { if (cnt) RAYS_WIDE(true, 1); else RAYS_WIDE(false, 1); }
+            if (ctx->sc.haveInstances) { if (cnt) RAYS_WIDE(true, 1); else RAYS_WIDE(false, 1); }
             else                    { if (cnt) RAYS_WIDE(true, 0); else RAYS_WIDE(false, 0); }
 #undef RAYS_WIDE
         }
-        else if (ctx->haveInstances) {
+        else if (ctx->sc.haveInstances) {
             if (cnt) hipLaunchKernelGGL((k_trace_rays<true, false, 1>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats);
             else     hipLaunchKernelGGL((k_trace_rays<false, false, 1>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats);
         }

@@ -8,6 +8,7 @@
 #include "Integrator.hpp"
 #include "Sampling.hpp"
 #include "Scene.hpp"
+#include "SceneCheck.hpp"
 #include "TraceableScene.hpp"
 
 #include <chrono>
@@ -488,6 +489,24 @@ int tgh_top_tree_for_scene(const TgHipObject *objects, uint32_t num_objects, con
 int tgh_leaf_bounds(const TgHipObject *object, uint32_t kind, float lo[3], float hi[3])
 {
     return (object && lo && hi && referenceLeafBounds(*object, kind, lo, hi)) ? 1 : 0;
+}
+
+int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out, char *err, size_t errlen)
+{
+    if (!scene) { setErr(err, errlen, "no scene description"); return TGHIP_E_INVALID; }
+    SceneTraits t;
+    std::string error;
+    const int rc = checkScene(scene, SceneCheckOptions(), t, error);
+    if (rc != TGHIP_OK) { setErr(err, errlen, error); return rc; }
+    if (out) {
+        *out = TgHostSceneTraits{t.haveMedia, t.haveInstances, t.haveMeshLight, t.haveForward, t.haveSolids, t.allFeaturesShading, t.haveProcTex,
+                                 t.leanScene, t.mediaSimple, t.thinlens, t.cameraFix, t.haveComplex, t.topTree, t.tablesFit,
+                                 t.bvhDepth, t.bvhMasterDepth, t.wideDepth, t.wideMasterDepth,
+                                 {t.classPresent[0], t.classPresent[1], t.classPresent[2], t.classPresent[3]},
+                                 {t.classMask[0], t.classMask[1], t.classMask[2], t.classMask[3]}, t.complexMask,
+                                 t.hoisted.record, t.env_tex};
+    }
+    return TGHIP_OK;
 }
 
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h)
