@@ -21,8 +21,8 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
-# (the shim reads what csrc/host/SceneCheck.cpp decided about a scene: SceneTraits)
-HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp
+# (the shim reads what csrc/host/SceneCheck.cpp decided about a scene, SceneTraits, and what csrc/host/PassPlan.cpp decided about a pass, PassPlan)
+HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp
 # -ffp-contract=off: no FMA contraction, so device arithmetic rounds like the CPU reference/oracle
 # (DESIGN.md "Numerics"); TG_FAST=1 allows contraction.
 FPFLAGS  := $(if $(TG_FAST),-ffp-contract=fast,-ffp-contract=off)

@@ -184,6 +184,42 @@ typedef struct TgHostSceneTraits {
 } TgHostSceneTraits;
 int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may be NULL */, char *err, size_t errlen);
 
+/* What tghip_render_pass and tghip_wait decide about a pass before they touch the device (csrc/host/PassPlan.cpp), on its own, no device: the plan of
+ * `pass` for a width x height image under the options "max_items", "max_slots" and "chunk_samples" -- or NULL, in *rc (may be NULL) the refusal's code
+ * (TGHIP_E_INVALID from the checks of tghip_render_pass, TGHIP_E_UNSUPPORTED for a pass past 2^32 samples or items) and in `err` its message.
+ * scene_has_sobol: whether the scene the pass is meant for carries sobol_matrices.  The arrays belong to the plan and live until tgh_pass_plan_free. */
+typedef struct TgHostPassPlan {
+    uint32_t empty;                                   /* 1: nothing to render (no owned tile, or no sample); the fields from `chunk` on are then 0 */
+    uint32_t tiles_x, tiles_y, num_tiles;
+    uint32_t shard_count, shard_skew, owned_tiles;
+    uint32_t record_pass, variance_w, num_records;    /* TGHIP_PASS_RECORDS; records per row; records */
+    uint32_t spp, spp_begin;                          /* the sample range the batches cut (record passes: [0, largest count of an owned record)) */
+    uint32_t aux_pass;
+    uint32_t chunk, group, chunks_all;                /* samples per work item; chunks k_resolve adds up together; chunks of the whole range */
+    uint32_t short_batch;                             /* 2*batch_items <= max_slots */
+    uint32_t reserved;
+    uint64_t lum_floats;                              /* record passes: 16 x count floats per owned record */
+    uint64_t record_items, hint_entries;              /* record passes: items of the gap-free enumeration; entries of the device's hint table */
+    uint64_t total_items, batch_items;                /* of the whole pass; of its largest batch */
+} TgHostPassPlan;
+/* what differs between the batches of one pass (PassParams of the same names) */
+typedef struct TgHostPassBatch { uint32_t spp_begin, spp_end, chunks, pix_slots, total_items, first_tile, item_base; } TgHostPassBatch;
+typedef struct tgh_pass_plan tgh_pass_plan;
+tgh_pass_plan *tgh_pass_plan_create(const TgHipPassDesc *pass, uint32_t width, uint32_t height, int scene_has_sobol,
+                                    uint64_t max_items, uint64_t max_slots, uint32_t chunk_samples, int *rc, char *err, size_t errlen);
+void tgh_pass_plan_info(tgh_pass_plan *p, TgHostPassPlan *out);
+const TgHostPassBatch *tgh_pass_plan_batches(tgh_pass_plan *p, uint32_t *num_batches);
+const uint32_t *tgh_pass_plan_owned_tiles(tgh_pass_plan *p, uint32_t *n);    /* the shard's tiles, row-major; NULL / 0 for an unsharded pass (it owns every tile) */
+/* record passes (else NULL / 0): per record its first sample index, its samples per pixel, the offset of its luminance block (num_records entries each) */
+const uint32_t *tgh_pass_plan_rec_index(tgh_pass_plan *p);
+const uint32_t *tgh_pass_plan_rec_count(tgh_pass_plan *p);
+const uint32_t *tgh_pass_plan_rec_lum(tgh_pass_plan *p);
+/* ... the owned records with a count above 0 by descending count, ties in record order; the first item of every chunk of that order, the item total and
+ * the sentinel 0xFFFFFFFF behind them (chunks_all + 2 entries).  An empty plan has neither. */
+const uint32_t *tgh_pass_plan_sorted(tgh_pass_plan *p, uint32_t *n);
+const uint32_t *tgh_pass_plan_chunk_starts(tgh_pass_plan *p, uint32_t *n);
+void tgh_pass_plan_free(tgh_pass_plan *p);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

@@ -199,6 +199,17 @@ class TgHostSceneTraits(C.Structure):
                [("class_present", i32*4), ("class_mask", u32*4), ("complex_mask", u32), ("hoisted_rec", i32), ("env_tex", i32)]
 
 
+class TgHostPassPlan(C.Structure):
+    _fields_ = [(n, u32) for n in ("empty", "tiles_x", "tiles_y", "num_tiles", "shard_count", "shard_skew", "owned_tiles",
+                                   "record_pass", "variance_w", "num_records", "spp", "spp_begin", "aux_pass",
+                                   "chunk", "group", "chunks_all", "short_batch", "reserved")] + \
+               [(n, u64) for n in ("lum_floats", "record_items", "hint_entries", "total_items", "batch_items")]
+
+
+class TgHostPassBatch(C.Structure):
+    _fields_ = [(n, u32) for n in ("spp_begin", "spp_end", "chunks", "pix_slots", "total_items", "first_tile", "item_base")]
+
+
 # every symbol the two headers declare: name -> (restype, argtypes)
 VP = C.c_void_p
 TGHIP_COMM_ID_BYTES = 128
@@ -287,6 +298,16 @@ PROTOTYPES = {
     "tgh_top_tree_for_scene": (C.c_int, [VP, C.c_uint32, VP, C.c_uint32, VP, C.c_uint32]),
     "tgh_leaf_bounds": (C.c_int, [VP, C.c_uint32, VP, VP]),
     "tgh_scene_check": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(TgHostSceneTraits), C.c_char_p, C.c_size_t]),
+    "tgh_pass_plan_create": (VP, [C.POINTER(TgHipPassDesc), u32, u32, C.c_int, u64, u64, u32, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
+    "tgh_pass_plan_info": (None, [VP, C.POINTER(TgHostPassPlan)]),
+    "tgh_pass_plan_batches": (C.POINTER(TgHostPassBatch), [VP, C.POINTER(u32)]),
+    "tgh_pass_plan_owned_tiles": (C.POINTER(u32), [VP, C.POINTER(u32)]),
+    "tgh_pass_plan_rec_index": (C.POINTER(u32), [VP]),
+    "tgh_pass_plan_rec_count": (C.POINTER(u32), [VP]),
+    "tgh_pass_plan_rec_lum": (C.POINTER(u32), [VP]),
+    "tgh_pass_plan_sorted": (C.POINTER(u32), [VP, C.POINTER(u32)]),
+    "tgh_pass_plan_chunk_starts": (C.POINTER(u32), [VP, C.POINTER(u32)]),
+    "tgh_pass_plan_free": (None, [VP]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

@@ -6,6 +6,7 @@
 #include "denoise.h"
 #include "develop.h"
 #include "../host/SceneCheck.hpp"
+#include "../host/PassPlan.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -251,10 +252,9 @@ struct tghip_ctx {
     TgHipSampleRecord *dRecords = nullptr;   // SampleRecords, ceil(W/4) x ceil(H/4)
     float *lum = nullptr;                 // per-sample luminance of the running pass
     size_t lumCap = 0;
-    std::vector<uint32_t> hostRecLum, hostRecIndex, hostRecCount, hostSorted, hostChunkStart;
+    PassPlan plan;                        // what planPass decided about the running pass (csrc/host/PassPlan.hpp); reused from pass to pass, with the shard's tile list
     uint32_t *dSorted = nullptr, *dChunkStart = nullptr, *dHint = nullptr;   // gap-free item enumeration of record passes
     size_t sortedCap = 0, chunkStartCap = 0, hintCap = 0;
-    std::vector<uint32_t> hostBucket, hostSortTmp;   // counting sort of the owned records by sample count
 
     // path pool
     DeviceBuffers poolMem;
@@ -277,7 +277,7 @@ struct tghip_ctx {
     int slotsPerBlockOpt = 0;             // "slots_per_block": upper bound on the slots of one workgroup (0 = PT_MAX_SLOTS_PER_BLOCK)
     bool maxSlotsSet = false;             // "max_slots" was given explicitly
     long long maxItems = 1ll << 26;       // work items per batch (partial-sum buffer = 16 B each)
-    int chunkSamples = 0;                 // "chunk_samples": samples per work item; 0 = 4, or fewer when the pass is short (tghip_wait)
+    int chunkSamples = 0;                 // "chunk_samples": samples per work item; 0 = 4, or one when the pass is short (csrc/host/PassPlan.cpp)
     size_t partialCap = 0;
     float4 *partial = nullptr;
 
@@ -303,11 +303,9 @@ struct tghip_ctx {
     float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
     uint32_t *redCount = nullptr;
     size_t redCap = 0;                    // pixels redSum / redCount were allocated for (a re-upload may change the resolution)
-    // the tiles of the shard the last pass rendered (tghip_tile_owner), on the host and on the device; key = {W, H, shard index, shard count}
-    std::vector<uint32_t> hostOwnedTiles;
+    // the tiles of the shard the last pass rendered (plan.ownedList), on the device
     uint32_t *dOwnedTiles = nullptr;
     size_t ownedCap = 0;
-    uint32_t ownedKey[4] = {0, 0, 0, 0};
     size_t samplesCap = 0, samplesFloats = 0;
     bool auxPass = false;                 // the pass being rendered keeps them: BSDF_MASK_ALL shading, no fused / dynamic-fetch shadow kernels
     int thrShadeAll = 256;                // workgroup size of k_shade<BSDF_MASK_ALL> (media scenes, TGHIP_PASS_AUX passes)
@@ -392,9 +390,29 @@ static int allocArray(tghip_ctx *ctx, DeviceBuffers &mem, size_t count, T **dst)
     return TGHIP_OK;
 }
 
+// A device array of the context that grows on demand and is never shrunk: room for `need` elements.  (The old contents are dropped.  An allocation
+// is never empty: it happens only for need > cap >= 0.)
+template<typename T>
+static int growArray(tghip_ctx *ctx, T *&dev, size_t &cap, size_t need)
+{
+    if (cap >= need) return TGHIP_OK;
+    if (dev) (void)hipFree(dev);
+    dev = nullptr; cap = 0;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dev), need*sizeof(T)));
+    cap = need;
+    return TGHIP_OK;
+}
+
 static bool isFlat(const tghip_ctx *ctx) { return ctx->scene.num_recs <= TGHIP_FLAT_MAX_RECS && !ctx->sc.haveInstances; }
 // the single-level traversal kernels walk the 8-wide BVH when the scene carries one
 static bool useWide(const tghip_ctx *ctx) { return ctx->sc.wideDepth > 0 && ctx->wideOpt && ctx->dynamicFetch && !isFlat(ctx); }
+// the running pass traces and shadow-tests inside k_shade ("fuse_flat": flat-list scenes without forward lobes) ...
+static bool fusedFlat(const tghip_ctx *ctx)
+{
+    return isFlat(ctx) && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit && !ctx->sc.cameraFix;
+}
+// ... and one such launch renders a whole batch ("run_to_completion": all materials of class 0)
+static bool oneLaunch(const tghip_ctx *ctx) { return fusedFlat(ctx) && !ctx->sc.haveComplex && ctx->loopOpt; }
 
 
 static bool wideClosest(const tghip_ctx *ctx);
@@ -1212,8 +1230,8 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     const int grid = int(ctx->poolGrid);
     const bool count = ctx->countTraversal;
     const bool flat = isFlat(ctx);
-    const bool fused = flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit && !ctx->sc.cameraFix;
-    const bool runToCompletion = fused && !ctx->sc.haveComplex && ctx->loopOpt;   // one launch renders the whole batch
+    const bool fused = fusedFlat(ctx);
+    const bool runToCompletion = oneLaunch(ctx);   // one launch renders the whole batch
     const size_t ldsBytes = traceLdsBytes(ctx, ctx->thrClosest);
 
     // optional per-launch timing: one event pair per kernel launch of a check interval, read back at the
@@ -1554,23 +1572,8 @@ int tghip_render_pass(tghip_ctx *ctx, const TgHipPassDesc *pass)
 {
     if (!ctx || !pass) return TGHIP_E_INVALID;
     if (!ctx->haveScene) { ctx->error = "render before upload"; return TGHIP_E_NOSCENE; }
-    if (pass->spp_end < pass->spp_begin || (pass->shard_count && pass->shard_index >= pass->shard_count)) {
-        ctx->error = "invalid pass description";
-        return TGHIP_E_INVALID;
-    }
-    if (pass->flags & ~(TGHIP_PASS_SOBOL | TGHIP_PASS_RECORDS | TGHIP_PASS_AUX | TGHIP_PASS_SAMPLES)) { ctx->error = "unknown pass flags"; return TGHIP_E_INVALID; }
-    if ((pass->flags & TGHIP_PASS_SOBOL) && (!ctx->scene.sobol || !pass->tile_seeds)) {
-        ctx->error = "TGHIP_PASS_SOBOL needs sobol_matrices in the scene description and tile_seeds in the pass";
-        return TGHIP_E_INVALID;
-    }
-    if ((pass->record_count != nullptr) != (pass->record_index != nullptr) || (pass->record_count && !(pass->flags & TGHIP_PASS_RECORDS))) {
-        ctx->error = "record_index and record_count go together and need TGHIP_PASS_RECORDS";
-        return TGHIP_E_INVALID;
-    }
-    if ((pass->flags & TGHIP_PASS_SAMPLES) && (pass->record_count || uint64_t(ctx->width)*ctx->height*(pass->spp_end - pass->spp_begin)*3u >= (1ull << 31))) {
-        ctx->error = "TGHIP_PASS_SAMPLES keeps W*H*spp*3 floats (< 2^31) and does not combine with per-record sample counts";
-        return TGHIP_E_INVALID;
-    }
+    const int rc = checkPass(*pass, ctx->width, ctx->height, ctx->scene.sobol != nullptr, ctx->error);   // (csrc/host/PassPlan.cpp)
+    if (rc != TGHIP_OK) return rc;
     ctx->abortRequested.store(false, std::memory_order_release);   // the only place a request is cleared
     ctx->passPending = true;
     ctx->passResult = TGHIP_OK;
@@ -1589,111 +1592,60 @@ int tghip_wait(tghip_ctx *ctx)
     auto msSince = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const TgHipPassDesc pass = ctx->pendingPass;
-    const uint32_t shardCount = pass.shard_count ? pass.shard_count : 1;
     const uint32_t w = ctx->width, h = ctx->height;
-    const uint32_t tilesX = (w + 15)/16, tilesY = (h + 15)/16;
-    const uint32_t numTiles = tilesX*tilesY;
-    // the shard's tiles (tghip_tile_owner: a diagonal interleave), row-major; the device indexes this list (PassParams::owned_tiles)
-    const uint32_t shardSkew = tghip_shard_skew(shardCount);
-    auto ownsTile = [&](uint32_t tx, uint32_t ty) { return tghip_tile_owner(tx, ty, shardCount) == pass.shard_index; };
-    uint32_t ownedTiles = numTiles;
-    if (shardCount > 1) {
-        if (ctx->ownedKey[0] != w || ctx->ownedKey[1] != h || ctx->ownedKey[2] != pass.shard_index || ctx->ownedKey[3] != shardCount) {
-            std::vector<uint32_t> &list = ctx->hostOwnedTiles;
-            list.clear();
-            for (uint32_t ty = 0; ty < tilesY; ++ty)
-                for (uint32_t tx = 0; tx < tilesX; ++tx)
-                    if (ownsTile(tx, ty)) list.push_back(tx + ty*tilesX);
-            if (ctx->ownedCap < list.size()) {
-                if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
-                ctx->dOwnedTiles = nullptr; ctx->ownedCap = 0;
-                HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dOwnedTiles), std::max<size_t>(list.size(), 1)*sizeof(uint32_t)));
-                ctx->ownedCap = list.size();
-            }
-            if (!list.empty())
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->dOwnedTiles, list.data(), list.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the list is host memory of the context; keep it simple: rare)
-            ctx->ownedKey[0] = w; ctx->ownedKey[1] = h; ctx->ownedKey[2] = pass.shard_index; ctx->ownedKey[3] = shardCount;
-        }
-        ownedTiles = uint32_t(ctx->hostOwnedTiles.size());
-    }
-    uint32_t spp = pass.spp_end - pass.spp_begin, sppBegin = pass.spp_begin;
+    // which tiles, records, work items and batches the pass is made of: host arithmetic on its own (csrc/host/PassPlan.cpp)
+    PassPlan &plan = ctx->plan;
+    const PassPlanOptions planOpt = {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), uint32_t(std::max(ctx->chunkSamples, 0))};
+    int rc = planPass(pass, w, h, planOpt, plan, ctx->error);
+    if (rc != TGHIP_OK || plan.empty)
+        return ctx->passResult = rc;
+    ctx->auxPass = plan.auxPass;
+
+    // the device arrays the plan names
+    auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
+        const int grc = growArray(ctx, dev, cap, src.size());
+        if (grc != TGHIP_OK) return grc;
+        if (!src.empty())
+            HIP_TRY(ctx, hipMemcpyAsync(dev, src.data(), src.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        return TGHIP_OK;
+    };
     PassParams base{};
-    base.shard_skew = shardSkew;
-    base.owned_tiles = shardCount > 1 ? ctx->dOwnedTiles : nullptr;
+    base.shard_index = pass.shard_index; base.shard_count = plan.shardCount;
+    base.shard_skew = plan.shardSkew;
+    base.tiles_x = plan.tilesX; base.num_tiles = plan.numTiles;
+    base.width = w; base.height = h;
     base.flags = pass.flags | (ctx->sc.thinlens ? PT_PASS_THINLENS : 0u) | (ctx->sc.haveMedia ? PT_PASS_MEDIA : 0u);
-    base.variance_w = (w + 3)/4;
+    base.variance_w = plan.varianceW;
+    if (plan.shardCount > 1) {
+        if (plan.ownedStale) {                   // the shard's tile list changed: rare
+            if ((rc = upload(ctx->dOwnedTiles, ctx->ownedCap, plan.ownedList)) != TGHIP_OK) return ctx->passResult = rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            plan.ownedStale = false;
+        }
+        base.owned_tiles = ctx->dOwnedTiles;
+    }
     if (pass.flags & TGHIP_PASS_SOBOL) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dTileSeeds, pass.tile_seeds, size_t(numTiles)*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dTileSeeds, pass.tile_seeds, size_t(plan.numTiles)*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         base.tile_seeds = ctx->dTileSeeds;
     }
-    const uint32_t numRecords = base.variance_w*((h + 3)/4);
-    if (pass.flags & TGHIP_PASS_RECORDS) {
-        // per record: first sample index, samples per pixel, offset of its 16 x count luminance block.  The sample
-        // range of the batches below becomes relative to each record's first index: [0, max count of an owned record).
-        std::vector<uint32_t> &idx = ctx->hostRecIndex, &cnt = ctx->hostRecCount, &off = ctx->hostRecLum;
-        idx.resize(numRecords); cnt.resize(numRecords); off.resize(numRecords);
-        uint64_t total = 0;
-        uint32_t maxCount = 0;
-        for (uint32_t r = 0; r < numRecords; ++r) {
-            uint32_t rx = r % base.variance_w, ry = r/base.variance_w;
-            bool owned = ownsTile(rx >> 2, ry >> 2);
-            idx[r] = pass.record_index ? pass.record_index[r] : pass.spp_begin;
-            cnt[r] = pass.record_count ? pass.record_count[r] : spp;
-            off[r] = uint32_t(total);
-            if (owned) {
-                total += uint64_t(cnt[r])*16u;
-                maxCount = std::max(maxCount, cnt[r]);
-            }
-            if (total >= (1ull << 32)) {
-                ctx->error = "pass too large for SampleRecord keeping (more than 2^32 samples per device): lower spp_step";
-                return ctx->passResult = TGHIP_E_UNSUPPORTED;
-            }
-        }
-        spp = maxCount;
-        sppBegin = 0;
-        if (ctx->lumCap < total) {
-            if (ctx->lum) (void)hipFree(ctx->lum);
-            ctx->lum = nullptr; ctx->lumCap = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->lum), std::max<uint64_t>(total, 1)*sizeof(float)));
-            ctx->lumCap = total;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecIndex, idx.data(), numRecords*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecCount, cnt.data(), numRecords*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecLum, off.data(), numRecords*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (plan.recordPass) {
+        const size_t recBytes = size_t(plan.numRecords)*sizeof(uint32_t);
+        if ((rc = growArray(ctx, ctx->lum, ctx->lumCap, size_t(plan.lumFloats))) != TGHIP_OK) return ctx->passResult = rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecIndex, plan.recIndex.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecCount, plan.recCount.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecLum, plan.recLum.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = upload(ctx->dSorted, ctx->sortedCap, plan.sorted)) != TGHIP_OK) return ctx->passResult = rc;
+        if ((rc = upload(ctx->dChunkStart, ctx->chunkStartCap, plan.chunkStart)) != TGHIP_OK) return ctx->passResult = rc;
+        // the hint table -- for every 64 items the chunk their first one lies in -- is filled by a launch from the chunk starts
+        if ((rc = growArray(ctx, ctx->dHint, ctx->hintCap, plan.hintEntries)) != TGHIP_OK) return ctx->passResult = rc;
+        hipLaunchKernelGGL(k_record_hints, dim3(uint32_t((plan.hintEntries + 255)/256)), dim3(256), 0, ctx->stream, ctx->dChunkStart, plan.chunksAll, ctx->dHint, uint32_t(plan.hintEntries));
+        HIP_TRY(ctx, hipGetLastError());
         base.rec_index = ctx->dRecIndex; base.rec_count = ctx->dRecCount; base.rec_lum = ctx->dRecLum;
         base.lum = ctx->lum;
+        base.rec_sorted = ctx->dSorted; base.rec_chunk_start = ctx->dChunkStart; base.rec_hint = ctx->dHint;
+        base.num_sorted = uint32_t(plan.sorted.size());
+        base.num_chunks = plan.chunksAll;
     }
-    const uint32_t sppEnd = sppBegin + spp;
-    if (ownedTiles == 0 || spp == 0)
-        return ctx->passResult = TGHIP_OK;
-
-    // TGHIP_PASS_AUX: one work item per pixel, so that a pixel's samples reach OutputBuffer::addSample in index order (auxAdd)
-    ctx->auxPass = (pass.flags & TGHIP_PASS_AUX) != 0;
-    // Samples per work item: 4 when the pass is long (256 spp at 720p: 59 M items over 8 M slots) -- but a slot works its item's samples
-    // off one after the other, so a SHORT pass cut into 4-sample items is a few long sequential chains on a half-empty pool: the 16-spp
-    // passes of the as-shipped materialtest (3.7 M items) ran at half the throughput of one 256-spp pass.  Such passes -- and one rank's
-    // share of a multi-GPU render -- get smaller items, down to one sample each, so that the items outnumber the slots about twice.
-    uint32_t chunk = ctx->auxPass ? std::max(spp, 1u) : uint32_t(std::max(ctx->chunkSamples, 0));
-    if (chunk == 0) {
-        uint64_t passSamples = 0;
-        if (pass.flags & TGHIP_PASS_RECORDS) {
-            uint64_t c16 = 0;
-            for (uint32_t r = 0; r < numRecords; ++r) {
-                const uint32_t rx = r % base.variance_w, ry = r/base.variance_w;
-                if (ownsTile(rx >> 2, ry >> 2)) c16 += ctx->hostRecCount[r];
-            }
-            passSamples = c16*16u;
-        } else {
-            passSamples = uint64_t(ownedTiles)*256u*spp;
-        }
-        // One sample or four, nothing in between: k_resolve adds one-sample items up in groups of four, so both choices -- and with them
-        // the unsharded pass and every shard of it, which pick by their OWN sample counts -- round a pixel's sum alike (pt_wavefront.h:
-        // k_resolve; tests/test_gpu_parity.py::test_shards_and_batches_round_like_the_whole_pass).  An explicit "chunk_samples" of 2 or 3
-        // gives up that property, not the result's validity.
-        chunk = (passSamples >> 24) >= 3 ? 4u : 1u;
-    }
-    const uint32_t group = chunk == 1u ? 4u : 1u;
     if (ctx->auxPass && !ctx->dAux) {
         const size_t npix = size_t(w)*h;
         HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dAux), npix*sizeof(TgHipAuxPixel)));
@@ -1701,144 +1653,25 @@ int tghip_wait(tghip_ctx *ctx)
     }
     base.aux = ctx->dAux;
     if (pass.flags & TGHIP_PASS_SAMPLES) {
-        const size_t need = size_t(w)*h*spp*3u;
-        if (ctx->samplesCap < need) {
-            if (ctx->dSamples) (void)hipFree(ctx->dSamples);
-            ctx->dSamples = nullptr; ctx->samplesCap = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dSamples), need*sizeof(float)));
-            ctx->samplesCap = need;
-        }
+        const size_t need = size_t(w)*h*plan.spp*3u;
+        if ((rc = growArray(ctx, ctx->dSamples, ctx->samplesCap, need)) != TGHIP_OK) return ctx->passResult = rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->dSamples, 0, need*sizeof(float), ctx->stream));
         ctx->samplesFloats = need;
-        base.samples = ctx->dSamples; base.samples_begin = sppBegin; base.samples_spp = spp;
-    }
-    const uint64_t maxItems = uint64_t(std::max<long long>(ctx->maxItems, 256));
-    const bool recordPass = (pass.flags & TGHIP_PASS_RECORDS) != 0;
-    uint64_t recordItems = 0;
-    if (recordPass) {
-        // Gap-free work items for uneven per-record sample counts (PassParams): owned records sorted by descending count,
-        // chunk c covers the first chunkStart[c + 1] - chunkStart[c] pixel slots of that order.
-        std::vector<uint32_t> &sorted = ctx->hostSorted, &start = ctx->hostChunkStart;
-        const std::vector<uint32_t> &cnt = ctx->hostRecCount;
-        sorted.clear();
-        for (uint32_t r = 0; r < numRecords; ++r) {
-            uint32_t rx = r % base.variance_w, ry = r/base.variance_w;
-            if (ownsTile(rx >> 2, ry >> 2) && cnt[r] > 0)
-                sorted.push_back(r);
-        }
-        // descending by count, ties in record order (a counting sort: the counts of a pass are small integers)
-        if (spp < (1u << 16)) {
-            std::vector<uint32_t> &bucket = ctx->hostBucket;
-            bucket.assign(size_t(spp) + 2, 0u);
-            for (uint32_t r : sorted) bucket[spp - cnt[r] + 1]++;
-            for (size_t i = 1; i < bucket.size(); ++i) bucket[i] += bucket[i - 1];
-            std::vector<uint32_t> &tmp = ctx->hostSortTmp;
-            tmp.resize(sorted.size());
-            for (uint32_t r : sorted) tmp[bucket[spp - cnt[r]]++] = r;
-            sorted.swap(tmp);
-        } else {
-            std::stable_sort(sorted.begin(), sorted.end(), [&cnt](uint32_t a, uint32_t b) { return cnt[a] > cnt[b]; });
-        }
-        const uint32_t numChunks = (spp + chunk - 1)/chunk;
-        start.assign(size_t(numChunks) + 2, 0u);
-        size_t alive = sorted.size();                // records with cnt > c*chunk: a prefix of `sorted`
-        for (uint32_t c = 0; c < numChunks; ++c) {
-            while (alive > 0 && cnt[sorted[alive - 1]] <= uint64_t(c)*chunk) --alive;
-            recordItems += uint64_t(alive)*16u;
-            if (recordItems >= (1ull << 32)) {
-                ctx->error = "pass too large for SampleRecord keeping (more than 2^32 work items per device): lower spp_step";
-                return ctx->passResult = TGHIP_E_UNSUPPORTED;
-            }
-            start[c + 1] = uint32_t(recordItems);
-        }
-        start[numChunks + 1] = 0xFFFFFFFFu;          // sentinel for the device's `while (w >= start[c + 1])`
-        // (the hint table -- for every 64 items the chunk their first one lies in, 230 k entries for a 16-spp pass at 720p -- is filled by a launch
-        // from the chunk starts: building and uploading it here was a third of the host's set-up time between two passes)
-        const size_t hintEntries = size_t((recordItems + 63)/64) + 1;
-        auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
-            if (cap < src.size()) {
-                if (dev) (void)hipFree(dev);
-                dev = nullptr; cap = 0;
-                HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dev), std::max<size_t>(src.size(), 1)*sizeof(uint32_t)));
-                cap = src.size();
-            }
-            if (!src.empty())
-                HIP_TRY(ctx, hipMemcpyAsync(dev, src.data(), src.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            return TGHIP_OK;
-        };
-        int urc;
-        if ((urc = upload(ctx->dSorted, ctx->sortedCap, sorted)) != TGHIP_OK) return ctx->passResult = urc;
-        if ((urc = upload(ctx->dChunkStart, ctx->chunkStartCap, start)) != TGHIP_OK) return ctx->passResult = urc;
-        if (ctx->hintCap < hintEntries) {
-            if (ctx->dHint) (void)hipFree(ctx->dHint);
-            ctx->dHint = nullptr; ctx->hintCap = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dHint), hintEntries*sizeof(uint32_t)));
-            ctx->hintCap = hintEntries;
-        }
-        hipLaunchKernelGGL(k_record_hints, dim3(uint32_t((hintEntries + 255)/256)), dim3(256), 0, ctx->stream, ctx->dChunkStart, numChunks, ctx->dHint, uint32_t(hintEntries));
-        HIP_TRY(ctx, hipGetLastError());
-        base.rec_sorted = ctx->dSorted; base.rec_chunk_start = ctx->dChunkStart; base.rec_hint = ctx->dHint;
-        base.num_sorted = uint32_t(sorted.size());
-        base.num_chunks = numChunks;
-        if (recordItems == 0)
-            return ctx->passResult = TGHIP_OK;
+        base.samples = ctx->dSamples; base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
     }
 
-    // Batches: work items = (pixel slot of an owned tile) x (chunk of `chunkSamples` sample indices).  One batch
-    // holds at most maxItems items (16 B of partial sum each); larger passes are split by sample range first,
-    // then by tiles.  (Record passes: consecutive ranges of the gap-free enumeration above.)
-    const uint32_t chunksAll = (spp + chunk - 1)/chunk;
-    uint32_t tilesPerBatch = ownedTiles, chunksPerBatch = chunksAll;
-    if (!recordPass && uint64_t(ownedTiles)*256*chunksAll > maxItems) {
-        chunksPerBatch = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(chunksAll, maxItems/(uint64_t(ownedTiles)*256))));
-        chunksPerBatch = std::max(group, chunksPerBatch/group*group);          // whole groups of k_resolve
-        if (uint64_t(ownedTiles)*256*chunksPerBatch > maxItems)
-            tilesPerBatch = uint32_t(std::max<uint64_t>(1, maxItems/(256ull*chunksPerBatch)));
+    // a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch; chooseThreads picks grid and workgroup sizes)
+    if (plan.shortBatch != ctx->shortBatch) {
+        ctx->shortBatch = plan.shortBatch;
+        chooseThreads(ctx);
     }
-    // record passes: consecutive ranges of the gap-free enumeration that hold whole groups of chunks (the items of chunk c are
-    // [start[c], start[c + 1])), as many groups as fit maxItems, at least one
-    std::vector<uint64_t> recordBatchEnd;
-    if (recordPass) {
-        const std::vector<uint32_t> &start = ctx->hostChunkStart;
-        uint64_t begin = 0;
-        for (uint32_t c = 0; c < chunksAll; c += group) {
-            const uint64_t end = start[std::min(c + group, chunksAll)];
-            if (end - begin > maxItems && start[c] > begin) { recordBatchEnd.push_back(start[c]); begin = start[c]; }
-        }
-        recordBatchEnd.push_back(recordItems);
-    }
-    uint64_t recordBatchMax = 0;
-    for (size_t i = 0; i < recordBatchEnd.size(); ++i)
-        recordBatchMax = std::max(recordBatchMax, recordBatchEnd[i] - (i ? recordBatchEnd[i - 1] : 0));
-    const uint64_t batchItems = recordPass ? recordBatchMax : uint64_t(tilesPerBatch)*256*chunksPerBatch;
-    {
-        // A pass whose work items fill less than half the pool never refills a slot: it is one long drain, every iteration of which
-        // pays the fixed cost of its launches.  Such passes (the 16-spp passes of the as-shipped materialtest: 3.7 M items) run on ONE
-        // stream with 4 workgroups per CU -- 431 against 372 Msamples/s with four parts.  (chooseThreads picks grid and workgroup sizes)
-        const bool shortBatch = 2u*batchItems <= uint64_t(ctx->maxSlots);   // (one rank's share of an 8-GPU render of the metric's workload, 7.4 M items, stays on four parts)
-        if (shortBatch != ctx->shortBatch) {
-            ctx->shortBatch = shortBatch;
-            chooseThreads(ctx);
-        }
-    }
-    uint64_t wantSlots = std::min<uint64_t>(uint64_t(ctx->maxSlots), batchItems);
-    {
-        // the run-to-completion kernel (runBatch) gives every thread its own slots for the whole launch: one slot per
-        // thread keeps the whole path state (112 B x 0.5 M slots) inside the Infinity Cache -- measured +5 % over four
-        const bool flat = isFlat(ctx);
-        const bool loop = flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->sc.cameraFix && !ctx->sc.haveComplex && ctx->loopOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit;
-        if (loop && !ctx->maxSlotsSet)
-            wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->thrShadeSimple));
-    }
-    const uint32_t slots = uint32_t(wantSlots);
-    int rc = ensurePool(ctx, slots);
-    if (rc != TGHIP_OK) return ctx->passResult = rc;
-    if (ctx->partialCap < batchItems) {
-        if (ctx->partial) (void)hipFree(ctx->partial);
-        ctx->partial = nullptr; ctx->partialCap = 0;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->partial), batchItems*sizeof(float4)));
-        ctx->partialCap = batchItems;
-    }
+    uint64_t wantSlots = std::min<uint64_t>(uint64_t(ctx->maxSlots), plan.batchItems);
+    // the run-to-completion kernel (runBatch) gives every thread its own slots for the whole launch: one slot per
+    // thread keeps the whole path state (112 B x 0.5 M slots) inside the Infinity Cache -- measured +5 % over four
+    if (oneLaunch(ctx) && !ctx->maxSlotsSet)
+        wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->thrShadeSimple));
+    if ((rc = ensurePool(ctx, uint32_t(wantSlots))) != TGHIP_OK) return ctx->passResult = rc;
+    if ((rc = growArray(ctx, ctx->partial, ctx->partialCap, size_t(plan.batchItems))) != TGHIP_OK) return ctx->passResult = rc;
     // the device word still holds the previous pass's abort, if any; a request for THIS pass is re-mirrored by runBatch
     HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev, 0, sizeof(uint32_t), ctx->stream));
 
@@ -1846,46 +1679,21 @@ int tghip_wait(tghip_ctx *ctx)
     const unsigned long long itersBefore = ctx->counters.iterations;
     const auto tLoop0 = std::chrono::steady_clock::now();
     HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
-    for (size_t bi = 0; recordPass && bi < recordBatchEnd.size() && rc == TGHIP_OK; ++bi) {
-        const uint64_t w0 = bi ? recordBatchEnd[bi - 1] : 0;
+    for (size_t bi = 0; bi < plan.batches.size() && rc == TGHIP_OK; ++bi) {
+        const PassBatch &b = plan.batches[bi];
         PassParams pp = base;
-        pp.spp_begin = 0; pp.spp_end = spp; pp.seed = pass.seed;
-        pp.chunk = chunk;
-        pp.group = group;
-        pp.chunks = chunksAll;
-        pp.pix_slots = 1;                            // unused by the record enumeration
-        pp.item_base = uint32_t(w0);
-        pp.total_items = uint32_t(recordBatchEnd[bi] - w0);
-        pp.first_tile = 0;
-        pp.shard_index = pass.shard_index; pp.shard_count = shardCount;
-        pp.tiles_x = tilesX; pp.num_tiles = numTiles;
-        pp.width = w; pp.height = h;
+        pp.spp_begin = b.sppBegin; pp.spp_end = b.sppEnd; pp.seed = pass.seed;
+        pp.chunk = plan.chunk;
+        pp.group = plan.group;
+        pp.chunks = b.chunks;
+        pp.pix_slots = b.pixSlots;
+        pp.item_base = b.itemBase;
+        pp.total_items = b.totalItems;
+        pp.first_tile = b.firstTile;
         rc = runBatch(ctx, pp);
     }
-    for (uint32_t sppFirst = sppBegin; !recordPass && sppFirst < sppEnd && rc == TGHIP_OK; sppFirst += chunksPerBatch*chunk) {
-        const uint32_t sppLast = uint32_t(std::min<uint64_t>(uint64_t(sppFirst) + uint64_t(chunksPerBatch)*chunk, sppEnd));
-        for (uint32_t first = 0; first < ownedTiles; first += tilesPerBatch) {
-            PassParams pp = base;
-            pp.spp_begin = sppFirst; pp.spp_end = sppLast; pp.seed = pass.seed;
-            pp.chunk = chunk;
-            pp.group = group;
-            pp.chunks = (sppLast - sppFirst + chunk - 1)/chunk;
-            pp.pix_slots = std::min(tilesPerBatch, ownedTiles - first)*256;
-            pp.total_items = pp.pix_slots*pp.chunks;
-            pp.first_tile = first;
-            pp.shard_index = pass.shard_index; pp.shard_count = shardCount;
-            pp.tiles_x = tilesX; pp.num_tiles = numTiles;
-            pp.width = w; pp.height = h;
-            rc = runBatch(ctx, pp);
-            if (rc != TGHIP_OK) break;
-        }
-    }
-    if ((pass.flags & TGHIP_PASS_RECORDS) && rc == TGHIP_OK) {
-        PassParams pp = base;
-        pp.shard_index = pass.shard_index; pp.shard_count = shardCount;
-        pp.tiles_x = tilesX; pp.num_tiles = numTiles;
-        pp.width = w; pp.height = h;
-        hipLaunchKernelGGL(k_records, dim3((numRecords + 63)/64), dim3(64), 0, ctx->stream, pp, ctx->dRecords, numRecords);
+    if (plan.recordPass && rc == TGHIP_OK) {
+        hipLaunchKernelGGL(k_records, dim3((plan.numRecords + 63)/64), dim3(64), 0, ctx->stream, base, ctx->dRecords, plan.numRecords);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
@@ -1895,8 +1703,8 @@ int tghip_wait(tghip_ctx *ctx)
     ctx->counters.ms_total += ms;
     if (verbose)
         std::fprintf(stderr, "[tghip] pass spp [%u, %u) flags %u: %llu items of %u samples in batches of %llu, %u slots, short %d; setup %.2f ms, loop %.2f ms (%llu iterations, device %.2f ms)\n",
-                     pass.spp_begin, pass.spp_end, pass.flags, (unsigned long long)(recordPass ? recordItems : uint64_t(ownedTiles)*256*chunksAll), chunk,
-                     (unsigned long long)batchItems, ctx->pool.num_slots, int(ctx->shortBatch), msSetup, msSince(tLoop0), (unsigned long long)(ctx->counters.iterations - itersBefore), double(ms));
+                     pass.spp_begin, pass.spp_end, pass.flags, (unsigned long long)plan.totalItems, plan.chunk,
+                     (unsigned long long)plan.batchItems, ctx->pool.num_slots, int(ctx->shortBatch), msSetup, msSince(tLoop0), (unsigned long long)(ctx->counters.iterations - itersBefore), double(ms));
     return ctx->passResult = rc;
 }
 
@@ -2033,18 +1841,9 @@ int tghip_develop(tghip_ctx *ctx, const TgHipDevelopDesc *desc, float *hdr_out, 
     if (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) {
         if ((reinterpret_cast<uintptr_t>(hdr) & 15u) || (reinterpret_cast<uintptr_t>(ldr) & 3u)) { ctx->error = "tghip_develop: device outputs must be aligned (hdr_out to 16 bytes, ldr_out to 4)"; return TGHIP_E_INVALID; }
     } else {
-        if (hdr_out && ctx->developHdrCap < hdrFloats) {
-            if (ctx->developHdr) (void)hipFree(ctx->developHdr);
-            ctx->developHdr = nullptr; ctx->developHdrCap = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developHdr), hdrFloats*sizeof(float)));
-            ctx->developHdrCap = hdrFloats;
-        }
-        if (ldr_out && ctx->developLdrCap < npixels*3) {
-            if (ctx->developLdr) (void)hipFree(ctx->developLdr);
-            ctx->developLdr = nullptr; ctx->developLdrCap = 0;
-            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developLdr), npixels*3));
-            ctx->developLdrCap = npixels*3;
-        }
+        int grc;
+        if (hdr_out && (grc = growArray(ctx, ctx->developHdr, ctx->developHdrCap, hdrFloats)) != TGHIP_OK) return grc;
+        if (ldr_out && (grc = growArray(ctx, ctx->developLdr, ctx->developLdrCap, npixels*3)) != TGHIP_OK) return grc;
         hdr = hdr_out ? ctx->developHdr : nullptr;
         ldr = ldr_out ? ctx->developLdr : nullptr;
     }
@@ -2104,11 +1903,8 @@ int tghip_nlmeans(tghip_ctx *ctx, const TgHipNlMeansDesc *desc, const float *ima
     float *result = out;
     for (int b = 0; b < 4; ++b) {
         const bool needed = b < 3 ? (!pointers || !device) : !device;
-        if (!needed || ctx->nlmCap[b] >= nfloats) continue;
-        if (ctx->nlmBuf[b]) (void)hipFree(ctx->nlmBuf[b]);
-        ctx->nlmBuf[b] = nullptr; ctx->nlmCap[b] = 0;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->nlmBuf[b]), nbytes));
-        ctx->nlmCap[b] = nfloats;
+        int grc;
+        if (needed && (grc = growArray(ctx, ctx->nlmBuf[b], ctx->nlmCap[b], nfloats)) != TGHIP_OK) return grc;
     }
     if (pointers && !device)
         for (int b = 0; b < 3; ++b) {

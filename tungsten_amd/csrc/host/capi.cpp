@@ -6,6 +6,7 @@
 #include "EmbreeTopTree.hpp"
 #include "ImageIO.hpp"
 #include "Integrator.hpp"
+#include "PassPlan.hpp"
 #include "Sampling.hpp"
 #include "Scene.hpp"
 #include "SceneCheck.hpp"
@@ -36,6 +37,12 @@ struct tgh_accel
     InstancedAccel inst;
     std::vector<TgHipPrimRec> recs;
     std::vector<TgHipTriAttr> attrs;
+};
+
+struct tgh_pass_plan
+{
+    PassPlan plan;
+    std::vector<TgHostPassBatch> batches;
 };
 
 struct tgh_renderer
@@ -508,6 +515,56 @@ int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out, char *e
     }
     return TGHIP_OK;
 }
+
+tgh_pass_plan *tgh_pass_plan_create(const TgHipPassDesc *pass, uint32_t width, uint32_t height, int scene_has_sobol,
+                                    uint64_t max_items, uint64_t max_slots, uint32_t chunk_samples, int *rc, char *err, size_t errlen)
+{
+    int dummy;
+    if (!rc) rc = &dummy;
+    if (!pass) { setErr(err, errlen, "no pass description"); *rc = TGHIP_E_INVALID; return nullptr; }
+    std::string error;
+    std::unique_ptr<tgh_pass_plan> out(new tgh_pass_plan());
+    const PassPlanOptions opt = {max_items, max_slots, chunk_samples};
+    if ((*rc = checkPass(*pass, width, height, scene_has_sobol != 0, error)) != TGHIP_OK ||
+        (*rc = planPass(*pass, width, height, opt, out->plan, error)) != TGHIP_OK) {
+        setErr(err, errlen, error);
+        return nullptr;
+    }
+    for (const PassBatch &b : out->plan.batches)
+        out->batches.push_back(TgHostPassBatch{b.sppBegin, b.sppEnd, b.chunks, b.pixSlots, b.totalItems, b.firstTile, b.itemBase});
+    return out.release();
+}
+
+void tgh_pass_plan_info(tgh_pass_plan *p, TgHostPassPlan *out)
+{
+    if (!p || !out) return;
+    const PassPlan &q = p->plan;
+    *out = TgHostPassPlan{q.empty, q.tilesX, q.tilesY, q.numTiles, q.shardCount, q.shardSkew, q.ownedTiles, q.recordPass, q.varianceW, q.numRecords,
+                          q.spp, q.sppBegin, q.auxPass, q.chunk, q.group, q.chunksAll, q.shortBatch, 0u,
+                          q.lumFloats, q.recordItems, uint64_t(q.hintEntries), q.totalItems, q.batchItems};
+}
+
+static const uint32_t *planArray(const std::vector<uint32_t> *v, bool have, uint32_t *n)
+{
+    have = have && v && !v->empty();
+    if (n) *n = have ? uint32_t(v->size()) : 0u;
+    return have ? v->data() : nullptr;
+}
+
+const TgHostPassBatch *tgh_pass_plan_batches(tgh_pass_plan *p, uint32_t *num_batches)
+{
+    if (num_batches) *num_batches = p ? uint32_t(p->batches.size()) : 0u;
+    return (p && !p->batches.empty()) ? p->batches.data() : nullptr;
+}
+
+const uint32_t *tgh_pass_plan_owned_tiles(tgh_pass_plan *p, uint32_t *n) { return planArray(p ? &p->plan.ownedList : nullptr, p && p->plan.shardCount > 1, n); }
+const uint32_t *tgh_pass_plan_rec_index(tgh_pass_plan *p) { return planArray(p ? &p->plan.recIndex : nullptr, p && p->plan.recordPass, nullptr); }
+const uint32_t *tgh_pass_plan_rec_count(tgh_pass_plan *p) { return planArray(p ? &p->plan.recCount : nullptr, p && p->plan.recordPass, nullptr); }
+const uint32_t *tgh_pass_plan_rec_lum(tgh_pass_plan *p) { return planArray(p ? &p->plan.recLum : nullptr, p && p->plan.recordPass, nullptr); }
+const uint32_t *tgh_pass_plan_sorted(tgh_pass_plan *p, uint32_t *n) { return planArray(p ? &p->plan.sorted : nullptr, p && p->plan.recordPass, n); }
+const uint32_t *tgh_pass_plan_chunk_starts(tgh_pass_plan *p, uint32_t *n) { return planArray(p ? &p->plan.chunkStart : nullptr, p && p->plan.recordPass, n); }
+
+void tgh_pass_plan_free(tgh_pass_plan *p) { delete p; }
 
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h)
 {
