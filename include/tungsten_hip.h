@@ -306,7 +306,11 @@ enum { TGHIP_MEDIUM_HOMOGENEOUS = 0, TGHIP_MEDIUM_EXPONENTIAL = 1, TGHIP_MEDIUM_
  *     res_u = _numBlades          scale = _angle
  *     on_color[0] = _bladeAngle   on_color[1] = _area        on_color[2] = 1.0f/_area (the pdf inside the polygon)
  *     off_color[0], [1] = _baseNormal                        off_color[2], pad = _baseEdge
- * Both are evaluated by the all-features shading family only (a scene that holds one is shaded by it throughout). */
+ * Both are evaluated by the all-features shading family only (a scene that holds one is shaded by it throughout).
+ * Where a texture is SAMPLED -- the emission of a sampled infinite_sphere (primitives/InfiniteSphere.cpp:161-176, 218-229) and a thin lens's aperture
+ * (TgHipCamera) --, every type goes through its own sample / pdf: a bitmap through its Distribution2D (dist_offset), disk and blade as above, a
+ * TGHIP_TEX_CHECKER through CheckerTexture::sample / pdf (textures/CheckerTexture.cpp:85-123) from on_color, off_color, res_u and res_v as they are --
+ * in the all-features family again: a scene whose sampled infinite_sphere has a checker emission is shaded by it throughout --, a constant uniformly. */
 enum { TGHIP_TEX_CONSTANT = 0, TGHIP_TEX_CHECKER = 1, TGHIP_TEX_BITMAP = 2, TGHIP_TEX_DISK = 3, TGHIP_TEX_BLADE = 4 };
 #define TGHIP_TEXF_LINEAR 1u
 #define TGHIP_TEXF_CLAMP  2u
@@ -337,7 +341,14 @@ enum { TGHIP_CAMERA_PINHOLE = 0, TGHIP_CAMERA_THINLENS = 1,     /* cameras/Pinho
        TGHIP_CAMERA_CUBEMAP = 3 };         /* cameras/CubemapCamera.cpp: six 90-degree faces laid out as a cross, a row or a column; inv_xf as for the
                                               equirectangular camera, blade_count = CubemapCamera::ProjectionMode (0 horizontal_cross, 1 vertical_cross, 2 row, 3 column) */
 enum { TGHIP_APERTURE_DISK = 0, TGHIP_APERTURE_BLADE = 1,       /* textures/DiskTexture.cpp:78-81, textures/BladeTexture.cpp:110-130 */
-       TGHIP_APERTURE_BITMAP = 2 };                             /* textures/BitmapTexture.cpp:433-439 with the MAP_UNIFORM distribution (:400-431) */
+       TGHIP_APERTURE_BITMAP = 2,                               /* textures/BitmapTexture.cpp:433-439 with the MAP_UNIFORM distribution (:400-431); an `ies`
+                                                                   aperture too: IesTexture is a BitmapTexture and its bake is what makeSamplable weighs */
+       /* (3 is no aperture and stays refused) */
+       TGHIP_APERTURE_CONSTANT = 4,                             /* textures/ConstantTexture.cpp:69-72: the lens sample as it is, a square aperture */
+       TGHIP_APERTURE_CHECKER = 5 };                            /* textures/CheckerTexture.cpp:85-112: aperture_w = _resU, aperture_h = _resV,
+                                                                   blade_edge[0] = _onColor.max(), blade_edge[1] = _offColor.max() (finite, not negative,
+                                                                   not both zero: a checker of two blacks samples like TGHIP_APERTURE_CONSTANT, :88-91, and
+                                                                   is flattened as that) */
 typedef struct TgHipCamera {
     float   pos[3];
     float   plane_dist;
@@ -348,8 +359,9 @@ typedef struct TgHipCamera {
     float   filter_width, filter_bin_size;
     float   filter_cdf[32];   /* ReconstructionFilter::_cdf (RFILTER_RESOLUTION = 31) */
     /* thin lens (cameras/ThinlensCamera.cpp:85-126); the aperture texture is only ever sampled by the forward path tracer
-     * (samplePosition, :85-97): the default disk (textures/DiskTexture.cpp:78-86), an n-blade polygon (BladeTexture.cpp:21-31, 110-130) or a
-     * bitmap (BitmapTexture::sample) */
+     * (samplePosition, :85-97): the default disk (textures/DiskTexture.cpp:78-86), an n-blade polygon (BladeTexture.cpp:21-31, 110-130), a
+     * bitmap or an IES bake (BitmapTexture::sample), a constant or a checker -- every texture type the reference's factory makes.  A checker's
+     * parameters ride in fields its type does not otherwise use (TGHIP_APERTURE_CHECKER above); the struct keeps its size */
     int32_t type;             /* TGHIP_CAMERA_*                                   */
     float   focus_dist, aperture_size, cat_eye;
     float   inv_xf[12];       /* rows 0..2 of Camera::_invTransform (3x4, row-major, translation in column 3) */

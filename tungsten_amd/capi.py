@@ -73,6 +73,11 @@ class TgHipCamera(C.Structure):
                 ("aperture_w", i32), ("aperture_h", i32), ("aperture_dist", u32)]
 
 
+# TgHipCamera.aperture_type (3 is no aperture; a checker: aperture_w / aperture_h = res_u / res_v, blade_edge = the two colours' maxima)
+(TGHIP_APERTURE_DISK, TGHIP_APERTURE_BLADE, TGHIP_APERTURE_BITMAP) = range(3)
+(TGHIP_APERTURE_CONSTANT, TGHIP_APERTURE_CHECKER) = (4, 5)
+
+
 class TgHipSettings(C.Structure):
     _fields_ = [("min_bounces", i32), ("max_bounces", i32), ("enable_light_sampling", i32),
                 ("enable_two_sided_shading", i32), ("enable_consistency_checks", i32), ("enable_volume_light_sampling", i32), ("pad", i32*2)]

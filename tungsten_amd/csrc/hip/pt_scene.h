@@ -155,6 +155,37 @@ PT_DEV float procTexPdf(const TgHipTexture &t, float u, float v)
         return diskTexInside(u, v) ? PT_INV_PI*4.0f : 0.0f;
     return bladeTexInside(t, u, v) ? t.on_color[2] : 0.0f;
 }
+// CheckerTexture::sample / pdf (textures/CheckerTexture.cpp:85-123; the jacobian is ignored), as they are: the first number picks the colour by
+// onProb = onWeight/(onWeight + offWeight) and, stretched back to [0, 1), the column; the second one of the rows that hold that colour in this
+// column.  The pdf has no factor of two and an odd res_v gives the two row parities different cell counts ("biased for odd resolutions", the
+// reference's own remark): restated, not repaired.  onWeight / offWeight = _onColor.max() / _offColor.max().
+PT_DEV void checkerTexSample(float onWeight, float offWeight, int resU, int resV, float xi0, float xi1, float &u, float &v)
+{
+    u = xi0; v = xi1;
+    if (onWeight + offWeight == 0.0f)
+        return;
+    const float onProb = onWeight/(onWeight + offWeight);
+    int rowOffset;
+    if (u < onProb) {
+        u = xi0/onProb;
+        rowOffset = ((int)(u*(float)resU) + 1) & 1;
+    } else {
+        u = (xi0 - onProb)/(1.0f - onProb);
+        rowOffset = (int)(u*(float)resU) & 1;
+    }
+    const int numVCells = (resV + 1 - rowOffset)/2;
+    const float scaledV = v*(float)numVCells;
+    const int onCell = (int)scaledV;
+    const float vBase = (float)(onCell*2 + rowOffset)/(float)resV;
+    v = vBase + (scaledV - (float)onCell)/(float)resV;
+}
+PT_DEV float checkerTexPdf(float onWeight, float offWeight, int resU, int resV, float u, float v)
+{
+    if (onWeight + offWeight == 0.0f)
+        return 1.0f;
+    const int ui = (int)(u*(float)resU), vi = (int)(v*(float)resV);
+    return (((ui ^ vi) & 1) ? onWeight : offWeight)/(onWeight + offWeight);
+}
 
 template<uint32_t M>
 PT_DEV f3 textureEval(const DeviceScene &s, int texIdx, float u0, float v0)
@@ -2053,6 +2084,8 @@ PT_DEV float lightDirectPdf(const DeviceScene &s, int objIdx, f3 w, f3 p, const 
     if constexpr (HAS_PROCTEX(M)) {
         if (t.type == TGHIP_TEX_DISK || t.type == TGHIP_TEX_BLADE)     /* the texture's own pdf (InfiniteSphere.cpp:223-228) */
             return PT_INV_PI*PT_INV_TWO_PI*procTexPdf(t, lh.u, lh.v)/lh.sinTheta;
+        if (t.type == TGHIP_TEX_CHECKER)                                /* (not isConstant(), whatever its colours: CheckerTexture.cpp:43-46) */
+            return PT_INV_PI*PT_INV_TWO_PI*checkerTexPdf(max3(ld3(t.on_color)), max3(ld3(t.off_color)), t.res_u, t.res_v, lh.u, lh.v)/lh.sinTheta;
     }
     if (!(M & FEAT_BITMAP) || t.type != TGHIP_TEX_BITMAP)
         return PT_INV_FOUR_PI;
@@ -2231,6 +2264,14 @@ PT_DEV bool lightSampleDirect(const DeviceScene &s, int objIdx, f3 p, Rng &rng, 
             procTexSample(t, xi0, xi1, u, v);
             d = infUvToDirection(o, u, v, sinTheta);
             pdf = PT_INV_PI*PT_INV_TWO_PI*procTexPdf(t, u, v)/sinTheta;
+            return pdf != 0.0f;
+        }
+        if (t.type == TGHIP_TEX_CHECKER) {                             /* CheckerTexture::sample / pdf, the same way */
+            const float onWeight = max3(ld3(t.on_color)), offWeight = max3(ld3(t.off_color));
+            float u, v, sinTheta;
+            checkerTexSample(onWeight, offWeight, t.res_u, t.res_v, xi0, xi1, u, v);
+            d = infUvToDirection(o, u, v, sinTheta);
+            pdf = PT_INV_PI*PT_INV_TWO_PI*checkerTexPdf(onWeight, offWeight, t.res_u, t.res_v, u, v)/sinTheta;
             return pdf != 0.0f;
         }
     }

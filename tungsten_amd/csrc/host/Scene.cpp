@@ -1094,8 +1094,7 @@ std::shared_ptr<Primitive> Scene::instantiatePrimitive(const JsonValue &v) const
         p->type = Primitive::InfiniteSphereCap;
         v.getField("sample", p->doSample);
         v.getField("cap_angle", p->capAngleDeg);
-        if (v["skydome"])
-            throw JsonLoadException("infinite_sphere_cap 'skydome' pivots (procedural sky) are outside the path_tracer_hip hot-path scope");
+        v.getField("skydome", p->domeName);       // resolved by Scene::fromJson, once every primitive exists
     } else if (type == "instances") {
         // Instance::fromJson (Instance.cpp:60-93)
         p->type = Primitive::Instances;
@@ -1350,7 +1349,8 @@ void Primitive::prepareForRender()
         scale = (emission && !power) ? emission->average()*(4.0f*PI) : Vec3f(0.0f);
         break;
     } case InfiniteSphereCap: { // InfiniteSphereCap.cpp:233-249
-        normal = transform.transformVector(Vec3f(0.0f, 1.0f, 0.0f)).normalized();      // _capDir
+        const Mat4f &tform = pivoted ? pivotTransform : transform;                     // the "skydome" pivot's transform (:235-242)
+        normal = tform.transformVector(Vec3f(0.0f, 1.0f, 0.0f)).normalized();          // _capDir
         scale = Vec3f(std::cos(capAngleDeg*(PI/180.0f)), 0.0f, 0.0f);                  // _cosCapAngle
         float sign = copysignf(1.0f, normal.z());                                     // TangentFrame(_capDir)
         const float a = -1.0f/(sign + normal.z());
@@ -1488,9 +1488,11 @@ void Camera::fromJson(const JsonValue &v, const Scene &scene)
                 bladeEdge[1] = cosAngle*2.0f*k;
             } else if (!ap.isObject() || apType != "disk") {
                 // ThinlensCamera::fromJson: scene.fetchTexture(aperture, TexelConversion::REQUEST_AVERAGE) (cameras/ThinlensCamera.cpp:62-63)
+                // -- a bitmap, an `ies` profile (IesTexture is a BitmapTexture: its bake is what makeSamplable(MAP_UNIFORM) weighs, and _valid, which
+                // the reference leaves false, is not looked at there, BitmapTexture.cpp:400-431), a constant (a number, an RGB triple or
+                // {"type": "constant"}) or a checker.  Non-bitmaps ignore the scalar request (io/Scene.cpp:129-132): a checker keeps its RGB colours.
+                // (An .ies file that cannot be read stays what DESIGN.md section 10 records for lookups: the reference cannot render it.)
                 apertureTex = scene.fetchTexture(ap, false);
-                if (!apertureTex || apertureTex->type != Texture::Bitmap)
-                    throw JsonLoadException("thinlens apertures other than the 'disk' and 'blade' textures and bitmaps are outside the path_tracer_hip hot-path scope");
             }
         }
     } else if (type == "equirectangular") {        // EquirectangularCamera::fromJson = Camera::fromJson (no parameters of its own)
@@ -1626,6 +1628,21 @@ void Scene::fromJson(const JsonValue &root)
     if (const JsonValue &jp = root["primitives"])
         for (size_t i = 0; i < jp.size(); ++i)
             primitives.push_back(instantiatePrimitive(jp[i]));
+    // InfiniteSphereCap::prepareForRender (InfiniteSphereCap.cpp:233-250): a cap that names a primitive -- the sky, usually; any name counts, the
+    // first primitive that bears it (Scene::findPrimitive, io/Scene.cpp:175-181) -- points where that primitive's transform turns "up"
+    for (auto &p : primitives) {
+        if (p->type != Primitive::InfiniteSphereCap || p->domeName.empty())
+            continue;
+        const Primitive *pivot = nullptr;
+        for (const auto &q : primitives)
+            if (q->name == p->domeName) { pivot = q.get(); break; }
+        if (pivot) {
+            p->pivoted = true;
+            p->pivotTransform = pivot->transform;
+        } else {
+            std::fprintf(stderr, "Note: unable to find pivot object '%s' for infinity sphere cap\n", p->domeName.c_str());
+        }
+    }
     if (const JsonValue &cam = root["camera"])
         camera.fromJson(cam, *this);
     if (const JsonValue &integ = root["integrator"])

@@ -145,6 +145,11 @@ struct Primitive
     float coneAngle = 90.0f;
     // infinite sphere cap (primitives/InfiniteSphereCap.hpp): emission from directions within cap_angle of the transform's up axis
     float capAngleDeg = 10.0f;
+    // "skydome": the name of the primitive whose transform gives the cap its direction (InfiniteSphereCap.cpp:233-250); Scene::fromJson resolves it
+    // once every primitive exists, as _scene->findPrimitive would at prepareForRender
+    std::string domeName;
+    bool pivoted = false;
+    Mat4f pivotTransform;
     // instances (primitives/Instance.hpp:13-31): rigid placements (position + rotation) of master primitives
     std::vector<std::shared_ptr<Primitive>> masters;
     std::string instanceFile;
@@ -189,7 +194,8 @@ struct Camera
     // "aperture": {"type": "blade", "blades": n, "angle": a} (textures/BladeTexture.cpp:14-41); 0 blades = the disk
     int blades = 0;
     // "aperture": a bitmap (a file name or {"type": "bitmap", ...}; scalar request REQUEST_AVERAGE, ThinlensCamera.cpp:62-63): the lens
-    // point is drawn from the image (BitmapTexture::sample with the MAP_UNIFORM distribution)
+    // point is drawn from the image (BitmapTexture::sample with the MAP_UNIFORM distribution); an `ies` aperture is such a bitmap (its bake);
+    // a constant or a checker: the lens point is ConstantTexture::sample's / CheckerTexture::sample's (non-bitmaps ignore the scalar request)
     std::shared_ptr<Texture> apertureTex;
     float bladeAngle = 0.0f, bladeStep = 0.0f;
     float bladeEdge[2] = {0.0f, 0.0f};

@@ -42,7 +42,7 @@ bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
     case TGHIP_BSDF_VARIANT_COAT:    return !fwd && (tm & ~MASK_COAT) == 0;
     case TGHIP_BSDF_VARIANT_GLASS:   return !fwd && (tm & ~MASK_GLASS) == 0;
     case TGHIP_BSDF_VARIANT_PLASTIC: return (tm & ~MASK_PLASTIC) == 0;
-    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0 && !HAS_PROCTEX(tm);   // (bits 0 .. 18: the BSDF types; tghip_debug_bsdf_info's marker of a disk / blade scene)
+    case TGHIP_BSDF_VARIANT_MEDIA:   return (tm & ~MASK_MEDIA & 0x7FFFFu) == 0 && !HAS_PROCTEX(tm);   // (bits 0 .. 18: the BSDF types; tghip_debug_bsdf_info's marker of a scene with a disk / blade texture or a sampled checker environment)
     case TGHIP_BSDF_VARIANT_TAIL:    return !fwd && (tm & ~MASK_TAIL) == 0;
     case TGHIP_BSDF_VARIANT_FULL:    return (tm & ~MASK_FULL) == 0;
     case TGHIP_BSDF_VARIANT_ALL:     return true;
@@ -315,6 +315,9 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
                    ty != TGHIP_OBJ_INFINITE_SPHERE_CAP && ty != TGHIP_OBJ_POINT && ty != TGHIP_OBJ_CYLINDER) {
             return fail(TGHIP_E_UNSUPPORTED, "unknown emitter type");
         }
+        // a SAMPLED infinite sphere samples its emission through the texture's own sample / pdf: a checker's are compiled where disk's and blade's are
+        // (an unsampled one, and a checker that is only looked up, keep the scene where it is)
+        if (ty == TGHIP_OBJ_INFINITE_SPHERE && lo.emission >= 0 && sd->textures[lo.emission].type == TGHIP_TEX_CHECKER) t.haveProcTex = true;
     }
     if (sd->wide_nodes && sd->num_wide_nodes) {
         // the wide nodes and the primitive records share ONE allocation, so that a lane of the wide kernels addresses
@@ -364,7 +367,13 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
         for (uint64_t i = 0; usable && i < ah; ++i)
             usable = std::isfinite(mcdf[i + 1]) && mcdf[i + 1] >= mcdf[i];
         if (!usable) return fail(TGHIP_E_INVALID, "the bitmap aperture's distribution is not a CDF (zero total weight or non-finite entries)");
-    } else if (t.thinlens && cam.aperture_type != TGHIP_APERTURE_DISK && cam.aperture_type != TGHIP_APERTURE_BLADE) {
+    } else if (t.thinlens && cam.aperture_type == TGHIP_APERTURE_CHECKER) {
+        // CheckerTexture::sample scales by the resolutions, divides by res_v and by the sum of the two weights (TgHipCamera: blade_edge)
+        const float on = cam.blade_edge[0], off = cam.blade_edge[1];
+        if (cam.aperture_w <= 0 || cam.aperture_h <= 0) return fail(TGHIP_E_INVALID, "the checker aperture needs positive resolutions");
+        if (!std::isfinite(on) || !std::isfinite(off) || on < 0.0f || off < 0.0f || !std::isfinite(on + off) || on + off == 0.0f)
+            return fail(TGHIP_E_INVALID, "the checker aperture's weights must be finite, not negative and not both zero");
+    } else if (t.thinlens && cam.aperture_type != TGHIP_APERTURE_DISK && cam.aperture_type != TGHIP_APERTURE_BLADE && cam.aperture_type != TGHIP_APERTURE_CONSTANT) {
         return fail(TGHIP_E_UNSUPPORTED, "unknown aperture type");
     }
 
@@ -374,7 +383,7 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
     t.bsdfForward.assign(sd->num_bsdfs, 0);
     for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
         typeMask[i] = bsdfTypeMask(sd, int(i), 0);
-        // (FEAT_FAMILY_ALL: the scene holds a `disk` or `blade` texture, so every material of it is shaded by the all-features family -- no other
+        // (FEAT_FAMILY_ALL: the scene holds a `disk` or `blade` texture -- or samples a checkered environment --, so every material of it is shaded by the all-features family -- no other
         // family covers the entry)
         t.bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u) | (t.haveProcTex ? FEAT_FAMILY_ALL : 0u);
         t.bsdfForward[i] = (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ? 1 : 0;

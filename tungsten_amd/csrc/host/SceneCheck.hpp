@@ -29,7 +29,7 @@ struct SceneTraits {
     uint32_t classMask[PT_NUM_CLASSES] = {0, 0, 0, 0};                  // ... and the BSDF types inside each
     bool haveForward = false;             // some BSDF has a forward lobe (shadow rays attenuate instead of stop) -- or the scene has media: shadow rays pick up
                                           // transmittance segment by segment (the closest-hit shadow walk)
-    std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when the scene holds a disk / blade texture (tghip_debug_bsdf_info)
+    std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
@@ -40,7 +40,8 @@ struct SceneTraits {
     bool haveSolids = false;              // cube / sphere / disk records: the dynamic-fetch kernels' SOLIDS variants
     bool allFeaturesShading = false;      // cylinder primitives -- or a bump-mapped bsdf (TgHipBsdf::bump1), or a disk / blade texture: BSDF_MASK_ALL shading (the only
                                           // FEAT_CYLINDER / FEAT_BUMP variant), never fused
-    bool haveProcTex = false;             // a `disk` or `blade` texture (TGHIP_TEX_DISK / _BLADE): evaluated by the all-features family only -- sets allFeaturesShading (BSDF_MASK_ALL
+    bool haveProcTex = false;             // a `disk` or `blade` texture (TGHIP_TEX_DISK / _BLADE), or a sampled infinite sphere whose emission is a checker (its sample / pdf):
+                                          // evaluated by the all-features family only -- sets allFeaturesShading (BSDF_MASK_ALL
                                           // shading, never fused, no k_tail) and sends a closest-hit shadow walk to k_trace_shadow<., true, ., ., BSDF_MASK_ALL>
     bool haveMedia = false;               // participating media: BSDF_MASK_ALL shading (the only FEAT_MEDIA variant), closest-hit shadow walk, never fused
     bool mediaSimple = false;             // a media scene whose surface BSDFs MASK_MEDIA covers (no instances, no mesh emitters)

@@ -734,7 +734,7 @@ void TraceableScene::flatten()
     c.aperture_size = cam.apertureSize;
     c.cat_eye = cam.catEye;
     c.aperture_type = cam.blades > 0 ? TGHIP_APERTURE_BLADE : TGHIP_APERTURE_DISK;
-    if (cam.apertureTex) {
+    if (cam.apertureTex && cam.apertureTex->type == Texture::Bitmap) {
         // ThinlensCamera::precompute: _aperture->makeSamplable(MAP_UNIFORM) (cameras/ThinlensCamera.cpp:27-35); the forward path tracer
         // only ever samples the aperture, so its Distribution2D is all the device gets
         Texture &t = *cam.apertureTex;
@@ -752,6 +752,19 @@ void TraceableScene::flatten()
     c.blade_count = cam.blades;
     c.blade_angle = cam.bladeAngle; c.blade_step = cam.bladeStep;
     c.blade_edge[0] = cam.bladeEdge[0]; c.blade_edge[1] = cam.bladeEdge[1];
+    if (cam.apertureTex && cam.apertureTex->type != Texture::Bitmap) {
+        // the textures whose makeSamplable does nothing: ConstantTexture::sample hands the lens sample back (a square aperture), and so does
+        // CheckerTexture::sample where both colours are black (textures/CheckerTexture.cpp:88-91); else the checker's parameters ride in the
+        // fields of the other aperture types (include/tungsten_hip.h: TGHIP_APERTURE_CHECKER)
+        const Texture &t = *cam.apertureTex;
+        const float onWeight = t.onColor.max(), offWeight = t.offColor.max();
+        c.aperture_type = TGHIP_APERTURE_CONSTANT;
+        if (t.type == Texture::Checker && onWeight + offWeight != 0.0f) {
+            c.aperture_type = TGHIP_APERTURE_CHECKER;
+            c.aperture_w = t.resU; c.aperture_h = t.resV;
+            c.blade_edge[0] = onWeight; c.blade_edge[1] = offWeight;
+        }
+    }
     for (int i = 0; i < 12; ++i) c.inv_xf[i] = cam.invTransform[i];
     if (cam.equirectangular || cam.cubemapMode >= 0) {
         // EquirectangularCamera::prepareForRender (cameras/EquirectangularCamera.cpp:129-134): _rot = _transform.extractRotation(); Camera::_pixelSize.y
