@@ -243,7 +243,17 @@ enum { TGHIP_BSDF_LAMBERT = 0, TGHIP_BSDF_NULL = 1, TGHIP_BSDF_ROUGH_CONDUCTOR =
         *   OREN_NAYAR            roughness (scalar texture)
         *   ROUGH_COAT            ior, thickness, sigma_a, scaled_sigma_a, avg_transmittance, distribution, roughness, sub0 = _substrate */
        TGHIP_BSDF_DIFFUSE_TRANSMISSION = 14, TGHIP_BSDF_PHONG = 15, TGHIP_BSDF_THINSHEET = 16, TGHIP_BSDF_OREN_NAYAR = 17,
-       TGHIP_BSDF_ROUGH_COAT = 18 };
+       TGHIP_BSDF_ROUGH_COAT = 18,
+       /* Two of the factory's three fibre BCSDFs (bsdfs/LambertianFiberBcsdf.cpp, bsdfs/RoughWireBcsdf.cpp; `hair` is not restated), on ANY primitive:
+        * they read the shading frame only, which -- their lobes carrying TGHIP_LOBE_ANISOTROPIC -- is the primitive's own tangent space
+        * (Primitive::setupTangentFrame, Primitive.cpp:125-163; the cylinder's tangent is its axis).  Same ABI version: no struct changes, and a
+        * description without them reads as before.  The kernels' type masks have no bit for them (bits 19 and 20 are scene features): the
+        * all-features shading family alone evaluates them (tghip_debug_bsdf_info).  Their own parameters:
+        *   LAMBERTIAN_FIBER      none (albedo); lobes = DIFFUSE_R | DIFFUSE_T | ANISOTROPIC
+        *   ROUGH_WIRE            eta, k (the conductors' fields: `eta` / `k` of the JSON, or the `material` looked up, default Cu);
+        *                         thickness = _v = sqr(_roughness*PI_HALF) of RoughWireBcsdf::prepareForRender (:171-174) -- `roughness` is a
+        *                         plain float there, not a texture, so the texture index `roughness` stays -1; lobes = GLOSSY_R | GLOSSY_T | ANISOTROPIC */
+       TGHIP_BSDF_LAMBERTIAN_FIBER = 19, TGHIP_BSDF_ROUGH_WIRE = 20 };
 enum { TGHIP_DIST_BECKMANN = 0, TGHIP_DIST_PHONG = 1, TGHIP_DIST_GGX = 2 };
 /* lobe bits, identical to bsdfs/BsdfLobes.hpp:13-33 */
 enum { TGHIP_LOBE_GLOSSY_R = 1, TGHIP_LOBE_GLOSSY_T = 2, TGHIP_LOBE_DIFFUSE_R = 4, TGHIP_LOBE_DIFFUSE_T = 8,
@@ -628,7 +638,9 @@ enum { TGHIP_LIBM_SINF = 0, TGHIP_LIBM_COSF = 1, TGHIP_LIBM_LOGF = 2, TGHIP_LIBM
        TGHIP_LIBM_ACOSF = 6, TGHIP_LIBM_ATAN2F = 7, TGHIP_LIBM_POWF = 8, TGHIP_LIBM_CBRTF = 9,
        TGHIP_LIBM_EMBREE_RCP = 10, TGHIP_LIBM_RCPPS = 11, TGHIP_LIBM_TANF = 12,
        /* double precision (AtmosphericMedium::inverseOpticalDepth: std::exp / log / erf / sqrt on doubles): x and y then point to n DOUBLES */
-       TGHIP_LIBM_EXPD = 13, TGHIP_LIBM_LOGD = 14, TGHIP_LIBM_ERFD = 15, TGHIP_LIBM_SQRTD = 16 };
+       TGHIP_LIBM_EXPD = 13, TGHIP_LIBM_LOGD = 14, TGHIP_LIBM_ERFD = 15, TGHIP_LIBM_SQRTD = 16,
+       /* float again: glibc's sinhf on its restated domain (0, 10] (the rough_wire BCSDF's sinh(1/v), v >= 0.1), NaN outside it */
+       TGHIP_LIBM_SINHF = 17 };
 int tghip_debug_libm(tghip_ctx *ctx, int fn, const float *x, float *y, size_t n);
 /* Self-test of the device's BSDF code (csrc/hip/pt_scene.h: bsdfEval / bsdfPdf / bsdfSample, the wrappers the shading kernels call) on caller-supplied
  * cases against the uploaded scene's flattened bsdf table, one thread per case (csrc/hip/debug_units.hip), host pointers.  Per case: eval and pdf of
@@ -661,7 +673,8 @@ int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult
 /* What the shading-class rule sees of the uploaded scene's bsdfs (num_bsdfs entries each; any pointer may be NULL): type_mask = the set of bsdf types
  * inside the material, nested ones included (bit = 1 << TGHIP_BSDF_*; bit 19 when a microfacet bsdf inside uses the Phong distribution; bit 24 when a
  * texture inside is a bitmap; bits 20 - 23 together when the scene holds a `disk` or `blade` texture anywhere -- such a scene is shaded by the all-features
- * family throughout, so TGHIP_BSDF_VARIANT_ALL alone covers its entries), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
+ * family throughout, so TGHIP_BSDF_VARIANT_ALL alone covers its entries; the same four bits when the scene holds a fibre BCSDF, TGHIP_BSDF_LAMBERTIAN_FIBER / _ROUGH_WIRE, anywhere:
+ * those two types have no bit of their own, bits 19 and 20 being the Phong and the bump feature), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
  * materials into shading classes and picks each class's kernel.  variant_mask (one word): the type / feature mask the variant's kernel is compiled for. */
 int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint32_t *forward, uint32_t *covered, uint32_t *variant_mask);
 int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "count_traversal", "max_slots", ...; "top_tree" = 0 before an upload:

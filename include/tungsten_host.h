@@ -181,6 +181,7 @@ typedef struct TgHostSceneTraits {
     int32_t  class_present[4];
     uint32_t class_mask[4], complex_mask;
     int32_t  hoisted_rec, env_tex;
+    int32_t  have_fibre;      /* the bsdf table holds a fibre BCSDF (TGHIP_BSDF_LAMBERTIAN_FIBER / _ROUGH_WIRE): steers where have_proc_tex steers */
 } TgHostSceneTraits;
 int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may be NULL */, char *err, size_t errlen);
 

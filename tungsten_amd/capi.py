@@ -115,7 +115,7 @@ class TgHipSceneDesc(C.Structure):
 TGHIP_PASS_SOBOL, TGHIP_PASS_RECORDS, TGHIP_PASS_AUX, TGHIP_PASS_SAMPLES = 1, 2, 4, 8
 (TGHIP_LIBM_SINF, TGHIP_LIBM_COSF, TGHIP_LIBM_LOGF, TGHIP_LIBM_EXPF, TGHIP_LIBM_SINCOS_SIN, TGHIP_LIBM_SINCOS_COS,
  TGHIP_LIBM_ACOSF, TGHIP_LIBM_ATAN2F, TGHIP_LIBM_POWF, TGHIP_LIBM_CBRTF, TGHIP_LIBM_EMBREE_RCP, TGHIP_LIBM_RCPPS, TGHIP_LIBM_TANF,
- TGHIP_LIBM_EXPD, TGHIP_LIBM_LOGD, TGHIP_LIBM_ERFD, TGHIP_LIBM_SQRTD) = range(17)
+ TGHIP_LIBM_EXPD, TGHIP_LIBM_LOGD, TGHIP_LIBM_ERFD, TGHIP_LIBM_SQRTD, TGHIP_LIBM_SINHF) = range(18)
 
 
 class TgHipAuxPixel(C.Structure):
@@ -201,7 +201,7 @@ class TgHostSceneTraits(C.Structure):
     _fields_ = [(n, i32) for n in ("have_media", "have_instances", "have_mesh_light", "have_forward", "have_solids", "all_features_shading", "have_proc_tex",
                                    "lean_scene", "media_simple", "thinlens", "camera_fix", "have_complex", "top_tree", "tables_fit",
                                    "bvh_depth", "bvh_master_depth", "wide_depth", "wide_master_depth")] + \
-               [("class_present", i32*4), ("class_mask", u32*4), ("complex_mask", u32), ("hoisted_rec", i32), ("env_tex", i32)]
+               [("class_present", i32*4), ("class_mask", u32*4), ("complex_mask", u32), ("hoisted_rec", i32), ("env_tex", i32), ("have_fibre", i32)]
 
 
 class TgHostPassPlan(C.Structure):

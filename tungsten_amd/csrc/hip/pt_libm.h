@@ -379,6 +379,64 @@ PT_LIBM_FN float tanfCore(float x)
     return kernelTanf(head, tail, 1 - ((n & 1) << 1));
 }
 
+// ---- sinhf: e_sinhf.c with the expm1f it calls (s_expm1f.c) -- glibc 2.35: fdlibm's float algorithms, no FMA variant, every operation a
+// float operation rounded on its own.  The one caller is the rough_wire BCSDF's longitudinal lobe (RoughWireBcsdf.cpp:81: std::sinh(1/v) with
+// v >= 0.1), so the RESTATED DOMAIN is 0 < x <= 10; every other argument (zero, negative, above 10, infinite, NaN) returns NaN, as tanfCore does
+// outside its range.  Inside it, all of e_sinhf.c's and s_expm1f.c's branches a positive x <= 10 can take are here: x < 2^-28 (sinh x = x),
+// expm1f's x < 2^-25 (returns x), no reduction (x <= ln(2)/2), k = 1 (x < 3 ln(2)/2) and 2 <= k <= 14 (always < 23: the `t = 1 - 2^-k` form),
+// and sinhf's two result forms on either side of 1.  Matched against the host libm on EVERY float of (0, 10] (tools/libm_sinhf_sweep.cpp:
+// 0 differences), on the device by tests/test_gpu_fibres.py.
+PT_LIBM_FN float expm1fPos(float x)                  // 2^-28 <= x <= 10
+{
+    const float ln2Hi = 6.9313812256e-01f, ln2Lo = 9.0580006145e-06f, invLn2 = 1.4426950216e+00f;
+    const float Q1 = -3.3333335072e-02f, Q2 = 1.5873016091e-03f, Q3 = -7.9365076090e-05f, Q4 = 4.0082177293e-06f, Q5 = -2.0109921195e-07f;
+    const uint32_t hx = f2u(x);
+    float hi, lo, c = 0.0f;
+    int k = 0;
+    if (hx > 0x3eb17218u) {                         // x > 0.5 ln 2
+        if (hx < 0x3F851592u) {                     // and x < 1.5 ln 2
+            hi = x - ln2Hi; lo = ln2Lo; k = 1;
+        } else {
+            k = (int)(invLn2*x + 0.5f);
+            const float t = (float)k;
+            hi = x - t*ln2Hi;                       // (t*ln2_hi is exact here)
+            lo = t*ln2Lo;
+        }
+        x = hi - lo;
+        c = (hi - x) - lo;
+    } else if (hx < 0x33000000u) {                  // x < 2^-25
+        return x;
+    }
+    const float hfx = 0.5f*x;
+    const float hxs = x*hfx;
+    const float r1 = 1.0f + hxs*(Q1 + hxs*(Q2 + hxs*(Q3 + hxs*(Q4 + hxs*Q5))));
+    float t = 3.0f - r1*hfx;
+    float e = hxs*((r1 - t)/(6.0f - x*t));
+    if (k == 0)
+        return x - (x*e - hxs);
+    e = (x*(e - c) - c);
+    e -= hxs;
+    if (k == 1) {
+        if (x < -0.25f) return -2.0f*(e - (x + 0.5f));
+        return 1.0f + 2.0f*(x - e);
+    }
+    t = u2f(0x3f800000u - (0x1000000u >> k));       // 1 - 2^-k, 2 <= k < 23
+    const float y = t - (e - x);
+    return u2f(f2u(y) + ((uint32_t)k << 23));       // add k to y's exponent
+}
+PT_LIBM_FN float sinhfCore(float x)
+{
+    const uint32_t ix = f2u(x);
+    if (!(ix - 1u < 0x41200000u))                   // not in (0, 10]: bit patterns 1 .. 0x41200000
+        return u2f(0x7fc00000u);
+    if (ix < 0x31800000u)                           // x < 2^-28
+        return x;
+    const float t = expm1fPos(x);
+    if (ix < 0x3f800000u)
+        return 0.5f*(2.0f*t - t*t/(t + 1.0f));
+    return 0.5f*(t + t/(t + 1.0f));
+}
+
 // ---- double precision (round 6): exp, log, erf as glibc 2.35 computes them on an x86-64 host with FMA3 -----------------------------------
 // media/AtmosphericMedium.cpp:113-122 inverts its optical depth in double: std::erf, std::exp, and -- inside Erf::erfInv -- std::log and std::sqrt.
 // exp and log are the "optimized routines" algorithms (e_exp.c, e_log.c; N = 128 tables) in their __ieee754_exp_fma / __ieee754_log_fma builds:

@@ -123,6 +123,7 @@ PT_DEV float atan2fH(float y, float x) { return ptlibm::atan2fCore(y, x); }
 PT_DEV float powfH(float x, float y) { return ptlibm::powInRange(x, y) ? ptlibm::powfCore(x, y) : powf(x, y); }
 PT_DEV float cbrtfH(float x) { return ptlibm::cbrtfCore(x); }
 PT_DEV float tanfH(float x) { return ptlibm::tanfCore(x); }      // |x| < 120 (OrenNayarBsdf: angles in [0, pi/2])
+PT_DEV float sinhfH(float x) { return ptlibm::sinhfCore(x); }    // 0 < x <= 10 (RoughWireBcsdf::M: 1/v with v >= 0.1), NaN outside
 
 PT_DEV f3 mk3(float x, float y, float z) { f3 r; r.x = x; r.y = y; r.z = z; return r; }
 PT_DEV f3 splat3(float s) { return mk3(s, s, s); }

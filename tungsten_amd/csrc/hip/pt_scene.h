@@ -616,6 +616,133 @@ PT_DEV f3 absorb(const TgHipBsdf &b, f3 f, float cosA, float cosB)
     return f;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The fibre BCSDFs (bsdfs/LambertianFiberBcsdf.cpp, bsdfs/RoughWireBcsdf.cpp): local y is the fibre's axis (the shading frame's bitangent
+// follows from the primitive's tangent space, shadingFrame), theta the angle to the plane across it, phi the azimuth around it.
+// Compiled where HAS_FIBRE(M) says so -- the all-features family -- and called from BsdfOps in FRONT of its switch: the two types have no bit in M
+// (pt_variants.h), and no case label is added to the switch the other families compile.
+// ---------------------------------------------------------------------------------------------
+#define LOBE_GLOSSY  (TGHIP_LOBE_GLOSSY_R | TGHIP_LOBE_GLOSSY_T)
+#define LOBE_DIFFUSE (TGHIP_LOBE_DIFFUSE_R | TGHIP_LOBE_DIFFUSE_T)
+// math/MathUtil.hpp:100-113 (its min / max are `a < b ? a : b` / `a > b ? a : b`)
+PT_DEV float trigInverse(float x)
+{
+    const float a = 1.0f - x*x;
+    const float r = sqrtf(a > 0.0f ? a : 0.0f);
+    return r < 1.0f ? r : 1.0f;
+}
+PT_DEV float trigHalfAngle(float x)
+{
+    const float a = x*0.5f + 0.5f;
+    const float r = sqrtf(a > 0.0f ? a : 0.0f);
+    return r < 1.0f ? r : 1.0f;
+}
+// LambertianFiberBcsdf::lambertianCylinder (:20-28): the closed-form far field of a Lambertian cylinder
+PT_DEV float lambertianCylinder(f3 wo)
+{
+    const float cosThetaO = trigInverse(wo.y);
+    float phi = atan2fH(wo.x, wo.z);
+    if (phi < 0.0f)
+        phi += PT_TWO_PI;
+    return cosThetaO*fabsf(((PT_PI - phi)*cosfH(phi) + sinfH(phi))*PT_INV_FOUR_PI);
+}
+// RoughWireBcsdf::I0 / logI0 / N / M / sampleM (:32-95)
+PT_DEV float wireI0(float x)
+{
+    float result = 1.0f;
+    const float xSq = x*x;
+    float xi = xSq;
+    float denom = 4.0f;
+#pragma unroll
+    for (int i = 1; i <= 10; ++i) {
+        result += xi/denom;
+        xi *= xSq;
+        denom *= 4.0f*float((i + 1)*(i + 1));
+    }
+    return result;
+}
+PT_DEV float wireLogI0(float x)
+{
+    if (x > 12.0f)
+        return x + 0.5f*(logfH(1.0f/(PT_TWO_PI*x)) + 1.0f/(8.0f*x));
+    return logfH(wireI0(x));
+}
+PT_DEV float wireN(float cosPhi) { return 0.25f*trigHalfAngle(cosPhi); }
+PT_DEV float wireM(float v, float sinThetaI, float sinThetaO, float cosThetaI, float cosThetaO)
+{
+    const float a = cosThetaI*cosThetaO/v;
+    const float b = sinThetaI*sinThetaO/v;
+    if (v < 0.1f)
+        return expfH(-b + wireLogI0(a) - 1.0f/v + 0.6931f + logfH(1.0f/(2.0f*v)));
+    return expfH(-b)*wireI0(a)/(2.0f*v*sinhfH(1.0f/v));       // (1/v in (0, 10]: sinhfH's domain)
+}
+PT_DEV float wireSampleM(float v, float sinThetaI, float cosThetaI, float xi1, float xi2)
+{
+    const float cosTheta = 1.0f + v*logfH(xi1 + (1.0f - xi1)*expfH(-2.0f/v));
+    const float sinTheta = trigInverse(cosTheta);
+    const float cosPhi = cosfH(PT_TWO_PI*xi2);
+    return -cosTheta*sinThetaI + sinTheta*cosPhi*cosThetaI;
+}
+PT_DEV bool isFibreBsdf(int type) { return type == TGHIP_BSDF_LAMBERTIAN_FIBER || type == TGHIP_BSDF_ROUGH_WIRE; }
+template<uint32_t M> PT_DEV f3 fibreEval(const DeviceScene &s, const TgHipBsdf &b, const Event &e)
+{
+    if (b.type == TGHIP_BSDF_LAMBERTIAN_FIBER) {               /* LambertianFiberBcsdf.cpp:37-42 */
+        if (!(e.requested & LOBE_DIFFUSE)) return splat3(0.0f);
+        return bsdfAlbedo<M>(s, b, e)*lambertianCylinder(e.wo);
+    }
+    /* RoughWireBcsdf.cpp:121-135; TgHipBsdf::thickness = _v */
+    if (!(e.requested & LOBE_GLOSSY) || e.wo.z == 0.0f) return splat3(0.0f);
+    const float sinThetaI = e.wi.y, sinThetaO = e.wo.y;
+    const float cosThetaI = trigInverse(sinThetaI), cosThetaO = trigInverse(sinThetaO);
+    const float cosPhi = e.wo.z/sqrtf(e.wo.x*e.wo.x + e.wo.z*e.wo.z);
+    const f3 attenuation = bsdfAlbedo<M>(s, b, e)*conductorReflectance(b.eta, b.k, trigHalfAngle(dot(e.wi, e.wo)));
+    return attenuation*wireN(cosPhi)*wireM(b.thickness, sinThetaI, sinThetaO, cosThetaI, cosThetaO);
+}
+template<uint32_t M> PT_DEV bool fibreSample(const DeviceScene &s, const TgHipBsdf &b, Event &e)
+{
+    if (b.type == TGHIP_BSDF_LAMBERTIAN_FIBER) {               /* LambertianFiberBcsdf.cpp:44-61 */
+        if (!(e.requested & LOBE_DIFFUSE)) return false;
+        const float h = RNG1D(*e.rng)*2.0f - 1.0f;
+        const float nx = h;
+        const float nz = trigInverse(nx);
+        const float xi0 = RNG1D(*e.rng), xi1 = RNG1D(*e.rng);
+        const f3 d = cosineHemisphere(xi0, xi1);
+        e.wo = mk3(d.z*nx + d.x*nz, d.y, d.z*nz - d.x*nx);
+        e.pdf = lambertianCylinder(e.wo);
+        e.weight = bsdfAlbedo<M>(s, b, e);
+        e.sampled = LOBE_DIFFUSE;
+        return true;
+    }
+    /* RoughWireBcsdf.cpp:137-157 */
+    if (!(e.requested & LOBE_GLOSSY)) return false;
+    const float xi1 = RNG1D(*e.rng);
+    const float xi2 = RNG1D(*e.rng), xi3 = RNG1D(*e.rng);
+    const float sinThetaI = e.wi.y;
+    const float cosThetaI = trigInverse(sinThetaI);
+    const float sinPhi = 2.0f*xi1 - 1.0f;
+    const float sinThetaO = wireSampleM(b.thickness, sinThetaI, cosThetaI, xi2, xi3);
+    const float cosPhi = trigInverse(sinPhi);
+    const float cosThetaO = trigInverse(sinThetaO);
+    e.wo = mk3(sinPhi*cosThetaO, sinThetaO, cosPhi*cosThetaO);
+    e.pdf = wireN(cosPhi)*wireM(b.thickness, sinThetaI, sinThetaO, cosThetaI, cosThetaO);
+    e.weight = bsdfAlbedo<M>(s, b, e)*conductorReflectance(b.eta, b.k, trigHalfAngle(dot(e.wi, e.wo)));
+    e.sampled = LOBE_GLOSSY;
+    return true;
+}
+PT_DEV float fibrePdf(const TgHipBsdf &b, const Event &e)
+{
+    if (b.type == TGHIP_BSDF_LAMBERTIAN_FIBER) {               /* LambertianFiberBcsdf.cpp:63-68 */
+        if (!(e.requested & LOBE_DIFFUSE)) return 0.0f;
+        return lambertianCylinder(e.wo);
+    }
+    /* RoughWireBcsdf.cpp:159-171 */
+    if (!(e.requested & LOBE_GLOSSY)) return 0.0f;
+    const float sinThetaI = e.wi.y, sinThetaO = e.wo.y;
+    const float cosThetaI = trigInverse(sinThetaI), cosThetaO = trigInverse(sinThetaO);
+    const float cosPhi = e.wo.z/sqrtf(e.wo.x*e.wo.x + e.wo.z*e.wo.z);
+    return wireN(cosPhi)*wireM(b.thickness, sinThetaI, sinThetaO, cosThetaI, cosThetaO);
+}
+
 template<int D, uint32_t M> struct BsdfOps;
 
 template<int D, uint32_t M>
@@ -625,6 +752,9 @@ struct BsdfOps {
     static __device__ f3 eval(const DeviceScene &s, int bi, const Event &e)
     {
         const TgHipBsdf &b = s.bsdfs[bi];
+        if constexpr (HAS_FIBRE(M)) {
+            if (isFibreBsdf(b.type)) return fibreEval<M>(s, b, e);
+        }
         switch (b.type) {
         case TGHIP_BSDF_LAMBERT: case TGHIP_BSDF_ERROR:        /* LambertBsdf.cpp:40-47 */
             if (!(M & (BSDF_BIT(TGHIP_BSDF_LAMBERT) | BSDF_BIT(TGHIP_BSDF_ERROR)))) return splat3(0.0f);
@@ -852,6 +982,9 @@ struct BsdfOps {
     static __device__ bool sample(const DeviceScene &s, int bi, Event &e)
     {
         const TgHipBsdf &b = s.bsdfs[bi];
+        if constexpr (HAS_FIBRE(M)) {
+            if (isFibreBsdf(b.type)) return fibreSample<M>(s, b, e);
+        }
         switch (b.type) {
         case TGHIP_BSDF_LAMBERT: case TGHIP_BSDF_ERROR: {      /* LambertBsdf.cpp:27-38 */
             if (!(M & (BSDF_BIT(TGHIP_BSDF_LAMBERT) | BSDF_BIT(TGHIP_BSDF_ERROR)))) return false;
@@ -1224,6 +1357,9 @@ struct BsdfOps {
     static __device__ float pdf(const DeviceScene &s, int bi, const Event &e)
     {
         const TgHipBsdf &b = s.bsdfs[bi];
+        if constexpr (HAS_FIBRE(M)) {
+            if (isFibreBsdf(b.type)) return fibrePdf(b, e);
+        }
         switch (b.type) {
         case TGHIP_BSDF_LAMBERT: case TGHIP_BSDF_ERROR:        /* LambertBsdf.cpp:61-68 */
             if (!(M & (BSDF_BIT(TGHIP_BSDF_LAMBERT) | BSDF_BIT(TGHIP_BSDF_ERROR)))) return 0.0f;
@@ -1674,12 +1810,25 @@ PT_DEV void cylinderSurface(const TgHipObject &o, const RayD &ray, float t, floa
 }
 
 /* normal and uv of a point on a cube / sphere (Cube.cpp:157-170, Sphere.cpp:120-129) */
+// REF_TIES: Vec::maxDim (math/Vec.hpp:369-380) to the letter -- the first of equal components wins.  A hit point that lies on two faces at once, to the
+// bit, is what the fibre BCSDFs make: rough_wire samples wo exactly along the cube's tangent when cosThetaO is 0, the ray runs IN the face it starts on and
+// leaves the cube through an edge, where |p| - scale is 0 on two axes.  The selection below the `else` gives such a tie to the LAST of the equal components;
+// it stays in every family whose instructions this header must not change and is exact wherever the components differ (the all-features family, the one
+// that renders fibres, takes the reference's rule: intersectionInfo / lightIntersect pass HAS_FIBRE(M)).
+template<bool REF_TIES = false>
 PT_DEV void cubeSurface(const TgHipObject &o, f3 hp, f3 &n, float &u, float &v)
 {
     f3 p = mat3TMul(o.rot, hp - ld3(o.pos));
     float pa[3] = {p.x, p.y, p.z};
     float ex[3] = {fabsf(p.x) - o.scale[0], fabsf(p.y) - o.scale[1], fabsf(p.z) - o.scale[2]};
-    int dim = ex[0] > ex[1] ? (ex[0] > ex[2] ? 0 : 2) : (ex[1] > ex[2] ? 1 : 2);
+    int dim;
+    if constexpr (REF_TIES) {
+        dim = 0;
+        if (ex[1] > ex[dim]) dim = 1;
+        if (ex[2] > ex[dim]) dim = 2;
+    } else {
+        dim = ex[0] > ex[1] ? (ex[0] > ex[2] ? 0 : 2) : (ex[1] > ex[2] ? 1 : 2);
+    }
     float nn[3] = {0.0f, 0.0f, 0.0f};
     nn[dim] = pa[dim] < 0.0f ? -1.0f : 1.0f;
     float uvw[3];
@@ -1869,7 +2018,7 @@ PT_DEV void intersectionInfo(const DeviceScene &s, const RayD &ray, float4 hit, 
             }
         }
     } else if (!(M & FEAT_SOLIDS) || kind == TGHIP_REC_CUBE) {   /* Cube.cpp:157-170 */
-        cubeSurface(o, info.p, info.Ng, info.u, info.v);
+        cubeSurface<HAS_FIBRE(M)>(o, info.p, info.Ng, info.u, info.v);
         info.Ns = info.Ng;
         info.bsdf = o.bsdf;
         info.backSide = hit.y != 0.0f;
@@ -1939,24 +2088,34 @@ PT_DEV void textureDerivatives(const DeviceScene &s, int texIdx, float u0, float
 }
 
 // Primitive::setupTangentFrame (primitives/Primitive.cpp:125-163): the frame of the shading normal -- unless the bsdf carries a non-constant
-// bump map (TgHipBsdf::bump1; FEAT_BUMP variants): then tangent and bitangent come from the primitive's tangent space, tilted by the map's
-// derivatives.  (Anisotropic lobes, the other reason for the long way, belong to the hair bcsdfs.)
+// bump map (TgHipBsdf::bump1; FEAT_BUMP variants) or its lobes are anisotropic (TGHIP_LOBE_ANISOTROPIC: the fibre BCSDFs and what wraps them;
+// HAS_FIBRE variants): then tangent and bitangent come from the primitive's tangent space -- tilted by the map's derivatives where there is a map.
+// Every way back to the normal's own frame is the reference's: no tangent space (:135-138), a bumped normal of length zero (:146-149), a tangent
+// that vanishes once projected off the normal (:155-158).
 template<uint32_t M>
 PT_DEV Frame shadingFrame(const DeviceScene &s, const Info &info)
 {
     if constexpr ((M & FEAT_BUMP) != 0u) {
         const int bump = s.bsdfs[info.bsdf].bump1 - 1;
-        if (bump >= 0 && info.hasTB) {
+        bool anisotropic = false;
+        if constexpr (HAS_FIBRE(M)) anisotropic = (s.bsdfs[info.bsdf].lobes & TGHIP_LOBE_ANISOTROPIC) != 0u;
+        if ((bump >= 0 || anisotropic) && info.hasTB) {
             f3 T = info.T, B = info.B, N = info.Ns;
-            float du, dv;
-            textureDerivatives(s, bump, info.u, info.v, du, dv);
-            T = T + info.Ns*(du - dot(info.Ns, T));
-            B = B + info.Ns*(dv - dot(info.Ns, B));
-            N = cross(T, B);
-            if (!(N.x == 0.0f && N.y == 0.0f && N.z == 0.0f)) {
-                if (dot(N, info.Ns) < 0.0f)
-                    N = -N;
-                N = normalized(N);
+            bool valid = true;
+            if (bump >= 0) {
+                float du, dv;
+                textureDerivatives(s, bump, info.u, info.v, du, dv);
+                T = T + info.Ns*(du - dot(info.Ns, T));
+                B = B + info.Ns*(dv - dot(info.Ns, B));
+                N = cross(T, B);
+                valid = !(N.x == 0.0f && N.y == 0.0f && N.z == 0.0f);
+                if (valid) {
+                    if (dot(N, info.Ns) < 0.0f)
+                        N = -N;
+                    N = normalized(N);
+                }
+            }
+            if (valid) {
                 T = T - N*dot(N, T);
                 if (!(T.x == 0.0f && T.y == 0.0f && T.z == 0.0f)) {
                     Frame f;
@@ -2009,7 +2168,7 @@ PT_DEV bool lightIntersect(const DeviceScene &s, int objIdx, const RayD &ray, Li
     }
     if ((M & FEAT_SOLIDS) && o.type == TGHIP_OBJ_CUBE) {       /* Cube::intersect + intersectionInfo */
         if (!cubeTest(&o, ray, ray.tmax, lh.t, lh.backSide)) return false;
-        cubeSurface(o, ray.o + ray.d*lh.t, lh.n, lh.u, lh.v);
+        cubeSurface<HAS_FIBRE(M)>(o, ray.o + ray.d*lh.t, lh.n, lh.u, lh.v);
         return true;
     }
     if ((M & FEAT_CYLINDER) && o.type == TGHIP_OBJ_CYLINDER) {   /* Cylinder::intersect + intersectionInfo */

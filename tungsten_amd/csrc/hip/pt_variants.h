@@ -43,6 +43,11 @@
 #define FEAT_FAMILY_ALL (FEAT_MEDIA | FEAT_AUX | FEAT_CYLINDER | FEAT_BUMP)
 #define HAS_PROCTEX(M)  ((((M) & FEAT_FAMILY_ALL)) == FEAT_FAMILY_ALL)
 #define MASK_ALL_NO_PROCTEX (BSDF_MASK_ALL & ~FEAT_AUX)
+// The two fibre BCSDFs (TGHIP_BSDF_LAMBERTIAN_FIBER = 19, TGHIP_BSDF_ROUGH_WIRE = 20) live by the same rule: bits 19 and 20 of M are FEAT_PHONG and FEAT_BUMP, so
+// BSDF_BIT is never formed for them; their code, and the shading frame from a primitive's tangent space that their anisotropic lobes ask for, is compiled
+// only where the marker is set, and a scene that holds one is shaded by that family throughout and keeps the loop to the end, as TYPES_LATE scenes do
+// (SceneCheck.hpp: haveFibre).  MASK_ALL_NO_PROCTEX has neither.
+#define HAS_FIBRE(M)    HAS_PROCTEX(M)
 
 // BSDF type sets of the shading-kernel variants (pt_scene.h BsdfOps<D, M>)
 #define TYPES_SIMPLE (BSDF_BIT(TGHIP_BSDF_LAMBERT) | BSDF_BIT(TGHIP_BSDF_NULL) | BSDF_BIT(TGHIP_BSDF_ERROR))

@@ -661,7 +661,7 @@ static void chooseThreads(tghip_ctx *ctx)
         ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false>, 256, 3);
     else if (!flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && dyn)
         ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_dyn<false, true>, 256, 2) : pickThreads(ctx, k_trace_shadow_dyn<false, false>, 256, 2);   // measured: 192 / 256 / 320 / 384 threads = 525 / 462 / 633 / 619 us per launch
-    else if (ctx->sc.haveProcTex && (ctx->sc.haveForward || ctx->sc.haveMeshLight))
+    else if ((ctx->sc.haveProcTex || ctx->sc.haveFibre) && (ctx->sc.haveForward || ctx->sc.haveMeshLight))   // (launchShadow's choice)
         ctx->thrShadow = inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>, 512, 1))
                               : flat ? pickThreads(ctx, k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>, 512, 1);
     else if (inst)
@@ -1154,7 +1154,7 @@ static bool launchShadow(tghip_ctx *ctx, int grid, const PathState &st, const Pa
     const bool flat = isFlat(ctx);
     const bool closestWalk = ctx->sc.haveForward || ctx->sc.haveMeshLight;   // shadow rays are closest-hit walks, not any-hit queries
     const bool wideShadow = wideShadowRays(ctx) && !closestWalk && !ctx->auxPass;
-    if (ctx->sc.haveProcTex && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels)
+    if ((ctx->sc.haveProcTex || ctx->sc.haveFibre) && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels; haveFibre: the one family with the fibre BCSDFs)
 #define SHADOW_TEX(FLAT, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, true, FLAT, I, BSDF_MASK_ALL>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
         if (ctx->sc.haveInstances) { if (ctx->sc.haveSolids) SHADOW_TEX(false, 1); else SHADOW_TEX(false, 2); }
         else if (flat) SHADOW_TEX(true, 0);
@@ -2064,6 +2064,7 @@ __global__ void k_debug_libm(int fn, const float *x, float *y, uint32_t n)
     case TGHIP_LIBM_EXPF: r = expfH(v); break;
     case TGHIP_LIBM_SINCOS_SIN: sincosfH(v, s, c); r = s; break;
     case TGHIP_LIBM_SINCOS_COS: sincosfH(v, s, c); r = c; break;
+    case TGHIP_LIBM_SINHF: r = sinhfH(v); break;
     default: r = acosfExact(v); break;
     }
     y[i] = r;
@@ -2082,10 +2083,10 @@ int tghip_debug_libm(tghip_ctx *ctx, int fn, const float *x, float *y, size_t n)
 {
     if (!ctx) return TGHIP_E_INVALID;
     if (n == 0) return TGHIP_OK;
-    if (!x || !y || n > 0x3FFFFFFFu || fn < TGHIP_LIBM_SINF || fn > TGHIP_LIBM_SQRTD) { ctx->error = "invalid libm self-test arguments"; return TGHIP_E_INVALID; }
+    if (!x || !y || n > 0x3FFFFFFFu || fn < TGHIP_LIBM_SINF || fn > TGHIP_LIBM_SINHF) { ctx->error = "invalid libm self-test arguments"; return TGHIP_E_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float *dx = nullptr, *dy = nullptr;
-    const bool dbl = fn >= TGHIP_LIBM_EXPD;                       // n doubles in, n doubles out
+    const bool dbl = fn >= TGHIP_LIBM_EXPD && fn <= TGHIP_LIBM_SQRTD;   // n doubles in, n doubles out
     const size_t nx = (fn == TGHIP_LIBM_ATAN2F || fn == TGHIP_LIBM_POWF || dbl) ? 2*n : n, ny = dbl ? 2*n : n;
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dx), nx*sizeof(float)));
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&dy), ny*sizeof(float));

@@ -12,6 +12,7 @@
 namespace tungsten_amd {
 
 static const float PI          = 3.1415926536f;
+static const float PI_HALF     = PI*0.5f;
 static const float TWO_PI      = PI*2.0f;
 static const float INV_PI      = 1.0f/PI;
 static const float INV_TWO_PI  = 0.5f*INV_PI;

@@ -607,7 +607,7 @@ void Bsdf::prepareForRender()
     if (sub0) sub0->prepareForRender();
     if (sub1) sub1->prepareForRender();
 
-    enum { GR = 1, GT = 2, DR = 4, DT = 8, SR = 16, ST = 32, FWD = 128 };
+    enum { GR = 1, GT = 2, DR = 4, DT = 8, SR = 16, ST = 32, ANISO = 64, FWD = 128 };
     switch (type) {
     case Lambert:         lobes = DR; break;
     case Null:            lobes = 0; break;
@@ -653,6 +653,13 @@ void Bsdf::prepareForRender()
         avgTransmittance = std::exp(-2.0f*scaledSigmaA.avg());
         lobes = GR | sub0->lobes;
         break;
+    case LambertianFiber: lobes = DR | DT | ANISO; break;   // LambertianFiberBcsdf.cpp:12-15: DiffuseLobe | AnisotropicLobe
+    case RoughWire: {     // RoughWireBcsdf.cpp:17-25 (GlossyLobe | AnisotropicLobe), :171-174: _v = sqr(_roughness*PI_HALF); TgHipBsdf::thickness
+        lobes = GR | GT | ANISO;
+        const float beta = wireRoughness*PI_HALF;
+        thickness = beta*beta;
+        break;
+    }
     }
 }
 
@@ -865,6 +872,17 @@ std::shared_ptr<Bsdf> Scene::instantiateBsdf(const JsonValue &v) const
             b->sub0->albedo = constantTexture(1.0f);
             b->sub0->roughness = constantTexture(0.1f);
         }
+    } else if (type == "lambertian_fiber") {       // LambertianFiberBcsdf.cpp (no fromJson of its own)
+        b->type = Bsdf::LambertianFiber;
+    } else if (type == "rough_wire") {             // RoughWireBcsdf.cpp:97-105
+        b->type = Bsdf::RoughWire;
+        v.getField("roughness", b->wireRoughness);
+        // (`eta` is kept even where `k` is missing, and `k` is not looked at without `eta`: the && of :101.  Without either and without a
+        // material the constructor's Cu stands, Scene.hpp: the defaults of Bsdf::eta / k)
+        if (getVec3(v, "eta", b->eta)) getVec3(v, "k", b->k);
+        std::string material;
+        if (v.getField("material", material) && !lookupComplexIor(material, b->eta, b->k))
+            throw JsonLoadException("Unable to find material with name '" + material + "'");
     } else if (type == "transparency") {
         b->type = Bsdf::Transparency;
         if (const JsonValue &base = v["base"]) b->sub0 = fetchBsdf(base);

@@ -64,7 +64,8 @@ struct Bsdf
 {
     enum Type { Lambert = 0, Null = 1, RoughConductor = 2, SmoothCoat = 3, Dielectric = 4, RoughDielectric = 5,
                 Mirror = 6, Conductor = 7, Plastic = 8, RoughPlastic = 9, Mixed = 10, Transparency = 11,
-                Forward = 12, Error = 13, DiffuseTransmission = 14, Phong = 15, ThinSheet = 16, OrenNayar = 17, RoughCoat = 18 };
+                Forward = 12, Error = 13, DiffuseTransmission = 14, Phong = 15, ThinSheet = 16, OrenNayar = 17, RoughCoat = 18,
+                LambertianFiber = 19, RoughWire = 20 };
     std::string name;
     Type type = Lambert;
     unsigned lobes = 0;
@@ -78,6 +79,7 @@ struct Bsdf
     Vec3f sigmaA = Vec3f(0.0f), scaledSigmaA = Vec3f(0.0f);
     float avgTransmittance = 1.0f, diffuseFresnel = 0.0f;
     float exponent = 64.0f, diffuseRatio = 0.2f;   // PhongBsdf (PhongBsdf.hpp: defaults of its constructor)
+    float wireRoughness = 0.1f;                 // RoughWireBcsdf::_roughness, a plain float (RoughWireBcsdf.cpp:17-25, 100); prepareForRender leaves _v in `thickness`
     bool prepared = false;
 
     bool unnamed() const { return name.empty(); }

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <utility>
 
+static bool isFibre(int32_t type) { return type == TGHIP_BSDF_LAMBERTIAN_FIBER || type == TGHIP_BSDF_ROUGH_WIRE; }
 static bool nestsOne(int32_t type) { return type == TGHIP_BSDF_SMOOTH_COAT || type == TGHIP_BSDF_ROUGH_COAT || type == TGHIP_BSDF_TRANSPARENCY; }
 
 int bsdfDepth(const TgHipSceneDesc *s, int bi, int depth)
@@ -23,7 +24,9 @@ uint32_t bsdfTypeMask(const TgHipSceneDesc *s, int bi, int depth)
 {
     if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return 0;
     const TgHipBsdf &b = s->bsdfs[bi];
-    uint32_t m = b.type >= 0 && b.type < 32 ? 1u << uint32_t(b.type) : 0u;   // (a type no word has a bit for is a type no kernel shades)
+    // (a type no word has a bit for is a type no kernel shades -- but for the two fibre BCSDFs, types 19 and 20, whose bits are FEAT_PHONG and FEAT_BUMP:
+    // they leave no bit here, and checkScene marks every material of a scene that holds one with FEAT_FAMILY_ALL, bsdfHasFibre)
+    uint32_t m = b.type >= 0 && b.type < 32 && !isFibre(b.type) ? BSDF_BIT(uint32_t(b.type)) : 0u;
     if ((b.type == TGHIP_BSDF_ROUGH_CONDUCTOR || b.type == TGHIP_BSDF_ROUGH_DIELECTRIC || b.type == TGHIP_BSDF_ROUGH_PLASTIC || b.type == TGHIP_BSDF_ROUGH_COAT) &&
         b.distribution == TGHIP_DIST_PHONG)
         m |= FEAT_PHONG;                     // outside every family mask: such a material is shaded by the full variant (pt_scene.h: mfDist)
@@ -32,6 +35,18 @@ uint32_t bsdfTypeMask(const TgHipSceneDesc *s, int bi, int depth)
     if (b.type == TGHIP_BSDF_MIXED)
         m |= bsdfTypeMask(s, b.sub0, depth + 1) | bsdfTypeMask(s, b.sub1, depth + 1);
     return m;
+}
+
+bool bsdfHasFibre(const TgHipSceneDesc *s, int bi, int depth)
+{
+    if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return false;
+    const TgHipBsdf &b = s->bsdfs[bi];
+    if (isFibre(b.type)) return true;
+    if (nestsOne(b.type))
+        return bsdfHasFibre(s, b.sub0, depth + 1);
+    if (b.type == TGHIP_BSDF_MIXED)
+        return bsdfHasFibre(s, b.sub0, depth + 1) || bsdfHasFibre(s, b.sub1, depth + 1);
+    return false;
 }
 
 bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
@@ -331,8 +346,10 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
     for (uint32_t i = 0; i < sd->num_bsdfs; ++i) {
         if (sd->bsdfs[i].bump1 < 0 || uint32_t(sd->bsdfs[i].bump1) > sd->num_textures) return fail(TGHIP_E_INVALID, "bsdf bump map index out of range");
         if (sd->bsdfs[i].bump1 > 0) t.allFeaturesShading = true;      // (shaded by the same one variant)
+        // a fibre BCSDF anywhere, nested or not referred to at all: the table is what the kernels index
+        if (isFibre(sd->bsdfs[i].type)) t.haveFibre = true;
     }
-    if (t.haveProcTex) t.allFeaturesShading = true;                    // (that variant again: the only one that evaluates them, pt_variants.h HAS_PROCTEX)
+    if (t.haveProcTex || t.haveFibre) t.allFeaturesShading = true;     // (that variant again: the only one that evaluates them, pt_variants.h HAS_PROCTEX)
     t.haveMedia = sd->num_media > 0;
     if (t.haveMedia) {
         if (!sd->media || sd->num_media > PT_MAX_MEDIA) return fail(TGHIP_E_UNSUPPORTED, "more than 126 media are not supported");
@@ -385,7 +402,8 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
         typeMask[i] = bsdfTypeMask(sd, int(i), 0);
         // (FEAT_FAMILY_ALL: the scene holds a `disk` or `blade` texture -- or samples a checkered environment --, so every material of it is shaded by the all-features family -- no other
         // family covers the entry)
-        t.bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u) | (t.haveProcTex ? FEAT_FAMILY_ALL : 0u);
+        // (the same marker for a scene that holds a fibre BCSDF: types 19 and 20 have no bit in the word)
+        t.bsdfTypes[i] = typeMask[i] | (bsdfUsesBitmap(sd, int(i), 0) ? FEAT_BITMAP : 0u) | ((t.haveProcTex || t.haveFibre) ? FEAT_FAMILY_ALL : 0u);
         t.bsdfForward[i] = (sd->bsdfs[i].lobes & TGHIP_LOBE_FORWARD) ? 1 : 0;
         if (t.bsdfForward[i]) t.haveForward = true;
     }
@@ -399,7 +417,8 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
         const int bi = kind == TGHIP_REC_TRIANGLE ? sd->tri_attrs[i].bsdf : sd->objects[TGHIP_REC_OBJECT(meta)].bsdf;
         if (bi < 0 || uint32_t(bi) >= sd->num_bsdfs) return fail(TGHIP_E_INVALID, "primitive record without a valid bsdf");
         // the smallest family that covers every type inside the material (nested ones included); forward lobes -> "everything else"
-        const uint32_t tm = typeMask[size_t(bi)];
+        // (a material with a fibre BCSDF inside carries the all-features marker instead of a type bit: no smaller family covers it -- class 3)
+        const uint32_t tm = typeMask[size_t(bi)] | (t.haveFibre && bsdfHasFibre(sd, bi, 0) ? FEAT_FAMILY_ALL : 0u);
         const bool fwd = t.bsdfForward[size_t(bi)] != 0;
         const int c = familyCovers(TGHIP_BSDF_VARIANT_SIMPLE, tm, fwd) ? 0 : familyCovers(TGHIP_BSDF_VARIANT_COAT, tm, fwd) ? 1 :
                       familyCovers(TGHIP_BSDF_VARIANT_GLASS, tm, fwd) ? 2 : 3;

@@ -29,7 +29,7 @@ struct SceneTraits {
     uint32_t classMask[PT_NUM_CLASSES] = {0, 0, 0, 0};                  // ... and the BSDF types inside each
     bool haveForward = false;             // some BSDF has a forward lobe (shadow rays attenuate instead of stop) -- or the scene has media: shadow rays pick up
                                           // transmittance segment by segment (the closest-hit shadow walk)
-    std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex (tghip_debug_bsdf_info)
+    std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex or haveFibre (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
@@ -43,6 +43,8 @@ struct SceneTraits {
     bool haveProcTex = false;             // a `disk` or `blade` texture (TGHIP_TEX_DISK / _BLADE), or a sampled infinite sphere whose emission is a checker (its sample / pdf):
                                           // evaluated by the all-features family only -- sets allFeaturesShading (BSDF_MASK_ALL
                                           // shading, never fused, no k_tail) and sends a closest-hit shadow walk to k_trace_shadow<., true, ., ., BSDF_MASK_ALL>
+    bool haveFibre = false;               // a fibre BCSDF (TGHIP_BSDF_LAMBERTIAN_FIBER / _ROUGH_WIRE) in the bsdf table: compiled where disk's and blade's code is, so it steers
+                                          // exactly where haveProcTex steers (allFeaturesShading, the closest-hit shadow walk's BSDF_MASK_ALL instantiation)
     bool haveMedia = false;               // participating media: BSDF_MASK_ALL shading (the only FEAT_MEDIA variant), closest-hit shadow walk, never fused
     bool mediaSimple = false;             // a media scene whose surface BSDFs MASK_MEDIA covers (no instances, no mesh emitters)
     bool haveInstances = false;           // instance records: two-level traversal kernels (INST), MASK_FULL shading, never the flat list
@@ -76,6 +78,7 @@ int bsdfDepth(const TgHipSceneDesc *s, int bi, int depth);
 uint32_t bsdfTypeMask(const TgHipSceneDesc *s, int bi, int depth);
 // does a texture inside bsdf `bi` (nested ones included) hold a bitmap?
 bool bsdfUsesBitmap(const TgHipSceneDesc *s, int bi, int depth);
+bool bsdfHasFibre(const TgHipSceneDesc *s, int bi, int depth);   // a fibre BCSDF inside the material (bsdfTypeMask has no bit for the two types)
 // May shading family `variant` (TGHIP_BSDF_VARIANT_*) be given a material with type set `tm` (bsdfTypeMask) and forward lobe `fwd`?  The one
 // statement of the rules the upload and the launch plan apply to type sets (they call it on a material's set or on the union over a class / the scene):
 // the shading classes 0 / 1 / 2 (SIMPLE / COAT / GLASS) take materials without a forward lobe whose types their mask covers, in that order; what is left

@@ -511,7 +511,7 @@ int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out, char *e
                                  t.bvhDepth, t.bvhMasterDepth, t.wideDepth, t.wideMasterDepth,
                                  {t.classPresent[0], t.classPresent[1], t.classPresent[2], t.classPresent[3]},
                                  {t.classMask[0], t.classMask[1], t.classMask[2], t.classMask[3]}, t.complexMask,
-                                 t.hoisted.record, t.env_tex};
+                                 t.hoisted.record, t.env_tex, t.haveFibre};
     }
     return TGHIP_OK;
 }
