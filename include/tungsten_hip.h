@@ -26,6 +26,8 @@
  *                              the device's restatements evaluated on the device, for the parity tests.
  *   tghip_debug_bsdf / tghip_debug_bsdf_info <- Bsdf::eval / pdf / sample (bsdfs/Bsdf.hpp:71-97) of single scatter events: the shading kernels'
  *                              BSDF code on caller-supplied cases, per shading family, for the parity tests.
+ *   tghip_debug_light / tghip_debug_light_info <- TraceBase::chooseLight (integrators/TraceBase.cpp:416-459) and Primitive::sampleDirect / approximateRadiance /
+ *                              intersect + intersectionInfo / evalDirect / directPdf of single calls: the shading kernels' light code, the same way.
  *
  * Ownership: the caller owns every host array (borrowed for the duration of the call; the
  * shim copies with hipMemcpyAsync); the shim owns device memory behind the opaque handle.
@@ -677,6 +679,42 @@ int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult
  * those two types have no bit of their own, bits 19 and 20 being the Phong and the bump feature), forward = 1 when it has a forward lobe, covered = 1 when family `variant` is allowed to shade it by the rule that sorts
  * materials into shading classes and picks each class's kernel.  variant_mask (one word): the type / feature mask the variant's kernel is compiled for. */
 int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint32_t *forward, uint32_t *covered, uint32_t *variant_mask);
+/* Self-test of the device's light code (csrc/hip/pt_scene.h: chooseLight / lightSampleDirect / lightApproximateRadiance / lightIntersect / lightEvalDirect /
+ * lightDirectPdf) on caller-supplied cases against the uploaded scene, one thread per case (csrc/hip/debug_units.hip), host pointers; the calls are made
+ * as the shading kernels' next-event estimation makes them, under the feature mask of family `variant` (no Sobol' sampler).  Per case:
+ *   choose   chooseLight(p) drawing from the stream (seed, stream, 0): the chosen OBJECT index (-1: none), its weight, and the stream's next number;
+ *   sample   lightSampleDirect of the light in slot `light` from p, drawing from the stream (seed, stream, 1): ok, d, dist, pdf, the stream's next number;
+ *   approx   lightApproximateRadiance of that light at p;
+ *   hit      lightIntersect with the ray (p, w, tmin 5e-4, tmax inf): hit, t, u, v, back_side and, where it hits, lightEvalDirect and lightDirectPdf.
+ * A mesh emitter is never intersected here (its hit leg belongs to the shadow kernel): hit = 0.  Neither is a point light, whose shadow ray ends at the
+ * sampled distance: hit = 0, and direct_pdf is lightDirectPdf with the hit record the shading kernel builds there (t = the sampled dist).
+ * Outputs behind a failed choose / sample / intersect are unspecified.  TGHIP_E_INVALID (context left usable) for null pointers with n > 0, a light slot
+ * outside TgHipSceneDesc::lights, an unknown variant, or no scene; n == 0 succeeds. */
+typedef struct TgHipLightCase {
+    int32_t  light;           /* slot in TgHipSceneDesc::lights */
+    uint32_t variant;         /* TGHIP_BSDF_VARIANT_* */
+    float    p[3], w[3];      /* the shading point; a unit direction */
+    uint32_t seed, stream;    /* the samplers: rngStart(seed, stream, 0) and (seed, stream, 1) */
+} TgHipLightCase;             /* 40 B */
+typedef struct TgHipLightResult {
+    int32_t  chosen;          /* object index of the chosen light, -1 = none */
+    float    choose_weight;
+    uint32_t sample_ok;
+    float    d[3], dist, pdf;
+    float    approx;
+    uint32_t hit;
+    float    t, u, v;
+    uint32_t back_side;
+    float    emission[3], direct_pdf;
+    float    choose_next, sample_next;   /* the two streams' next numbers after the calls returned */
+    uint32_t reserved[4];
+} TgHipLightResult;           /* 96 B */
+int tghip_debug_light(tghip_ctx *ctx, const TgHipLightCase *cases, TgHipLightResult *results, size_t n);
+/* What the light code of family `variant` needs of the uploaded scene's sampled lights (num_lights entries each; any pointer may be NULL): needs = the
+ * feature bits the branches of the light's emitter type sit behind in csrc/hip/pt_scene.h and the shading kernels (csrc/host/SceneCheck.cpp: lightNeeds;
+ * the bits are those of csrc/hip/pt_variants.h: FEAT_SOLIDS, FEAT_INFINITE, FEAT_BITMAP, FEAT_MESHLIGHT, FEAT_CYLINDER, the four bits of FEAT_FAMILY_ALL
+ * together, FEAT_MULTILIGHT), covered = 1 when the variant's mask holds them all.  variant_mask (one word): the mask the variant's kernel is compiled for. */
+int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
 int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "count_traversal", "max_slots", ...; "top_tree" = 0 before an upload:
                                                                              TgHipSceneDesc::top_nodes is ignored, flat lists are walked in record order.
                                                                              Instrumentation that never changes an image (tests hold that): "lds_tables" = 0

@@ -184,6 +184,10 @@ typedef struct TgHostSceneTraits {
     int32_t  have_fibre;      /* the bsdf table holds a fibre BCSDF (TGHIP_BSDF_LAMBERTIAN_FIBER / _ROUGH_WIRE): steers where have_proc_tex steers */
 } TgHostSceneTraits;
 int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may be NULL */, char *err, size_t errlen);
+/* What tghip_debug_light_info answers (tungsten_hip.h), on its own, no device: per slot of scene->lights the feature bits the light's code needs
+ * (csrc/host/SceneCheck.cpp: lightNeeds) and whether the mask of shading family `variant` (TGHIP_BSDF_VARIANT_*, without the Sobol' sampler's bit) holds
+ * them; variant_mask: that mask.  Any output pointer may be NULL.  TGHIP_E_INVALID for no scene, an unknown variant or a description tgh_scene_check refuses. */
+int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
 
 /* What tghip_render_pass and tghip_wait decide about a pass before they touch the device (csrc/host/PassPlan.cpp), on its own, no device: the plan of
  * `pass` for a width x height image under the options "max_items", "max_slots" and "chunk_samples" -- or NULL, in *rc (may be NULL) the refusal's code

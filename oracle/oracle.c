@@ -230,6 +230,80 @@ static v3 bitmap_texel(const TgHipSceneDesc *s, const TgHipTexture *t, int x, in
     }
 }
 
+/* DiskTexture::operator[] / pdf (textures/DiskTexture.cpp:51-54, 75-78) and BladeTexture::operator[] / pdf (textures/BladeTexture.cpp:73-87, 125-138):
+ * is uv inside the disk / the polygon?  The blade's parameters where the flattened texture carries them (include/tungsten_hip.h: TGHIP_TEX_BLADE). */
+static int disk_tex_inside(float u, float v)
+{
+    float du = u - 0.5f, dv = v - 0.5f;
+    return du*du + dv*dv < 0.25f;
+}
+static int blade_tex_inside(const TgHipTexture *t, float u, float v)
+{
+    if (u + v == 0.0f)
+        return 1;
+    const float angle = t->scale, bladeAngle = t->on_color[0];
+    float gx = u*2.0f - 1.0f, gy = v*2.0f - 1.0f;
+    float phi = atan2f(gy, gx) - angle;
+    phi = -(floorf(phi/bladeAngle)*bladeAngle + angle);
+    float sinPhi = sinf(phi), cosPhi = cosf(phi);
+    float lx = gx*cosPhi - gy*sinPhi, ly = gy*cosPhi + gx*sinPhi;
+    return !(t->off_color[0]*(lx - 1.0f) + t->off_color[1]*(ly - 0.0f) > 0.0f);
+}
+/* Texture::sample / pdf (MAP_SPHERICAL; the jacobian is ignored) of the disk (DiskTexture.cpp:70-78), the blade (BladeTexture.cpp:103-138) and the
+ * checker (CheckerTexture.cpp:85-123): what a sampled infinite sphere draws its direction with (InfiniteSphere.cpp:161-176, 218-229) */
+static void proc_tex_sample(const TgHipTexture *t, float xi0, float xi1, float *u, float *v)
+{
+    if (t->type == TGHIP_TEX_DISK) {
+        float phi = xi0*O_TWO_PI, r = sqrtf(xi1);        /* SampleWarp::uniformDisk */
+        *u = cosf(phi)*r*0.5f + 0.5f; *v = sinf(phi)*r*0.5f + 0.5f;
+        return;
+    }
+    if (t->type == TGHIP_TEX_BLADE) {
+        float bu = xi0*(float)t->res_u;
+        int blade = (int)bu;
+        bu -= (float)blade;
+        float phi = t->scale + (float)blade*t->on_color[0];
+        float sinPhi = sinf(phi), cosPhi = cosf(phi);
+        float uSqrt = sqrtf(bu);
+        float alpha = 1.0f - uSqrt, beta = (1.0f - xi1)*uSqrt;
+        float lx = (1.0f + t->off_color[2])*beta + (1.0f - alpha - beta), ly = t->pad*beta;
+        *u = (lx*cosPhi - ly*sinPhi)*0.5f + 0.5f; *v = (ly*cosPhi + lx*sinPhi)*0.5f + 0.5f;
+        return;
+    }
+    /* checker */
+    const float onWeight = vmax3(ld3(t->on_color)), offWeight = vmax3(ld3(t->off_color));
+    *u = xi0; *v = xi1;
+    if (onWeight + offWeight == 0.0f)
+        return;
+    const float onProb = onWeight/(onWeight + offWeight);
+    int rowOffset;
+    if (*u < onProb) {
+        *u = xi0/onProb;
+        rowOffset = ((int)(*u*(float)t->res_u) + 1) & 1;
+    } else {
+        *u = (xi0 - onProb)/(1.0f - onProb);
+        rowOffset = (int)(*u*(float)t->res_u) & 1;
+    }
+    const int numVCells = (t->res_v + 1 - rowOffset)/2;
+    const float scaledV = *v*(float)numVCells;
+    const int onCell = (int)scaledV;
+    const float vBase = (float)(onCell*2 + rowOffset)/(float)t->res_v;
+    *v = vBase + (scaledV - (float)onCell)/(float)t->res_v;
+}
+static float proc_tex_pdf(const TgHipTexture *t, float u, float v)
+{
+    if (t->type == TGHIP_TEX_DISK)
+        return disk_tex_inside(u, v) ? O_INV_PI*4.0f : 0.0f;
+    if (t->type == TGHIP_TEX_BLADE)
+        return blade_tex_inside(t, u, v) ? t->on_color[2] : 0.0f;
+    const float onWeight = vmax3(ld3(t->on_color)), offWeight = vmax3(ld3(t->off_color));
+    if (onWeight + offWeight == 0.0f)
+        return 1.0f;
+    const int ui = (int)(u*(float)t->res_u), vi = (int)(v*(float)t->res_v);
+    return (((ui ^ vi) & 1) ? onWeight : offWeight)/(onWeight + offWeight);
+}
+static int tex_is_procedural(const TgHipTexture *t) { return t->type == TGHIP_TEX_DISK || t->type == TGHIP_TEX_BLADE || t->type == TGHIP_TEX_CHECKER; }
+
 static v3 texture_eval(const TgHipSceneDesc *s, int texIdx, float u0, float v0)
 {
     const TgHipTexture *t = &s->textures[texIdx];
@@ -240,6 +314,10 @@ static v3 texture_eval(const TgHipSceneDesc *s, int texIdx, float u0, float v0)
         int on = (ui ^ vi) & 1;
         return on ? ld3(t->on_color) : ld3(t->off_color);
     }
+    if (t->type == TGHIP_TEX_DISK)
+        return disk_tex_inside(u0, v0) ? ld3(t->value) : vs(0.0f);
+    if (t->type == TGHIP_TEX_BLADE)
+        return blade_tex_inside(t, u0, v0) ? ld3(t->value) : vs(0.0f);
     /* bitmap */
     int w = t->w, h = t->h;
     float u = u0*w;
@@ -2410,7 +2488,9 @@ static void intersection_info(const TgHipSceneDesc *s, const Ray *ray, const Hit
 static void inf_directionToUV(const TgHipObject *o, v3 wi, float *u, float *v, float *sinTheta)
 {
     /* Skydome::directionToUV (Skydome.cpp:41-50) is the same map without the primitive's rotation */
-    v3 wLocal = (o->flags & TGHIP_OBJF_SKYDOME) ? wi : mat3_tmul(o->rot, wi);
+    /* (InfiniteSphere's _invRotTransform*wi is Mat4f times Vec3f, Mat4f.hpp:320-327: it adds the matrix's translation column, +0 -- which turns a
+     * component of -0 into +0, and with it atan2f's branch for a direction exactly on the seam or at a pole) */
+    v3 wLocal = (o->flags & TGHIP_OBJF_SKYDOME) ? wi : vadd(mat3_tmul(o->rot, wi), vs(0.0f));
     if (sinTheta) *sinTheta = sqrtf(fmaxf(1.0f - wLocal.y*wLocal.y, 0.0f));
     *u = atan2f(wLocal.z, wLocal.x)*O_INV_TWO_PI + 0.5f;
     *v = acosf(-wLocal.y)*O_INV_PI;
@@ -2421,7 +2501,7 @@ static v3 inf_uvToDirection(const TgHipObject *o, float u, float v, float *sinTh
     float theta = v*O_PI;
     *sinTheta = sinf(theta);
     v3 wLocal = V(cosf(phi)**sinTheta, -cosf(theta), sinf(phi)**sinTheta);
-    return (o->flags & TGHIP_OBJF_SKYDOME) ? wLocal : mat3_mul(o->rot, wLocal);          /* Skydome.cpp:51-61 */
+    return (o->flags & TGHIP_OBJF_SKYDOME) ? wLocal : vadd(mat3_mul(o->rot, wLocal), vs(0.0f));   /* Skydome.cpp:51-61; + the translation column, as above */
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -3290,9 +3370,13 @@ static float light_directPdf(const TgHipSceneDesc *s, int objIdx, const LightHit
         return O_INV_TWO_PI/(1.0f - cosTheta);         /* SampleWarp::uniformSphericalCapPdf */
     } else {
         const TgHipTexture *t = &s->textures[o->emission];
-        if (t->type != TGHIP_TEX_BITMAP)       /* _emission->isConstant() (checker envmaps are outside the scope) */
-            return O_INV_FOUR_PI;
         float sinTheta, u, v;
+        if (tex_is_procedural(t)) {            /* the texture's own pdf: a checker is not isConstant(), whatever its colours (CheckerTexture.cpp:43-46) */
+            inf_directionToUV(o, lh->w, &u, &v, &sinTheta);
+            return O_INV_PI*O_INV_TWO_PI*proc_tex_pdf(t, u, v)/sinTheta;
+        }
+        if (t->type != TGHIP_TEX_BITMAP)       /* _emission->isConstant() */
+            return O_INV_FOUR_PI;
         inf_directionToUV(o, lh->w, &u, &v, &sinTheta);
         return O_INV_PI*O_INV_TWO_PI*bitmap_pdf(s, t, u, v)/sinTheta;
     }
@@ -3448,6 +3532,14 @@ static int light_sampleDirect(const TgHipSceneDesc *s, int objIdx, v3 p, Sampler
     } else {
         const TgHipTexture *t = &s->textures[o->emission];
         float xi0 = next1D(smp), xi1 = next1D(smp);
+        if (tex_is_procedural(t)) {            /* the texture's own sample / pdf (InfiniteSphere.cpp:168-174) */
+            float u, v, sinTheta;
+            proc_tex_sample(t, xi0, xi1, &u, &v);
+            *d = inf_uvToDirection(o, u, v, &sinTheta);
+            *pdf = O_INV_PI*O_INV_TWO_PI*proc_tex_pdf(t, u, v)/sinTheta;
+            *dist = INFINITY;
+            return *pdf != 0.0f;
+        }
         if (t->type != TGHIP_TEX_BITMAP) {
             *d = uniformSphere(xi0, xi1);
             *dist = INFINITY;
@@ -4459,6 +4551,12 @@ void oracle_rng_streams(uint32_t seed, uint32_t first, uint32_t count, int n, fl
     for (uint32_t i = 0; i < count; ++i) oracle_rng_stream(seed, first + i, 0, n, out + (size_t)i*(size_t)n);
 }
 
+/* ... of the streams (seed, first + i, sample) */
+void oracle_rng_streams_at(uint32_t seed, uint32_t first, uint32_t count, uint32_t sample, int n, float *out)
+{
+    for (uint32_t i = 0; i < count; ++i) oracle_rng_stream(seed, first + i, sample, n, out + (size_t)i*(size_t)n);
+}
+
 void oracle_camera_ray(const TgHipSceneDesc *s, uint32_t px, uint32_t py, float xi0, float xi1, float *o, float *d)
 {
     /* re-uses traceSample's prologue through a replay sampler */
@@ -4548,6 +4646,66 @@ int oracle_light_sample(const TgHipSceneDesc *s, int li, const float *p, float x
     int ok = light_sampleDirect(s, s->lights[li], ld3(p), &smp, &dd, dist, pdf);
     d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
     return ok;
+}
+
+/* The light calls of TraceBase::estimateDirect on n caller-supplied cases (tests/light_cases.py), as the device's tghip_debug_light makes them: per case
+ * the light slot light[i] (index into s->lights), a point p and a unit direction w (3 floats each), nxc replay numbers for chooseLight and nxs for
+ * sampleDirect.  out: 20 words per case, the layout of TgHipLightResult's first 18 and of ref_harness light-cases --
+ *   chosen (OBJECT index, -1 = none), choose_weight | sample_ok, d[3], dist, pdf | approx | hit, t, u, v, back_side, emission[3], direct_pdf |
+ *   numbers consumed by chooseLight, by sampleDirect.
+ * The hit block is intersect + intersectionInfo + evalDirect + directPdf for the ray (p, w, tmin 5e-4, tmax inf).  A mesh emitter is not intersected
+ * (hit = 0: its hit leg is the shadow kernel's); neither is a point light (hit = 0), whose direct_pdf is taken with the hit record attenuatedEmission
+ * builds for a Dirac light (t = the sampled distance).  Words behind a failed choose / sample / intersect are zero. */
+void oracle_light_cases(const TgHipSceneDesc *s, int n, const int32_t *light, const float *p, const float *w,
+                        const float *xi_choose, int nxc, const float *xi_sample, int nxs, uint32_t *out)
+{
+    #pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        union { float f; uint32_t u; int32_t i; } r[20];
+        memset(r, 0, sizeof(r));
+        uint32_t *o = out + 20*(size_t)i;
+        if (light[i] < 0 || (uint32_t)light[i] >= s->num_lights) { memcpy(o, r, sizeof(r)); continue; }
+        const int obj = s->lights[light[i]];
+        const v3 pp = ld3(p + 3*(size_t)i), ww = ld3(w + 3*(size_t)i);
+        Sampler smp;
+        memset(&smp, 0, sizeof(smp));
+        smp.replay = xi_choose + (size_t)nxc*(size_t)i; smp.replay_n = nxc;
+        Ctx c;
+        memset(&c, 0, sizeof(c));
+        c.s = s; c.sampler = &smp;
+        float weight = 1.0f;
+        r[0].i = chooseLight(&c, pp, &weight);
+        r[1].f = weight;
+        r[18].u = (uint32_t)smp.replay_pos;
+        Sampler smp2;
+        memset(&smp2, 0, sizeof(smp2));
+        smp2.replay = xi_sample + (size_t)nxs*(size_t)i; smp2.replay_n = nxs;
+        v3 d = vs(0.0f);
+        float dist = 0.0f, pdf = 0.0f;
+        const int ok = light_sampleDirect(s, obj, pp, &smp2, &d, &dist, &pdf);
+        r[2].u = ok ? 1u : 0u;
+        r[3].f = d.x; r[4].f = d.y; r[5].f = d.z; r[6].f = dist; r[7].f = pdf;
+        r[19].u = (uint32_t)smp2.replay_pos;
+        r[8].f = light_approximateRadiance(s, obj, pp);
+        const int type = s->objects[obj].type;
+        LightHit lh;
+        memset(&lh, 0, sizeof(lh));
+        if (type == TGHIP_OBJ_POINT) {
+            lh.t = dist; lh.w = ww; lh.o = pp;
+            r[17].f = light_directPdf(s, obj, &lh, pp);
+        } else if (type != TGHIP_OBJ_MESH) {
+            Ray ray = {pp, ww, 5e-4f, INFINITY};
+            if (light_intersect(s, obj, &ray, &lh)) {
+                v3 e = light_evalDirect(s, obj, &lh);
+                r[9].u = 1u;
+                r[10].f = lh.t; r[11].f = lh.u; r[12].f = lh.v;
+                r[13].u = lh.backSide ? 1u : 0u;
+                r[14].f = e.x; r[15].f = e.y; r[16].f = e.z;
+                r[17].f = light_directPdf(s, obj, &lh, pp);
+            }
+        }
+        memcpy(o, r, sizeof(r));
+    }
 }
 
 void oracle_texture_eval(const TgHipSceneDesc *s, int tex, float u, float v, float *rgb)

@@ -26,6 +26,8 @@
 //       bounds() of every finite primitive in scene order: the items' boxes of the reference's top-level Embree geometry.
 //   ref_harness bsdf-cases <scene.json> <cases.bin> <out.bin>
 //       eval / pdf / sample of the scene's bsdfs on caller-supplied cases, raw float32 / uint32 in and out.
+//   ref_harness light-cases <scene.json> <cases.bin> <out.bin>
+//       chooseLight and sampleDirect / approximateRadiance / intersect / evalDirect / directPdf of the scene's lights on caller-supplied cases, likewise.
 //
 // Nothing here is copied from the reference; it only calls its public classes.
 #include <atomic>
@@ -69,6 +71,8 @@
 #include "integrators/path_tracer/PathTracer.hpp"
 #include "primitives/EmbreeUtil.hpp"
 #include "primitives/InfiniteSphere.hpp"
+#include "primitives/TriangleMesh.hpp"
+#include "integrators/TraceBase.hpp"
 #include "renderer/TraceableScene.hpp"
 #include "sampling/PathSampleGenerator.hpp"
 #include "sampling/UniformSampler.hpp"
@@ -662,6 +666,97 @@ static int cmdBsdfCases(int argc, char **argv)
     return os ? 0 : 1;
 }
 
+// TraceBase keeps chooseLight protected: a derived class opens it (the constructor makes every light samplable, TraceBase.cpp:5-22)
+class OpenTraceBase : public TraceBase
+{
+public:
+    OpenTraceBase(TraceableScene *scene, const TraceSettings &settings) : TraceBase(scene, settings, 0) {}
+    using TraceBase::chooseLight;
+};
+
+// ref_harness light-cases <scene.json> <cases.bin> <out.bin>: the light calls of TraceBase::estimateDirect on caller-supplied cases, binary in and out.
+// cases.bin: u32 n, nxc, nxs; per case i32 light (index in TraceableScene::lights()), f32 p[3], w[3], xi_choose[nxc], xi_sample[nxs] (the numbers the two
+// samplers replay).  out.bin: 20 words per case -- i32 chosen (index in lights(), -1 = none), f32 choose_weight; u32 sample_ok, f32 d[3], dist, pdf;
+// f32 approx; u32 hit, f32 t, u, v, u32 back_side, f32 emission[3], direct_pdf; u32 numbers consumed by chooseLight, by sampleDirect -- from
+// TraceBase::chooseLight, Primitive::sampleDirect, approximateRadiance, and intersect + intersectionInfo + evalDirect + directPdf for the ray
+// (p, w, nearT 5e-4).  A mesh is not intersected (hit = 0); a Dirac light cannot be (hit = 0) and reports its directPdf all the same
+// (tools/make_light_golden.py -> tests/golden/light_corners.npz).
+static int cmdLightCases(int argc, char **argv)
+{
+    if (argc < 5) return 2;
+    ThreadUtils::startThreads(1);
+    Loaded L;
+    const uint32 seed = 0xBA5EBA11u;
+    if (!loadScene(argv[2], seed, L)) return 1;
+    TraceableScene &ts = *L.ts;
+    std::ifstream in(argv[3], std::ios::binary);
+    uint32 header[3] = {0, 0, 0};
+    in.read(reinterpret_cast<char *>(header), sizeof(header));
+    if (!in || header[1] > 64 || header[2] > 64) { std::fprintf(stderr, "ref_harness: bad case file\n"); return 1; }
+    const uint32 n = header[0], nxc = header[1], nxs = header[2];
+    OpenTraceBase tracer(L.ts.get(), L.pti->settings());
+    auto &lights = ts.lights();
+    std::vector<uint32> out(size_t(n)*20, 0u);
+    std::vector<float> rec(7 + nxc + nxs);
+    for (uint32 c = 0; c < n; ++c) {
+        in.read(reinterpret_cast<char *>(rec.data()), std::streamsize(rec.size()*sizeof(float)));
+        if (!in) { std::fprintf(stderr, "ref_harness: case file ends at case %u\n", c); return 1; }
+        int32 li;
+        std::memcpy(&li, &rec[0], 4);
+        if (li < 0 || size_t(li) >= lights.size()) { std::fprintf(stderr, "ref_harness: case %u names light %d\n", c, li); return 1; }
+        Primitive &light = *lights[size_t(li)];
+        const Vec3f p(rec[1], rec[2], rec[3]), w(rec[4], rec[5], rec[6]);
+        float f[20] = {0.0f};
+        uint32 *o = &out[size_t(c)*20];
+        auto word = [&](int k, uint32 v) { std::memcpy(&f[k], &v, 4); };
+
+        GraftPathSampler sc(seed);
+        sc.setReplay(std::vector<float>(rec.begin() + 7, rec.begin() + 7 + nxc));
+        float weight = 1.0f;
+        const Primitive *chosen = tracer.chooseLight(sc, p, weight);
+        int32 chosenIndex = -1;
+        for (size_t k = 0; k < lights.size(); ++k)
+            if (lights[k].get() == chosen) chosenIndex = int32(k);
+        word(0, uint32(chosenIndex));
+        f[1] = weight;
+        word(18, uint32(sc.consumed()));
+
+        GraftPathSampler ss(seed);
+        ss.setReplay(std::vector<float>(rec.begin() + 7 + nxc, rec.end()));
+        LightSample ls;
+        ls.d = Vec3f(0.0f); ls.dist = 0.0f; ls.pdf = 0.0f;
+        const bool ok = light.sampleDirect(0, p, ss, ls);
+        word(2, ok ? 1u : 0u);
+        f[3] = ls.d.x(); f[4] = ls.d.y(); f[5] = ls.d.z(); f[6] = ls.dist; f[7] = ls.pdf;
+        word(19, uint32(ss.consumed()));
+        f[8] = light.approximateRadiance(0, p);
+
+        IntersectionTemporary data;
+        IntersectionInfo info;
+        if (light.isDirac()) {
+            f[17] = light.directPdf(0, data, info, p);
+        } else if (!dynamic_cast<TriangleMesh *>(&light)) {
+            Ray ray(p, w, 5e-4f);
+            if (light.intersect(ray, data)) {
+                info.p = ray.pos() + ray.dir()*ray.farT();
+                info.w = ray.dir();
+                light.intersectionInfo(data, info);
+                const Vec3f e = light.evalDirect(data, info);
+                word(9, 1u);
+                f[10] = ray.farT(); f[11] = info.uv.x(); f[12] = info.uv.y();
+                word(13, light.hitBackside(data) ? 1u : 0u);
+                f[14] = e.x(); f[15] = e.y(); f[16] = e.z();
+                f[17] = light.directPdf(0, data, info, p);
+            }
+        }
+        std::memcpy(o, f, sizeof(f));
+    }
+    std::ofstream os(argv[4], std::ios::binary);
+    os.write(reinterpret_cast<const char *>(out.data()), std::streamsize(out.size()*4));
+    std::fprintf(stderr, "ref_harness: %u light cases on %zu lights\n", n, lights.size());
+    return os ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {
@@ -680,6 +775,7 @@ int main(int argc, char **argv)
     else if (cmd == "sky-image") rc = cmdSkyImage(argc, argv);
     else if (cmd == "bounds") rc = cmdBounds(argc, argv);
     else if (cmd == "bsdf-cases") rc = cmdBsdfCases(argc, argv);
+    else if (cmd == "light-cases") rc = cmdLightCases(argc, argv);
     if (rc == 2) std::fprintf(stderr, "ref_harness: bad arguments\n");
     return rc;
 }

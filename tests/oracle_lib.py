@@ -172,6 +172,16 @@ def rng_streams(seed, first, count, n):
     return out
 
 
+_lib.oracle_rng_streams_at.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+
+
+def rng_streams_at(seed, first, count, sample, n):
+    """[count, n]: the first n numbers of the streams (seed, first + i, sample)."""
+    out = np.empty((count, n), np.float32)
+    _lib.oracle_rng_streams_at(seed & 0xFFFFFFFF, first, count, sample, n, out.ctypes.data)
+    return out
+
+
 def camera_ray(desc, px, py, xi0, xi1):
     o, d = np.empty(3, np.float32), np.empty(3, np.float32)
     _lib.oracle_camera_ray(desc, px, py, xi0, xi1, o.ctypes.data, d.ctypes.data)
@@ -209,6 +219,23 @@ def bsdf_cases(desc, bsdf, requested, wi, wo, uv, xi):
     out = np.zeros((n, 14), np.uint32)
     _lib.oracle_bsdf_cases(desc, n, bsdf.ctypes.data, requested.ctypes.data, wi.ctypes.data, wo.ctypes.data, uv.ctypes.data, xi.ctypes.data,
                            xi.shape[1], out.ctypes.data)
+    return out
+
+
+_lib.oracle_light_cases.argtypes = [DESC_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+
+
+def light_cases(desc, light, p, w, xi_choose, xi_sample):
+    """chooseLight, sampleDirect, approximateRadiance and intersect + evalDirect + directPdf over n cases at once: [n, 20] uint32 words -- chosen
+    (object index), choose_weight, sample_ok, d[3], dist, pdf, approx, hit, t, u, v, back_side, emission[3], direct_pdf, then the numbers chooseLight
+    and sampleDirect consumed (the floats as bit patterns) -- the layout the reference harness writes for the same cases.  light: slots of desc.lights."""
+    light = np.ascontiguousarray(light, np.int32)
+    p, w, xi_choose, xi_sample = [np.ascontiguousarray(v, np.float32) for v in (p, w, xi_choose, xi_sample)]
+    n = light.size
+    assert p.shape == (n, 3) and w.shape == (n, 3) and xi_choose.shape[0] == n and xi_sample.shape[0] == n
+    out = np.zeros((n, 20), np.uint32)
+    _lib.oracle_light_cases(desc, n, light.ctypes.data, p.ctypes.data, w.ctypes.data, xi_choose.ctypes.data, xi_choose.shape[1],
+                            xi_sample.ctypes.data, xi_sample.shape[1], out.ctypes.data)
     return out
 
 

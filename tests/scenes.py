@@ -1097,3 +1097,98 @@ def bsdf_corners(tmpdir, **kw):
     kw.setdefault("resolution", (32, 18))
     kw.setdefault("spp", 2)
     return cornell(tmpdir, name=kw.pop("name", "bsdf_corners.json"), edit=both, **kw)
+
+
+# ---- the scenes of the per-call light comparisons (tests/light_cases.py) ----
+# the first four nested -- each holds the lights of the one before --, then two small scenes for the legs of chooseLight no scene with a sky reaches:
+# `backs`, two one-sided quads lying face down on the floor (every weight 0 from above: no light is chosen), and `unknown`, two mesh emitters and
+# nothing else (every weight "unknown": all lights equally likely)
+LIGHT_CORNER_SCENES = ("lean", "solids", "mesh", "all", "backs", "unknown")
+
+
+def light_corner_list(which="all"):
+    """The sampled lights of scenes.light_corners(which) in scene order -- the order of TraceableScene::lights() and of TgHipSceneDesc::lights --
+    as (name, emitter kind, primitive).  16 in `all`: what one scene may hold (SceneCheck.cpp: "more than 16 sampled lights")."""
+    if which == "backs":
+        return [("back%d" % i, "quad", {"type": "quad", "bsdf": "light", "emission": e,
+                                        "transform": {"position": pos, "scale": [0.3, 0.3, 0.2], "rotation": [0, 20*i, 180]}})
+                for i, (e, pos) in enumerate((([5, 4, 3], [-0.4, 1e-3, 0.3]), ([2, 6, 9], [0.5, 1e-3, -0.2])))]
+    if which == "unknown":
+        return [("shard%d" % i, "mesh", {"type": "mesh", "file": "light_shard.wo3", "smooth": False, "bsdf": "light", "emission": e,
+                                         "transform": {"position": pos, "rotation": rot}})
+                for i, (e, pos, rot) in enumerate((([9, 7, 4], [-0.3, 1.2, 0.4], [15, 40, -25]), ([1, 3, 8], [0.4, 0.7, -0.3], [-70, 10, 130])))]
+    level = LIGHT_CORNER_SCENES.index(which)
+    lights = [("light", "quad", None)]                        # the Cornell box's own one-sided quad emitter
+    if level >= 1:
+        lights += [
+            # a quad four millimetres across: from afar its solid angle rounds to zero or below ("unknown", TraceBase.cpp:434-446)
+            ("speck", "quad", {"type": "quad", "bsdf": "light", "emission": [4e4, 3e4, 2e4],
+                               "transform": {"position": [0.4, 1.2, -0.3], "scale": [4e-3, 4e-3, 4e-3], "rotation": [0, 0, 180]}}),
+            ("brick", "cube", {"type": "cube", "bsdf": "light", "emission": [2, 5, 3],
+                               "transform": {"position": [0.6, 0.42, 0.6], "scale": [0.2, 0.12, 0.31], "rotation": [20, 30, -10]}}),
+            ("bulb", "sphere", {"type": "sphere", "bsdf": "light",
+                                "emission": {"type": "checker", "on_color": [6, 3, 1], "off_color": [1, 3, 6], "res_u": 6, "res_v": 3},
+                                "transform": {"position": [-0.55, 1.45, 0.1], "scale": 0.12, "rotation": [0, 25, 15]}}),
+            ("spot", "disk", {"type": "disk", "bsdf": "light", "emission": [30, 22, 8], "cone_angle": 65,
+                              "transform": {"position": [0.5, 1.6, -0.5], "scale": 0.3, "rotation": [160, 0, 20]}}),
+            ("lamp", "point", {"type": "point", "power": [3, 6, 9], "transform": {"position": [0.55, 1.5, 0.3]}}),
+            ("sky", "infinite_sphere", {"type": "infinite_sphere", "emission": [0.25, 0.35, 0.6], "sample": True}),
+            ("env", "infinite_sphere", {"type": "infinite_sphere", "emission": "light_env.png", "sample": True, "transform": {"rotation": [65, 35, -10]}}),
+            ("sun", "infinite_sphere_cap", {"type": "infinite_sphere_cap", "emission": [60, 52, 40], "cap_angle": 8, "sample": True,
+                                            "transform": {"rotation": [25, 0, -20]}}),
+            ("dome", "skydome", {"type": "skydome", "sample": True, "transform": {"rotation": [30, 10, -20]}}),
+        ]
+    if level >= 2:
+        lights += [("shard", "mesh", {"type": "mesh", "file": "light_shard.wo3", "smooth": False, "bsdf": "light", "emission": [9, 7, 4],
+                                      "transform": {"position": [-0.3, 1.2, 0.4], "rotation": [15, 40, -25]}})]
+    if level >= 3:
+        lights += [
+            ("neon", "cylinder", {"type": "cylinder", "bsdf": "light", "emission": [3, 7, 9],
+                                  "transform": {"position": [0.0, 1.6, -0.6], "scale": [0.08, 1.2, 0.08], "rotation": [0, 0, 90]}}),
+            ("tube", "cylinder", {"type": "cylinder", "bsdf": "light", "emission": [5, 2, 1], "capped": False,
+                                  "transform": {"position": [0.6, 0.9, -0.2], "scale": [0.1, 0.5, 0.1], "rotation": [30, 0, 40]}}),
+            ("env_checker", "infinite_sphere", {"type": "infinite_sphere", "sample": True, "transform": {"rotation": [10, -40, 5]},
+                                                "emission": {"type": "checker", "on_color": [1.7, 1.2, 0.6], "off_color": [0.25, 0.45, 0.9], "res_u": 6, "res_v": 3}}),
+            ("env_disk", "infinite_sphere", {"type": "infinite_sphere", "sample": True, "transform": {"rotation": [70, 30, 0]},
+                                             "emission": {"type": "disk", "value": [1.6, 1.3, 0.9]}}),
+            ("env_blade", "infinite_sphere", {"type": "infinite_sphere", "sample": True, "transform": {"rotation": [-60, 10, 25]},
+                                              "emission": {"type": "blade", "blades": 5, "angle": 0.25, "value": [0.8, 1.1, 1.7]}}),
+        ]
+    return lights
+
+
+def light_corners(tmpdir, which="all", **kw):
+    """The Cornell box with the emitters of light_corner_list(which): `lean` -- the box as it is, what k_shade<MASK_LEAN> renders --, `solids` -- every
+    analytic and infinite emitter the class-0 .. 3 families sample --, `mesh` -- a mesh emitter of four triangles of very unequal area, one of them
+    degenerate (MASK_FULL) --, `all` -- cylinders and the environments sampled through a checker, a disk and a blade texture (BSDF_MASK_ALL).  The
+    bitmap environment is CORNER_TEXTURE_SIZE texels.  `backs` and `unknown` replace the box's light by two emitters each (LIGHT_CORNER_SCENES)."""
+    import numpy as np
+    tmpdir = str(tmpdir)
+    level = {"backs": 0, "unknown": 2}.get(which, LIGHT_CORNER_SCENES.index(which))      # (which files the scene needs)
+    if level >= 1 and which != "unknown":
+        w, h = CORNER_TEXTURE_SIZE
+        y, x = np.mgrid[0:h, 0:w]
+        write_png(os.path.join(tmpdir, "light_env.png"), np.stack([(x*37 + 11) % 256, (y*71 + x*5 + 3) % 256, (255 - x*29 - y*13) % 256], axis=-1), 2, filters=(0,))
+    if level >= 2:
+        # pos3, normal3, uv2 per vertex: a large, a middling and a tiny triangle (areas 8e-2, 4e-3, 5e-7) and one whose corners lie on a line
+        pos = np.array([[0, 0, 0], [0.4, 0, 0], [0, 0, 0.4],  [0.5, 0.1, 0], [0.6, 0.1, 0], [0.5, 0.1, 0.08],
+                        [0.2, 0.3, 0.2], [0.201, 0.3, 0.2], [0.2, 0.3, 0.201],  [0.1, 0.2, 0.1], [0.2, 0.2, 0.2], [0.3, 0.2, 0.3]], np.float32)
+        verts = np.concatenate([pos, np.tile(np.array([[0, -1, 0]], np.float32), (12, 1)), pos[:, [0, 2]]], axis=1)
+        tris = np.array([[0, 1, 2, 0], [3, 4, 5, 0], [6, 7, 8, 0], [9, 10, 11, 0]], np.int32)
+        write_wo3(os.path.join(tmpdir, "light_shard.wo3"), verts, tris)
+
+    def edit(scene):
+        if which in ("backs", "unknown"):
+            scene["primitives"] = [p for p in scene["primitives"] if p["name"] != "light"]
+        for name, _, prim in light_corner_list(which):
+            if prim is not None:
+                scene["primitives"].append(dict(prim, name=name))
+    user = kw.pop("edit", None)
+
+    def both(scene):
+        edit(scene)
+        if user:
+            user(scene)
+    kw.setdefault("resolution", (32, 18))
+    kw.setdefault("spp", 2)
+    return cornell(tmpdir, name=kw.pop("name", "light_corners_%s.json" % which), edit=both, **kw)

@@ -44,7 +44,7 @@ def test_product_library_does_not_link_the_oracle():
 def test_ctypes_layout_matches_the_headers(tmp_path):
     structs = ["TgHipBvhNode", "TgHipWideNode", "TgHipPrimRec", "TgHipTriAttr", "TgHipObject", "TgHipBsdf", "TgHipTexture", "TgHipMedium", "TgHipCamera",
                "TgHipSettings", "TgHipSceneDesc", "TgHipPassDesc", "TgHipAuxPixel", "TgHipCounters", "TgHipRay", "TgHipHit", "TgHostSceneInfo",
-               "TgHipBsdfCase", "TgHipBsdfResult", "TgHostSceneTraits", "TgHostPassPlan", "TgHostPassBatch"]
+               "TgHipBsdfCase", "TgHipBsdfResult", "TgHipLightCase", "TgHipLightResult", "TgHostSceneTraits", "TgHostPassPlan", "TgHostPassBatch"]
     src = '#include <stdio.h>\n#include "tungsten_host.h"\nint main(void){\n'
     for s in structs:
         src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (s, s)
@@ -87,6 +87,33 @@ def test_ctypes_layout_of_the_bsdf_cases(tmp_path):
     assert int(got["variants"]) == capi.TGHIP_BSDF_VARIANT_COUNT == len(capi.TGHIP_BSDF_VARIANT_NAMES)
 
 
+def test_ctypes_layout_of_the_light_cases(tmp_path):
+    """TgHipLightCase / TgHipLightResult (tghip_debug_light): every field of the ctypes mirror and of the numpy record type at the C offset."""
+    fields = {"TgHipLightCase": ["light", "variant", "p", "w", "seed", "stream"],
+              "TgHipLightResult": ["chosen", "choose_weight", "sample_ok", "d", "dist", "pdf", "approx", "hit", "t", "u", "v", "back_side", "emission",
+                                   "direct_pdf", "choose_next", "sample_next", "reserved"]}
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tungsten_hip.h"\nint main(void){\n'
+    for s, names in fields.items():
+        src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (s, s)
+        for n in names:
+            src += 'printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (s, n, s, n)
+    src += 'return 0;}\n'
+    c = tmp_path/"light.c"
+    c.write_text(src)
+    exe = str(tmp_path/"light")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe])
+    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
+    for s, names in fields.items():
+        ct, dt = getattr(capi, s), {"TgHipLightCase": tg.LIGHT_CASE_DTYPE, "TgHipLightResult": tg.LIGHT_RESULT_DTYPE}[s]
+        assert int(got[s]) == C.sizeof(ct) == dt.itemsize, s
+        assert [f[0] for f in ct._fields_] == names == list(dt.names)
+        for n in names:
+            assert int(got["%s.%s" % (s, n)]) == getattr(ct, n).offset == dt.fields[n][1], (s, n)
+    assert C.sizeof(capi.TgHipLightCase) == 40 and C.sizeof(capi.TgHipLightResult) == 96
+    # the first 18 words of a result are the words the oracle and the reference harness write for the same case (tests/light_cases.py: WORDS)
+    assert tg.LIGHT_RESULT_DTYPE.fields["choose_next"][1] == 18*4
+
+
 def test_error_paths_without_arguments():
     lib = tg.lib
     assert lib.tghip_upload_scene(None, None) == -1
@@ -95,6 +122,9 @@ def test_error_paths_without_arguments():
     assert lib.tghip_set_option(None, b"x", 1) == -1
     assert lib.tghip_debug_bsdf(None, None, None, 0) == -1
     assert lib.tghip_debug_bsdf_info(None, 0, None, None, None, None) == -1
+    assert lib.tghip_debug_light(None, None, None, 0) == -1
+    assert lib.tghip_debug_light_info(None, 0, None, None, None) == -1
+    assert lib.tgh_light_needs(None, 0, None, None, None) == -1
     lib.tghip_destroy(None)   # no-op
     with pytest.raises(tg.TungstenError):
         tg.FlattenedScene("/nonexistent/scene.json")

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import light_cases as lc
 import oracle_lib
 import scenes
 import tungsten_amd as tg
@@ -203,6 +204,32 @@ def test_oracle_units(scene, tmp_path):
                 assert close(pdf, c["pdf"], 2e-4), (c, pdf)
                 if c["dist"] < 1e29:
                     assert close(dist, c["dist"], 1e-5), c
+
+    # lights: approximateRadiance at every recorded point and -- along the recorded sampled direction, the ray of the BSDF-sampling leg -- directPdf and
+    # evalDirect, through the batched entry of the per-call light comparisons.  "%.9g" round-trips a float32, so these are float32 equalities; a case
+    # that differs would be pinned by scene, light and case in tests/golden/units_light_residual.json (there is none).
+    pinned = json.load(open(lc.UNITS_RESIDUAL)).get(scene, {}) if os.path.exists(lc.UNITS_RESIDUAL) else {}
+    differing, total = {}, 0
+    for L in u["lights"]:
+        cs = L["cases"]
+        n = len(cs)
+        total += n
+        p = np.array([c["p"] for c in cs], np.float32)
+        w = np.array([c.get("d", [0.0, 1.0, 0.0]) for c in cs], np.float32)
+        xs = np.full((n, lc.NXS), 0.5, np.float32)
+        xs[:, :2] = [c["xi"] for c in cs]
+        words = oracle_lib.light_cases(d, np.full(n, L["index"], np.int32), p, w, np.full((n, lc.NXC), 0.5, np.float32), xs)
+        fl = words.view(np.float32)
+        for k, c in enumerate(cs):
+            same = fl[k, 8] == np.float32(c["approx"]) and bool(words[k, 2]) == bool(c["ok"])
+            if "direct_pdf" in c:
+                same = same and words[k, 9] == 1 and fl[k, 17] == np.float32(c["direct_pdf"]) and (fl[k, 14:17] == np.array(c["emission"], np.float32)).all()
+            elif c["ok"]:
+                same = same and words[k, 9] == 0             # the reference's ray along the sampled direction missed the light
+            if not same:
+                differing.setdefault(L["name"], []).append(k)
+    assert differing == pinned, "%s: light cases that are not the reference's: %s" % (scene, differing)
+    assert sum(len(v) for v in pinned.values()) <= 0.001*total
     flat.close()
 
 

@@ -27,6 +27,12 @@ BSDF_CASE_DTYPE = np.dtype([("bsdf", np.int32), ("requested", np.uint32), ("wi",
 BSDF_RESULT_DTYPE = np.dtype([("f", np.float32, 3), ("pdf", np.float32), ("sample_ok", np.uint32), ("sample_wo", np.float32, 3),
                               ("sample_weight", np.float32, 3), ("sample_pdf", np.float32), ("sampled", np.uint32), ("next", np.float32),
                               ("reserved", np.uint32, 2)])
+# capi.TgHipLightCase / TgHipLightResult (Renderer.debug_light)
+LIGHT_CASE_DTYPE = np.dtype([("light", np.int32), ("variant", np.uint32), ("p", np.float32, 3), ("w", np.float32, 3), ("seed", np.uint32), ("stream", np.uint32)])
+LIGHT_RESULT_DTYPE = np.dtype([("chosen", np.int32), ("choose_weight", np.float32), ("sample_ok", np.uint32), ("d", np.float32, 3), ("dist", np.float32),
+                               ("pdf", np.float32), ("approx", np.float32), ("hit", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
+                               ("back_side", np.uint32), ("emission", np.float32, 3), ("direct_pdf", np.float32), ("choose_next", np.float32),
+                               ("sample_next", np.float32), ("reserved", np.uint32, 4)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 DEVELOP_PART_NAMES = ("mean", "a", "b", "variance")                          # capi.TGHIP_DEVELOP_*
@@ -179,6 +185,26 @@ class Renderer(object):
         if rc != 0:
             raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
         return tm, fwd.astype(bool), cov.astype(bool), int(mask.value)
+
+    def debug_light(self, cases, device=0):
+        """The shading kernels' light code on caller-supplied cases (tghip_debug_light): `cases` an array of LIGHT_CASE_DTYPE, the result an
+        array of LIGHT_RESULT_DTYPE of the same length."""
+        cases = np.ascontiguousarray(cases, LIGHT_CASE_DTYPE).reshape(-1)
+        out = np.zeros(cases.size, LIGHT_RESULT_DTYPE)
+        rc = lib.tghip_debug_light(self.context(device), cases.ctypes.data if cases.size else None, out.ctypes.data if cases.size else None, cases.size)
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        return out
+
+    def debug_light_info(self, variant=capi.TGHIP_BSDF_VARIANT_ALL, device=0):
+        """(needs, covered) per slot of the scene's sampled lights and the mask the variant's kernel is compiled for (tghip_debug_light_info)."""
+        n = int(self.info.num_lights)
+        needs, cov = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        mask = C.c_uint32(0)
+        rc = lib.tghip_debug_light_info(self.context(device), int(variant), needs.ctypes.data, cov.ctypes.data, C.addressof(mask))
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        return needs, cov.astype(bool), int(mask.value)
 
     def trace_samples(self, spp_begin, spp_end, seed=DEFAULT_SEED, tile_seeds=None, device=0):
         """One TGHIP_PASS_SAMPLES pass on the device (into a cleared framebuffer): the radiance of every individual sample,

@@ -157,6 +157,16 @@ class TgHipBsdfResult(C.Structure):
                 ("sampled", u32), ("next", f32), ("reserved", u32*2)]
 
 
+class TgHipLightCase(C.Structure):
+    _fields_ = [("light", i32), ("variant", u32), ("p", f32*3), ("w", f32*3), ("seed", u32), ("stream", u32)]
+
+
+class TgHipLightResult(C.Structure):
+    _fields_ = [("chosen", i32), ("choose_weight", f32), ("sample_ok", u32), ("d", f32*3), ("dist", f32), ("pdf", f32), ("approx", f32),
+                ("hit", u32), ("t", f32), ("u", f32), ("v", f32), ("back_side", u32), ("emission", f32*3), ("direct_pdf", f32),
+                ("choose_next", f32), ("sample_next", f32), ("reserved", u32*4)]
+
+
 class TgHipPassDesc(C.Structure):
     _fields_ = [("spp_begin", u32), ("spp_end", u32), ("seed", u32), ("shard_index", u32), ("shard_count", u32),
                 ("flags", u32),
@@ -247,6 +257,8 @@ PROTOTYPES = {
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
+    "tghip_debug_light": (C.c_int, [VP, VP, VP, C.c_size_t]),
+    "tghip_debug_light_info": (C.c_int, [VP, C.c_int, VP, VP, VP]),
     "tghip_set_option": (C.c_int, [VP, C.c_char_p, C.c_longlong]),
     "tghip_get_counters": (C.c_int, [VP, C.POINTER(TgHipCounters)]),
     "tghip_reset_counters": (C.c_int, [VP]),
@@ -303,6 +315,7 @@ PROTOTYPES = {
     "tgh_top_tree_for_scene": (C.c_int, [VP, C.c_uint32, VP, C.c_uint32, VP, C.c_uint32]),
     "tgh_leaf_bounds": (C.c_int, [VP, C.c_uint32, VP, VP]),
     "tgh_scene_check": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(TgHostSceneTraits), C.c_char_p, C.c_size_t]),
+    "tgh_light_needs": (C.c_int, [C.POINTER(TgHipSceneDesc), C.c_int, VP, VP, VP]),
     "tgh_pass_plan_create": (VP, [C.POINTER(TgHipPassDesc), u32, u32, C.c_int, u64, u64, u32, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "tgh_pass_plan_info": (None, [VP, C.POINTER(TgHostPassPlan)]),
     "tgh_pass_plan_batches": (C.POINTER(TgHostPassBatch), [VP, C.POINTER(u32)]),

@@ -1,9 +1,12 @@
 // Kernels of tghip_debug_bsdf (include/tungsten_hip.h): bsdfEval / bsdfPdf / bsdfSample -- the wrappers the shading kernels call (pt_scene.h) --
 // on caller-supplied cases, one thread per case, instantiated once per shading family's mask (pt_wavefront.h).  Parity instrumentation
 // (tests/test_gpu_bsdf_units.py compares every word with the oracle and the reference's recorded answers); no render launches these.
+// Likewise tghip_debug_light: chooseLight / lightSampleDirect / lightApproximateRadiance / lightIntersect / lightEvalDirect / lightDirectPdf in the
+// order and with the arguments of k_shade's next-event estimation (tests/test_gpu_light_units.py).
 #include "pt_wavefront.h"
 #include "debug_units.h"
 
+// One instantiation per family of PT_FAMILY_VARIANTS (pt_variants.h), the masks familyMask reports (csrc/host/SceneCheck.cpp).
 // Every instantiation has FEAT_QMC cleared: the Sobol' twin of the sampler reads generator matrices a debug call does not have.
 #define DEBUG_MASK(m) ((m) & ~FEAT_QMC)
 
@@ -43,20 +46,61 @@ __global__ void __launch_bounds__(64) k_debug_bsdf(DeviceScene s, const TgHipBsd
     results[i] = r;
 }
 
-uint32_t debugBsdfVariantMask(uint32_t variant)
+// One light case (TgHipLightCase): the calls of k_shade's estimateDirect block (pt_wavefront.h), each on the unstaged scene in global memory.
+template<uint32_t M>
+__global__ void __launch_bounds__(64) k_debug_light(DeviceScene s, const TgHipLightCase *cases, TgHipLightResult *results, uint32_t n, uint32_t variant)
 {
-    switch (variant) {
-    case TGHIP_BSDF_VARIANT_LEAN:    return DEBUG_MASK(MASK_LEAN);
-    case TGHIP_BSDF_VARIANT_SIMPLE:  return DEBUG_MASK(MASK_SIMPLE);
-    case TGHIP_BSDF_VARIANT_COAT:    return DEBUG_MASK(MASK_COAT);
-    case TGHIP_BSDF_VARIANT_GLASS:   return DEBUG_MASK(MASK_GLASS);
-    case TGHIP_BSDF_VARIANT_PLASTIC: return DEBUG_MASK(MASK_PLASTIC);
-    case TGHIP_BSDF_VARIANT_MEDIA:   return DEBUG_MASK(MASK_MEDIA);
-    case TGHIP_BSDF_VARIANT_TAIL:    return DEBUG_MASK(MASK_TAIL);
-    case TGHIP_BSDF_VARIANT_FULL:    return DEBUG_MASK(MASK_FULL);
-    case TGHIP_BSDF_VARIANT_ALL:     return DEBUG_MASK(BSDF_MASK_ALL);
-    default: return 0u;
+    static_assert((M & FEAT_QMC) == 0, "the debug kernels draw from the counter-based stream only");
+    const uint32_t i = blockIdx.x*blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const TgHipLightCase c = cases[i];
+    if (c.variant != variant || c.light < 0 || (uint32_t)c.light >= s.num_lights) return;     // (the shim has refused such a slot already)
+    const f3 p = mk3(c.p[0], c.p[1], c.p[2]), w = mk3(c.w[0], c.w[1], c.w[2]);
+    const int light = s.lights[c.light];
+    TgHipLightResult r;
+    // TraceBase::chooseLight on the case's first stream
+    Rng rng = rngStart(c.seed, c.stream, 0u);
+    float lightWeight = 1.0f;
+    r.chosen = chooseLight<M>(s, rng, p, lightWeight);
+    r.choose_weight = lightWeight;
+    r.choose_next = rngNext1D(rng);
+    // lightSample's sampleDirect on the second
+    Rng rng2 = rngStart(c.seed, c.stream, 1u);
+    f3 d = splat3(0.0f);
+    float dist = 0.0f, pdf = 0.0f;
+    const bool sampled = lightSampleDirect<M>(s, light, p, rng2, d, dist, pdf);
+    r.sample_ok = sampled ? 1u : 0u;
+    r.d[0] = d.x; r.d[1] = d.y; r.d[2] = d.z;
+    r.dist = dist; r.pdf = pdf;
+    r.sample_next = rngNext1D(rng2);
+    r.approx = lightApproximateRadiance<M>(s, light, p);
+    // bsdfSample's leg: the analytic hit, the emission and the light's pdf for a direction the BSDF chose
+    const bool meshLight = (M & FEAT_MESHLIGHT) && s.objects[light].type == TGHIP_OBJ_MESH;
+    const bool diracLight = (M & FEAT_SOLIDS) && s.objects[light].type == TGHIP_OBJ_POINT;
+    LightHit lh;
+    lh.t = 0.0f; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f); lh.sinTheta = 0.0f;
+    bool hit = false;
+    f3 e = splat3(0.0f);
+    float lightPdf = 0.0f;
+    if (diracLight) {
+        // never intersected: the shadow ray ends at the sampled distance, with this hit record
+        lh.t = dist; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f);
+        lightPdf = lightDirectPdf<M>(s, light, w, p, lh);
+    } else if (!meshLight) {
+        RayD sr; sr.o = p; sr.d = w; sr.tmin = 5e-4f; sr.tmax = PT_INF;
+        hit = lightIntersect<M>(s, light, sr, lh);
+        if (hit) {
+            e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
+            lightPdf = lightDirectPdf<M>(s, light, w, p, lh);
+        }
     }
+    r.hit = hit ? 1u : 0u;
+    r.t = lh.t; r.u = lh.u; r.v = lh.v;
+    r.back_side = lh.backSide ? 1u : 0u;
+    r.emission[0] = e.x; r.emission[1] = e.y; r.emission[2] = e.z;
+    r.direct_pdf = lightPdf;
+    r.reserved[0] = r.reserved[1] = r.reserved[2] = r.reserved[3] = 0u;
+    results[i] = r;
 }
 
 hipError_t debugBsdfLaunch(hipStream_t stream, const DeviceScene &scene, const TgHipBsdfCase *cases, TgHipBsdfResult *results, uint32_t n,
@@ -64,16 +108,19 @@ hipError_t debugBsdfLaunch(hipStream_t stream, const DeviceScene &scene, const T
 {
     const dim3 grid((n + 63u)/64u), block(64);
 #define DEBUG_LAUNCH(V, MASK) \
-    if (variants & (1u << (V))) hipLaunchKernelGGL(k_debug_bsdf<DEBUG_MASK(MASK)>, grid, block, 0, stream, scene, cases, results, n, uint32_t(V))
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_LEAN, MASK_LEAN);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_SIMPLE, MASK_SIMPLE);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_COAT, MASK_COAT);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_GLASS, MASK_GLASS);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_PLASTIC, MASK_PLASTIC);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_MEDIA, MASK_MEDIA);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_TAIL, MASK_TAIL);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_FULL, MASK_FULL);
-    DEBUG_LAUNCH(TGHIP_BSDF_VARIANT_ALL, BSDF_MASK_ALL);
+    if (variants & (1u << (V))) hipLaunchKernelGGL(k_debug_bsdf<DEBUG_MASK(MASK)>, grid, block, 0, stream, scene, cases, results, n, uint32_t(V));
+    PT_FAMILY_VARIANTS(DEBUG_LAUNCH)
+#undef DEBUG_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t debugLightLaunch(hipStream_t stream, const DeviceScene &scene, const TgHipLightCase *cases, TgHipLightResult *results, uint32_t n,
+                            uint32_t variants)
+{
+    const dim3 grid((n + 63u)/64u), block(64);
+#define DEBUG_LAUNCH(V, MASK) \
+    if (variants & (1u << (V))) hipLaunchKernelGGL(k_debug_light<DEBUG_MASK(MASK)>, grid, block, 0, stream, scene, cases, results, n, uint32_t(V));
+    PT_FAMILY_VARIANTS(DEBUG_LAUNCH)
 #undef DEBUG_LAUNCH
     return hipGetLastError();
 }

@@ -2135,7 +2135,10 @@ PT_DEV void infDirectionToUV(const TgHipObject &o, f3 wi, float &u, float &v, fl
 {
     // (a skydome maps world directions to its image as they are, Skydome.cpp:41-50; not through an identity matrix: -0 + 0 = +0 would move
     // atan2f's branch cut)
-    f3 wLocal = (o.flags & TGHIP_OBJF_SKYDOME) ? wi : mat3TMul(o.rot, wi);
+    // (InfiniteSphere's _invRotTransform*wi is Mat4f times Vec3f, math/Mat4f.hpp:320-327: it adds the matrix's translation column, +0 -- which turns a
+    // component of -0 into +0 and with it atan2f's branch: a direction exactly on the seam read u = 0 here and u = 1 there, one exactly at a pole of
+    // an unrotated sphere u = 0 and u = 0.5.  tests/test_gpu_light_units.py holds both.)
+    f3 wLocal = (o.flags & TGHIP_OBJF_SKYDOME) ? wi : mat3TMul(o.rot, wi) + splat3(0.0f);
     sinTheta = sqrtf(fmaxf(1.0f - wLocal.y*wLocal.y, 0.0f));
     u = atan2fH(wLocal.z, wLocal.x)*PT_INV_TWO_PI + 0.5f;
     v = acosfExact(-wLocal.y)*PT_INV_PI;
@@ -2148,7 +2151,7 @@ PT_DEV f3 infUvToDirection(const TgHipObject &o, float u, float v, float &sinThe
     sincosfH(theta, sinTheta, cosTheta);
     sincosfH(phi, sinPhi, cosPhi);
     const f3 wLocal = mk3(cosPhi*sinTheta, -cosTheta, sinPhi*sinTheta);
-    return (o.flags & TGHIP_OBJF_SKYDOME) ? wLocal : mat3Mul(o.rot, wLocal);     // (Skydome.cpp:51-61)
+    return (o.flags & TGHIP_OBJF_SKYDOME) ? wLocal : mat3Mul(o.rot, wLocal) + splat3(0.0f);     // (Skydome.cpp:51-61; + the translation column, as above)
 }
 
 struct LightHit { float t, u, v; bool backSide; f3 n; float sinTheta; };   /* n: surface normal at the hit (cube lights); sinTheta: infinite sphere (below) */

@@ -72,6 +72,13 @@
 #define MASK_GLASS_INST   (MASK_GLASS | FEAT_INSTANCES)
 #define MASK_PLASTIC_INST (MASK_PLASTIC | FEAT_INSTANCES)
 
+// The shading families by their ABI number (TGHIP_BSDF_VARIANT_*) and mask: the ONE table behind familyMask (csrc/host/SceneCheck.cpp) and the
+// instantiations of the per-call debug kernels (csrc/hip/debug_units.hip) -- a family added here is in both.
+#define PT_FAMILY_VARIANTS(X) \
+    X(TGHIP_BSDF_VARIANT_LEAN, MASK_LEAN) X(TGHIP_BSDF_VARIANT_SIMPLE, MASK_SIMPLE) X(TGHIP_BSDF_VARIANT_COAT, MASK_COAT) \
+    X(TGHIP_BSDF_VARIANT_GLASS, MASK_GLASS) X(TGHIP_BSDF_VARIANT_PLASTIC, MASK_PLASTIC) X(TGHIP_BSDF_VARIANT_MEDIA, MASK_MEDIA) \
+    X(TGHIP_BSDF_VARIANT_TAIL, MASK_TAIL) X(TGHIP_BSDF_VARIANT_FULL, MASK_FULL) X(TGHIP_BSDF_VARIANT_ALL, BSDF_MASK_ALL)
+
 // most media of a scene: the path's medium travels as index + 1 in seven bits of the slot flags (pt_kernels.h: FLAG_MEDIUM)
 #define PT_MAX_MEDIA 126u
 

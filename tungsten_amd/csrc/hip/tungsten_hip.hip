@@ -1384,6 +1384,8 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
             // into the workgroup's bitmaps (k_shade: CONCURRENT), so their launches MAY run side by side on three streams ("class_streams"
             // option).  Measured slower than one after the other (materialtest 735-800 against 825-830 Msamples/s, mesh1m 409 against 508,
             // for 2 to 24 hardware queues): with four parts in flight the chip is not short of independent launches.
+            // (which family a scene may get is restated for the tests in tests/light_cases.py: families_for -- the rule check of the lights' feature bits
+            // reads it; a change of this decision or of launchComplexClass's goes there as well)
             auto shadeClass = [&](int cls) {
                 const bool simple = cls == 0 || cls == CLS_MISS || cls == CLS_0_AND_MISS;
                 if (ctx->sc.mediaSimple && ctx->mediaLeanOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && !ctx->sc.haveMeshLight)
@@ -2139,11 +2141,55 @@ int tghip_debug_bsdf_info(tghip_ctx *ctx, int variant, uint32_t *type_mask, uint
     if (!ctx) return TGHIP_E_INVALID;
     if (!ctx->haveScene) { ctx->error = "bsdf self-test without an uploaded scene"; return TGHIP_E_INVALID; }
     if (variant < 0 || variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "bsdf self-test: unknown variant"; return TGHIP_E_INVALID; }
-    if (variant_mask) *variant_mask = debugBsdfVariantMask(uint32_t(variant));
+    if (variant_mask) *variant_mask = familyMask(uint32_t(variant));
     for (size_t i = 0; i < ctx->sc.bsdfTypes.size(); ++i) {
         if (type_mask) type_mask[i] = ctx->sc.bsdfTypes[i];
         if (forward) forward[i] = ctx->sc.bsdfForward[i];
         if (covered) covered[i] = familyCovers(uint32_t(variant), ctx->sc.bsdfTypes[i], ctx->sc.bsdfForward[i] != 0) ? 1u : 0u;
+    }
+    return TGHIP_OK;
+}
+
+// the light functions exactly as the shading kernels' next-event estimation calls them, per shading family (debug_units.hip)
+int tghip_debug_light(tghip_ctx *ctx, const TgHipLightCase *cases, TgHipLightResult *results, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (n == 0) return TGHIP_OK;
+    if (!cases || !results || n > 0x3FFFFFFFu) { ctx->error = "invalid light self-test arguments"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "light self-test without an uploaded scene"; return TGHIP_E_INVALID; }
+    uint32_t variants = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (cases[i].light < 0 || uint32_t(cases[i].light) >= ctx->scene.num_lights) { ctx->error = "light self-test: light slot outside the scene's table"; return TGHIP_E_INVALID; }
+        if (cases[i].variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "light self-test: unknown variant"; return TGHIP_E_INVALID; }
+        variants |= 1u << cases[i].variant;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TgHipLightCase *dc = nullptr;
+    TgHipLightResult *dr = nullptr;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dc), n*sizeof(TgHipLightCase)));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dr), n*sizeof(TgHipLightResult));
+    if (e == hipSuccess) e = hipMemcpyAsync(dc, cases, n*sizeof(TgHipLightCase), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dr, 0, n*sizeof(TgHipLightResult), ctx->stream);
+    if (e == hipSuccess) e = debugLightLaunch(ctx->stream, ctx->scene, dc, dr, uint32_t(n), variants);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dr, n*sizeof(TgHipLightResult), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(dc);
+    if (dr) (void)hipFree(dr);
+    if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    return TGHIP_OK;
+}
+
+int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!ctx->haveScene) { ctx->error = "light self-test without an uploaded scene"; return TGHIP_E_INVALID; }
+    if (variant < 0 || variant >= TGHIP_BSDF_VARIANT_COUNT) { ctx->error = "light self-test: unknown variant"; return TGHIP_E_INVALID; }
+    const uint32_t mask = familyMask(uint32_t(variant));
+    if (variant_mask) *variant_mask = mask;
+    for (size_t i = 0; i < ctx->sc.lightNeeds.size(); ++i) {
+        if (needs) needs[i] = ctx->sc.lightNeeds[i];
+        if (covered) covered[i] = (ctx->sc.lightNeeds[i] & ~mask) == 0u ? 1u : 0u;
     }
     return TGHIP_OK;
 }

@@ -65,6 +65,56 @@ bool familyCovers(uint32_t variant, uint32_t tm, bool fwd)
     }
 }
 
+uint32_t familyMask(uint32_t variant)
+{
+    switch (variant) {
+#define FAMILY_CASE(V, MASK) case V: return (MASK) & ~FEAT_QMC;
+    PT_FAMILY_VARIANTS(FAMILY_CASE)
+#undef FAMILY_CASE
+    default: return 0u;
+    }
+}
+
+uint32_t lightNeeds(const TgHipSceneDesc *s, uint32_t slot)
+{
+    if (slot >= s->num_lights || s->lights[slot] < 0 || uint32_t(s->lights[slot]) >= s->num_objects) return 0u;
+    const TgHipObject &o = s->objects[s->lights[slot]];
+    const int32_t tex = o.emission >= 0 && uint32_t(o.emission) < s->num_textures ? s->textures[o.emission].type : -1;
+    // chooseLight: without the bit it answers lights[0] with weight one
+    uint32_t needs = s->num_lights > 1 ? FEAT_MULTILIGHT : 0u;
+    switch (o.type) {
+    case TGHIP_OBJ_QUAD:                    // the branch every function falls into when no other is compiled
+        break;
+    case TGHIP_OBJ_CUBE: case TGHIP_OBJ_SPHERE: case TGHIP_OBJ_DISK:
+        needs |= FEAT_SOLIDS;
+        break;
+    case TGHIP_OBJ_POINT:                   // its branches of lightSampleDirect / lightApproximateRadiance sit behind the quad's, which a mask without
+        needs |= FEAT_INFINITE | FEAT_SOLIDS;   // FEAT_INFINITE takes for every light; k_shade's diracLight asks for FEAT_SOLIDS
+        break;
+    case TGHIP_OBJ_INFINITE_SPHERE_CAP:     // (lightSampleDirect / lightApproximateRadiance again; lightIntersect and lightDirectPdf settle for either bit)
+        needs |= FEAT_INFINITE;
+        break;
+    case TGHIP_OBJ_INFINITE_SPHERE:         // a skydome is one whose emission is the baked sky image
+        needs |= FEAT_INFINITE;
+        // sampled through the texture's own sample / pdf: a bitmap's tables behind FEAT_BITMAP (without it: uniform), a checker's, a disk's and a
+        // blade's where all of FEAT_FAMILY_ALL is set (HAS_PROCTEX)
+        if (tex == TGHIP_TEX_CHECKER) needs |= FEAT_FAMILY_ALL;
+        break;
+    case TGHIP_OBJ_MESH:
+        needs |= FEAT_MESHLIGHT;
+        break;
+    case TGHIP_OBJ_CYLINDER:
+        needs |= FEAT_CYLINDER;
+        break;
+    default:
+        break;
+    }
+    // lightEvalDirect looks the emission up with textureEval<M>: black for a bitmap without FEAT_BITMAP, a disk or a blade only under HAS_PROCTEX
+    if (tex == TGHIP_TEX_BITMAP) needs |= FEAT_BITMAP;
+    if (tex == TGHIP_TEX_DISK || tex == TGHIP_TEX_BLADE) needs |= FEAT_FAMILY_ALL;
+    return needs;
+}
+
 bool bsdfUsesBitmap(const TgHipSceneDesc *s, int bi, int depth)
 {
     if (bi < 0 || uint32_t(bi) >= s->num_bsdfs || depth > 16) return false;
@@ -334,6 +384,8 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
         // (an unsampled one, and a checker that is only looked up, keep the scene where it is)
         if (ty == TGHIP_OBJ_INFINITE_SPHERE && lo.emission >= 0 && sd->textures[lo.emission].type == TGHIP_TEX_CHECKER) t.haveProcTex = true;
     }
+    t.lightNeeds.assign(sd->num_lights, 0u);
+    for (uint32_t i = 0; i < sd->num_lights; ++i) t.lightNeeds[i] = lightNeeds(sd, i);
     if (sd->wide_nodes && sd->num_wide_nodes) {
         // the wide nodes and the primitive records share ONE allocation, so that a lane of the wide kernels addresses
         // "a node or a record" with one base pointer and one 32-bit offset: without room for both below 2^32 the scene walks its BVH2

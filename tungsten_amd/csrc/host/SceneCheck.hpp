@@ -31,6 +31,7 @@ struct SceneTraits {
                                           // transmittance segment by segment (the closest-hit shadow walk)
     std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex or haveFibre (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
+    std::vector<uint32_t> lightNeeds;     // per slot of lights[]: the feature bits its light code needs (lightNeeds below; tghip_debug_light_info)
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
     // equirectangular / cubemap camera: k_camera_rays rewrites the fresh camera rays before they are traced, in a launch of its own in front of every
@@ -87,6 +88,14 @@ bool bsdfHasFibre(const TgHipSceneDesc *s, int bi, int depth);   // a fibre BCSD
 // leanScene: no bitmap texture anywhere, one quad light, quads and cubes only), so for LEAN this is tghip_debug_bsdf_info's per-material reading of that
 // rule -- SIMPLE's types and no bitmap inside the material (FEAT_BITMAP in tm, set for that entry only) -- and not a site the product calls.
 bool familyCovers(uint32_t variant, uint32_t tm, bool fwd);
+// The type / feature mask of shading family `variant` (TGHIP_BSDF_VARIANT_*) without the Sobol' sampler's bit; 0 for an unknown variant.
+uint32_t familyMask(uint32_t variant);
+// The feature bits the light code needs for the sampled light in slot `slot` of s->lights: the bits the branches of its emitter type are compiled
+// behind in chooseLight / lightSampleDirect / lightApproximateRadiance / lightIntersect / lightEvalDirect / lightDirectPdf (csrc/hip/pt_scene.h) and in
+// k_shade's next-event estimation (pt_wavefront.h: diracLight, meshLight).  A family may shade a scene only if its mask holds the needs of every
+// light: a branch that folds away leaves the light to the next one that compiles -- a cube sampled as a quad --, silently.  FEAT_FAMILY_ALL stands for
+// "all four bits" (HAS_PROCTEX): a disk or blade emission, a sampled checker environment.  FEAT_MULTILIGHT whenever the scene has a second light.
+uint32_t lightNeeds(const TgHipSceneDesc *s, uint32_t slot);
 // Depth of the subtree under `root` (also validates child references).  `level`: 0 = the scene's tree (leaves: non-instance records and
 // instance-set records, which are collected in `found`), 1 = the reference's tree behind a set record (leaves: one or two slots of
 // inst_prims; the instance records behind them are collected in `found`), 2 = a master's subtree (triangles and the like only).

@@ -516,6 +516,23 @@ int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out, char *e
     return TGHIP_OK;
 }
 
+int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask)
+{
+    if (!scene || variant < 0 || variant >= TGHIP_BSDF_VARIANT_COUNT) return TGHIP_E_INVALID;
+    SceneTraits t;
+    std::string error;
+    const int rc = checkScene(scene, SceneCheckOptions(), t, error);    // (every index lightNeeds reads through)
+    if (rc != TGHIP_OK) return TGHIP_E_INVALID;
+    const uint32_t mask = familyMask(uint32_t(variant));
+    if (variant_mask) *variant_mask = mask;
+    for (uint32_t i = 0; i < scene->num_lights; ++i) {
+        const uint32_t n = lightNeeds(scene, i);
+        if (needs) needs[i] = n;
+        if (covered) covered[i] = (n & ~mask) == 0u ? 1u : 0u;
+    }
+    return TGHIP_OK;
+}
+
 tgh_pass_plan *tgh_pass_plan_create(const TgHipPassDesc *pass, uint32_t width, uint32_t height, int scene_has_sobol,
                                     uint64_t max_items, uint64_t max_slots, uint32_t chunk_samples, int *rc, char *err, size_t errlen)
 {
