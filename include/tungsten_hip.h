@@ -15,6 +15,7 @@
  *   tghip_abort             <- PathTraceIntegrator::abortRender (PathTraceIntegrator.cpp:246-256).
  *   tghip_download_framebuffer <- OutputBuffer<Vec3f>::addSample / operator[] (cameras/OutputBuffer.hpp:104-144).
  *   tghip_trace_rays        <- TraceableScene::intersect (renderer/TraceableScene.hpp:170-192), batched.
+ *   tghip_query_rays        <- TraceableScene::intersect and ::occluded (renderer/TraceableScene.hpp:170-223), batched, on host or device memory.
  *   tghip_reduce_framebuffers <- the merge of per-machine partial renders the reference does offline on the host
  *                              (src/hdrmanip/hdrmanip.cpp:69-112: load N HDR images, add, divide); here the tile shards of
  *                              one frame, summed on the device side by RCCL over xGMI.
@@ -631,6 +632,29 @@ int tghip_comm_unique_id(void *id, size_t bytes);
 int tghip_comm_init_rank(tghip_ctx *ctx, const void *id, size_t bytes, int nranks, int rank);
 int tghip_reduce_framebuffer_rank(tghip_ctx *ctx, int root, float *rgb_sum, uint32_t *count, size_t npixels);
 int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_t n, int repeats, double *ms_per_launch);
+/* Batched ray queries against the uploaded scene (TraceableScene::intersect and ::occluded, renderer/TraceableScene.hpp:170-223), on host memory or on
+ * memory of the context's device, by kernels of their own (csrc/hip/ray_query.hip: persistent workgroups that claim rays from one counter as their
+ * lanes fall idle).
+ *   mode    TGHIP_QUERY_CLOSEST: out = n TgHipHit; for every ray what tghip_trace_rays returns on the same context -- rec, and on a hit t, u, v, bit
+ *           for bit -- in every kind of scene (flat list with or without the top-level tree, BVH2, 8-wide BVH, `instances` in the reference's
+ *           visiting order).  Infinite emitters are never hit.
+ *           TGHIP_QUERY_OCCLUDED: out = n bytes, 1 exactly when the closest-hit query of the same ray has rec >= 0, else 0: the closest-hit
+ *           formulation of the path tracer's shadow rays (TraceBase.cpp:79, 114-115) over geometry only -- no light is left out, nothing is
+ *           transparent; not the primitives' own `occluded` routines.
+ *   flags   0: rays and out are host memory (staged through buffers of the context that only grow); TGHIP_DEVELOP_DEVICE_POINTERS: both are memory
+ *           of the context's device, rays and hits 16-byte aligned, occlusion bytes unaligned.
+ * A ray with a non-finite component or a zero direction gets an unspecified answer; the call returns.  Runs on the context's stream, waits for a
+ * running pass like tghip_develop, returns when the answers are complete (device memory: the kernel has finished, the caller's streams need no
+ * further synchronisation) and allocates nothing per call.  n == 0 succeeds.  TGHIP_E_NOSCENE without an upload.  TGHIP_E_INVALID, the context still
+ * usable: no description, NULL rays or out with n > 0, an unknown mode, unknown flag bits, non-zero reserved words, n > 2^31 - 1, misaligned device
+ * pointers (tungsten_host.h: tgh_query_rays_check is the same check on its own).  The options "query_blocks" (workgroups; 0 = the measured default)
+ * and "query_refill_at" (1..64: idle lanes of a wave at which it claims; 0 = the measured default) steer the kernel and never change an answer.
+ * tghip_trace_rays and its exact visit counts stay as they are; these queries count no visits. */
+enum { TGHIP_QUERY_CLOSEST = 0, TGHIP_QUERY_OCCLUDED = 1 };
+typedef struct TgHipRayQueryDesc { uint32_t mode, flags, reserved[2]; } TgHipRayQueryDesc;   /* flags: TGHIP_DEVELOP_DEVICE_POINTERS */
+int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipRay *rays, void *out, size_t n);
+/* Instrumentation: HIP-event time of the kernel of the context's last tghip_query_rays, in milliseconds (profiles/ray_query_ab.txt) */
+int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

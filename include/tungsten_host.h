@@ -225,6 +225,10 @@ const uint32_t *tgh_pass_plan_sorted(tgh_pass_plan *p, uint32_t *n);
 const uint32_t *tgh_pass_plan_chunk_starts(tgh_pass_plan *p, uint32_t *n);
 void tgh_pass_plan_free(tgh_pass_plan *p);
 
+/* What tghip_query_rays decides about a call before it touches the device (csrc/host/RayQuery.cpp), on its own, no device and no scene: TGHIP_OK, or
+ * TGHIP_E_INVALID and in `err` the refusal's message.  Only the pointers' values are looked at, nothing is read through them. */
+int tgh_query_rays_check(const TgHipRayQueryDesc *desc, const void *rays, const void *out, size_t n, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

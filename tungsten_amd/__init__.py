@@ -35,6 +35,7 @@ LIGHT_RESULT_DTYPE = np.dtype([("chosen", np.int32), ("choose_weight", np.float3
                                ("sample_next", np.float32), ("reserved", np.uint32, 4)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
+QUERY_MODE_NAMES = ("closest", "occluded")                                  # capi.TGHIP_QUERY_*
 DEVELOP_PART_NAMES = ("mean", "a", "b", "variance")                          # capi.TGHIP_DEVELOP_*
 AUX_OUTPUT_NAMES = ("color", "depth", "normal", "albedo", "visibility")      # capi.TGHIP_AUX_*
 
@@ -153,6 +154,42 @@ class Renderer(object):
         if rc != 0:
             raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
         return hits, ms.value
+
+    def query_rays(self, rays, mode="closest", device=0):
+        """Batched TraceableScene::intersect / ::occluded (tghip_query_rays): rays [N,8] float32 (o, tmin, d, tmax) -> with mode "closest" the
+        structured hits of trace_rays (t, u, v, rec; the same bits), with "occluded" uint8 [N]: 1 where the closest-hit query has a hit."""
+        if mode not in QUERY_MODE_NAMES:
+            raise TungstenError("query_rays: mode must be 'closest' or 'occluded', not %r" % (mode,))
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if mode == "closest":
+            out = np.empty(rays.shape[0], dtype=[("t", np.float32), ("u", np.float32), ("v", np.float32), ("rec", np.int32)])
+        else:
+            out = np.empty(rays.shape[0], np.uint8)
+        desc = capi.TgHipRayQueryDesc(QUERY_MODE_NAMES.index(mode), 0)
+        ctx = self.context(device)
+        if lib.tghip_query_rays(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def query_rays_into(self, rays, out, mode="closest", device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 [N,4] for
+        "closest" (t, u, v and in the last column rec's bits) or uint8 [N] for "occluded", both contiguous.  The answers are complete when
+        the call returns."""
+        if mode not in QUERY_MODE_NAMES:
+            raise TungstenError("query_rays_into: mode must be 'closest' or 'occluded', not %r" % (mode,))
+        closest = mode == "closest"
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        for name, t, dtype, size in (("rays", rays, "torch.float32", 8), ("out", out, "torch.float32" if closest else "torch.uint8", 4 if closest else 1)):
+            if str(t.dtype) != dtype:
+                raise TungstenError("query_rays_into: %s must be %s, not %s" % (name, dtype, t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("query_rays_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("query_rays_into: rays must be contiguous [N, 8] and out contiguous with N x %d elements" % (4 if closest else 1))
+        desc = capi.TgHipRayQueryDesc(QUERY_MODE_NAMES.index(mode), capi.TGHIP_DEVELOP_DEVICE_POINTERS)
+        ctx = self.context(device)
+        if lib.tghip_query_rays(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
 
     def debug_libm(self, fn, x, device=0):
         """The device's restatement of a host libm function (capi.TGHIP_LIBM_*) evaluated on the device: float32 in, float32 out."""

@@ -199,6 +199,13 @@ class TgHipHit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("rec", i32)]
 
 
+TGHIP_QUERY_CLOSEST, TGHIP_QUERY_OCCLUDED = 0, 1
+
+
+class TgHipRayQueryDesc(C.Structure):
+    _fields_ = [("mode", u32), ("flags", u32), ("reserved", u32*2)]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -254,6 +261,8 @@ PROTOTYPES = {
     "tghip_nlmeans_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_reduce_framebuffers": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, VP, VP, C.c_size_t]),
     "tghip_trace_rays": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
+    "tghip_query_rays": (C.c_int, [VP, C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t]),
+    "tghip_query_rays_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -326,6 +335,7 @@ PROTOTYPES = {
     "tgh_pass_plan_sorted": (C.POINTER(u32), [VP, C.POINTER(u32)]),
     "tgh_pass_plan_chunk_starts": (C.POINTER(u32), [VP, C.POINTER(u32)]),
     "tgh_pass_plan_free": (None, [VP]),
+    "tgh_query_rays_check": (C.c_int, [C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

@@ -5,8 +5,10 @@
 #include "debug_units.h"
 #include "denoise.h"
 #include "develop.h"
+#include "ray_query.h"
 #include "../host/SceneCheck.hpp"
 #include "../host/PassPlan.hpp"
+#include "../host/RayQuery.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -298,6 +300,14 @@ struct tghip_ctx {
     size_t nlmCap[4] = {0, 0, 0, 0};
     uint32_t nlmBatch = 0;
     double nlmMs = 0.0;
+    // tghip_query_rays: the work counter the kernel's workgroups claim rays from (one word, reset in-stream before every launch), the rays and the
+    // answers on the device when they are the caller's host memory (grown on demand), the "query_blocks" / "query_refill_at" options (0: the
+    // measured defaults, RAY_QUERY_BLOCKS_PER_CU / RAY_QUERY_REFILL_AT), the kernel's time
+    uint32_t *queryCounter = nullptr;
+    float4 *queryRays = nullptr, *queryOut = nullptr;
+    size_t queryRaysCap = 0, queryOutCap = 0;
+    int queryBlocks = 0, queryRefillAt = 0;
+    double queryMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context
     int rankCount = 0, rankIndex = 0;
     float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
@@ -814,6 +824,9 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->developLdr) (void)hipFree(ctx->developLdr);
     if (ctx->developMax) (void)hipFree(ctx->developMax);
     for (float *b : ctx->nlmBuf) if (b) (void)hipFree(b);
+    if (ctx->queryCounter) (void)hipFree(ctx->queryCounter);
+    if (ctx->queryRays) (void)hipFree(ctx->queryRays);
+    if (ctx->queryOut) (void)hipFree(ctx->queryOut);
     if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
     if (ctx->redSum) (void)hipFree(ctx->redSum);
@@ -911,6 +924,8 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "shade_fused") ctx->shadeFusedOpt = value != 0;
     else if (k == "develop_host") ctx->developHost = value != 0;   // tghip_develop answers TGHIP_E_UNSUPPORTED: the host integrator then develops a download itself
     else if (k == "nlmeans_batch") ctx->nlmBatch = uint32_t(std::min<long long>(std::max<long long>(value, 0), NLMEANS_MAX_BATCH));   // offsets box-filtered at once by tghip_nlmeans (0: the measured choice, denoise.hip)
+    else if (k == "query_blocks") ctx->queryBlocks = int(std::min<long long>(std::max<long long>(value, 0), 1 << 16));       // workgroups of tghip_query_rays (0: the measured default)
+    else if (k == "query_refill_at") ctx->queryRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 64));   // idle lanes of a wave at which it claims rays (0: the measured default)
     else if (k == "run_to_completion") ctx->loopOpt = value != 0;
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
@@ -2313,6 +2328,62 @@ int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_
     (void)hipFree(dRays); (void)hipFree(dHits);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
     if (ms_per_launch) *ms_per_launch = double(ms)/repeats;
+    return TGHIP_OK;
+}
+
+// Idle lanes of a wave at which the wide walk of tghip_query_rays claims new rays, and its workgroups per CU (swept: profiles/ray_query_ab.txt)
+#define RAY_QUERY_REFILL_AT 48
+#define RAY_QUERY_BLOCKS_PER_CU 2
+
+int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipRay *rays, void *out, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    int rc = checkRayQuery(desc, rays, out, n, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    if (!ctx->haveScene) { ctx->error = "tghip_query_rays before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    if (n == 0) return TGHIP_OK;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool occluded = desc->mode == TGHIP_QUERY_OCCLUDED, device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    const size_t outBytes = occluded ? n : n*sizeof(TgHipHit);
+    if (!ctx->queryCounter) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->queryCounter), 64));
+    const float4 *dRays = reinterpret_cast<const float4 *>(rays);
+    void *dOut = out;
+    if (!device) {
+        int grc;
+        if ((grc = growArray(ctx, ctx->queryRays, ctx->queryRaysCap, n*2)) != TGHIP_OK) return grc;
+        if ((grc = growArray(ctx, ctx->queryOut, ctx->queryOutCap, (outBytes + sizeof(float4) - 1)/sizeof(float4))) != TGHIP_OK) return grc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->queryRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream));
+        dRays = ctx->queryRays;
+        dOut = ctx->queryOut;
+    }
+    // the walk tghip_trace_rays answers with on this scene, and its stack
+    const bool wide = useWide(ctx) && !ctx->sc.haveInstances;
+    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : ctx->sc.haveInstances ? RAY_QUERY_INST : isFlat(ctx) ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
+                            : std::max<size_t>(traceLdsBytes(ctx, RAY_QUERY_THREADS), sizeof(int));
+    // workgroups: as many as stay resident, no more than the batch has waves for (a workgroup without a ray only reads the counter)
+    const size_t perWave = (n + 63)/64;
+    const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
+                                                 : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
+    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter, 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    HIP_TRY(ctx, rayQueryLaunch(ctx->stream, ctx->scene, walk, occluded, dRays, dOut, uint32_t(n), ctx->queryCounter, blocks, refillAt, lds));
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    if (!device) HIP_TRY(ctx, hipMemcpyAsync(out, dOut, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
+    ctx->queryMs = ms;
+    return TGHIP_OK;
+}
+
+int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->queryMs;
     return TGHIP_OK;
 }
 
