@@ -739,6 +739,44 @@ int tghip_debug_light(tghip_ctx *ctx, const TgHipLightCase *cases, TgHipLightRes
  * the bits are those of csrc/hip/pt_variants.h: FEAT_SOLIDS, FEAT_INFINITE, FEAT_BITMAP, FEAT_MESHLIGHT, FEAT_CYLINDER, the four bits of FEAT_FAMILY_ALL
  * together, FEAT_MULTILIGHT), covered = 1 when the variant's mask holds them all.  variant_mask (one word): the mask the variant's kernel is compiled for. */
 int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
+/* Which kernels a pass runs on a scene, as the context decides it once per upload, option and kind of pass (csrc/host/LaunchChoice.cpp; tungsten_host.h:
+ * tgh_launch_choice answers the same without a device and documents the fields). */
+#define TGHIP_KERNEL_NAME_LEN 80
+typedef struct TgHipWalkLaunch {
+    char name[TGHIP_KERNEL_NAME_LEN], sized_by[TGHIP_KERNEL_NAME_LEN];
+    int32_t lds_formula, sized_lds_formula, max_threads, fixed_threads;
+} TgHipWalkLaunch;
+typedef struct TgHipShadeLaunch {
+    char name[TGHIP_KERNEL_NAME_LEN];
+    int32_t cls, variant;            /* the launch's class argument (4: the escaped paths, 5: class 0 and the escaped paths); TGHIP_BSDF_VARIANT_* of its family */
+    uint32_t mask;                   /* the family's mask, with the Sobol' sampler's bit where the pass runs that twin */
+    int32_t fuse, global_tables;     /* k_shade's FUSE bits and GLOBAL_TABLES */
+    int32_t size, lane;              /* its workgroup size: shade_size[size] (0 simple, 1 complex, 2 all); "class_streams": 0 the part's stream, 1 / 2 beside it */
+} TgHipShadeLaunch;
+typedef struct TgHipShadeSize { char sized_by[TGHIP_KERNEL_NAME_LEN]; int32_t max_threads, fixed_threads; } TgHipShadeSize;
+typedef struct TgHipLaunchChoice {
+    int32_t flat, fused_flat, one_launch, paired, paired_inst, blocks_per_cu, parts;   /* parts: wanted, before the grid and the batch's items are asked */
+    int32_t slot_cap, order_regs_cap, walk_arrays, fold_finish, nee_factors, camera_rays, tables_fit;
+    TgHipWalkLaunch closest, shadow;                    /* empty names when fused_flat */
+    int32_t num_shade, fused_pair, shade_launches;       /* entries of shade[]; the further class of k_shade_fused or 0; launches the counters book per iteration */
+    TgHipShadeLaunch shade[6];
+    TgHipShadeSize shade_size[3];
+    int32_t tail_eligible, reserved;                     /* before the occupancy probe */
+    char tail[TGHIP_KERNEL_NAME_LEN], tail_probe[TGHIP_KERNEL_NAME_LEN], camera_rays_name[TGHIP_KERNEL_NAME_LEN];
+    int32_t ray_walk, reserved2;                         /* tghip_trace_rays / tghip_query_rays: 0 flat list, 1 BVH2, 2 instances, 3 wide BVH */
+    char trace_rays[TGHIP_KERNEL_NAME_LEN];
+} TgHipLaunchChoice;
+/* What the context would launch for `pass` on the uploaded scene -- nothing is launched, no pool is allocated: the choice, the workgroup sizes the
+ * occupancy of this device gives (threads_shade: simple / complex / all), the dynamic LDS bytes of the walk launches, the persistent grid, the parts the
+ * loop runs as when the batch has items enough, and whether a workgroup of k_tail fits a CU.  TGHIP_E_INVALID for a pass tghip_render_pass refuses. */
+typedef struct TgHipLaunchPlan {
+    TgHipLaunchChoice choice;
+    int32_t threads_closest, threads_shadow, threads_shade[3], threads_tail;
+    uint32_t lds_closest, lds_shadow, lds_tail;
+    uint32_t grid;
+    int32_t parts, tail_fits;
+} TgHipLaunchPlan;
+int tghip_debug_launch_plan(tghip_ctx *ctx, const TgHipPassDesc *pass, TgHipLaunchPlan *out);
 int tghip_set_option(tghip_ctx *ctx, const char *key, long long value);  /* "count_traversal", "max_slots", ...; "top_tree" = 0 before an upload:
                                                                              TgHipSceneDesc::top_nodes is ignored, flat lists are walked in record order.
                                                                              Instrumentation that never changes an image (tests hold that): "lds_tables" = 0

@@ -189,6 +189,16 @@ int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may b
  * them; variant_mask: that mask.  Any output pointer may be NULL.  TGHIP_E_INVALID for no scene, an unknown variant or a description tgh_scene_check refuses. */
 int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
 
+/* Which kernels a pass runs on a scene (csrc/host/LaunchChoice.cpp), on its own, no device: the choice tghip_wait makes for a pass with the flags `pass_flags`
+ * (TGHIP_PASS_*), short or not (TgHostPassPlan::short_batch), under the options keys[i] = values[i] (tghip_set_option's keys; "count_traversal" among them)
+ * over the defaults.  Kernels are named in one canonical spelling -- every template argument, no blanks, masks as the decimal numbers of
+ * csrc/hip/pt_variants.h: k_trace_closest_wide<false,false,false,true> --; a launch that does not happen has an empty name.  lds_formula: 0 none, 1 the BVH2
+ * walks' stack over the queue, 2 the dynamic-fetch walks' queue + stack, 3 the wide walks' queue + group stack, 4 k_trace_closest_instw's.  A workgroup size is
+ * `fixed_threads`, or (0) the largest multiple of 64 from max_threads down at which blocks_per_cu workgroups of `sized_by` are resident.  TGHIP_E_INVALID for
+ * no scene or no `out`, an option the choice does not read, or a description tgh_scene_check refuses. */
+int tgh_launch_choice(const TgHipSceneDesc *scene, const char *const *keys, const long long *values, uint32_t num_options,
+                      uint32_t pass_flags, int short_batch, TgHipLaunchChoice *out /* tungsten_hip.h */, char *err, size_t errlen);
+
 /* What tghip_render_pass and tghip_wait decide about a pass before they touch the device (csrc/host/PassPlan.cpp), on its own, no device: the plan of
  * `pass` for a width x height image under the options "max_items", "max_slots" and "chunk_samples" -- or NULL, in *rc (may be NULL) the refusal's code
  * (TGHIP_E_INVALID from the checks of tghip_render_pass, TGHIP_E_UNSUPPORTED for a pass past 2^32 samples or items) and in `err` its message.

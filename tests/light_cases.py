@@ -382,12 +382,12 @@ def device_words(r):
 
 def families_for(t):
     """The shading families the launch code may pick for a scene with the traits t (capi.TgHostSceneTraits), in the order it decides
-    (tungsten_hip.hip: shadeClass, launchComplexClass, the fused flat launches, k_tail): the all-features family for a scene with cylinders, bump maps,
+    (csrc/host/LaunchChoice.cpp: the class families, the fused flat launches, k_tail): the all-features family for a scene with cylinders, bump maps,
     procedural textures or fibres, for a media scene the lean media family covers not, and for every auxiliary-output pass; the media family; the full
     family for mesh emitters and, next to the class families, for instances; else LEAN or SIMPLE for class 0 and COAT / GLASS / PLASTIC / TAIL
     (a superset of the launches of any one scene: which of them run depends on the materials, which no light cares about).  The `_INST` twins of
     SIMPLE / COAT / GLASS / PLASTIC that instanced scenes launch differ from them in FEAT_INSTANCES alone, a bit no light needs: SIMPLE ... stand for them.
-    A restatement: tungsten_hip.hip points here from shadeClass, and a change of that decision has to be made here as well."""
+    A restatement, and a superset on purpose: tests/test_launch_choice_cpu.py holds the families the launch choice names (csrc/host/LaunchChoice.cpp) to it."""
     fams = {ALL}
     if t.all_features_shading:
         return fams

@@ -232,6 +232,55 @@ class TgHostPassBatch(C.Structure):
     _fields_ = [(n, u32) for n in ("spp_begin", "spp_end", "chunks", "pix_slots", "total_items", "first_tile", "item_base")]
 
 
+TGHIP_KERNEL_NAME_LEN = 80
+_NAME = C.c_char*TGHIP_KERNEL_NAME_LEN
+
+
+class TgHipWalkLaunch(C.Structure):
+    _fields_ = [("name", _NAME), ("sized_by", _NAME)] + [(n, i32) for n in ("lds_formula", "sized_lds_formula", "max_threads", "fixed_threads")]
+
+
+class TgHipShadeLaunch(C.Structure):
+    _fields_ = [("name", _NAME), ("cls", i32), ("variant", i32), ("mask", u32), ("fuse", i32), ("global_tables", i32), ("size", i32), ("lane", i32)]
+
+
+class TgHipShadeSize(C.Structure):
+    _fields_ = [("sized_by", _NAME), ("max_threads", i32), ("fixed_threads", i32)]
+
+
+class TgHipLaunchChoice(C.Structure):
+    """Which kernels a pass runs on a scene (csrc/host/LaunchChoice.cpp; include/tungsten_host.h: tgh_launch_choice documents the fields)."""
+    _fields_ = [(n, i32) for n in ("flat", "fused_flat", "one_launch", "paired", "paired_inst", "blocks_per_cu", "parts",
+                                   "slot_cap", "order_regs_cap", "walk_arrays", "fold_finish", "nee_factors", "camera_rays", "tables_fit")] + \
+               [("closest", TgHipWalkLaunch), ("shadow", TgHipWalkLaunch), ("num_shade", i32), ("fused_pair", i32), ("shade_launches", i32),
+                ("shade", TgHipShadeLaunch*6), ("shade_size", TgHipShadeSize*3), ("tail_eligible", i32), ("reserved", i32),
+                ("tail", _NAME), ("tail_probe", _NAME), ("camera_rays_name", _NAME), ("ray_walk", i32), ("reserved2", i32), ("trace_rays", _NAME)]
+
+    def kernel_names(self):
+        """The kernels an iteration of the pass launches, k_tail where the pass may end in it, and k_camera_rays: the names a kernel trace of a render shows
+        (next to the fixed kernels around the loop: k_start, k_finish, k_resolve ...)."""
+        names = [l.name for l in self.shade[:self.num_shade]] + [self.tail, self.camera_rays_name]
+        if not self.fused_flat:
+            names += [self.closest.name, self.shadow.name]
+        return {n.decode() for n in names if n}
+
+
+class TgHipLaunchPlan(C.Structure):
+    _fields_ = [("choice", TgHipLaunchChoice), ("threads_closest", i32), ("threads_shadow", i32), ("threads_shade", i32*3), ("threads_tail", i32),
+                ("lds_closest", u32), ("lds_shadow", u32), ("lds_tail", u32), ("grid", u32), ("parts", i32), ("tail_fits", i32)]
+
+
+def launch_choice(lib, desc, options=(), pass_flags=0, short_batch=False):
+    """tgh_launch_choice for the scene description `desc` under options = {key: value} (or pairs): the TgHipLaunchChoice, or ValueError with the refusal."""
+    pairs = list(dict(options).items())
+    keys = (C.c_char_p*max(len(pairs), 1))(*[k.encode() for k, _ in pairs])
+    values = (C.c_longlong*max(len(pairs), 1))(*[int(v) for _, v in pairs])
+    out, err = TgHipLaunchChoice(), C.create_string_buffer(512)
+    if lib.tgh_launch_choice(desc, keys, values, len(pairs), int(pass_flags), int(bool(short_batch)), C.byref(out), err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return out
+
+
 # every symbol the two headers declare: name -> (restype, argtypes)
 VP = C.c_void_p
 TGHIP_COMM_ID_BYTES = 128
@@ -268,6 +317,7 @@ PROTOTYPES = {
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
     "tghip_debug_light": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_light_info": (C.c_int, [VP, C.c_int, VP, VP, VP]),
+    "tghip_debug_launch_plan": (C.c_int, [VP, C.POINTER(TgHipPassDesc), C.POINTER(TgHipLaunchPlan)]),
     "tghip_set_option": (C.c_int, [VP, C.c_char_p, C.c_longlong]),
     "tghip_get_counters": (C.c_int, [VP, C.POINTER(TgHipCounters)]),
     "tghip_reset_counters": (C.c_int, [VP]),
@@ -325,6 +375,8 @@ PROTOTYPES = {
     "tgh_leaf_bounds": (C.c_int, [VP, C.c_uint32, VP, VP]),
     "tgh_scene_check": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(TgHostSceneTraits), C.c_char_p, C.c_size_t]),
     "tgh_light_needs": (C.c_int, [C.POINTER(TgHipSceneDesc), C.c_int, VP, VP, VP]),
+    "tgh_launch_choice": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), u32, u32, C.c_int,
+                                    C.POINTER(TgHipLaunchChoice), C.c_char_p, C.c_size_t]),
     "tgh_pass_plan_create": (VP, [C.POINTER(TgHipPassDesc), u32, u32, C.c_int, u64, u64, u32, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),
     "tgh_pass_plan_info": (None, [VP, C.POINTER(TgHostPassPlan)]),
     "tgh_pass_plan_batches": (C.POINTER(TgHostPassBatch), [VP, C.POINTER(u32)]),

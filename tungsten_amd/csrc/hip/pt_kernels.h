@@ -50,14 +50,8 @@ enum { ST_DONE = 0, ST_ACTIVE = 1, ST_TERMINATED = 2, ST_TERMINATED_BLACK = 3 };
 // shadow-ray tag of a media scene: light object (16 bits) | medium the ray starts in + 1 (8 bits) | bounce (8 bits)
 #define SHADOW_TAG_MEDIA(light, medium, bounce) ((uint32_t)(light) | ((uint32_t)((medium) + 1) << 16) | ((uint32_t)(bounce) << 24))
 
-// the shading classes (pt_variants.h: PT_NUM_CLASSES) as queue indices; CLS_MISS: the path's ray left the scene
-#define CLS_MISS 4
-#define CLS_0_AND_MISS 5   /* a k_shade launch that consumes the queue of class 0 and, behind it, the escaped paths' (same shading variant) */
 #ifndef PT_ITEM_GROUP
 #define PT_ITEM_GROUP  64u        // consecutive work items handed to one workgroup (a wave's worth of pixels)
-#endif
-#ifndef PT_MAX_SLOTS_PER_BLOCK
-#define PT_MAX_SLOTS_PER_BLOCK 4096u
 #endif
 #define PT_MAX_WORDS   (PT_MAX_SLOTS_PER_BLOCK/32u)
 

@@ -27,7 +27,7 @@
 #define FEAT_SOLIDS     (1u << 28)   /* sphere records; sphere / cube emitters as sampled lights       */
 #define FEAT_ALL        (FEAT_BITMAP | FEAT_INFINITE | FEAT_MULTILIGHT | FEAT_TRIANGLES | FEAT_SOLIDS)
 #define FEAT_MESHLIGHT  (1u << 29)   /* triangle-mesh emitters as sampled lights: only in the MASK_FULL / BSDF_MASK_ALL variants */
-#define FEAT_QMC        (1u << 30)   /* TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS passes: every variant has a twin with this bit (launchShade) */
+#define FEAT_QMC        (1u << 30)   /* TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS passes: every variant has a twin with this bit (csrc/host/LaunchChoice.cpp) */
 #define FEAT_INSTANCES  (1u << 31)   /* hits reached through an instance record (primitives/Instance.cpp): only in MASK_FULL / BSDF_MASK_ALL */
 #define FEAT_MEDIA      (1u << 23)   /* participating media (media/HomogeneousMedium.cpp): only in the BSDF_MASK_ALL variant */
 #define FEAT_AUX        (1u << 22)   /* TGHIP_PASS_AUX passes (auxiliary output buffers): only in the BSDF_MASK_ALL variant */
@@ -87,6 +87,30 @@
 // family (MASK_GLASS: dielectric, rough dielectric), 3: everything else (plastics, mixed, transparency, forward: MASK_PLASTIC when that
 // covers them, else every type); CLS_MISS: the path's ray left the scene.  One queue and one launch per class that occurs in the scene.
 #define PT_NUM_CLASSES 4
+
+// What the host-side launch choice (csrc/host/LaunchChoice.cpp) reads next to the masks above: the queue indices of a k_shade launch, the FUSE bits of
+// the flat lists' launches, the waves per SIMD of the shading variants (a template argument, so part of a kernel's name) and the slot limit of a workgroup.
+// the shading classes (pt_variants.h: PT_NUM_CLASSES) as queue indices; CLS_MISS: the path's ray left the scene
+#define CLS_MISS 4
+#define CLS_0_AND_MISS 5   /* a k_shade launch that consumes the queue of class 0 and, behind it, the escaped paths' (same shading variant) */
+#define FUSE_TRACE  1
+#define FUSE_SHADOW 2
+#define FUSE_LOOP   4
+// waves per SIMD the shading-kernel variants are bounded for (their BSDF type sets: pt_variants.h)
+#ifndef SIMPLE_WAVES
+#define SIMPLE_WAVES 3   /* measured: 4 waves/SIMD (128 VGPRs, spills) is 10 % slower on materialtest's k_shade */
+#endif
+#ifndef COAT_WAVES
+#define COAT_WAVES   3   /* round 4, without Phong's pow(double) in the family variants (197 VGPRs at 2 waves/SIMD; 168 + 72 B of scratch at 3):
+                            materialtest 968.3 / 969.4 -> 977.8 / 974.5, mesh1m 616.9 / 614.2 -> 622.7 / 621.7 Msamples/s (two libraries alternated
+                            twice in one session, profiles/r4_ab_coat_waves.txt); round 3 had measured 3 waves as neutral at 223 VGPRs */
+#endif
+#ifndef LEAN_WAVES
+#define LEAN_WAVES   2   /* measured: 2 waves/SIMD without scratch beats 3 with 108 B of scratch (kernel is VALU-bound) */
+#endif
+#ifndef PT_MAX_SLOTS_PER_BLOCK
+#define PT_MAX_SLOTS_PER_BLOCK 4096u
+#endif
 
 // Guide tables (built at upload, SceneCheck.cpp) make the two CDF inversions of Distribution2D::warp short dependent
 // chains instead of 9- and 10-step binary searches over L2-resident arrays: for a CDF a[0..n] and B buckets,

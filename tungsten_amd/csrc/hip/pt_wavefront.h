@@ -55,19 +55,6 @@
             atomicAdd(&wk_[20], (unsigned long long)hi_); atomicAdd(&wk_[21], (unsigned long long)ra_); \
         } } while (0)
 
-// waves per SIMD the shading-kernel variants are bounded for (their BSDF type sets: pt_variants.h)
-#ifndef SIMPLE_WAVES
-#define SIMPLE_WAVES 3   /* measured: 4 waves/SIMD (128 VGPRs, spills) is 10 % slower on materialtest's k_shade */
-#endif
-#ifndef COAT_WAVES
-#define COAT_WAVES   3   /* round 4, without Phong's pow(double) in the family variants (197 VGPRs at 2 waves/SIMD; 168 + 72 B of scratch at 3):
-                            materialtest 968.3 / 969.4 -> 977.8 / 974.5, mesh1m 616.9 / 614.2 -> 622.7 / 621.7 Msamples/s (two libraries alternated
-                            twice in one session, profiles/r4_ab_coat_waves.txt); round 3 had measured 3 waves as neutral at 223 VGPRs */
-#endif
-#ifndef LEAN_WAVES
-#define LEAN_WAVES   2   /* measured: 2 waves/SIMD without scratch beats 3 with 108 B of scratch (kernel is VALU-bound) */
-#endif
-
 // Finalises the finished sample of every lane with `finished` set (OutputBuffer::addSample semantics,
 // cameras/OutputBuffer.hpp:104-107: NaN/Inf samples are dropped without counting; PathTracer.cpp:119-122,
 // 130-131: NaN radiance turns the sample black), moves the slot to its next sample or -- when its work item is
@@ -1412,9 +1399,6 @@ PT_DEV void auxPostLoop(const DeviceScene &s, f3 dir, bool asked, int bounce, fl
     }
 }
 
-#define FUSE_TRACE  1
-#define FUSE_SHADOW 2
-#define FUSE_LOOP   4
 // (the kernel's body as a function of the workgroup's LDS objects: k_shade below and k_tail run it; returns whether the workgroup's
 // extension queues hold work -- the FUSE launches report it)
 // STAGED: sg's small tables are in LDS already (k_tail stages them once for all its iterations)
@@ -2050,7 +2034,7 @@ __global__ __launch_bounds__(256, W) void k_shade(DeviceScene sg, PathState st, 
     __shared__ unsigned short order[PT_MAX_SLOTS_PER_BLOCK];
     (void)shadeBody<M, FUSE, false, GLOBAL_TABLES>(sg, st, pp, cls, L, ldsTables, order);
 }
-// The shading of a whole iteration in one launch, for single-level scenes with class 0 and exactly ONE further class (the shim: shadeFusedPair): every
+// The shading of a whole iteration in one launch, for single-level scenes with class 0 and exactly ONE further class (csrc/host/LaunchChoice.cpp: fusedPair): every
 // workgroup stages the scene tables once, shades its queue of the further class `clsFurther` with that class's variant MF, then its class-0 queue and
 // its escaped paths with the class-0 variant M0, and writes the queue bitmaps back once.  The two launches this replaces are independent -- disjoint
 // queues of disjoint slots -- but ran one after the other on the part's stream: a second table copy, a second queue prologue and epilogue, and a

@@ -7,12 +7,14 @@
 #include "develop.h"
 #include "ray_query.h"
 #include "../host/SceneCheck.hpp"
+#include "../host/LaunchChoice.hpp"
 #include "../host/PassPlan.hpp"
 #include "../host/RayQuery.hpp"
 
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <tuple>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded with dlopen at the first multi-GPU reduce
@@ -193,6 +195,17 @@ struct DeviceBuffers {
     void release() { for (void *p : allocs) (void)hipFree(p); allocs.clear(); }
 };
 
+// a launch of the plan: the kernel, its workgroup size and dynamic LDS bytes (the grid is the pool's, or a part of it)
+struct ResolvedLaunch { const void *fn = nullptr; int threads = 0; size_t lds = 0; };
+// what planLaunches made of the choice (csrc/host/LaunchChoice.hpp) on this device
+struct LaunchPlan {
+    PassKind kind;
+    LaunchChoice choice;
+    ResolvedLaunch closest, shadow, shade[2 + PT_NUM_CLASSES], tail;
+    int thrShade[3] = {192, 128, 256};    // workgroup sizes of the shading launches, by ShadeSize
+    bool tailFits = false;                // a workgroup of k_tail fits a CU
+};
+
 } // namespace
 
 struct tghip_ctx {
@@ -201,13 +214,8 @@ struct tghip_ctx {
     hipStream_t partStream[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams of parts 1..3 of the split wavefront loop ("streams" option)
     hipStream_t classStream[8][2] = {};   // per part: the streams of the shading classes that run beside the part's own ("class_streams" option)
     hipEvent_t evFork[8] = {}, evJoin[8][2] = {};
-    bool shortBatch = false;              // the pass being rendered does not fill the pool once: one stream, 4 workgroups per CU (tghip_render_pass)
-    int instSimpleOpt = 1;                // "inst_simple": classes 0 / 2 of instanced scenes on the MASK_SIMPLE_INST variant instead of MASK_FULL
-    int classStreamsOpt = 0;              // measured: 735-800 Msamples/s against 825-830 with the classes one after the other on the part's stream
     hipStream_t launchStream = nullptr;   // where the launch helpers put their kernels (stream, or the stream of the part being launched)
     hipEvent_t evPart[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, evMain = nullptr;
-    int streamsOpt = 0;                   // "streams": 1 .. 4 parts of the pool on as many streams, 0 = the measured default (four for single-level
-                                          // BVH scenes; instanced scenes lose 2.5 % with two)
     hipDeviceProp_t prop;
     std::string error = "no error";
 
@@ -216,28 +224,13 @@ struct tghip_ctx {
     DeviceBuffers sceneMem;
     DeviceScene scene;
     SceneTraits sc;                       // what checkScene decided about it (csrc/host/SceneCheck.hpp): the facts the launch code branches on, the derived tables
-    bool wideOpt = true;                  // "wide_bvh" option: use it when the scene carries one
-    // "wide_closest" / "wide_shadow": which kernels walk the wide BVH when the scene has one.  -1 = the measured default:
-    // both, except that closest-hit rays of instanced scenes stay on the two-level BVH2 kernel (instances10k 1080p, one MI355X:
-    // closest-hit 849 us per launch on the BVH2 against 1061 us on the wide tree -- every instance entered costs the wide
-    // walk extra turns --, shadow rays 905 against 517 us)
-    int instDynOpt = 1;                   // "inst_dyn": closest-hit rays of instanced scenes on the dynamic-fetch kernel (k_trace_closest_inst) instead of the static one
-    int instWideOpt = 1;                  // "inst_wide": ... with the masters' subtrees walked through the wide BVH (k_trace_closest_instw); 0 = the BVH2 walk of round 5
+    LaunchOptions opt;                    // the options the choice of a pass's kernels reads (csrc/host/LaunchChoice.hpp) ...
+    LaunchPlan lp;                        // ... and what the last upload, option or pass of another kind made of them: choice, kernels, workgroup sizes, LDS bytes
+    std::map<std::tuple<const void *, int, size_t>, int> occupancy;   // residentBlocks: the runtime's answers, per kernel, workgroup size and LDS bytes
     int instPhaseMin = 24;                // "inst_phase_min" / "inst_refill_at" (PathState::inst_*)
     int instRefillAt = 48;
-    int wideClosestOpt = -1, wideShadowOpt = -1;
-    // "tail_kernel" / "tail_threshold": once a host check finds at most tail_threshold paths alive in the pool, the rest of the batch runs in
-    // k_tail (one launch per part: every workgroup iterates over its own slots until they are done).  The kernel is built for latency, not
-    // throughput (one shading variant for every class, one wave per SIMD): measured, Msamples/s for thresholds off / 2 Ki / 8 Ki / 32 Ki / 128 Ki:
-    // mesh1m 605 / 625 / 611 / 575 / 514, materialtest 963 / 966 / 964 / 968 / 966, materialtest as shipped 573 / 611 / 630 / 623 / 625
-    bool mediaLeanOpt = true;             // "media_lean": shade media scenes whose surface BSDFs MASK_MEDIA covers (sc.mediaSimple) with k_shade<MASK_MEDIA> instead of <BSDF_MASK_ALL>
-    bool foldFinishOpt = true;            // "fold_finish"
     bool topTreeOpt = true;               // "top_tree": 0 = ignore TgHipSceneDesc::top_nodes at the next upload (flat lists walked in record order: faster, not the reference's ties)
-    bool mergeMissOpt = true;             // "merge_miss"
-    bool tailOpt = true;
-    long long tailThreshold = 8192;
-    bool instShadowFast = true;           // "inst_shadow_fast": instanced scenes' shadow rays on k_trace_shadow_fast_inst (0: k_trace_shadow_wide<., ., INST>)
-    bool instShadowJoin = true;           // "inst_shadow_join": 0 = the instanced wide shadow kernel without PT_TURN_JOIN (the miscompiled variant; repro tool only)
+    long long tailThreshold = 8192;       // "tail_threshold" (LaunchOptions::tailOpt)
     bool failReduce = false;              // "fail_reduce" option (fault injection for the reduce's callers)
     int wideStride = int(PT_WIDE_NODE_BYTES);   // bytes per device node: 80 (TgHipWideNode), or 128 -- a cache line each ("wide_node_stride" option, at the next upload)
     uint32_t width = 0, height = 0;
@@ -276,7 +269,6 @@ struct tghip_ctx {
     // 347 -> 518 us, k_shade 421 -> 665 us per launch for twice the rays -- so the pool is as large as the 32-bit slot offsets allow
     // (8 M slots x 272 B = 2.2 GB of the 288 GB): 1280x720x256 669 -> 745 (4 M) -> 818 (8 M) Msamples/s, mesh1m 404 -> 472 -> 507
     long long maxSlots = 1ll << 23;
-    int slotsPerBlockOpt = 0;             // "slots_per_block": upper bound on the slots of one workgroup (0 = PT_MAX_SLOTS_PER_BLOCK)
     bool maxSlotsSet = false;             // "max_slots" was given explicitly
     long long maxItems = 1ll << 26;       // work items per batch (partial-sum buffer = 16 B each)
     int chunkSamples = 0;                 // "chunk_samples": samples per work item; 0 = 4, or one when the pass is short (csrc/host/PassPlan.cpp)
@@ -317,35 +309,20 @@ struct tghip_ctx {
     uint32_t *dOwnedTiles = nullptr;
     size_t ownedCap = 0;
     size_t samplesCap = 0, samplesFloats = 0;
-    bool auxPass = false;                 // the pass being rendered keeps them: BSDF_MASK_ALL shading, no fused / dynamic-fetch shadow kernels
-    int thrShadeAll = 256;                // workgroup size of k_shade<BSDF_MASK_ALL> (media scenes, TGHIP_PASS_AUX passes)
     bool hoistOpt = true;                 // "hoist_quad": the scene's one quad tested before the decoupled walks instead of inside them (at the next upload)
-    bool tailFamilyOpt = true;            // "tail_family": k_tail<MASK_COAT> for scenes without class-2 / class-3 materials and without solids
-    bool tablesFit = true;                // sc.tablesFit, or false under "lds_tables" = 0: shade as if the small tables did not fit the LDS copy (the GLOBAL_TABLES variant: tests).
-                                          // Likewise scene.hoisted_rec and scene.env_tex are sc.hoisted.record / sc.env_tex unless "hoist_quad" / "env_lds" = 0 say -1
+                                          // (scene.hoisted_rec and scene.env_tex are sc.hoisted.record / sc.env_tex unless "hoist_quad" / "env_lds" = 0 say -1)
     bool countTraversal = false;
     int checkInterval = 0;                // "check_interval": wavefront iterations between host-side liveness checks; 0 = 16 for batches that refill
                                           // the pool several times (every check drains all streams: materialtest 825 / 835 / 845 Msamples/s for
                                           // 4 / 8 / 16), 4 for short ones (the iterations after the last path ended are wasted)
-    int blocksPerCuOpt = 0;               // "blocks_per_cu" option; 0 = auto (see chooseThreads)
-    int blocksPerCu = 4;                  // persistent workgroups per CU (the same grid for every kernel of a pass)
     int gridRounds = 1;                   // "grid_rounds": launch this many times the resident workgroups (each owns 1/rounds of the slots);
                                           // the dispatcher starts the later ones as the first finish, filling the drain tail of a launch
-    // threads per workgroup, per kernel: chosen at upload so that `blocksPerCu` workgroups of EVERY kernel are
-    // resident at once (no second scheduling round), i.e. each kernel runs at its own best occupancy on one grid
-    int thrClosest = 256, thrShadow = 256, thrShadeSimple = 192, thrShadeComplex = 128;
-    int thrOverride[4] = {0, 0, 0, 0};
-    bool loopOpt = true;                  // "run_to_completion": fused flat-list scenes whose materials are all of class 0 render in ONE launch
-    bool fuseFlatOpt = true;              // "fuse_flat": flat-list scenes without forward lobes trace + shadow-test inside k_shade
-    bool shadeFusedOpt = true;            // "shade_fused": scenes with class 0 and one further class shade an iteration in ONE launch (k_shade_fused)
     // "suspend_lanes" / "suspend_turns" / "suspend_min_queue" (PathState::suspend_*): walk time-slicing of the wide traversal kernels
     int suspendLanes = 12, suspendTurns = 16, suspendMinQueue = 1024;   // (measured, profiles/README.md: materialtest +0.5 %, mesh1m +4 % over none; round 5 on the final kernels, r5_sweep_final_kernels.txt: 12 lanes +0.5 % / +1 % over 16, 8 lanes +0.8 % / -3 %)
     uint32_t numWideNodes = 0;
-    int decoupleOpt = 1;                  // "decouple": the wide kernels of single-level scenes test a record AND visit a node per turn (k_trace_closest_wide<.., DECOUPLED>)
     int leafBatch = 1;                    // "leaf_batch" (PathState::leaf_batch)
     int leafBatchBvh2 = 0;                // "leaf_batch_bvh2" (PathState::leaf_batch_bvh2); 0 = leaf_batch, or the measured value for two-level scenes
     long long poolPad = 9472;             // bytes between the per-slot arrays of the pool (multiple of 16)
-    bool dynamicFetch = true;             // BVH scenes: closest-hit kernel with dynamic ray fetch (k_trace_closest_dyn)
     bool timeKernels = false;             // HIP events around every launch of the wavefront loop (bench.py roofline)
     std::vector<hipEvent_t> evPool;
 
@@ -413,80 +390,154 @@ static int growArray(tghip_ctx *ctx, T *&dev, size_t &cap, size_t need)
     return TGHIP_OK;
 }
 
-static bool isFlat(const tghip_ctx *ctx) { return ctx->scene.num_recs <= TGHIP_FLAT_MAX_RECS && !ctx->sc.haveInstances; }
-// the single-level traversal kernels walk the 8-wide BVH when the scene carries one
-static bool useWide(const tghip_ctx *ctx) { return ctx->sc.wideDepth > 0 && ctx->wideOpt && ctx->dynamicFetch && !isFlat(ctx); }
-// the running pass traces and shadow-tests inside k_shade ("fuse_flat": flat-list scenes without forward lobes) ...
-static bool fusedFlat(const tghip_ctx *ctx)
-{
-    return isFlat(ctx) && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && ctx->fuseFlatOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && ctx->tablesFit && !ctx->sc.cameraFix;
-}
-// ... and one such launch renders a whole batch ("run_to_completion": all materials of class 0)
-static bool oneLaunch(const tghip_ctx *ctx) { return fusedFlat(ctx) && !ctx->sc.haveComplex && ctx->loopOpt; }
+// ---- Kernel identities (csrc/host/LaunchChoice.hpp) to kernels: per family the one place where run-time flags become template arguments.  What is
+// named here is what this translation unit instantiates (the k_shade, k_shade_fused, k_tail, k_trace_shadow_fast and <., BSDF_MASK_ALL> families: extern, above).
+#define KERNEL(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+template<typename F>
+static const void *withBool(bool b, F f) { return b ? f(std::true_type()) : f(std::false_type()); }
 
-
-static bool wideClosest(const tghip_ctx *ctx);
-static bool wideShadowRays(const tghip_ctx *ctx);
-// Most slots a workgroup of the uploaded scene owns (the pool is sized by it, and the traversal kernels' LDS queue area): 4096 where both
-// traversal kernels are the wide ones.  The static-fetch BVH2 kernels of flat-list and instanced scenes keep a thread's queue entries in
-// 16 half registers (OrderRegs: <= 16 x threads), and their deep stacks leave less LDS: 2048, as measured (instances10k: 4096 slots with
-// the smaller workgroups that then fit are not faster).
-static uint32_t slotCap(const tghip_ctx *ctx)
+static const void *walkKernelFn(const KernelId &k)
 {
-    const bool allWide = !isFlat(ctx) && !ctx->sc.haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && !ctx->sc.haveForward && !ctx->sc.haveMeshLight;
-    uint32_t cap = allWide ? PT_MAX_SLOTS_PER_BLOCK : 2048u;      // (BlockLdsSmall in the other traversal kernels)
-    if (ctx->slotsPerBlockOpt > 0)
-        cap = std::min<uint32_t>(cap, uint32_t(ctx->slotsPerBlockOpt));
-    return std::max(cap, 64u);
-}
-
-// Dynamic LDS of the traversal kernels: one node stack of bvhDepth ints per thread (a root-to-leaf walk pushes at
-// most one far child per internal level), aliased with the expanded queue (2 B per slot) that is consumed before
-// traversal starts.  Flat-list scenes need no stack.
-static size_t traceLdsBytes(const tghip_ctx *ctx, int threads)
-{
-    const bool flat = isFlat(ctx);
-    size_t stack = flat ? 0 : size_t(std::max(ctx->sc.bvhDepth, 1))*size_t(threads)*sizeof(int);
-    return std::max<size_t>(stack, size_t(slotCap(ctx))*sizeof(unsigned short));
-}
-
-// dynamic-fetch traversal kernels keep the expanded queue next to the stacks
-static size_t dynLdsBytes(const tghip_ctx *ctx, int threads)
-{
-    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->sc.bvhDepth, 1))*size_t(threads)*sizeof(int);
-}
-
-// the wide kernels: expanded queue + one 8-byte group entry per tree level and thread
-static size_t wideLdsBytes(const tghip_ctx *ctx, int threads)
-{
-    return size_t(slotCap(ctx))*sizeof(unsigned short) + size_t(std::max(ctx->sc.wideDepth, 1))*size_t(threads)*sizeof(uint2);
+    return withBool(k.count, [&](auto C) { return withBool(k.solids, [&](auto S) -> const void * {
+        constexpr bool c = decltype(C)::value, s = decltype(S)::value;
+        switch (k.family) {
+        case K_CLOSEST:             return k.inst == 1 ? KERNEL(k_trace_closest<c, false, 1>) : k.inst == 2 ? KERNEL(k_trace_closest<c, false, 2>)
+                                         : k.flat ? KERNEL(k_trace_closest<c, true>) : KERNEL(k_trace_closest<c, false>);
+        case K_CLOSEST_DYN:         return KERNEL(k_trace_closest_dyn<c, s>);
+        case K_CLOSEST_INST:        return KERNEL(k_trace_closest_inst<c, s>);
+        case K_CLOSEST_INSTW:       return KERNEL(k_trace_closest_instw<c, s>);
+        case K_CLOSEST_WIDE:        return k.inst ? KERNEL(k_trace_closest_wide<c, s, true, false>) : k.decoupled ? KERNEL(k_trace_closest_wide<c, s, false, true>)
+                                                                                                                  : KERNEL(k_trace_closest_wide<c, s, false, false>);
+        case K_FINISH_CLOSEST_WIDE: return KERNEL(k_finish_trace_closest_wide<c, s>);
+        case K_SHADOW:
+            if (k.mask == BSDF_MASK_ALL)      // walk_shadow_tex.hip: closest-hit shadow walks only
+                return k.inst == 1 ? KERNEL(k_trace_shadow<c, true, false, 1, BSDF_MASK_ALL>) : k.inst == 2 ? KERNEL(k_trace_shadow<c, true, false, 2, BSDF_MASK_ALL>)
+                     : k.flat ? KERNEL(k_trace_shadow<c, true, true, 0, BSDF_MASK_ALL>) : KERNEL(k_trace_shadow<c, true, false, 0, BSDF_MASK_ALL>);
+            return withBool(k.forward, [&](auto FW) -> const void * {
+                constexpr bool fw = decltype(FW)::value;
+                return k.inst == 1 ? KERNEL(k_trace_shadow<c, fw, false, 1>) : k.inst == 2 ? KERNEL(k_trace_shadow<c, fw, false, 2>)
+                     : k.flat ? KERNEL(k_trace_shadow<c, fw, true>) : KERNEL(k_trace_shadow<c, fw, false>);
+            });
+        case K_SHADOW_DYN:          return KERNEL(k_trace_shadow_dyn<c, s>);
+        // (rounds 2 and 3 launched the counting variant for instanced scenes: the non-counting one lost occluders inside instances.  The cause is the loop
+        // latch the backend generates for the turn without PT_TURN_JOIN, pt_wavefront.h; "inst_shadow_join" = 0 launches that variant for tools/repro_latch_miscompile.py)
+        case K_SHADOW_WIDE:         return !k.join ? KERNEL(k_trace_shadow_wide<false, false, true, false>)
+                                         : k.inst ? KERNEL(k_trace_shadow_wide<c, s, true>) : KERNEL(k_trace_shadow_wide<c, s, false>);
+        case K_SHADOW_FAST:         return KERNEL(k_trace_shadow_fast<c, s>);
+        case K_SHADOW_FAST_INST:    return KERNEL(k_trace_shadow_fast_inst<c, s>);
+        case K_TRACE_RAYS:          return k.decoupled ? KERNEL(k_trace_rays<c, false, 0, true>) : k.inst ? KERNEL(k_trace_rays<c, false, 1>)
+                                         : k.flat ? KERNEL(k_trace_rays<c, true>) : KERNEL(k_trace_rays<c, false>);
+        default:                    return nullptr;
+        }
+    }); });
 }
 
-// k_trace_closest_instw: expanded queue + the BVH2 stack of the scene's tree and the reference's tree over the instances (no master on it) + the
-// masters' group stack (8-byte entries, 8-byte aligned)
-static int instTreeDepth(const tghip_ctx *ctx) { return std::max(ctx->sc.bvhDepth - ctx->sc.bvhMasterDepth, 1); }
-static size_t instWideLdsBytes(const tghip_ctx *ctx, int threads)
+// (mask, waves per SIMD, FUSE) of the k_shade instantiations that have a FEAT_QMC twin, and the further classes' families of k_shade_fused
+#define SHADE_KERNELS(X) \
+    X(MASK_LEAN, LEAN_WAVES, 0) X(MASK_LEAN, LEAN_WAVES, 3) X(MASK_LEAN, LEAN_WAVES, 7) \
+    X(MASK_SIMPLE, SIMPLE_WAVES, 0) X(MASK_SIMPLE, SIMPLE_WAVES, 3) X(MASK_SIMPLE, SIMPLE_WAVES, 7) X(MASK_SIMPLE_INST, SIMPLE_WAVES, 0) \
+    X(MASK_COAT, COAT_WAVES, 0) X(MASK_COAT, COAT_WAVES, 2) X(MASK_GLASS, 2, 0) X(MASK_GLASS, 2, 2) X(MASK_PLASTIC, 2, 0) X(MASK_PLASTIC, 2, 2) \
+    X(MASK_COAT_INST, 2, 0) X(MASK_GLASS_INST, 2, 0) X(MASK_PLASTIC_INST, 2, 0) X(MASK_FULL, 2, 0) X(MASK_FULL, 2, 2)
+#define SHADE_FUSED_KERNELS(X) X(MASK_COAT, COAT_WAVES) X(MASK_GLASS, 2) X(MASK_PLASTIC, 2)
+static const void *shadeKernelFn(const KernelId &k)
 {
-    const size_t ints = ((size_t(slotCap(ctx)) >> 1) + size_t(instTreeDepth(ctx))*size_t(threads) + 1u) & ~size_t(1);
-    return ints*sizeof(int) + size_t(std::max(ctx->sc.wideMasterDepth, 1))*size_t(threads)*sizeof(uint2);
-}
-static bool instWide(const tghip_ctx *ctx) { return ctx->sc.haveInstances && ctx->instWideOpt && ctx->sc.wideDepth > 0 && ctx->sc.wideMasterDepth > 0 && ctx->wideOpt; }
-static bool wideClosest(const tghip_ctx *ctx) { return useWide(ctx) && (ctx->wideClosestOpt < 0 ? !ctx->sc.haveInstances : ctx->wideClosestOpt != 0); }
-static bool wideShadowRays(const tghip_ctx *ctx) { return useWide(ctx) && ctx->wideShadowOpt != 0; }
-
-static int launchGrid(const tghip_ctx *ctx) { return ctx->prop.multiProcessorCount*std::max(ctx->blocksPerCu, 1)*std::max(ctx->gridRounds, 1); }
-
-// Largest workgroup size (multiple of 64, <= maxThreads) at which `blocksPerCu` workgroups of `kernel` fit on a CU.
-template<typename K>
-static int pickThreads(const tghip_ctx *ctx, K kernel, int maxThreads, int ldsMode)   // 0: no dynamic LDS, 1: traceLdsBytes, 2: dynLdsBytes, 3: wideLdsBytes, 4: instWideLdsBytes
-{
-    for (int t = maxThreads; t >= 128; t -= 64) {
-        int nb = 0;
-        size_t lds = ldsMode == 1 ? traceLdsBytes(ctx, t) : ldsMode == 2 ? dynLdsBytes(ctx, t) : ldsMode == 3 ? wideLdsBytes(ctx, t) : ldsMode == 4 ? instWideLdsBytes(ctx, t) : 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kernel), t, lds) == hipSuccess && nb >= ctx->blocksPerCu)
-            return t;
+    if (k.family == K_SHADE_FUSED) {
+#define X(M, W) if (k.mask == (M)) return KERNEL(k_shade_fused<M, MASK_SIMPLE, W>); \
+                if (k.mask == ((M) | FEAT_QMC)) return KERNEL(k_shade_fused<((M) | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), W>);
+        SHADE_FUSED_KERNELS(X)
+#undef X
+        return nullptr;
     }
-    return 128;
+    if (k.family == K_TAIL) {
+        if ((k.mask & ~FEAT_QMC) == MASK_COAT) return (k.mask & FEAT_QMC) ? KERNEL(k_tail<(MASK_COAT | FEAT_QMC), false>) : KERNEL(k_tail<MASK_COAT, false>);
+        if (k.mask & FEAT_QMC) return k.solids ? KERNEL(k_tail<(MASK_TAIL | FEAT_QMC), true>) : KERNEL(k_tail<(MASK_TAIL | FEAT_QMC), false>);
+        return k.solids ? KERNEL(k_tail<MASK_TAIL, true>) : KERNEL(k_tail<MASK_TAIL, false>);
+    }
+    if (k.globalTables) return KERNEL(k_shade<BSDF_MASK_ALL, 2, 0, true>);
+    if (k.mask == BSDF_MASK_ALL) return KERNEL(k_shade<BSDF_MASK_ALL, 2, 0>);   // the one variant with FEAT_MEDIA / FEAT_AUX / FEAT_CYLINDER; FEAT_QMC is in it
+    if (k.mask == MASK_MEDIA) return KERNEL(k_shade<MASK_MEDIA, 2, 0>);
+#define X(M, W, F) if (k.fuse == F && k.mask == (M)) return KERNEL(k_shade<M, W, F>); \
+                   if (k.fuse == F && k.mask == ((M) | FEAT_QMC)) return KERNEL(k_shade<((M) | FEAT_QMC), W, F>);
+    SHADE_KERNELS(X)
+#undef X
+    return nullptr;
+}
+static const void *kernelFn(const KernelId &k) { return (k.family == K_SHADE || k.family == K_SHADE_FUSED || k.family == K_TAIL) ? shadeKernelFn(k) : walkKernelFn(k); }
+
+// hipLaunchKernel takes the arguments by address and does not know the kernel's parameter list: every argument must HAVE the type of its parameter.  The
+// kernels launched through here take structs, pointers, `int` and `uint32_t`; a number of any other type is refused at compile time.
+template<typename... A>
+static void launchKernel(const ResolvedLaunch &l, int grid, hipStream_t stream, const A &... args)
+{
+    static_assert(((!std::is_arithmetic<A>::value || (std::is_integral<A>::value && sizeof(A) == 4)) && ...),
+                  "launchKernel: pass structs, pointers, int or uint32_t -- the kernel's own parameter types");
+    void *argv[] = {(void *)&args...};
+    (void)hipLaunchKernel(l.fn, dim3(grid), dim3(l.threads), argv, l.lds, stream);
+}
+
+static int launchGrid(const tghip_ctx *ctx) { return ctx->prop.multiProcessorCount*std::max(ctx->lp.choice.blocksPerCu, 1)*std::max(ctx->gridRounds, 1); }
+
+// Workgroups of `fn` resident on a CU at `threads` threads with `lds` bytes of dynamic LDS.  Asked of the runtime once per context: passes of
+// alternating kinds (adaptive renders: normal and record passes) plan again without asking again.
+static int residentBlocks(tghip_ctx *ctx, const void *fn, int threads, size_t lds)
+{
+    const auto key = std::make_tuple(fn, threads, lds);
+    const auto it = ctx->occupancy.find(key);
+    if (it != ctx->occupancy.end()) return it->second;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds) != hipSuccess) nb = 0;
+    return ctx->occupancy[key] = nb;
+}
+
+// Resolves the choice for a pass of `kind` on the uploaded scene into `p`: kernels, workgroup sizes (threads per workgroup, per kernel: chosen so that
+// blocksPerCu workgroups of EVERY kernel are resident at once -- no second scheduling round --, i.e. each kernel runs at its own best occupancy on one
+// grid) and dynamic LDS bytes.  Runs when an input changes -- an upload, an option, a pass of another kind; an iteration only reads the result.
+static int planLaunches(tghip_ctx *ctx, const PassKind &kind, LaunchPlan &p)
+{
+    p.kind = kind;
+    LaunchChoice &c = p.choice;
+    chooseLaunches(ctx->sc, ctx->scene.num_recs, ctx->numWideNodes, ctx->opt, kind, c);
+    auto threadsFor = [&](const WorkgroupSize &w) {
+        if (w.fixed) return w.fixed;
+        const void *fn = kernelFn(w.sizedBy);
+        for (int t = w.maxThreads; t >= 128; t -= 64)
+            if (residentBlocks(ctx, fn, t, ldsBytes(ctx->sc, c, w.lds, t)) >= c.blocksPerCu) return t;
+        return 128;
+    };
+    bool missing = false;
+    const WalkLaunch *walks[2] = {&c.closest, &c.shadow};
+    ResolvedLaunch *resolved[2] = {&p.closest, &p.shadow};
+    for (int i = 0; i < 2; ++i) {
+        const int t = threadsFor(walks[i]->size);
+        *resolved[i] = ResolvedLaunch{kernelFn(walks[i]->kernel), t, ldsBytes(ctx->sc, c, walks[i]->lds, t)};
+        missing = missing || !resolved[i]->fn || !kernelFn(walks[i]->size.sizedBy);
+    }
+    for (int i = 0; i < 3; ++i) {
+        p.thrShade[i] = threadsFor(c.shadeSize[i]);
+        missing = missing || !kernelFn(c.shadeSize[i].sizedBy);
+    }
+    for (int i = 0; i < c.numShade; ++i) {
+        p.shade[i] = ResolvedLaunch{kernelFn(c.shade[i].kernel), p.thrShade[c.shade[i].size], 0};
+        missing = missing || !p.shade[i].fn;
+    }
+    // (k_tail runs 256 threads whatever the depth of the tree: it is used only where a workgroup of it fits a CU -- its static LDS plus the walk stacks
+    // of a very deep tree may not)
+    p.tail = ResolvedLaunch{kernelFn(c.tail), 256, ldsBytes(ctx->sc, c, LDS_WIDE, 256)};
+    p.tailFits = c.tailEligible && residentBlocks(ctx, kernelFn(c.tailProbe), 256, p.tail.lds) >= 1;
+    missing = missing || !p.tail.fn || !kernelFn(c.tailProbe);
+    if (missing) { ctx->error = "launch plan: a chosen kernel is not among the instantiated ones"; return TGHIP_E_UNSUPPORTED; }
+    if (std::getenv("TGHIP_VERBOSE") && &p == &ctx->lp)
+        std::fprintf(stderr, "[tghip] grid %d x threads closest %d (%s) shadow %d (%s) shade %d/%d/%d (flat %d, forward %d, complex mask 0x%x)\n",
+                     launchGrid(ctx), p.closest.threads, kernelName(c.closest.kernel).c_str(), p.shadow.threads, kernelName(c.shadow.kernel).c_str(),
+                     p.thrShade[SIZE_SIMPLE], p.thrShade[SIZE_COMPLEX], p.thrShade[SIZE_ALL], int(c.flat), int(ctx->sc.haveForward), ctx->sc.complexMask);
+    return TGHIP_OK;
+}
+// ... for the context itself: the kind of the last pass (an upload or an option between two passes keeps it), "count_traversal" as it stands
+static int replan(tghip_ctx *ctx)
+{
+    PassKind kind = ctx->lp.kind;
+    kind.countTraversal = ctx->countTraversal;
+    return planLaunches(ctx, kind, ctx->lp);
 }
 
 // Adds the per-workgroup statistics on the device to ctx->counters and zeroes them there.
@@ -581,14 +632,15 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
 {
     const uint32_t grid = uint32_t(launchGrid(ctx));
     uint32_t perBlock = (wantSlots + grid - 1)/grid;
-    uint32_t cap = slotCap(ctx);
-    if (isFlat(ctx) || ctx->sc.haveInstances)
-        cap = std::min<uint32_t>(cap, 16u*uint32_t(std::min(ctx->thrClosest, ctx->thrShadow))/64u*64u);   // OrderRegs
+    const LaunchPlan &lp = ctx->lp;
+    uint32_t cap = lp.choice.slotCap;
+    if (lp.choice.orderRegsCap)
+        cap = std::min<uint32_t>(cap, 16u*uint32_t(std::min(lp.closest.threads, lp.shadow.threads))/64u*64u);   // OrderRegs
     perBlock = std::min<uint32_t>(cap, std::max<uint32_t>(64u, (perBlock + 63u)/64u*64u));
     const uint32_t slots = perBlock*grid;
     PathState &p = ctx->pool;
     // the walk arrays behind the A_* ones (suspended walks of the wide kernels, PathState::walk_base): only where they fit the 32-bit offsets
-    uint32_t walkArrays = useWide(ctx) && !ctx->sc.haveInstances ? 4u + uint32_t(ctx->sc.wideDepth + 1)/2u : 0u;
+    uint32_t walkArrays = lp.choice.walkArrays;
     if (ctx->poolSlots >= slots && ctx->poolGrid == grid && (ctx->poolWalkWanted == walkArrays || ctx->poolWalkArrays >= walkArrays)) {
         p.num_slots = slots;
         p.slots_per_block = perBlock;
@@ -628,90 +680,6 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     ctx->poolSlots = slots;
     ctx->poolGrid = grid;
     return TGHIP_OK;
-}
-
-// Picks the workgroup size of each kernel of the wavefront loop for the uploaded scene (see tghip_ctx::thr*).
-static void chooseThreads(tghip_ctx *ctx)
-{
-    const bool flat = isFlat(ctx);
-    // Measured (profiles/README.md).  On one stream BVH scenes run best with every workgroup of every kernel resident at once
-    // (4 per CU, workgroup size per kernel = that kernel's occupancy limit / 4: the fallback kernels still run so); flat-list scenes are
-    // streaming-bound and prefer 8 small workgroups per CU that the dispatcher load-balances.
-    // Scenes on the wide kernels run the loop as PARTS of the pool on streams of their own (runBatch), each kernel launched with its part
-    // of the grid: with 8 workgroups per CU kernels of different parts share every CU, and the issue-bound walk of one part fills the
-    // memory waits of the shading of another (materialtest 1280x720x256: 608 -> 657 Msamples/s against 4 per CU; workgroup sizes below
-    // from the same sweep).  Instanced scenes with the dynamic-fetch closest-hit kernel: two parts, 8 per CU (instances10k: 141 -> 153
-    // Msamples/s; with the static-fetch kernel parts lost: 127 against 114-120).
-    const bool oneStream = ctx->streamsOpt == 1 || (ctx->streamsOpt == 0 && ctx->shortBatch);   // (shortBatch: tghip_render_pass)
-    const bool pairedInst = !flat && ctx->sc.haveInstances && !oneStream && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt && wideShadowRays(ctx) &&
-                            !ctx->sc.haveForward && !ctx->sc.haveMeshLight;
-    const bool paired = (!flat && !ctx->sc.haveInstances && !oneStream && wideClosest(ctx) && wideShadowRays(ctx)) || pairedInst;
-    ctx->blocksPerCu = ctx->blocksPerCuOpt > 0 ? ctx->blocksPerCuOpt : ((flat || paired) ? 8 : 4);
-    if (flat && ctx->blocksPerCuOpt == 0) {
-        ctx->thrClosest = ctx->thrShadow = ctx->thrShadeSimple = ctx->thrShadeComplex = 256;
-    } else {
-    const bool inst = ctx->sc.haveInstances;
-    const bool dyn = ctx->dynamicFetch && !inst;               // (the two-level dynamic-fetch kernel is chosen by instDynOpt below)
-    const bool wide = useWide(ctx);
-    const bool wideC = wideClosest(ctx), wideS = wideShadowRays(ctx);
-    // (wide closest-hit kernel, materialtest 1280x720x256 / mesh1m, one MI355X: 128 / 192 / 256 / 320 threads = 505 / 433 / 394 / 469 us per
-    // launch, but the shading launches behind it run 6 % faster after 192 than after 256: 579 / 571 / 552 Msamples/s for 192 / 256 / 320)
-    ctx->thrClosest = wideC && inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false, true>, 192, 3))
-                    : wideC ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_wide<false, true>, 192, 3) : pickThreads(ctx, k_trace_closest_wide<false, false>, 192, 3))
-                    : flat ? pickThreads(ctx, k_trace_closest<false, true>, 512, 1)
-                    : (inst && ctx->dynamicFetch && ctx->instDynOpt && instWide(ctx)) ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_instw<false, true>, 320, 4) : pickThreads(ctx, k_trace_closest_instw<false, false>, 320, 4))
-                    : (inst && ctx->dynamicFetch && ctx->instDynOpt) ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_inst<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_inst<false, false>, 320, 2))
-                    : inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest<false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_closest<false, false, 2>, 512, 1))
-                    : dyn ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_closest_dyn<false, true>, 320, 2) : pickThreads(ctx, k_trace_closest_dyn<false, false>, 320, 2))   // 20 waves/CU measured best (profiles/README.md)
-                                        : pickThreads(ctx, k_trace_closest<false, false>, 512, 1);
-    if (wideS && inst && !ctx->sc.haveForward && !ctx->sc.haveMeshLight)
-        ctx->thrShadow = ctx->instShadowFast ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_fast_inst<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_fast_inst<false, false>, 256, 3))
-                                             : (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false, true>, 256, 3));
-    else if (wideS && !ctx->sc.haveForward && !ctx->sc.haveMeshLight)
-        ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_wide<false, true>, 256, 3) : pickThreads(ctx, k_trace_shadow_wide<false, false>, 256, 3);
-    else if (!flat && !ctx->sc.haveForward && !ctx->sc.haveMeshLight && dyn)
-        ctx->thrShadow = ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow_dyn<false, true>, 256, 2) : pickThreads(ctx, k_trace_shadow_dyn<false, false>, 256, 2);   // measured: 192 / 256 / 320 / 384 threads = 525 / 462 / 633 / 619 us per launch
-    else if ((ctx->sc.haveProcTex || ctx->sc.haveFibre) && (ctx->sc.haveForward || ctx->sc.haveMeshLight))   // (launchShadow's choice)
-        ctx->thrShadow = inst ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>, 512, 1))
-                              : flat ? pickThreads(ctx, k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>, 512, 1);
-    else if (inst)
-        ctx->thrShadow = (ctx->sc.haveForward || ctx->sc.haveMeshLight)
-                       ? (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, true, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false, 2>, 512, 1))
-                       : (ctx->sc.haveSolids ? pickThreads(ctx, k_trace_shadow<false, false, false, 1>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, false, false, 2>, 512, 1));
-    else if (ctx->sc.haveForward || ctx->sc.haveMeshLight)
-        ctx->thrShadow = flat ? pickThreads(ctx, k_trace_shadow<false, true, true>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, true, false>, 512, 1);
-    else
-        ctx->thrShadow = flat ? pickThreads(ctx, k_trace_shadow<false, false, true>, 512, 1) : pickThreads(ctx, k_trace_shadow<false, false, false>, 512, 1);
-    if (ctx->sc.haveMeshLight || inst) ctx->thrShadeSimple = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
-    else ctx->thrShadeSimple = ctx->sc.leanScene ? pickThreads(ctx, k_shade<MASK_LEAN, LEAN_WAVES, 0>, 256, 0) : pickThreads(ctx, k_shade<MASK_SIMPLE, SIMPLE_WAVES, 0>, 256, 0);
-    // (one workgroup size for the launches of classes 1 .. 3: that of the largest variant among them)
-    if (ctx->sc.haveMeshLight || inst || (ctx->sc.classPresent[3] && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false)))
-                                                    ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_FULL, 2, 0>, 256, 0);
-    else if (ctx->sc.classPresent[3])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_PLASTIC, 2, 0>, 256, 0);
-    else if (ctx->sc.classPresent[2])                  ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_GLASS, 2, 0>, 256, 0);
-    else                                            ctx->thrShadeComplex = pickThreads(ctx, k_shade<MASK_COAT, COAT_WAVES, 0>, 256, 0);
-    if (ctx->sc.haveMedia) ctx->thrShadeSimple = ctx->thrShadeComplex = pickThreads(ctx, k_shade<BSDF_MASK_ALL, 2, 0>, 256, 0);
-    if (paired && ctx->blocksPerCuOpt == 0) {
-        // (closest / shadow / shade simple / shade complex, Msamples/s: 256/256/128/128 657, 192/256/128/128 634, 128/256/128/128 623,
-        //  320/256/128/128 556, 256/320/128/128 549, 256/256/256/128 646, 256/256/128/64 623; 4 per CU with 192/256/192/128: 608)
-        ctx->thrClosest = pairedInst ? 192 : 256;
-        if (!ctx->sc.haveForward && !ctx->sc.haveMeshLight) ctx->thrShadow = 256;
-        ctx->thrShadeSimple = ctx->thrShadeComplex = 128;
-        // (round 5, the same sweep at today's kernels, three rounds A B C in one session, profiles/r5_sweep_shade_threads.jsonl: materialtest
-        // 128/128 965, 192/192 967, 256/256 979 Msamples/s -- k_shade's 26 KB of LDS per workgroup then serve four waves instead of two --, but
-        // mesh1m 604 -> 597, materialtest with a rough dielectric 453 -> 451 / 431, with a dielectric 480 -> 480: 256 threads only for what it
-        // was measured to help, a small tree with the conductor family as its only other shading class)
-        if (!pairedInst && ctx->numWideNodes <= 32768u && ctx->sc.classPresent[1] && !ctx->sc.classPresent[2] && !ctx->sc.classPresent[3])
-            ctx->thrShadeSimple = ctx->thrShadeComplex = 256;
-    }
-    }
-    ctx->thrShadeAll = flat && ctx->blocksPerCuOpt == 0 ? 256 : pickThreads(ctx, k_shade<BSDF_MASK_ALL, 2, 0>, 256, 0);
-    int *dst[4] = {&ctx->thrClosest, &ctx->thrShadow, &ctx->thrShadeSimple, &ctx->thrShadeComplex};
-    for (int i = 0; i < 4; ++i)
-        if (ctx->thrOverride[i] >= 64) *dst[i] = std::min(ctx->thrOverride[i]/64*64, i < 2 ? 512 : 256);
-    if (std::getenv("TGHIP_VERBOSE"))
-        std::fprintf(stderr, "[tghip] grid %d x threads closest %d shadow %d shade %d/%d (flat %d, forward %d, complex mask 0x%x)\n",
-                     launchGrid(ctx), ctx->thrClosest, ctx->thrShadow, ctx->thrShadeSimple, ctx->thrShadeComplex, int(flat), int(ctx->sc.haveForward), ctx->sc.complexMask);
 }
 
 extern "C" {
@@ -879,67 +847,43 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
 {
     if (!ctx || !key) return TGHIP_E_INVALID;
     std::string k(key);
-    if (k == "count_traversal") ctx->countTraversal = value != 0;
-    else if (k == "max_slots") { ctx->maxSlots = std::max<long long>(value, 256); ctx->maxSlotsSet = true; }
+    // the options the choice of a pass's kernels reads: stored, and the plan of the uploaded scene made again
+    if (k == "count_traversal" || setLaunchOption(ctx->opt, k, value)) {
+        if (k == "count_traversal") ctx->countTraversal = value != 0;
+        if (k == "slots_per_block") { ctx->poolMem.release(); ctx->poolSlots = 0; }
+        for (int kk = 0; kk < 8 && k == "class_streams" && value != 0; ++kk)     // (created when the option is first switched on: an experiment's streams)
+            for (int a = 0; a < 2; ++a)
+                if (!ctx->classStream[kk][a]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->classStream[kk][a], hipStreamNonBlocking));
+        return ctx->haveScene ? replan(ctx) : TGHIP_OK;
+    }
+    if (k == "max_slots") { ctx->maxSlots = std::max<long long>(value, 256); ctx->maxSlotsSet = true; }
     else if (k == "max_items") ctx->maxItems = std::max<long long>(value, 256);
-    else if (k == "slots_per_block") { ctx->slotsPerBlockOpt = int(std::min<long long>(std::max<long long>(value, 0), PT_MAX_SLOTS_PER_BLOCK))/64*64; ctx->poolMem.release(); ctx->poolSlots = 0; if (ctx->haveScene) chooseThreads(ctx); }
     else if (k == "chunk_samples") ctx->chunkSamples = int(std::min<long long>(std::max<long long>(value, 0), 1 << 20));
     else if (k == "check_interval") ctx->checkInterval = int(std::min<long long>(std::max<long long>(value, 0), 64));
     else if (k == "time_kernels") ctx->timeKernels = value != 0;
-    else if (k == "streams") { ctx->streamsOpt = int(std::min<long long>(std::max<long long>(value, 0), 8)); if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "class_streams") {
-        ctx->classStreamsOpt = value != 0;
-        for (int kk = 0; kk < 8 && value != 0; ++kk)     // (created when the option is first switched on: an experiment's streams)
-            for (int a = 0; a < 2; ++a)
-                if (!ctx->classStream[kk][a]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->classStream[kk][a], hipStreamNonBlocking));
-    }
-    else if (k == "inst_simple") ctx->instSimpleOpt = value != 0;
-    else if (k == "inst_dyn") { ctx->instDynOpt = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "inst_shadow_fast") { ctx->instShadowFast = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "inst_wide") { ctx->instWideOpt = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
     else if (k == "inst_phase_min") ctx->instPhaseMin = int(std::min<long long>(std::max<long long>(value, 1), 64));
     else if (k == "inst_refill_at") ctx->instRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 63));
     else if (k == "grid_rounds") { ctx->gridRounds = int(std::min<long long>(std::max<long long>(value, 1), 8)); ctx->poolMem.release(); ctx->poolSlots = 0; }
-    else if (k == "blocks_per_cu") { ctx->blocksPerCuOpt = int(std::min<long long>(std::max<long long>(value, 0), 8)); if (ctx->haveScene) chooseThreads(ctx); }
     else if (k == "leaf_batch_bvh2") ctx->leafBatchBvh2 = int(std::min<long long>(std::max<long long>(value, 0), 64));
     else if (k == "suspend_lanes") ctx->suspendLanes = int(std::min<long long>(std::max<long long>(value, 0), 64));
     else if (k == "suspend_turns") ctx->suspendTurns = int(std::min<long long>(std::max<long long>(value, 1), 1 << 20));   // (>= 1: every launch advances every walk)
     else if (k == "suspend_min_queue") ctx->suspendMinQueue = int(std::min<long long>(std::max<long long>(value, 0), 1 << 20));
-    else if (k == "decouple") ctx->decoupleOpt = value != 0;
-    else if (k == "inst_shadow_join") ctx->instShadowJoin = value != 0;
     else if (k == "fail_reduce") ctx->failReduce = value != 0;   // fault injection: tghip_reduce_framebuffers with this context as a rank fails (the hosts' fallbacks are tested with it)
-    else if (k == "tail_kernel") ctx->tailOpt = value != 0;
-    else if (k == "tail_family") ctx->tailFamilyOpt = value != 0;
     else if (k == "hoist_quad") { ctx->hoistOpt = value != 0; if (!ctx->hoistOpt) ctx->scene.hoisted_rec = -1; else ctx->scene.hoisted_rec = ctx->sc.hoisted.record; }
-    else if (k == "merge_miss") ctx->mergeMissOpt = value != 0;
-    else if (k == "fold_finish") ctx->foldFinishOpt = value != 0;
     else if (k == "top_tree") ctx->topTreeOpt = value != 0;
-    else if (k == "lds_tables") ctx->tablesFit = ctx->sc.tablesFit && value != 0;
     else if (k == "env_lds") ctx->scene.env_tex = value != 0 ? ctx->sc.env_tex : -1;
-    else if (k == "media_lean") ctx->mediaLeanOpt = value != 0;
     else if (k == "tail_threshold") ctx->tailThreshold = value;
     else if (k == "lds_nodes") {}   // (accepted, no effect: the top of the wide tree in LDS was measured without gain and is gone, profiles/r5_ab_walk_fetch.txt)
     else if (k == "leaf_batch") ctx->leafBatch = int(std::min<long long>(std::max<long long>(value, 1), 64));
-    else if (k == "fuse_flat") ctx->fuseFlatOpt = value != 0;
-    else if (k == "shade_fused") ctx->shadeFusedOpt = value != 0;
     else if (k == "develop_host") ctx->developHost = value != 0;   // tghip_develop answers TGHIP_E_UNSUPPORTED: the host integrator then develops a download itself
     else if (k == "nlmeans_batch") ctx->nlmBatch = uint32_t(std::min<long long>(std::max<long long>(value, 0), NLMEANS_MAX_BATCH));   // offsets box-filtered at once by tghip_nlmeans (0: the measured choice, denoise.hip)
     else if (k == "query_blocks") ctx->queryBlocks = int(std::min<long long>(std::max<long long>(value, 0), 1 << 16));       // workgroups of tghip_query_rays (0: the measured default)
     else if (k == "query_refill_at") ctx->queryRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 64));   // idle lanes of a wave at which it claims rays (0: the measured default)
-    else if (k == "run_to_completion") ctx->loopOpt = value != 0;
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
     else if (k == "wide_node_stride") {
         if (value != 128 && value != 80) { ctx->error = "wide_node_stride is 80 or 128"; return TGHIP_E_INVALID; }
         ctx->wideStride = int(value);
     }
-    else if (k == "wide_closest") { ctx->wideClosestOpt = value < 0 ? -1 : value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "wide_shadow") { ctx->wideShadowOpt = value < 0 ? -1 : value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "wide_bvh") { ctx->wideOpt = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "dynamic_fetch") { ctx->dynamicFetch = value != 0; if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "threads_closest") { ctx->thrOverride[0] = int(value); if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "threads_shadow") { ctx->thrOverride[1] = int(value); if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "threads_shade_simple") { ctx->thrOverride[2] = int(value); if (ctx->haveScene) chooseThreads(ctx); }
-    else if (k == "threads_shade_complex") { ctx->thrOverride[3] = int(value); if (ctx->haveScene) chooseThreads(ctx); }
     else { ctx->error = "unknown option '" + k + "'"; return TGHIP_E_INVALID; }
     return TGHIP_OK;
 }
@@ -1017,7 +961,7 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
     s.env_tex = sc.env_tex; s.env_h = sc.env_h;
     s.env_marginal = sc.env_tex >= 0 ? s.dist + sd->textures[sc.env_tex].dist_offset : nullptr;   // mpdf[h] mcdf[h + 1] (device pointer arithmetic only)
     if ((rc = uploadArray(ctx, ctx->sceneMem, sc.envGuide.data(), sc.envGuide.size(), &s.env_guide)) != TGHIP_OK) return rc;
-    ctx->tablesFit = sc.tablesFit;
+    ctx->opt.ldsTables = true;            // ("lds_tables" = 0 holds until the next upload)
     if ((rc = uploadArray(ctx, ctx->sceneMem, sc.recClass.data(), sc.recClass.size(), &s.rec_class)) != TGHIP_OK) return rc;
     s.num_nodes = sd->num_nodes; s.num_recs = sd->num_recs; s.num_objects = sd->num_objects;
     s.num_lights = sd->num_lights; s.num_infinite_lights = sd->num_infinite_lights;
@@ -1065,7 +1009,7 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->haveScene = true;
-    chooseThreads(ctx);
+    if ((rc = replan(ctx)) != TGHIP_OK) return rc;
     return tghip_clear_framebuffer(ctx);
 }
 
@@ -1094,135 +1038,6 @@ int tghip_bind_framebuffer(tghip_ctx *ctx, float *dev_rgb_sum, uint32_t *dev_cou
     return TGHIP_OK;
 }
 
-extern "C++" {
-template<uint32_t M, int FUSE>
-static void launchShadeVariant(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int cls)
-{
-    constexpr uint32_t B = M & ~FEAT_QMC;
-    if (!ctx->tablesFit) {
-        // the scene's small tables do not fit the shading workgroups' LDS copy (pt_kernels.h: stageSceneTables): every class shades with the
-        // all-features variant that reads them from global memory (runBatch keeps such scenes off the fused and the tail launches)
-        hipLaunchKernelGGL((k_shade<BSDF_MASK_ALL, 2, 0, true>), dim3(grid), dim3(ctx->thrShadeAll), 0, ctx->launchStream, ctx->scene, st, pp, cls);
-        return;
-    }
-    hipLaunchKernelGGL((k_shade<M, ((B == MASK_SIMPLE || B == MASK_SIMPLE_INST) ? SIMPLE_WAVES : B == MASK_LEAN ? LEAN_WAVES : B == MASK_COAT ? COAT_WAVES : 2), FUSE>), dim3(grid),
-                       dim3((M == BSDF_MASK_ALL || M == MASK_MEDIA) ? ctx->thrShadeAll : (cls >= 1 && cls < PT_NUM_CLASSES) ? ctx->thrShadeComplex : ctx->thrShadeSimple), 0, ctx->launchStream, ctx->scene, st, pp, cls);
-}
-// TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS passes run the FEAT_QMC twin of the variant the scene would use anyway
-template<uint32_t M, int FUSE = 0>
-static void launchShade(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int cls)
-{
-    if (pp.flags) launchShadeVariant<M | FEAT_QMC, FUSE>(ctx, grid, st, pp, cls);
-    else          launchShadeVariant<M, FUSE>(ctx, grid, st, pp, cls);
-}
-
-// the launch of shading class `cls` (1 .. 3) of a scene without media / auxiliary outputs / cylinders / mesh emitters: the smallest variant
-// that covers the BSDF types of the class's materials (pt_kernels.h: PT_NUM_CLASSES)
-template<int FUSE>
-static void launchComplexClass(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int cls)
-{
-    const bool plasticOnly = familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false);
-    if constexpr (FUSE == 0) {
-        if (ctx->sc.haveInstances) {
-            if (cls == 1)                     launchShade<MASK_COAT_INST>(ctx, grid, st, pp, cls);
-            else if (cls == 2)                launchShade<MASK_GLASS_INST>(ctx, grid, st, pp, cls);
-            else if (plasticOnly)             launchShade<MASK_PLASTIC_INST>(ctx, grid, st, pp, cls);
-            else                              launchShade<MASK_FULL>(ctx, grid, st, pp, cls);
-            return;
-        }
-    }
-    if (cls == 1)         launchShade<MASK_COAT, FUSE>(ctx, grid, st, pp, cls);
-    else if (cls == 2)    launchShade<MASK_GLASS, FUSE>(ctx, grid, st, pp, cls);
-    else if (plasticOnly) launchShade<MASK_PLASTIC, FUSE>(ctx, grid, st, pp, cls);
-    else                  launchShade<MASK_FULL, FUSE>(ctx, grid, st, pp, cls);
-}
-
-// The further class (1 .. 3) of a scene whose iterations shade in one launch of k_shade_fused, 0 for every other scene: single-level BVH scenes
-// whose tables fit the LDS copy, with class 0 and exactly ONE further class that one of the instantiated pairs covers, on the launch sequence the
-// pairs were built from (class 0 merged with the escaped paths, one stream per part).  Three or more classes, instanced scenes, media, auxiliary
-// outputs, cylinders, mesh emitters, lean scenes and flat lists keep their per-class launches.
-static int shadeFusedPair(const tghip_ctx *ctx)
-{
-    if (!ctx->shadeFusedOpt || isFlat(ctx) || ctx->sc.haveInstances || ctx->sc.haveMedia || ctx->auxPass || ctx->sc.allFeaturesShading || ctx->sc.haveMeshLight ||
-        ctx->sc.leanScene || !ctx->tablesFit || !ctx->mergeMissOpt || ctx->classStreamsOpt != 0)
-        return 0;
-    int further = 0, n = 0;
-    for (int c = 1; c < PT_NUM_CLASSES; ++c)
-        if (ctx->sc.classPresent[c]) { further = c; ++n; }
-    if (n != 1 || (further == 3 && !familyCovers(TGHIP_BSDF_VARIANT_PLASTIC, ctx->sc.classMask[3], false)))
-        return 0;
-    return further;
-}
-// (the workgroup size of the further class's launches: both phases run at it)
-template<uint32_t MF, int W>
-static void launchShadeFused(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, int further)
-{
-    if (pp.flags) hipLaunchKernelGGL((k_shade_fused<(MF | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), W>), dim3(grid), dim3(ctx->thrShadeComplex), 0, ctx->launchStream, ctx->scene, st, pp, further);
-    else          hipLaunchKernelGGL((k_shade_fused<MF, MASK_SIMPLE, W>), dim3(grid), dim3(ctx->thrShadeComplex), 0, ctx->launchStream, ctx->scene, st, pp, further);
-}
-
-// true when the shadow step needs its second half, k_finish (the dynamic-fetch kernel does not regenerate paths itself)
-template<bool COUNT>
-static bool launchShadow(tghip_ctx *ctx, int grid, const PathState &st, const PassParams &pp, uint32_t iterTag)
-{
-    const size_t ldsBytes = traceLdsBytes(ctx, ctx->thrShadow);
-    const bool flat = isFlat(ctx);
-    const bool closestWalk = ctx->sc.haveForward || ctx->sc.haveMeshLight;   // shadow rays are closest-hit walks, not any-hit queries
-    const bool wideShadow = wideShadowRays(ctx) && !closestWalk && !ctx->auxPass;
-    if ((ctx->sc.haveProcTex || ctx->sc.haveFibre) && closestWalk) {       // (closestWalk: never the wide or the dynamic-fetch any-hit kernels; haveFibre: the one family with the fibre BCSDFs)
-#define SHADOW_TEX(FLAT, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, true, FLAT, I, BSDF_MASK_ALL>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (ctx->sc.haveInstances) { if (ctx->sc.haveSolids) SHADOW_TEX(false, 1); else SHADOW_TEX(false, 2); }
-        else if (flat) SHADOW_TEX(true, 0);
-        else           SHADOW_TEX(false, 0);
-#undef SHADOW_TEX
-        return false;
-    }
-    if (ctx->sc.haveInstances && !wideShadow) {
-#define SHADOW_INST(FWD, I) hipLaunchKernelGGL((k_trace_shadow<COUNT, FWD, false, I>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (closestWalk) { if (ctx->sc.haveSolids) SHADOW_INST(true, 1); else SHADOW_INST(true, 2); }
-        else             { if (ctx->sc.haveSolids) SHADOW_INST(false, 1); else SHADOW_INST(false, 2); }
-#undef SHADOW_INST
-        return false;
-    }
-    if (wideShadow) {
-        const size_t lds = wideLdsBytes(ctx, ctx->thrShadow);
-#define SHADOW_WIDE(S, I) hipLaunchKernelGGL((k_trace_shadow_wide<COUNT, S, I>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag)
-        if (ctx->sc.haveInstances) {
-            // (rounds 2 and 3 launched the counting variant here: the non-counting one lost occluders inside instances.  The cause is the
-            // loop latch the backend generates for the turn without PT_TURN_JOIN, pt_wavefront.h; "inst_shadow_join" = 0 launches that
-            // variant for tools/repro_latch_miscompile.py)
-            if (!ctx->instShadowJoin && !ctx->sc.haveSolids && !COUNT)
-                hipLaunchKernelGGL((k_trace_shadow_wide<false, false, true, false>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
-            else if (ctx->instShadowFast) {      // round 6: the two-level walk inside the fast kernel's slot handling
-                if (ctx->sc.haveSolids) hipLaunchKernelGGL((k_trace_shadow_fast_inst<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
-                else                 hipLaunchKernelGGL((k_trace_shadow_fast_inst<COUNT, false>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag);
-            }
-            else if (ctx->sc.haveSolids) SHADOW_WIDE(true, true); else SHADOW_WIDE(false, true);
-        }
-        else if (ctx->decoupleOpt) {
-#define SHADOW_WIDE_D(S) hipLaunchKernelGGL((k_trace_shadow_fast<COUNT, S>), dim3(grid), dim3(ctx->thrShadow), lds, ctx->launchStream, ctx->scene, st, pp, iterTag)
-            if (ctx->sc.haveSolids) SHADOW_WIDE_D(true); else SHADOW_WIDE_D(false);
-#undef SHADOW_WIDE_D
-        }
-        else                    { if (ctx->sc.haveSolids) SHADOW_WIDE(true, false); else SHADOW_WIDE(false, false); }
-#undef SHADOW_WIDE
-        return true;
-    }
-    if (!flat && !closestWalk && ctx->dynamicFetch && !ctx->auxPass) {   // (the dynamic-fetch kernel does not report transmittances)
-        if (ctx->sc.haveSolids) hipLaunchKernelGGL((k_trace_shadow_dyn<COUNT, true>), dim3(grid), dim3(ctx->thrShadow), dynLdsBytes(ctx, ctx->thrShadow), ctx->launchStream,
-                                                ctx->scene, st, pp, iterTag);
-        else                 hipLaunchKernelGGL((k_trace_shadow_dyn<COUNT, false>), dim3(grid), dim3(ctx->thrShadow), dynLdsBytes(ctx, ctx->thrShadow), ctx->launchStream,
-                                                ctx->scene, st, pp, iterTag);
-        return true;
-    }
-#define SHADOW_LAUNCH(FWD, FLAT) hipLaunchKernelGGL((k_trace_shadow<COUNT, FWD, FLAT>), dim3(grid), dim3(ctx->thrShadow), ldsBytes, ctx->launchStream, ctx->scene, st, pp, iterTag)
-    if (closestWalk) { if (flat) SHADOW_LAUNCH(true, true); else SHADOW_LAUNCH(true, false); }
-    else                  { if (flat) SHADOW_LAUNCH(false, true); else SHADOW_LAUNCH(false, false); }
-#undef SHADOW_LAUNCH
-    return false;
-}
-
-} // extern "C++"
 
 // Runs the wavefront loop for one batch of work items until every slot is drained.
 static int runBatch(tghip_ctx *ctx, const PassParams &pp)
@@ -1233,21 +1048,20 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     st.partial = ctx->partial;
     st.abort_flag = ctx->abortFlagDev;
     st.leaf_batch = uint32_t(ctx->leafBatch);
-    st.inst_tree_depth = uint32_t(instTreeDepth(ctx));
+    const LaunchPlan &lp = ctx->lp;              // (tghip_wait planned the pass's kind)
+    const LaunchChoice &choice = lp.choice;
+    st.inst_tree_depth = uint32_t(choice.instTreeDepth);
     st.inst_phase_min = uint32_t(ctx->instPhaseMin);
     st.inst_refill_at = uint32_t(ctx->instRefillAt);
-    st.nee_factors = (ctx->sc.haveForward || ctx->sc.haveMeshLight) ? 1u : 0u;   // launchShadow: the closest-hit shadow walk, k_trace_shadow<., FORWARD>
+    st.nee_factors = choice.neeFactors ? 1u : 0u;   // the closest-hit shadow walk, k_trace_shadow<., FORWARD>
     st.suspend_lanes = ctx->poolWalkArrays ? uint32_t(ctx->suspendLanes) : 0u;
     st.suspend_turns = uint32_t(std::max(ctx->suspendTurns, 1));
     st.suspend_min_queue = uint32_t(ctx->suspendMinQueue);
     st.leaf_batch_bvh2 = uint32_t(ctx->leafBatchBvh2 > 0 ? ctx->leafBatchBvh2 : ctx->sc.haveInstances ? 16 : ctx->leafBatch);
     const DeviceScene &s = ctx->scene;
     const int grid = int(ctx->poolGrid);
-    const bool count = ctx->countTraversal;
-    const bool flat = isFlat(ctx);
-    const bool fused = fusedFlat(ctx);
-    const bool runToCompletion = oneLaunch(ctx);   // one launch renders the whole batch
-    const size_t ldsBytes = traceLdsBytes(ctx, ctx->thrClosest);
+    const bool fused = choice.fusedFlat;
+    const bool runToCompletion = choice.oneLaunch;   // one launch renders the whole batch
 
     // optional per-launch timing: one event pair per kernel launch of a check interval, read back at the
     // interval's host sync (events live on ctx->stream, the stream the kernels are launched on)
@@ -1270,12 +1084,10 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     auto tic = ticMain;
 
     // "streams" = N > 1: the workgroups (and with them the slots, queues and work items) are split into N parts that run the same
-    // wavefront loop on N streams: kernels of different parts share the CUs (chooseThreads), and the drain tail of one part's kernel
+    // wavefront loop on N streams: kernels of different parts share the CUs (csrc/host/LaunchChoice.cpp), and the drain tail of one part's kernel
     // overlaps the other parts' kernels
-    // (materialtest 1280x720x256 / mesh1m 1920x1080x32 on one box: 2 parts 656 / 398 Msamples/s, 4 parts 666 / 412)
-    // (instanced scenes: two parts in rounds 2-3; with the walk of the reference's instance tree four are 5 % faster -- profiles/r4_sweep_instances10k.jsonl)
-    int parts = ctx->streamsOpt >= 2 ? ctx->streamsOpt : (ctx->streamsOpt == 1 || ctx->shortBatch) ? 1 : (!ctx->sc.haveInstances || ctx->blocksPerCu >= 8) ? 4 : 1;
-    if (fused || flat || grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
+    int parts = choice.parts;
+    if (grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
         parts = 1;
     const bool split = parts > 1;
     PathState stPart[8] = {st, st, st, st, st, st, st, st};
@@ -1309,146 +1121,56 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
     } else {
         hipLaunchKernelGGL(k_start, dim3(grid), dim3(256), 0, ctx->stream, s, st, pp);
     }
-    // k_tail runs the wide single-level kernels' bodies: scenes those kernels render, passes without visit counts (per-launch timing does
-    // not see it: the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
-    const bool tailEligible = ctx->tailOpt && !ctx->sc.cameraFix && ctx->tablesFit && !flat && !ctx->sc.haveInstances && wideClosest(ctx) && wideShadowRays(ctx) && ctx->decoupleOpt &&
-                              familyCovers(TGHIP_BSDF_VARIANT_TAIL, ctx->sc.complexMask, ctx->sc.haveForward) &&
-                              !ctx->sc.haveMeshLight && !ctx->sc.haveMedia && !ctx->auxPass && !ctx->sc.allFeaturesShading && !count &&
-                              st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
+    // k_tail: per-launch timing does not see it (the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
+    const bool tailEligible = choice.tailEligible && st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
+    const bool tailFits = tailEligible && lp.tailFits;
     const uint64_t tailThreshold = uint64_t(std::max<long long>(ctx->tailThreshold, 0));
-    // (k_tail runs 256 threads whatever the depth of the tree: it is used only where a workgroup of it fits a CU -- its static LDS plus
-    // the walk stacks of a very deep tree may not)
-    bool tailFits = false;
-    if (tailEligible) {
-        int nb = 0;
-        // (the conductor-family tail, tailCoat below, needs no more than the all-types one)
-        const void *fn = pp.flags ? (ctx->sc.haveSolids ? reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), true>) : reinterpret_cast<const void *>(k_tail<(MASK_TAIL | FEAT_QMC), false>))
-                                  : (ctx->sc.haveSolids ? reinterpret_cast<const void *>(k_tail<MASK_TAIL, true>) : reinterpret_cast<const void *>(k_tail<MASK_TAIL, false>));
-        tailFits = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, wideLdsBytes(ctx, 256)) == hipSuccess && nb >= 1;
-    }
-    // "fold_finish": k_finish rides in front of the next iteration's closest-hit launch (single-level scenes on the decoupled wide walk)
-    const bool foldFinish = ctx->foldFinishOpt && !ctx->sc.cameraFix && !flat && !ctx->sc.haveInstances && wideClosest(ctx) && ctx->decoupleOpt;
-    const int fusedClass = shadeFusedPair(ctx);  // != 0: the iteration's shading is one launch of k_shade_fused
-    // shading launches of an iteration (per part): one for class 0 and the escaped paths (two when "merge_miss" = 0), one per further class
-    int shadeLaunches = 1;
-    if (!fusedClass) {
-        shadeLaunches = (ctx->classStreamsOpt != 0 || !ctx->mergeMissOpt) ? 2 : 1;
-        for (int c = 1; c < PT_NUM_CLASSES; ++c)
-            if (ctx->sc.classPresent[c]) ++shadeLaunches;
-    }
+    const bool foldFinish = choice.foldFinish;   // k_finish rides in front of the next iteration's closest-hit launch
+    const int shadeLaunches = choice.shadeLaunches;
     uint32_t iterTag = 1;                        // k_start publishes tag 1 when it queued anything
     bool first = true;
     int roundIters = checkInterval;              // launches of the wavefront loop between two host checks
         // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
+        // The shading launches of an iteration, in the choice's order.  The classes (the escaped paths, Q_MISS; 0; the classes 1 .. 3 that occur) consume queues
+        // of their own and OR what they append into the workgroup's bitmaps (k_shade: CONCURRENT), so their launches MAY run side by side on three
+        // streams: the "class_streams" option gives launches a lane beside the part's stream.  Measured slower than one after the other (materialtest
+        // 735-800 against 825-830 Msamples/s, mesh1m 409 against 508, for 2 to 24 hardware queues): with four parts in flight the chip is not short of
+        // independent launches.
+        auto launchShading = [&](const PathState &st, const PassParams &pp, int grid, int part) {
+            const hipStream_t mainStream = ctx->launchStream;
+            bool forked = false, lanes[3] = {false, false, false};
+            for (int i = 0; i < choice.numShade; ++i) {
+                const int lane = choice.shade[i].lane;
+                hipStream_t stream = mainStream;
+                if (lane) {
+                    stream = ctx->classStream[part][lane - 1];
+                    if (!forked) (void)hipEventRecord(ctx->evFork[part], mainStream);
+                    (void)hipStreamWaitEvent(stream, ctx->evFork[part], 0);
+                    forked = lanes[lane] = true;
+                }
+                launchKernel(lp.shade[i], grid, stream, s, st, pp, choice.shade[i].cls);
+                if (lane) (void)hipEventRecord(ctx->evJoin[part][lane - 1], stream);
+            }
+            for (int lane = 1; lane < 3; ++lane)
+                if (lanes[lane]) (void)hipStreamWaitEvent(mainStream, ctx->evJoin[part][lane - 1], 0);
+        };
+        // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
         auto launchIteration = [&](const PathState &st, const PassParams &pp, int grid, uint32_t iterTag, bool timed, int part) {
             auto tic = [&]() { if (timed) ticMain(); };
-            if (ctx->sc.cameraFix)                  // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
+            if (choice.cameraRays)                  // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
                 hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp);
             tic();
-            if (flat) {
-                if (count) hipLaunchKernelGGL((k_trace_closest<true, true>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
-                else       hipLaunchKernelGGL((k_trace_closest<false, true>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
-            } else if (ctx->sc.haveInstances && !wideClosest(ctx) && ctx->dynamicFetch && ctx->instDynOpt) {
-                // the three-level walk with dynamic ray fetch
-                const bool iw = instWide(ctx);               // the masters through the wide BVH (round 6)
-                const size_t ldsDyn = iw ? instWideLdsBytes(ctx, ctx->thrClosest) : dynLdsBytes(ctx, ctx->thrClosest);
-#define CLOSEST_DYN_INST(C, S) do { if (iw) hipLaunchKernelGGL((k_trace_closest_instw<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st); \
-                                    else hipLaunchKernelGGL((k_trace_closest_inst<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st); } while (0)
-                if (ctx->sc.haveSolids) { if (count) CLOSEST_DYN_INST(true, true); else CLOSEST_DYN_INST(false, true); }
-                else                 { if (count) CLOSEST_DYN_INST(true, false); else CLOSEST_DYN_INST(false, false); }
-#undef CLOSEST_DYN_INST
-            } else if (ctx->sc.haveInstances && !wideClosest(ctx)) {
-#define CLOSEST_INST(C, I) hipLaunchKernelGGL((k_trace_closest<C, false, I>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st)
-                if (ctx->sc.haveSolids) { if (count) CLOSEST_INST(true, 1); else CLOSEST_INST(false, 1); }
-                else                 { if (count) CLOSEST_INST(true, 2); else CLOSEST_INST(false, 2); }
-#undef CLOSEST_INST
-            } else if (wideClosest(ctx)) {
-                const size_t ldsWide = wideLdsBytes(ctx, ctx->thrClosest);
-#define CLOSEST_WIDE(C, S, I, D) hipLaunchKernelGGL((k_trace_closest_wide<C, S, I, D>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st)
-                if (ctx->sc.haveInstances) {
-                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, true, false); else CLOSEST_WIDE(false, true, true, false); }
-                    else                 { if (count) CLOSEST_WIDE(true, false, true, false); else CLOSEST_WIDE(false, false, true, false); }
-                } else if (ctx->decoupleOpt && foldFinish) {
-                    // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
-#define CLOSEST_FIN(C, S) hipLaunchKernelGGL((k_finish_trace_closest_wide<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsWide, ctx->launchStream, s, st, pp)
-                    if (ctx->sc.haveSolids) { if (count) CLOSEST_FIN(true, true); else CLOSEST_FIN(false, true); }
-                    else                 { if (count) CLOSEST_FIN(true, false); else CLOSEST_FIN(false, false); }
-#undef CLOSEST_FIN
-                } else if (ctx->decoupleOpt) {
-                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, false, true); else CLOSEST_WIDE(false, true, false, true); }
-                    else                 { if (count) CLOSEST_WIDE(true, false, false, true); else CLOSEST_WIDE(false, false, false, true); }
-                } else {
-                    if (ctx->sc.haveSolids) { if (count) CLOSEST_WIDE(true, true, false, false); else CLOSEST_WIDE(false, true, false, false); }
-                    else                 { if (count) CLOSEST_WIDE(true, false, false, false); else CLOSEST_WIDE(false, false, false, false); }
-                }
-#undef CLOSEST_WIDE
-            } else {
-                if (ctx->dynamicFetch) {
-                    const size_t ldsDyn = dynLdsBytes(ctx, ctx->thrClosest);
-#define CLOSEST_DYN(C, S) hipLaunchKernelGGL((k_trace_closest_dyn<C, S>), dim3(grid), dim3(ctx->thrClosest), ldsDyn, ctx->launchStream, s, st)
-                    if (ctx->sc.haveSolids) { if (count) CLOSEST_DYN(true, true); else CLOSEST_DYN(false, true); }
-                    else                 { if (count) CLOSEST_DYN(true, false); else CLOSEST_DYN(false, false); }
-#undef CLOSEST_DYN
-                } else {
-                    if (count) hipLaunchKernelGGL((k_trace_closest<true, false>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
-                    else       hipLaunchKernelGGL((k_trace_closest<false, false>), dim3(grid), dim3(ctx->thrClosest), ldsBytes, ctx->launchStream, s, st);
-                }
-            }
+            if (choice.closest.kernel.family == K_FINISH_CLOSEST_WIDE)   // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
+                launchKernel(lp.closest, grid, ctx->launchStream, s, st, pp);
+            else
+                launchKernel(lp.closest, grid, ctx->launchStream, s, st);
             tic(); tic();
-            // The shading classes of an iteration (the escaped paths, Q_MISS; 0; the classes 1 .. 3 that occur) consume queues of their own and OR what they append
-            // into the workgroup's bitmaps (k_shade: CONCURRENT), so their launches MAY run side by side on three streams ("class_streams"
-            // option).  Measured slower than one after the other (materialtest 735-800 against 825-830 Msamples/s, mesh1m 409 against 508,
-            // for 2 to 24 hardware queues): with four parts in flight the chip is not short of independent launches.
-            // (which family a scene may get is restated for the tests in tests/light_cases.py: families_for -- the rule check of the lights' feature bits
-            // reads it; a change of this decision or of launchComplexClass's goes there as well)
-            auto shadeClass = [&](int cls) {
-                const bool simple = cls == 0 || cls == CLS_MISS || cls == CLS_0_AND_MISS;
-                if (ctx->sc.mediaSimple && ctx->mediaLeanOpt && !ctx->auxPass && !ctx->sc.allFeaturesShading && !ctx->sc.haveMeshLight)
-                    launchShadeVariant<MASK_MEDIA, 0>(ctx, grid, st, pp, cls);                      // media scenes with simple surfaces: no scratch
-                else if (ctx->sc.haveMedia || ctx->auxPass || ctx->sc.allFeaturesShading) launchShadeVariant<BSDF_MASK_ALL, 0>(ctx, grid, st, pp, cls);   // the one variant with FEAT_MEDIA / FEAT_AUX / FEAT_CYLINDER
-                else if (ctx->sc.haveMeshLight) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);   // the only variant with mesh-emitter sampling (every BSDF type)
-                else if (ctx->sc.haveInstances && simple && ctx->instSimpleOpt) launchShade<MASK_SIMPLE_INST>(ctx, grid, st, pp, cls);   // Lambert / escaped paths of instanced scenes
-                else if (ctx->sc.haveInstances && (simple || !ctx->instSimpleOpt)) launchShade<MASK_FULL>(ctx, grid, st, pp, cls);
-                else if (simple) {               // the escaped paths run the class-0 variant: its surface code never runs there, so the launch is short
-                    if (ctx->sc.leanScene) launchShade<MASK_LEAN>(ctx, grid, st, pp, cls);
-                    else                launchShade<MASK_SIMPLE>(ctx, grid, st, pp, cls);
-                }
-                else launchComplexClass<0>(ctx, grid, st, pp, cls);
-            };
-            hipStream_t mainStream = ctx->launchStream;
-            if (fusedClass) {
-                // (class 0, the escaped paths and the scene's one further class in one launch: k_shade_fused, pt_wavefront.h)
-                if (fusedClass == 1)      launchShadeFused<MASK_COAT, COAT_WAVES>(ctx, grid, st, pp, fusedClass);
-                else if (fusedClass == 2) launchShadeFused<MASK_GLASS, 2>(ctx, grid, st, pp, fusedClass);
-                else                      launchShadeFused<MASK_PLASTIC, 2>(ctx, grid, st, pp, fusedClass);
-            } else if (ctx->classStreamsOpt != 0) {
-                hipStream_t *aux = ctx->classStream[part];
-                (void)hipEventRecord(ctx->evFork[part], mainStream);
-                const int nAux = ctx->sc.haveComplex ? 2 : 1;
-                for (int a = 0; a < nAux; ++a) {
-                    (void)hipStreamWaitEvent(aux[a], ctx->evFork[part], 0);
-                    ctx->launchStream = aux[a];
-                    shadeClass(a == 0 ? CLS_MISS : 0);
-                    (void)hipEventRecord(ctx->evJoin[part][a], aux[a]);
-                }
-                ctx->launchStream = mainStream;
-                if (!ctx->sc.haveComplex) shadeClass(0);             // the longest launches stay on the part's own stream
-                for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->sc.classPresent[c]) shadeClass(c);
-                for (int a = 0; a < nAux; ++a)
-                    (void)hipStreamWaitEvent(mainStream, ctx->evJoin[part][a], 0);
-            } else {
-                // (class 0 and the escaped paths run the same variant: one launch over both queues, "merge_miss" = 0 keeps them apart)
-                if (ctx->mergeMissOpt) shadeClass(CLS_0_AND_MISS);
-                else { shadeClass(CLS_MISS); shadeClass(0); }
-                for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->sc.classPresent[c]) shadeClass(c);
-            }
+            launchShading(st, pp, grid, part);
             tic(); tic();
-            const bool finish = count ? launchShadow<true>(ctx, grid, st, pp, iterTag) : launchShadow<false>(ctx, grid, st, pp, iterTag);
+            launchKernel(lp.shadow, grid, ctx->launchStream, s, st, pp, iterTag);
             tic();
-            (void)finish;                        // (always: the shading launches leave their finished paths to k_finish as well)
-            if (!foldFinish)                     // (folded: the next iteration's closest-hit launch, or finishParts before a host check)
+            if (!foldFinish)                     // (always: the shading launches leave their finished paths to k_finish as well; folded: the next iteration's
+                                                 // closest-hit launch, or finishParts before a host check)
                 hipLaunchKernelGGL(k_finish, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp, iterTag);
         };
         // folded k_finish: the last iteration's finish as a launch of its own -- before the host reads the liveness word, before k_tail
@@ -1491,23 +1213,14 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 break;                           // the last iteration left every extension queue empty
             if (tailFits && uint64_t(ctx->hostLive[1]) <= tailThreshold) {
                 // few paths left: each part of the pool finishes in one launch of k_tail (its workgroups iterate on their own)
-                const size_t ldsTail = wideLdsBytes(ctx, 256);
                 uint32_t classes = 1u;
                 for (int c = 1; c < PT_NUM_CLASSES; ++c)
                     if (ctx->sc.classPresent[c]) classes |= 1u << c;
                 for (int k = 0; k < parts; ++k) {
-                    const PathState &sp = split ? stPart[k] : st;
-                    const PassParams &ppk = split ? ppPart[k] : pp;
                     const hipStream_t stream = split ? streamOf[k] : ctx->stream;
                     if (k) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evMain, 0));   // (after the main stream's check above)
                     else if (split) HIP_TRY(ctx, hipEventRecord(ctx->evMain, ctx->stream));
-#define TAIL_LAUNCH(M, S) hipLaunchKernelGGL((k_tail<M, S>), dim3(grid/parts), dim3(256), ldsTail, stream, s, sp, ppk, classes)
-                    // scenes of Lambert / null and conductor-family materials only (the metric's): the narrower instantiation, "tail_family" = 0 for the A/B
-                    const bool tailCoat = ctx->tailFamilyOpt && !ctx->sc.haveSolids && !ctx->sc.classPresent[2] && !ctx->sc.classPresent[3];
-                    if (tailCoat) { if (pp.flags) TAIL_LAUNCH((MASK_COAT | FEAT_QMC), false); else TAIL_LAUNCH(MASK_COAT, false); }
-                    else if (pp.flags) { if (ctx->sc.haveSolids) TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), true); else TAIL_LAUNCH((MASK_TAIL | FEAT_QMC), false); }
-                    else          { if (ctx->sc.haveSolids) TAIL_LAUNCH(MASK_TAIL, true); else TAIL_LAUNCH(MASK_TAIL, false); }
-#undef TAIL_LAUNCH
+                    launchKernel(lp.tail, grid/parts, stream, s, split ? stPart[k] : st, split ? ppPart[k] : pp, classes);
                 }
                 for (int k = 1; k < parts; ++k) {
                     HIP_TRY(ctx, hipEventRecord(ctx->evPart[k - 1], streamOf[k]));
@@ -1532,14 +1245,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
                 PassParams ppi = pp;
                 ppi.iter_tag = iterTag;
                 tic(); tic(); tic();
-                if (runToCompletion) {
-                    if (ctx->sc.leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW | FUSE_LOOP>(ctx, grid, st, ppi, 0);
-                    else                launchShade<MASK_SIMPLE, FUSE_TRACE | FUSE_SHADOW | FUSE_LOOP>(ctx, grid, st, ppi, 0);
-                }
-                else if (ctx->sc.leanScene) launchShade<MASK_LEAN, FUSE_TRACE | FUSE_SHADOW>(ctx, grid, st, ppi, 0);
-                else                     launchShade<MASK_SIMPLE, FUSE_TRACE | FUSE_SHADOW>(ctx, grid, st, ppi, 0);
-                for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->sc.classPresent[c]) launchComplexClass<FUSE_SHADOW>(ctx, grid, st, ppi, c);
+                launchShading(st, ppi, grid, 0);
                 tic(); tic(); tic();
                 ctx->counters.iterations++;
                 continue;
@@ -1616,7 +1322,11 @@ int tghip_wait(tghip_ctx *ctx)
     int rc = planPass(pass, w, h, planOpt, plan, ctx->error);
     if (rc != TGHIP_OK || plan.empty)
         return ctx->passResult = rc;
-    ctx->auxPass = plan.auxPass;
+    // the kernels of a pass of this kind -- a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch) --: planned again only
+    // when the kind differs from the last pass's
+    const PassKind kind = passKindOf(ctx->sc, pass.flags, plan.shortBatch, ctx->countTraversal);
+    if (!(kind == ctx->lp.kind) && (rc = planLaunches(ctx, kind, ctx->lp)) != TGHIP_OK)
+        return ctx->passResult = rc;
 
     // the device arrays the plan names
     auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
@@ -1663,7 +1373,7 @@ int tghip_wait(tghip_ctx *ctx)
         base.num_sorted = uint32_t(plan.sorted.size());
         base.num_chunks = plan.chunksAll;
     }
-    if (ctx->auxPass && !ctx->dAux) {
+    if (plan.auxPass && !ctx->dAux) {
         const size_t npix = size_t(w)*h;
         HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dAux), npix*sizeof(TgHipAuxPixel)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->dAux, 0, npix*sizeof(TgHipAuxPixel), ctx->stream));
@@ -1677,16 +1387,11 @@ int tghip_wait(tghip_ctx *ctx)
         base.samples = ctx->dSamples; base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
     }
 
-    // a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch; chooseThreads picks grid and workgroup sizes)
-    if (plan.shortBatch != ctx->shortBatch) {
-        ctx->shortBatch = plan.shortBatch;
-        chooseThreads(ctx);
-    }
     uint64_t wantSlots = std::min<uint64_t>(uint64_t(ctx->maxSlots), plan.batchItems);
     // the run-to-completion kernel (runBatch) gives every thread its own slots for the whole launch: one slot per
     // thread keeps the whole path state (112 B x 0.5 M slots) inside the Infinity Cache -- measured +5 % over four
-    if (oneLaunch(ctx) && !ctx->maxSlotsSet)
-        wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->thrShadeSimple));
+    if (ctx->lp.choice.oneLaunch && !ctx->maxSlotsSet)
+        wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->lp.thrShade[SIZE_SIMPLE]));
     if ((rc = ensurePool(ctx, uint32_t(wantSlots))) != TGHIP_OK) return ctx->passResult = rc;
     if ((rc = growArray(ctx, ctx->partial, ctx->partialCap, size_t(plan.batchItems))) != TGHIP_OK) return ctx->passResult = rc;
     // the device word still holds the previous pass's abort, if any; a request for THIS pass is re-mirrored by runBatch
@@ -1721,7 +1426,7 @@ int tghip_wait(tghip_ctx *ctx)
     if (verbose)
         std::fprintf(stderr, "[tghip] pass spp [%u, %u) flags %u: %llu items of %u samples in batches of %llu, %u slots, short %d; setup %.2f ms, loop %.2f ms (%llu iterations, device %.2f ms)\n",
                      pass.spp_begin, pass.spp_end, pass.flags, (unsigned long long)plan.totalItems, plan.chunk,
-                     (unsigned long long)plan.batchItems, ctx->pool.num_slots, int(ctx->shortBatch), msSetup, msSince(tLoop0), (unsigned long long)(ctx->counters.iterations - itersBefore), double(ms));
+                     (unsigned long long)plan.batchItems, ctx->pool.num_slots, int(plan.shortBatch), msSetup, msSince(tLoop0), (unsigned long long)(ctx->counters.iterations - itersBefore), double(ms));
     return ctx->passResult = rc;
 }
 
@@ -2209,6 +1914,30 @@ int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_
     return TGHIP_OK;
 }
 
+int tghip_debug_launch_plan(tghip_ctx *ctx, const TgHipPassDesc *pass, TgHipLaunchPlan *out)
+{
+    if (!ctx || !pass || !out) return TGHIP_E_INVALID;
+    if (!ctx->haveScene) { ctx->error = "launch plan without an uploaded scene"; return TGHIP_E_NOSCENE; }
+    int rc = checkPass(*pass, ctx->width, ctx->height, ctx->scene.sobol != nullptr, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PassPlan passPlan;
+    const PassPlanOptions planOpt = {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), uint32_t(std::max(ctx->chunkSamples, 0))};
+    if ((rc = planPass(*pass, ctx->width, ctx->height, planOpt, passPlan, ctx->error)) != TGHIP_OK) return rc;
+    LaunchPlan lp;
+    if ((rc = planLaunches(ctx, passKindOf(ctx->sc, pass->flags, passPlan.shortBatch, ctx->countTraversal), lp)) != TGHIP_OK) return rc;
+    std::memset(out, 0, sizeof *out);
+    exportLaunchChoice(lp.choice, &out->choice);
+    out->threads_closest = lp.closest.threads; out->threads_shadow = lp.shadow.threads; out->threads_tail = lp.tail.threads;
+    for (int i = 0; i < 3; ++i) out->threads_shade[i] = lp.thrShade[i];
+    if (!lp.choice.fusedFlat) { out->lds_closest = uint32_t(lp.closest.lds); out->lds_shadow = uint32_t(lp.shadow.lds); }   // (fused flat lists launch no walk)
+    out->lds_tail = uint32_t(lp.tail.lds);
+    out->grid = uint32_t(ctx->prop.multiProcessorCount*std::max(lp.choice.blocksPerCu, 1)*std::max(ctx->gridRounds, 1));
+    out->parts = (int(out->grid) < 2*lp.choice.parts || int(out->grid) % lp.choice.parts != 0) ? 1 : lp.choice.parts;
+    out->tail_fits = lp.tailFits;
+    return TGHIP_OK;
+}
+
 extern "C++" void tghipDestroyRankComm(void *comm)
 {
     std::lock_guard<std::mutex> lock(g_rccl.mutex);
@@ -2297,28 +2026,16 @@ int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_
     if (rc != TGHIP_OK) { (void)hipFree(dRays); (void)hipFree(dHits); return rc; }
     (void)hipMemcpyAsync(dRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream);
     const int grid = int(std::min<size_t>(size_t(launchGrid(ctx)), (n + 255)/256));
-    const size_t ldsBytes = traceLdsBytes(ctx, 256);
+    // the walk of the choice (csrc/host/LaunchChoice.cpp); the wide one keeps no queue in LDS, only its group stack
+    const LaunchChoice &choice = ctx->lp.choice;
+    KernelId kernel = choice.traceRays;
+    const size_t lds = choice.rayWalk == LaunchChoice::RAYS_WIDE ? size_t(std::max(ctx->sc.wideDepth, 1))*256u*sizeof(uint2) : ldsBytes(ctx->sc, choice, LDS_TRACE, 256);
+    const uint32_t count = uint32_t(n);
     repeats = std::max(repeats, 1);
     (void)hipEventRecord(ctx->evA, ctx->stream);
     for (int r = 0; r < repeats; ++r) {
-        const bool cnt = ctx->countTraversal && r == 0;
-        const bool flat = isFlat(ctx);
-#define RAYS_LAUNCH(C, F) hipLaunchKernelGGL((k_trace_rays<C, F>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats)
-        // (closest hits of a scene with `instances` primitives are a matter of the reference's visiting order: the BVH2 walk, never the wide one)
-        if (useWide(ctx) && !ctx->sc.haveInstances) {
-            const size_t ldsWide = size_t(std::max(ctx->sc.wideDepth, 1))*256u*sizeof(uint2);
-#define RAYS_WIDE(C, I) hipLaunchKernelGGL((k_trace_rays<C, false, I, true>), dim3(grid), dim3(256), ldsWide, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats)
-            if (ctx->sc.haveInstances) { if (cnt) RAYS_WIDE(true, 1); else RAYS_WIDE(false, 1); }
-            else                    { if (cnt) RAYS_WIDE(true, 0); else RAYS_WIDE(false, 0); }
-#undef RAYS_WIDE
-        }
-        else if (ctx->sc.haveInstances) {
-            if (cnt) hipLaunchKernelGGL((k_trace_rays<true, false, 1>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats);
-            else     hipLaunchKernelGGL((k_trace_rays<false, false, 1>), dim3(grid), dim3(256), ldsBytes, ctx->stream, ctx->scene, dRays, dHits, uint32_t(n), ctx->pool.stats);
-        }
-        else if (cnt) { if (flat) RAYS_LAUNCH(true, true); else RAYS_LAUNCH(true, false); }
-        else          { if (flat) RAYS_LAUNCH(false, true); else RAYS_LAUNCH(false, false); }
-#undef RAYS_LAUNCH
+        kernel.count = ctx->countTraversal && r == 0;
+        launchKernel(ResolvedLaunch{walkKernelFn(kernel), 256, lds}, grid, ctx->stream, ctx->scene, dRays, dHits, count, ctx->pool.stats);
     }
     (void)hipEventRecord(ctx->evB, ctx->stream);
     (void)hipMemcpyAsync(hits, dHits, n*sizeof(TgHipHit), hipMemcpyDeviceToHost, ctx->stream);
@@ -2359,10 +2076,11 @@ int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipR
         dOut = ctx->queryOut;
     }
     // the walk tghip_trace_rays answers with on this scene, and its stack
-    const bool wide = useWide(ctx) && !ctx->sc.haveInstances;
-    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : ctx->sc.haveInstances ? RAY_QUERY_INST : isFlat(ctx) ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    const LaunchChoice &choice = ctx->lp.choice;
+    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE;
+    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : choice.rayWalk == LaunchChoice::RAYS_INST ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
     const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
-                            : std::max<size_t>(traceLdsBytes(ctx, RAY_QUERY_THREADS), sizeof(int));
+                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
     // workgroups: as many as stay resident, no more than the batch has waves for (a workgroup without a ray only reads the counter)
     const size_t perWave = (n + 63)/64;
     const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)

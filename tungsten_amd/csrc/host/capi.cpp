@@ -6,6 +6,7 @@
 #include "EmbreeTopTree.hpp"
 #include "ImageIO.hpp"
 #include "Integrator.hpp"
+#include "LaunchChoice.hpp"
 #include "PassPlan.hpp"
 #include "Sampling.hpp"
 #include "Scene.hpp"
@@ -530,6 +531,27 @@ int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, u
         if (needs) needs[i] = n;
         if (covered) covered[i] = (n & ~mask) == 0u ? 1u : 0u;
     }
+    return TGHIP_OK;
+}
+
+int tgh_launch_choice(const TgHipSceneDesc *scene, const char *const *keys, const long long *values, uint32_t num_options,
+                      uint32_t pass_flags, int short_batch, TgHipLaunchChoice *out, char *err, size_t errlen)
+{
+    if (!scene || !out || (num_options && (!keys || !values))) { setErr(err, errlen, "no scene description, no options or no output"); return TGHIP_E_INVALID; }
+    SceneTraits t;
+    std::string error;
+    const int rc = checkScene(scene, SceneCheckOptions(), t, error);
+    if (rc != TGHIP_OK) { setErr(err, errlen, error); return rc; }
+    LaunchOptions opt;
+    bool count = false;
+    for (uint32_t i = 0; i < num_options; ++i) {
+        const std::string k = keys[i] ? keys[i] : "";
+        if (k == "count_traversal") count = values[i] != 0;
+        else if (!setLaunchOption(opt, k, values[i])) { setErr(err, errlen, "the launch choice reads no option '" + k + "'"); return TGHIP_E_INVALID; }
+    }
+    LaunchChoice c;
+    chooseLaunches(t, scene->num_recs, scene->num_wide_nodes, opt, passKindOf(t, pass_flags, short_batch != 0, count), c);
+    exportLaunchChoice(c, out);
     return TGHIP_OK;
 }
 
