@@ -655,6 +655,55 @@ typedef struct TgHipRayQueryDesc { uint32_t mode, flags, reserved[2]; } TgHipRay
 int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipRay *rays, void *out, size_t n);
 /* Instrumentation: HIP-event time of the kernel of the context's last tghip_query_rays, in milliseconds (profiles/ray_query_ab.txt) */
 int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms);
+/* Radiance along caller-supplied rays: for ray i and every sample index s of [spp_begin, spp_end) one PathTracer::traceSample
+ * (integrators/path_tracer/PathTracer.cpp:14-149) from the point BEHIND the camera -- behind Camera::sampleDirection (:22-28) --, by the wavefront loop of
+ * tghip_render_pass / tghip_wait itself: a pass over a virtual image whose pixel i is ray i, with a small launch of its own (csrc/hip/radiance_query.hip:
+ * k_query_paths) in front of every closest-hit launch that puts the caller's ray where the camera's would be, and one behind it (k_query_clip) that ends
+ * the ray's first segment at its tmax.
+ *   path start   throughput 1, bounce 0, wasSpecular true (PathTracer.cpp:35-45: an emitter the ray hits directly is seen), in the medium the scene's
+ *                camera is in (Camera::_medium, :38-41); the first segment is [rays[i].tmin, rays[i].tmax) (the camera's ray has 1e-4 and infinity,
+ *                math/Ray.hpp:24), its end exact: a hit at t counts when t < tmax, whatever the walk's own arithmetic makes of a far distance a
+ *                few ulps from a hit (the walk looks 2^-10 further and k_query_clip, behind every closest-hit launch, turns a hit at t >= tmax into
+ *                a miss; tmin is the walk's near distance as it is); a ray that hits nothing inside it ends as
+ *                an escaped path does: the infinite emitters are evaluated under the usual
+ *                rule (TraceBase::handleInfiniteLights, integrators/TraceBase.cpp:573-590).  Everything behind the start is the loop as it is: next-event
+ *                estimation and MIS, media, roulette, the NaN guards, min_bounces / max_bounces and every other integrator setting of the uploaded scene.
+ *   numbers      ray i, sample s draws from the counter-based stream keyed (seed, i, s) -- the ray index where a pass has the pixel index -- from its
+ *                THIRD number on: numbers 0 and 1 are the two a pinhole camera spends on its pixel filter (cameras/PinholeCamera.cpp:70-86).  With
+ *                TGHIP_RADIANCE_SOBOL the path starts at Sobol' dimension 2 of the sampler TGHIP_PASS_SOBOL describes, its scramble sobol_seed ^ hash32(i)
+ *                (sampling/SobolPathSampler.hpp:47-52: every ray's "tile" has the seed sobol_seed).  So a query on a pinhole camera's own rays, in pixel
+ *                order, returns that camera's samples bit for bit.  The scene's camera TYPE changes nothing: on a thin-lens scene no lens point is drawn, on
+ *                an equirectangular or cubemap scene k_camera_rays does not run.
+ *   result       rgb_sum[3 i ..] = the float32 sum of the ray's samples, added one by one in sample-index order starting from zero (a query's work
+ *                items hold one sample each and are summed without a pass's groups of four); count[i] = the samples counted; both as OutputBuffer::addSample
+ *                keeps the framebuffer (cameras/OutputBuffer.hpp:104-132, PathTracer.cpp:130-131): a NaN radiance is a black sample that counts, an
+ *                infinite one is dropped without counting.  Overwritten, never accumulated; nothing outside the n entries is written.  count may be NULL.
+ *   memory       flags 0: rays, rgb_sum and count are host memory, staged through buffers of the context that only grow; TGHIP_DEVELOP_DEVICE_POINTERS:
+ *                memory of the context's device, rays 16-byte aligned, rgb_sum and count 4-byte aligned -- nothing is allocated per call once the
+ *                scratch (the virtual image's framebuffer, its tile seeds, the pool) has grown.  Returns when the answers are complete.
+ *   context      runs on the context's stream and waits for a running pass like tghip_develop; leaves the framebuffer (internal or bound), the
+ *                SampleRecords, the auxiliary buffers, the per-sample buffer and with them a resumed render exactly as they were: the passes after a
+ *                query are bit for bit the passes without it.  "max_slots", "max_items", "chunk_samples" and the other options are honoured and never
+ *                change an answer ("chunk_samples" is accepted and does not size a query's items: the order of the additions is part of the answer); the
+ *                counters advance as by a pass.
+ * A ray with a non-finite component or a zero direction gets an unspecified answer; the call returns.  Directions are expected to have unit length, as
+ * the camera's have.  n == 0 succeeds.  TGHIP_E_NOSCENE without an upload.  TGHIP_E_INVALID, the context still usable (tghip_last_error says which): no
+ * description, NULL rays or rgb_sum with n > 0, unknown flag bits, non-zero reserved words, spp_end <= spp_begin, TGHIP_RADIANCE_SOBOL on a scene without
+ * sobol_matrices, n > 2^31 - 1, misaligned device pointers.  TGHIP_E_UNSUPPORTED: n (spp_end - spp_begin) >= 2^32 samples, the size at which the pass
+ * plan refuses a record pass (tungsten_host.h: tgh_query_radiance_check is the same check on its own). */
+#define TGHIP_RADIANCE_SOBOL 2u      /* flags; bit 0 stays TGHIP_DEVELOP_DEVICE_POINTERS */
+typedef struct TgHipRadianceQueryDesc {
+    uint32_t flags;                  /* TGHIP_DEVELOP_DEVICE_POINTERS | TGHIP_RADIANCE_SOBOL */
+    uint32_t seed;
+    uint32_t spp_begin, spp_end;     /* sample indices [spp_begin, spp_end) of every ray */
+    uint32_t sobol_seed;             /* TGHIP_RADIANCE_SOBOL: the SobolPathSampler seed every ray's "tile" has */
+    uint32_t reserved[3];            /* zero */
+} TgHipRadianceQueryDesc;            /* 32 B */
+int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, const TgHipRay *rays, float *rgb_sum /* n*3 */, uint32_t *count /* n, may be NULL */,
+                         size_t n);
+/* Instrumentation: HIP-event time of the launches of the context's last tghip_query_radiance -- the pass and the copy of its answers --, in
+ * milliseconds (profiles/radiance_query/bench.txt) */
+int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

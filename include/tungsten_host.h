@@ -195,7 +195,11 @@ int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, u
  * csrc/hip/pt_variants.h: k_trace_closest_wide<false,false,false,true> --; a launch that does not happen has an empty name.  lds_formula: 0 none, 1 the BVH2
  * walks' stack over the queue, 2 the dynamic-fetch walks' queue + stack, 3 the wide walks' queue + group stack, 4 k_trace_closest_instw's.  A workgroup size is
  * `fixed_threads`, or (0) the largest multiple of 64 from max_threads down at which blocks_per_cu workgroups of `sized_by` are resident.  TGHIP_E_INVALID for
- * no scene or no `out`, an option the choice does not read, or a description tgh_scene_check refuses. */
+ * no scene or no `out`, an option the choice does not read, or a description tgh_scene_check refuses.
+ * TGH_CHOICE_RAY_PATHS in pass_flags: the choice for the pass of a tghip_query_radiance call, whose paths start on the caller's rays -- a flag of this
+ * question only, never of a TgHipPassDesc.  It behaves as the equirectangular and cubemap cameras do (camera_fix): no fused_flat / one_launch, no
+ * fold_finish, no tail, camera_rays with the name k_query_paths. */
+#define TGH_CHOICE_RAY_PATHS 0x40000000u
 int tgh_launch_choice(const TgHipSceneDesc *scene, const char *const *keys, const long long *values, uint32_t num_options,
                       uint32_t pass_flags, int short_batch, TgHipLaunchChoice *out /* tungsten_hip.h */, char *err, size_t errlen);
 
@@ -238,6 +242,12 @@ void tgh_pass_plan_free(tgh_pass_plan *p);
 /* What tghip_query_rays decides about a call before it touches the device (csrc/host/RayQuery.cpp), on its own, no device and no scene: TGHIP_OK, or
  * TGHIP_E_INVALID and in `err` the refusal's message.  Only the pointers' values are looked at, nothing is read through them. */
 int tgh_query_rays_check(const TgHipRayQueryDesc *desc, const void *rays, const void *out, size_t n, char *err, size_t errlen);
+
+/* What tghip_query_radiance decides about a call before it touches the device (csrc/host/RadianceQuery.cpp), on its own, no device and no scene:
+ * TGHIP_OK, or the call's refusal -- TGHIP_E_INVALID, or TGHIP_E_UNSUPPORTED for n (spp_end - spp_begin) >= 2^32 samples -- and in `err` its message.
+ * scene_has_sobol: whether the scene the call is meant for carries sobol_matrices.  Only the pointers' values are looked at, nothing is read through them. */
+int tgh_query_radiance_check(const TgHipRadianceQueryDesc *desc, const void *rays, const void *rgb_sum, const void *count, size_t n, int scene_has_sobol,
+                             char *err, size_t errlen);
 
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);

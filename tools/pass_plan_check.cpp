@@ -177,6 +177,18 @@ int main()
                 for (uint8_t s : tileSeen) REQUIRE(s == 1);
         }
     }
+    // a sample range that ends near 2^32: the batches' 32-bit sample counter must not wrap back below the range's end (a plan without end), and the
+    // batches must cover the range once, in order
+    {
+        ++g_cases;
+        TgHipPassDesc pass = TgHipPassDesc();
+        pass.spp_begin = 5; pass.spp_end = 0xFFFFFFFFu; pass.shard_count = 1;
+        const PassPlanOptions opt = {1ull << 26, 1ull << 23, 0};
+        REQUIRE(planPass(pass, 16, 16, opt, reused, error) == TGHIP_OK && !reused.empty && reused.batches.size() < (1u << 20));
+        uint64_t at = pass.spp_begin;
+        for (const PassBatch &b : reused.batches) { REQUIRE(b.sppBegin == at && b.sppEnd > b.sppBegin && b.firstTile == 0 && b.pixSlots == 256u); at = b.sppEnd; }
+        REQUIRE(at == pass.spp_end);
+    }
     std::printf("pass_plan_check: %ld passes planned: %ld empty, %ld refused\n", g_cases, empty, refused);
     return 0;
 }

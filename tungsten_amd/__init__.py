@@ -191,6 +191,42 @@ class Renderer(object):
         if lib.tghip_query_rays(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
             raise TungstenError(lib.tghip_last_error(ctx).decode())
 
+    def _radiance_desc(self, flags, spp_begin, spp_end, seed, sobol_seed):
+        if sobol_seed is not None:
+            flags |= capi.TGHIP_RADIANCE_SOBOL
+        return capi.TgHipRadianceQueryDesc(flags, int(seed) & 0xFFFFFFFF, int(spp_begin), int(spp_end), int(sobol_seed or 0) & 0xFFFFFFFF)
+
+    def query_radiance(self, rays, spp_begin=0, spp_end=1, seed=DEFAULT_SEED, sobol_seed=None, device=0):
+        """Radiance along caller-supplied rays (tghip_query_radiance): rays [N,8] float32 (o, tmin, d, tmax) -> (sum [N,3] float32, count [N] uint32):
+        for every ray the sum of PathTracer::traceSample over the sample indices [spp_begin, spp_end), each path starting on the ray behind the
+        camera, and the samples counted.  sobol_seed: the SobolPathSampler seed of every ray's "tile" (the scene needs its Sobol' matrices); None
+        draws from the counter-based stream keyed (seed, ray index, sample index)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        ssum, count = np.empty((rays.shape[0], 3), np.float32), np.empty(rays.shape[0], np.uint32)
+        desc = self._radiance_desc(0, spp_begin, spp_end, seed, sobol_seed)
+        ctx = self.context(device)
+        if lib.tghip_query_radiance(ctx, C.byref(desc), rays.ctypes.data, ssum.ctypes.data, count.ctypes.data, rays.shape[0]) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return ssum, count
+
+    def query_radiance_into(self, rays, out_sum, out_count, spp_begin=0, spp_end=1, seed=DEFAULT_SEED, sobol_seed=None, device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out_sum float32 with N x 3
+        elements, out_count int32 or uint32 with N elements (the counts' bits either way), all contiguous.  The answers are complete when
+        the call returns."""
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        for name, t, dtype, size in (("rays", rays, ("torch.float32",), 8), ("out_sum", out_sum, ("torch.float32",), 3),
+                                     ("out_count", out_count, ("torch.int32", "torch.uint32"), 1)):
+            if str(t.dtype) not in dtype:
+                raise TungstenError("query_radiance_into: %s must be %s, not %s" % (name, " or ".join(dtype), t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("query_radiance_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("query_radiance_into: rays must be contiguous [N, 8], out_sum contiguous with N x 3 and out_count with N elements")
+        desc = self._radiance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, spp_begin, spp_end, seed, sobol_seed)
+        ctx = self.context(device)
+        if lib.tghip_query_radiance(ctx, C.byref(desc), rays.data_ptr(), out_sum.data_ptr(), out_count.data_ptr(), n) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+
     def debug_libm(self, fn, x, device=0):
         """The device's restatement of a host libm function (capi.TGHIP_LIBM_*) evaluated on the device: float32 in, float32 out."""
         dbl = capi.TGHIP_LIBM_EXPD <= int(fn) <= capi.TGHIP_LIBM_SQRTD       # the double-precision functions: float64 in, float64 out

@@ -206,6 +206,14 @@ class TgHipRayQueryDesc(C.Structure):
     _fields_ = [("mode", u32), ("flags", u32), ("reserved", u32*2)]
 
 
+TGHIP_RADIANCE_SOBOL = 2
+TGH_CHOICE_RAY_PATHS = 0x40000000      # tgh_launch_choice's pass_flags: the choice for a tghip_query_radiance call
+
+
+class TgHipRadianceQueryDesc(C.Structure):
+    _fields_ = [("flags", u32), ("seed", u32), ("spp_begin", u32), ("spp_end", u32), ("sobol_seed", u32), ("reserved", u32*3)]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -312,6 +320,8 @@ PROTOTYPES = {
     "tghip_trace_rays": (C.c_int, [VP, VP, VP, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "tghip_query_rays": (C.c_int, [VP, C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t]),
     "tghip_query_rays_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_query_radiance": (C.c_int, [VP, C.POINTER(TgHipRadianceQueryDesc), VP, VP, VP, C.c_size_t]),
+    "tghip_query_radiance_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -388,6 +398,7 @@ PROTOTYPES = {
     "tgh_pass_plan_chunk_starts": (C.POINTER(u32), [VP, C.POINTER(u32)]),
     "tgh_pass_plan_free": (None, [VP]),
     "tgh_query_rays_check": (C.c_int, [C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "tgh_query_radiance_check": (C.c_int, [C.POINTER(TgHipRadianceQueryDesc), VP, VP, VP, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

@@ -6,10 +6,12 @@
 #include "denoise.h"
 #include "develop.h"
 #include "ray_query.h"
+#include "radiance_query.h"
 #include "../host/SceneCheck.hpp"
 #include "../host/LaunchChoice.hpp"
 #include "../host/PassPlan.hpp"
 #include "../host/RayQuery.hpp"
+#include "../host/RadianceQuery.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -206,6 +208,17 @@ struct LaunchPlan {
     bool tailFits = false;                // a workgroup of k_tail fits a CU
 };
 
+// Where a pass of the wavefront loop takes what a render pass takes from the context and its description: the framebuffer it resolves into, the tile
+// seeds of a Sobol' pass and -- tghip_query_radiance -- the rays that replace the camera's.
+struct PassTarget {
+    float *sum = nullptr;                 // W*H*3 floats and W*H counts on the device
+    uint32_t *count = nullptr;
+    const uint32_t *tileSeeds = nullptr;  // TGHIP_PASS_SOBOL: on the device already; nullptr = the description's host array, through ctx->dTileSeeds
+    const float4 *rays = nullptr;         // k_query_paths in front of every closest-hit launch (LaunchChoice::queryPaths): the caller's rays on the device ...
+    uint32_t numRays = 0;                 // ... and how many: the pixels from there on are padding
+    bool rayPaths = false;
+};
+
 } // namespace
 
 struct tghip_ctx {
@@ -300,6 +313,16 @@ struct tghip_ctx {
     size_t queryRaysCap = 0, queryOutCap = 0;
     int queryBlocks = 0, queryRefillAt = 0;
     double queryMs = 0.0;
+    // tghip_query_radiance: the plan of the query's pass (kept like `plan`), the framebuffer of its virtual image and that image's tile seeds -- all
+    // equal to radTileSeed where radTileSeedsSet entries are --, the rays on the device when they are the caller's host memory (all grown on demand),
+    // the time of the pass and the copy of its answers
+    PassPlan radPlan;
+    float *radSum = nullptr;
+    uint32_t *radCount = nullptr, *radTileSeeds = nullptr;
+    float4 *radRays = nullptr;
+    size_t radSumCap = 0, radCountCap = 0, radTileSeedsCap = 0, radRaysCap = 0, radTileSeedsSet = 0;
+    uint32_t radTileSeed = 0;
+    double radMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context
     int rankCount = 0, rankIndex = 0;
     float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
@@ -795,6 +818,10 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->queryCounter) (void)hipFree(ctx->queryCounter);
     if (ctx->queryRays) (void)hipFree(ctx->queryRays);
     if (ctx->queryOut) (void)hipFree(ctx->queryOut);
+    if (ctx->radSum) (void)hipFree(ctx->radSum);
+    if (ctx->radCount) (void)hipFree(ctx->radCount);
+    if (ctx->radTileSeeds) (void)hipFree(ctx->radTileSeeds);
+    if (ctx->radRays) (void)hipFree(ctx->radRays);
     if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
     if (ctx->redSum) (void)hipFree(ctx->redSum);
@@ -1040,7 +1067,7 @@ int tghip_bind_framebuffer(tghip_ctx *ctx, float *dev_rgb_sum, uint32_t *dev_cou
 
 
 // Runs the wavefront loop for one batch of work items until every slot is drained.
-static int runBatch(tghip_ctx *ctx, const PassParams &pp)
+static int runBatch(tghip_ctx *ctx, const PassParams &pp, const PassTarget &target)
 {
     if (ctx->abortRequested.load(std::memory_order_acquire))
         return TGHIP_E_ABORTED;                  // aborted before this batch started: nothing to drain
@@ -1157,14 +1184,21 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
         // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
         auto launchIteration = [&](const PathState &st, const PassParams &pp, int grid, uint32_t iterTag, bool timed, int part) {
             auto tic = [&]() { if (timed) ticMain(); };
-            if (choice.cameraRays)                  // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
+            if (choice.queryPaths)                  // (the fresh paths of the previous iteration's finish / of k_start get the caller's rays before they are traced)
+                radianceQueryLaunchPaths(ctx->launchStream, grid, st, target.rays, target.numRays);
+            else if (choice.cameraRays)             // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
                 hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp);
             tic();
             if (choice.closest.kernel.family == K_FINISH_CLOSEST_WIDE)   // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
                 launchKernel(lp.closest, grid, ctx->launchStream, s, st, pp);
             else
                 launchKernel(lp.closest, grid, ctx->launchStream, s, st);
-            tic(); tic();
+            tic();
+            // (the end of a query's first segment, before the hits are shaded.  Launched whether or not a ray of the batch has a finite tmax: the rays
+            // may be device memory, which the host could only know that of after a reduction over them -- about 10 us per launch, profiles/radiance_query/bench.txt)
+            if (choice.queryPaths)
+                radianceQueryLaunchClip(ctx->launchStream, grid, st, target.rays, target.numRays);
+            tic();
             launchShading(st, pp, grid, part);
             tic(); tic();
             launchKernel(lp.shadow, grid, ctx->launchStream, s, st, pp, iterTag);
@@ -1266,8 +1300,8 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp)
         if (foldFinish && !fused)
             finishParts(iterTag);
     }
-    float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    float *sum = target.sum;
+    uint32_t *cnt = target.count;
     if (pp.rec_sorted) hipLaunchKernelGGL(k_resolve_records, dim3((pp.num_sorted*16u + 255)/256), dim3(256), 0, ctx->stream, st, pp, sum, cnt);
     else               hipLaunchKernelGGL(k_resolve, dim3((pp.pix_slots + 255)/256), dim3(256), 0, ctx->stream, st, pp, sum, cnt);
     HIP_TRY(ctx, hipGetLastError());
@@ -1297,36 +1331,30 @@ int tghip_render_pass(tghip_ctx *ctx, const TgHipPassDesc *pass)
     if (!ctx->haveScene) { ctx->error = "render before upload"; return TGHIP_E_NOSCENE; }
     const int rc = checkPass(*pass, ctx->width, ctx->height, ctx->scene.sobol != nullptr, ctx->error);   // (csrc/host/PassPlan.cpp)
     if (rc != TGHIP_OK) return rc;
-    ctx->abortRequested.store(false, std::memory_order_release);   // the only place a request is cleared
+    ctx->abortRequested.store(false, std::memory_order_release);   // a request is cleared where a pass begins: here, and in tghip_query_radiance for its pass
     ctx->passPending = true;
     ctx->passResult = TGHIP_OK;
     ctx->pendingPass = *pass;
     return TGHIP_OK;
 }
 
-int tghip_wait(tghip_ctx *ctx)
+} // extern "C"
+
+// The planned pass `plan` of `pass` over a w x h image, into `target`: the launch plan of its kind, the device arrays the plan names, the pool, the
+// wavefront loop batch by batch.  What tghip_wait runs for a render pass (w x h the scene's image, the target the context's framebuffer) and
+// tghip_query_radiance for a query (the virtual image of the rays, a framebuffer of its own).  Synchronous.
+static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t h, PassPlan &plan, const PassTarget &target)
 {
-    if (!ctx) return TGHIP_E_INVALID;
-    if (!ctx->passPending)
-        return ctx->passResult;
-    ctx->passPending = false;
     const bool verbose = std::getenv("TGHIP_VERBOSE") != nullptr;
     const auto tWait0 = std::chrono::steady_clock::now();
     auto msSince = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const TgHipPassDesc pass = ctx->pendingPass;
-    const uint32_t w = ctx->width, h = ctx->height;
-    // which tiles, records, work items and batches the pass is made of: host arithmetic on its own (csrc/host/PassPlan.cpp)
-    PassPlan &plan = ctx->plan;
-    const PassPlanOptions planOpt = {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), uint32_t(std::max(ctx->chunkSamples, 0))};
-    int rc = planPass(pass, w, h, planOpt, plan, ctx->error);
-    if (rc != TGHIP_OK || plan.empty)
-        return ctx->passResult = rc;
+    int rc = TGHIP_OK;
     // the kernels of a pass of this kind -- a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch) --: planned again only
     // when the kind differs from the last pass's
-    const PassKind kind = passKindOf(ctx->sc, pass.flags, plan.shortBatch, ctx->countTraversal);
+    PassKind kind = passKindOf(ctx->sc, pass.flags, plan.shortBatch, ctx->countTraversal);
+    kind.rayPaths = target.rayPaths;
     if (!(kind == ctx->lp.kind) && (rc = planLaunches(ctx, kind, ctx->lp)) != TGHIP_OK)
-        return ctx->passResult = rc;
+        return rc;
 
     // the device arrays the plan names
     auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
@@ -1341,30 +1369,33 @@ int tghip_wait(tghip_ctx *ctx)
     base.shard_skew = plan.shardSkew;
     base.tiles_x = plan.tilesX; base.num_tiles = plan.numTiles;
     base.width = w; base.height = h;
-    base.flags = pass.flags | (ctx->sc.thinlens ? PT_PASS_THINLENS : 0u) | (ctx->sc.haveMedia ? PT_PASS_MEDIA : 0u);
+    // (a query's paths start behind the camera: no lens point is drawn for them)
+    base.flags = pass.flags | (ctx->sc.thinlens && !target.rayPaths ? PT_PASS_THINLENS : 0u) | (ctx->sc.haveMedia ? PT_PASS_MEDIA : 0u);
     base.variance_w = plan.varianceW;
     if (plan.shardCount > 1) {
         if (plan.ownedStale) {                   // the shard's tile list changed: rare
-            if ((rc = upload(ctx->dOwnedTiles, ctx->ownedCap, plan.ownedList)) != TGHIP_OK) return ctx->passResult = rc;
+            if ((rc = upload(ctx->dOwnedTiles, ctx->ownedCap, plan.ownedList)) != TGHIP_OK) return rc;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             plan.ownedStale = false;
         }
         base.owned_tiles = ctx->dOwnedTiles;
     }
-    if (pass.flags & TGHIP_PASS_SOBOL) {
+    if ((pass.flags & TGHIP_PASS_SOBOL) && target.tileSeeds) {
+        base.tile_seeds = target.tileSeeds;
+    } else if (pass.flags & TGHIP_PASS_SOBOL) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dTileSeeds, pass.tile_seeds, size_t(plan.numTiles)*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         base.tile_seeds = ctx->dTileSeeds;
     }
     if (plan.recordPass) {
         const size_t recBytes = size_t(plan.numRecords)*sizeof(uint32_t);
-        if ((rc = growArray(ctx, ctx->lum, ctx->lumCap, size_t(plan.lumFloats))) != TGHIP_OK) return ctx->passResult = rc;
+        if ((rc = growArray(ctx, ctx->lum, ctx->lumCap, size_t(plan.lumFloats))) != TGHIP_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecIndex, plan.recIndex.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecCount, plan.recCount.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecLum, plan.recLum.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = upload(ctx->dSorted, ctx->sortedCap, plan.sorted)) != TGHIP_OK) return ctx->passResult = rc;
-        if ((rc = upload(ctx->dChunkStart, ctx->chunkStartCap, plan.chunkStart)) != TGHIP_OK) return ctx->passResult = rc;
+        if ((rc = upload(ctx->dSorted, ctx->sortedCap, plan.sorted)) != TGHIP_OK) return rc;
+        if ((rc = upload(ctx->dChunkStart, ctx->chunkStartCap, plan.chunkStart)) != TGHIP_OK) return rc;
         // the hint table -- for every 64 items the chunk their first one lies in -- is filled by a launch from the chunk starts
-        if ((rc = growArray(ctx, ctx->dHint, ctx->hintCap, plan.hintEntries)) != TGHIP_OK) return ctx->passResult = rc;
+        if ((rc = growArray(ctx, ctx->dHint, ctx->hintCap, plan.hintEntries)) != TGHIP_OK) return rc;
         hipLaunchKernelGGL(k_record_hints, dim3(uint32_t((plan.hintEntries + 255)/256)), dim3(256), 0, ctx->stream, ctx->dChunkStart, plan.chunksAll, ctx->dHint, uint32_t(plan.hintEntries));
         HIP_TRY(ctx, hipGetLastError());
         base.rec_index = ctx->dRecIndex; base.rec_count = ctx->dRecCount; base.rec_lum = ctx->dRecLum;
@@ -1381,7 +1412,7 @@ int tghip_wait(tghip_ctx *ctx)
     base.aux = ctx->dAux;
     if (pass.flags & TGHIP_PASS_SAMPLES) {
         const size_t need = size_t(w)*h*plan.spp*3u;
-        if ((rc = growArray(ctx, ctx->dSamples, ctx->samplesCap, need)) != TGHIP_OK) return ctx->passResult = rc;
+        if ((rc = growArray(ctx, ctx->dSamples, ctx->samplesCap, need)) != TGHIP_OK) return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->dSamples, 0, need*sizeof(float), ctx->stream));
         ctx->samplesFloats = need;
         base.samples = ctx->dSamples; base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
@@ -1392,8 +1423,8 @@ int tghip_wait(tghip_ctx *ctx)
     // thread keeps the whole path state (112 B x 0.5 M slots) inside the Infinity Cache -- measured +5 % over four
     if (ctx->lp.choice.oneLaunch && !ctx->maxSlotsSet)
         wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->lp.thrShade[SIZE_SIMPLE]));
-    if ((rc = ensurePool(ctx, uint32_t(wantSlots))) != TGHIP_OK) return ctx->passResult = rc;
-    if ((rc = growArray(ctx, ctx->partial, ctx->partialCap, size_t(plan.batchItems))) != TGHIP_OK) return ctx->passResult = rc;
+    if ((rc = ensurePool(ctx, uint32_t(wantSlots))) != TGHIP_OK) return rc;
+    if ((rc = growArray(ctx, ctx->partial, ctx->partialCap, size_t(plan.batchItems))) != TGHIP_OK) return rc;
     // the device word still holds the previous pass's abort, if any; a request for THIS pass is re-mirrored by runBatch
     HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev, 0, sizeof(uint32_t), ctx->stream));
 
@@ -1406,13 +1437,13 @@ int tghip_wait(tghip_ctx *ctx)
         PassParams pp = base;
         pp.spp_begin = b.sppBegin; pp.spp_end = b.sppEnd; pp.seed = pass.seed;
         pp.chunk = plan.chunk;
-        pp.group = plan.group;
+        pp.group = target.rayPaths ? 1u : plan.group;   // (a query's one-sample items are added to the ray's sum one by one: tghip_query_radiance)
         pp.chunks = b.chunks;
         pp.pix_slots = b.pixSlots;
         pp.item_base = b.itemBase;
         pp.total_items = b.totalItems;
         pp.first_tile = b.firstTile;
-        rc = runBatch(ctx, pp);
+        rc = runBatch(ctx, pp, target);
     }
     if (plan.recordPass && rc == TGHIP_OK) {
         hipLaunchKernelGGL(k_records, dim3((plan.numRecords + 63)/64), dim3(64), 0, ctx->stream, base, ctx->dRecords, plan.numRecords);
@@ -1427,7 +1458,28 @@ int tghip_wait(tghip_ctx *ctx)
         std::fprintf(stderr, "[tghip] pass spp [%u, %u) flags %u: %llu items of %u samples in batches of %llu, %u slots, short %d; setup %.2f ms, loop %.2f ms (%llu iterations, device %.2f ms)\n",
                      pass.spp_begin, pass.spp_end, pass.flags, (unsigned long long)plan.totalItems, plan.chunk,
                      (unsigned long long)plan.batchItems, ctx->pool.num_slots, int(plan.shortBatch), msSetup, msSince(tLoop0), (unsigned long long)(ctx->counters.iterations - itersBefore), double(ms));
-    return ctx->passResult = rc;
+    return rc;
+}
+
+extern "C" {
+
+int tghip_wait(tghip_ctx *ctx)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!ctx->passPending)
+        return ctx->passResult;
+    ctx->passPending = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const TgHipPassDesc pass = ctx->pendingPass;
+    // which tiles, records, work items and batches the pass is made of: host arithmetic on its own (csrc/host/PassPlan.cpp)
+    const PassPlanOptions planOpt = {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), uint32_t(std::max(ctx->chunkSamples, 0))};
+    const int rc = planPass(pass, ctx->width, ctx->height, planOpt, ctx->plan, ctx->error);
+    if (rc != TGHIP_OK || ctx->plan.empty)
+        return ctx->passResult = rc;
+    PassTarget target;
+    target.sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
+    target.count = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    return ctx->passResult = runPass(ctx, pass, ctx->width, ctx->height, ctx->plan, target);
 }
 
 int tghip_abort(tghip_ctx *ctx)
@@ -2102,6 +2154,86 @@ int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms)
 {
     if (!ctx || !ms) return TGHIP_E_INVALID;
     *ms = ctx->queryMs;
+    return TGHIP_OK;
+}
+
+int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, const TgHipRay *rays, float *rgb_sum, uint32_t *count, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_query_radiance: no description"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "tghip_query_radiance before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    int rc = checkRadianceQuery(desc, rays, rgb_sum, count, n, ctx->scene.sobol != nullptr, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    if (n == 0) return TGHIP_OK;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the pass over the virtual image (csrc/host/RadianceQuery.cpp).  Its work items hold ONE sample each, whatever "chunk_samples" says, and k_resolve
+    // adds them to the ray's sum one by one (runPass: group 1): the order of the additions is part of the answer, not a matter of options.
+    const RadianceQueryImage im = radianceQueryImage(n);
+    const TgHipPassDesc pass = radianceQueryPass(*desc);
+    const PassPlanOptions planOpt = {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), 1u};
+    PassPlan &plan = ctx->radPlan;
+    if ((rc = planRadianceQuery(*desc, n, planOpt, plan, ctx->error)) != TGHIP_OK) return rc;
+    // the scratch: the image's framebuffer (zero: k_resolve adds), its tile seeds, the rays when they are host memory
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    const size_t npix = size_t(im.width)*im.height;
+    if ((rc = growArray(ctx, ctx->radSum, ctx->radSumCap, npix*3)) != TGHIP_OK) return rc;
+    if ((rc = growArray(ctx, ctx->radCount, ctx->radCountCap, npix)) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->radSum, 0, npix*3*sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->radCount, 0, npix*sizeof(uint32_t), ctx->stream));
+    PassTarget target;
+    target.sum = ctx->radSum; target.count = ctx->radCount;
+    target.rayPaths = true;
+    target.numRays = uint32_t(n);
+    if (pass.flags & TGHIP_PASS_SOBOL) {
+        const size_t had = ctx->radTileSeedsCap;
+        if ((rc = growArray(ctx, ctx->radTileSeeds, ctx->radTileSeedsCap, size_t(plan.numTiles))) != TGHIP_OK) return rc;
+        if (ctx->radTileSeedsCap != had) ctx->radTileSeedsSet = 0;
+        if (ctx->radTileSeedsSet < plan.numTiles || ctx->radTileSeed != desc->sobol_seed) {
+            HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->radTileSeeds), int(desc->sobol_seed), size_t(plan.numTiles), ctx->stream));
+            ctx->radTileSeedsSet = plan.numTiles; ctx->radTileSeed = desc->sobol_seed;
+        }
+        target.tileSeeds = ctx->radTileSeeds;
+    }
+    if (device) {
+        target.rays = reinterpret_cast<const float4 *>(rays);
+    } else {
+        if ((rc = growArray(ctx, ctx->radRays, ctx->radRaysCap, n*2)) != TGHIP_OK) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->radRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream));
+        target.rays = ctx->radRays;
+    }
+    // what the pass borrows of the context and gets back: the launch plan of the last render pass's kind (so that the next one plans nothing anew).
+    // An abort request left over from an earlier pass -- tghip_wait above has honoured it -- is cleared and NOT put back, as tghip_render_pass clears
+    // it where a pass begins; an abort DURING the query ends the query like a pass (TGHIP_E_ABORTED) and stays set until the next pass or query.
+    const LaunchPlan lpBefore = ctx->lp;
+    const double msTotalBefore = ctx->counters.ms_total;
+    ctx->abortRequested.store(false, std::memory_order_release);
+    rc = runPass(ctx, pass, im.width, im.height, plan, target);
+    ctx->lp = lpBefore;
+    ctx->radMs = ctx->counters.ms_total - msTotalBefore;
+    if (rc != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    if (device) {
+        HIP_TRY(ctx, radianceQueryLaunchResults(ctx->stream, ctx->radSum, ctx->radCount, rgb_sum, count, uint32_t(n)));
+    } else {                                     // (the first n pixels of the image are the n rays)
+        HIP_TRY(ctx, hipMemcpyAsync(rgb_sum, ctx->radSum, n*3*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (count) HIP_TRY(ctx, hipMemcpyAsync(count, ctx->radCount, n*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (device) {
+        float ms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
+        ctx->radMs += double(ms);
+    }
+    return TGHIP_OK;
+}
+
+int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->radMs;
     return TGHIP_OK;
 }
 

@@ -118,9 +118,12 @@ void chooseLaunches(const SceneTraits &sc, uint32_t numRecs, uint32_t numWideNod
     c.wideShadowRays = c.useWide && o.wideShadowOpt != 0;
     const bool instWide = inst && o.instWideOpt && sc.wideDepth > 0 && sc.wideMasterDepth > 0 && o.wideOpt;
     const bool instDyn = inst && !c.wideClosest && o.dynamicFetch && o.instDynOpt;   // the three-level walk with dynamic ray fetch
-    c.fusedFlat = flat && !closestWalk && o.fuseFlatOpt && !pass.aux && !sc.allFeaturesShading && c.tablesFit && !sc.cameraFix;
+    // a launch of its own rewrites the rays nextPath wrote before they are traced: never nextPath and the walk in one kernel, no k_finish folded into the walk
+    const bool cameraFix = sc.cameraFix || pass.rayPaths;
+    c.fusedFlat = flat && !closestWalk && o.fuseFlatOpt && !pass.aux && !sc.allFeaturesShading && c.tablesFit && !cameraFix;
     c.oneLaunch = c.fusedFlat && !sc.haveComplex && o.loopOpt;
-    c.cameraRays = sc.cameraFix;
+    c.cameraRays = cameraFix;
+    c.queryPaths = pass.rayPaths;
     c.neeFactors = closestWalk;
     c.instTreeDepth = std::max(sc.bvhDepth - sc.bvhMasterDepth, 1);
 
@@ -154,7 +157,7 @@ void chooseLaunches(const SceneTraits &sc, uint32_t numRecs, uint32_t numWideNod
     // the walk arrays behind the A_* ones (suspended walks of the wide kernels)
     c.walkArrays = c.useWide && !inst ? 4u + uint32_t(sc.wideDepth + 1)/2u : 0u;
     // "fold_finish": k_finish rides in front of the next iteration's closest-hit launch (single-level scenes on the decoupled wide walk)
-    c.foldFinish = o.foldFinishOpt && !sc.cameraFix && !flat && !inst && c.wideClosest && o.decoupleOpt;
+    c.foldFinish = o.foldFinishOpt && !cameraFix && !flat && !inst && c.wideClosest && o.decoupleOpt;
 
     // ---- the closest-hit walk ----
     WalkLaunch &cl = c.closest;
@@ -307,7 +310,7 @@ void chooseLaunches(const SceneTraits &sc, uint32_t numRecs, uint32_t numWideNod
         if (o.thrOverride[i] >= 64) dst[i]->fixed = std::min(o.thrOverride[i]/64*64, i < 2 ? 512 : 256);
 
     // ---- k_tail runs the wide single-level kernels' bodies: scenes those kernels render, passes without visit counts ----
-    c.tailEligible = o.tailOpt && !sc.cameraFix && c.tablesFit && !flat && !inst && c.wideClosest && c.wideShadowRays && o.decoupleOpt &&
+    c.tailEligible = o.tailOpt && !cameraFix && c.tablesFit && !flat && !inst && c.wideClosest && c.wideShadowRays && o.decoupleOpt &&
                      familyCovers(TGHIP_BSDF_VARIANT_TAIL, sc.complexMask, sc.haveForward) &&
                      !sc.haveMeshLight && !sc.haveMedia && !pass.aux && !sc.allFeaturesShading && !count;
     // scenes of Lambert / null and conductor-family materials only (the metric's): the narrower instantiation, "tail_family" = 0 for the A/B
@@ -380,7 +383,7 @@ void exportLaunchChoice(const LaunchChoice &c, TgHipLaunchChoice *out)
     }
     out->tail_eligible = c.tailEligible;
     if (c.tailEligible) { setName(out->tail, c.tail); setName(out->tail_probe, c.tailProbe); }
-    if (c.cameraRays) std::snprintf(out->camera_rays_name, sizeof out->camera_rays_name, "k_camera_rays");
+    if (c.cameraRays) std::snprintf(out->camera_rays_name, sizeof out->camera_rays_name, c.queryPaths ? "k_query_paths" : "k_camera_rays");
     out->ray_walk = c.rayWalk;
     setName(out->trace_rays, c.traceRays);
 }

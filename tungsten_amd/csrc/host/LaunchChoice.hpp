@@ -50,13 +50,24 @@ struct PassKind {
     bool shortBatch = false;              // the pass does not fill the pool once (PassPlan.cpp): one stream, 4 workgroups per CU
     bool qmc = false;                     // the pass's PassParams::flags are not 0: the FEAT_QMC twin of every shading variant
     bool countTraversal = false;          // "count_traversal": the COUNT instantiations of the walks, no k_tail
-    bool operator==(const PassKind &o) const { return aux == o.aux && shortBatch == o.shortBatch && qmc == o.qmc && countTraversal == o.countTraversal; }
+    // tghip_query_radiance: the pass's paths start on the caller's rays, which k_query_paths writes in front of every closest-hit launch -- the launch
+    // shape of the equirectangular / cubemap cameras (SceneTraits::cameraFix), whatever the scene's camera
+    bool rayPaths = false;
+    bool operator==(const PassKind &o) const
+    {
+        return aux == o.aux && shortBatch == o.shortBatch && qmc == o.qmc && countTraversal == o.countTraversal && rayPaths == o.rayPaths;
+    }
 };
+// the host-side choice flag that asks for such a pass where a choice is asked for by pass flags (tgh_launch_choice: TGH_CHOICE_RAY_PATHS, tungsten_host.h).
+// Not a flag of TgHipPassDesc: tghip_render_pass refuses it like every unknown bit.
+#define LAUNCH_CHOICE_RAY_PATHS 0x40000000u
 
 // the kind of a pass with the public flags `passFlags` (TGHIP_PASS_*) on a scene: thin-lens and media scenes add internal flags to every pass
 inline PassKind passKindOf(const SceneTraits &sc, uint32_t passFlags, bool shortBatch, bool countTraversal)
 {
     PassKind k;
+    k.rayPaths = (passFlags & LAUNCH_CHOICE_RAY_PATHS) != 0;
+    passFlags &= ~LAUNCH_CHOICE_RAY_PATHS;
     k.aux = (passFlags & TGHIP_PASS_AUX) != 0; k.shortBatch = shortBatch; k.qmc = passFlags != 0 || sc.thinlens || sc.haveMedia; k.countTraversal = countTraversal;
     return k;
 }
@@ -118,7 +129,8 @@ struct LaunchChoice {
     uint32_t walkArrays = 0;              // walk arrays the pool should carry behind the A_* ones
     bool foldFinish = false;              // no k_finish launch per iteration: it rides in the next closest-hit launch
     bool neeFactors = false;              // PathState::nee_factors: the shadow walk is a closest-hit walk
-    bool cameraRays = false;              // k_camera_rays in front of every closest-hit launch
+    bool cameraRays = false;              // a launch that rewrites the fresh paths' rays in front of every closest-hit launch: k_camera_rays, or ...
+    bool queryPaths = false;              // ... k_query_paths (PassKind::rayPaths) in its place
     bool tablesFit = true;
     int instTreeDepth = 1;
     // the walks of an iteration (unused by fused flat lists)

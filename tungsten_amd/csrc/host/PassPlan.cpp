@@ -195,8 +195,10 @@ int planPass(const TgHipPassDesc &pass, uint32_t w, uint32_t h, const PassPlanOp
         push(begin, recordItems);
         out.totalItems = recordItems;
     } else {
-        for (uint32_t sppFirst = sppBegin; sppFirst < sppEnd; sppFirst += chunksPerBatch*chunk) {
-            const uint32_t sppLast = uint32_t(std::min<uint64_t>(uint64_t(sppFirst) + uint64_t(chunksPerBatch)*chunk, sppEnd));
+        // (64 bits: a range that ends near 2^32 must not wrap the counter back below its end)
+        for (uint64_t sppFirst64 = sppBegin; sppFirst64 < sppEnd; sppFirst64 += uint64_t(chunksPerBatch)*chunk) {
+            const uint32_t sppFirst = uint32_t(sppFirst64);
+            const uint32_t sppLast = uint32_t(std::min<uint64_t>(sppFirst64 + uint64_t(chunksPerBatch)*chunk, sppEnd));
             for (uint32_t first = 0; first < ownedTiles; first += tilesPerBatch) {
                 PassBatch b;
                 b.sppBegin = sppFirst; b.sppEnd = sppLast;

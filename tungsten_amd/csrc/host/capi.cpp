@@ -549,6 +549,7 @@ int tgh_launch_choice(const TgHipSceneDesc *scene, const char *const *keys, cons
         if (k == "count_traversal") count = values[i] != 0;
         else if (!setLaunchOption(opt, k, values[i])) { setErr(err, errlen, "the launch choice reads no option '" + k + "'"); return TGHIP_E_INVALID; }
     }
+    static_assert(TGH_CHOICE_RAY_PATHS == LAUNCH_CHOICE_RAY_PATHS, "TGH_CHOICE_RAY_PATHS");
     LaunchChoice c;
     chooseLaunches(t, scene->num_recs, scene->num_wide_nodes, opt, passKindOf(t, pass_flags, short_batch != 0, count), c);
     exportLaunchChoice(c, out);
