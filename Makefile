@@ -17,7 +17,8 @@ LIBNAME  := $(if $(PROFILE),libtungsten_hip_prof.so,$(if $(VARIANT),libtungsten_
 HOSTSRC  := $(wildcard tungsten_amd/csrc/host/*.cpp)
 HOSTLIB  := $(filter-out tungsten_amd/csrc/host/main.cpp,$(HOSTSRC))
 HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB))
-# the shim + one translation unit per family of k_shade instantiations (they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
+# the shim (tungsten_hip.hip; its context: shim_context.h, device_array.h) + reduce.hip, its RCCL reduces (host code only) + one translation unit per family of
+# explicit instantiations (pt_instances.h lists each unit's; they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 # + ray_query.hip, the kernels of tghip_query_rays (its argument check csrc/host/RayQuery.cpp comes in through HOSTSRC)
 # + radiance_query.hip, the ray source and the result copy of tghip_query_radiance (its check and virtual image, csrc/host/RadianceQuery.cpp, likewise)

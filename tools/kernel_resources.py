@@ -4,10 +4,13 @@
 
 Each object file carries a clang offload bundle in its .hip_fatbin section; the gfx950 code object inside has the kernels' metadata as an ELF note
 (llvm-readelf --notes) and their code (llvm-objdump -d).  `--diff` prints only the kernels whose numbers changed against an earlier `--json` dump:
-the check a kernel change gets before it gets GPU time (an occupancy step crossed, a spill that appeared, a path that doubled in length)."""
+the check a kernel change gets before it gets GPU time (an occupancy step crossed, a spill that appeared, a path that doubled in length).  Each kernel
+also carries `code`, a hash of its instruction stream without addresses and encodings: a change of host code only leaves every hash, and the set of
+kernels per object file, as they were -- `--diff` prints nothing (a kernel that came or went is printed as well)."""
 import argparse
 import collections
 import glob
+import hashlib
 import json
 import os
 import re
@@ -49,6 +52,9 @@ def kernels_of(obj, tmp):
             continue
         ops = re.findall(r"^\s+((?:v|s|global|ds|buffer|scratch|flat)_[a-z0-9_]+)", fn, re.M)
         c = collections.Counter(ops)
+        # the instructions as text: mnemonic and operands, without the address / encoding comment behind them and without symbol+offset annotations
+        text = [re.sub(r"\s*<[^>]*>", "", ln.split("//")[0]).strip() for ln in fn.split("\n")[1:]]
+        out[m.group(1)]["code"] = hashlib.sha1("\n".join(t for t in text if t).encode()).hexdigest()[:16]
         out[m.group(1)].update(instructions=len(ops), f64=sum(v for k, v in c.items() if "f64" in k), branches=sum(v for k, v in c.items() if k.startswith("s_cbranch")),
                                vmem=sum(v for k, v in c.items() if k.split("_")[0] in ("global", "buffer", "flat", "scratch")))
     return {demangled.get(k, k).replace("(DeviceScene, PathState, PassParams, int)", "").replace("(DeviceScene, PathState, PassParams)", ""): v for k, v in out.items()}
@@ -70,12 +76,12 @@ def main():
         with open(a.json, "w") as f:
             json.dump(table, f, indent=1, sort_keys=True)
     old = json.load(open(a.diff)) if a.diff else None
-    cols = ("vgpr", "sgpr", "scratch", "vgpr_spills", "lds", "instructions", "f64", "branches", "vmem")
-    print("%-88s " % "kernel" + " ".join("%9s" % c for c in cols))
-    for k in sorted(table):
+    cols = ("vgpr", "sgpr", "scratch", "vgpr_spills", "lds", "instructions", "f64", "branches", "vmem", "code")
+    print("%-88s " % "kernel" + " ".join("%9s" % c for c in cols[:-1]) + " %16s" % cols[-1])
+    for k in sorted(set(table) | set(old or {})):
         if a.filter not in k:
             continue
-        v = table[k]
+        v = table.get(k, {})
         if old is not None:
             o = old.get(k)
             if o == v:

@@ -1,8 +1,6 @@
-// Explicit instantiations of k_shade variants (see pt_wavefront.h); the extern "C" shim in tungsten_hip.hip launches them.
+// Explicit instantiations of k_shade variants (see pt_wavefront.h; which ones: pt_instances.h); the extern "C" shim in tungsten_hip.hip launches them.
 #include "pt_wavefront.h"
+#include "pt_instances.h"
 
-template __global__ void k_shade<MASK_FULL, 2, 0>(DeviceScene, PathState, PassParams, int);
-template __global__ void k_shade<(MASK_FULL | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-template __global__ void k_shade<MASK_FULL, 2, 2>(DeviceScene, PathState, PassParams, int);
-template __global__ void k_shade<(MASK_FULL | FEAT_QMC), 2, 2>(DeviceScene, PathState, PassParams, int);
-template __global__ void k_shade<BSDF_MASK_ALL, 2, 0>(DeviceScene, PathState, PassParams, int);
+#define PT_KERNEL PT_INSTANTIATE_KERNEL
+PT_UNIT_shade_full

@@ -1,4 +1,6 @@
-// Explicit instantiation of the lean media shading variant (see pt_wavefront.h: MASK_MEDIA); the extern "C" shim in tungsten_hip.hip launches it.
+// Explicit instantiation of the lean media shading variant (see pt_wavefront.h: MASK_MEDIA; pt_instances.h); the extern "C" shim in tungsten_hip.hip launches it.
 #include "pt_wavefront.h"
+#include "pt_instances.h"
 
-template __global__ void k_shade<MASK_MEDIA, 2, 0>(DeviceScene, PathState, PassParams, int);
+#define PT_KERNEL PT_INSTANTIATE_KERNEL
+PT_UNIT_shade_media

@@ -2,97 +2,22 @@
 // gfx950 (MI355X) only.  See pt_kernels.h for the execution model and DESIGN.md for the layout.
 #define PT_WAVEFRONT_MAIN
 #include "pt_wavefront.h"
+#include "pt_instances.h"
+#include "shim_context.h"
 #include "debug_units.h"
 #include "denoise.h"
 #include "develop.h"
 #include "ray_query.h"
 #include "radiance_query.h"
-#include "../host/SceneCheck.hpp"
-#include "../host/LaunchChoice.hpp"
-#include "../host/PassPlan.hpp"
 #include "../host/RayQuery.hpp"
 #include "../host/RadianceQuery.hpp"
 
-#include <atomic>
 #include <chrono>
-#include <map>
-#include <tuple>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and prototypes only: the library is loaded with dlopen at the first multi-GPU reduce
-
-// The k_shade variants are instantiated in shade_simple.hip / shade_class.hip / shade_full.hip (parallel compilation).
-extern template __global__ void k_shade<MASK_LEAN, LEAN_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_LEAN | FEAT_QMC), LEAN_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_LEAN, LEAN_WAVES, 3>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_LEAN | FEAT_QMC), LEAN_WAVES, 3>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_LEAN, LEAN_WAVES, 7>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_LEAN | FEAT_QMC), LEAN_WAVES, 7>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_SIMPLE, SIMPLE_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_SIMPLE | FEAT_QMC), SIMPLE_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_SIMPLE_INST, SIMPLE_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_SIMPLE_INST | FEAT_QMC), SIMPLE_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_SIMPLE, SIMPLE_WAVES, 3>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_SIMPLE | FEAT_QMC), SIMPLE_WAVES, 3>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_SIMPLE, SIMPLE_WAVES, 7>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_SIMPLE | FEAT_QMC), SIMPLE_WAVES, 7>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_COAT, COAT_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_COAT | FEAT_QMC), COAT_WAVES, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_COAT, COAT_WAVES, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_COAT | FEAT_QMC), COAT_WAVES, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_GLASS, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_GLASS | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_GLASS, 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_GLASS | FEAT_QMC), 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_PLASTIC, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_PLASTIC | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_PLASTIC, 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_PLASTIC | FEAT_QMC), 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_COAT_INST, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_COAT_INST | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_GLASS_INST, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_GLASS_INST | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_PLASTIC_INST, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_PLASTIC_INST | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_FULL, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_FULL | FEAT_QMC), 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_FULL, 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<(MASK_FULL | FEAT_QMC), 2, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<BSDF_MASK_ALL, 2, 0>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade<MASK_MEDIA, 2, 0>(DeviceScene, PathState, PassParams, int);   // shade_media.hip
-extern template __global__ void k_shade<BSDF_MASK_ALL, 2, 0, true>(DeviceScene, PathState, PassParams, int);   // shade_global.hip
-// shade_fused.hip: one further class + class 0 and the escaped paths in one launch
-extern template __global__ void k_shade_fused<MASK_COAT, MASK_SIMPLE, COAT_WAVES>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade_fused<(MASK_COAT | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), COAT_WAVES>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade_fused<MASK_GLASS, MASK_SIMPLE, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade_fused<(MASK_GLASS | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade_fused<MASK_PLASTIC, MASK_SIMPLE, 2>(DeviceScene, PathState, PassParams, int);
-extern template __global__ void k_shade_fused<(MASK_PLASTIC | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), 2>(DeviceScene, PathState, PassParams, int);
-// k_tail: tail.hip
-// walk_shadow.hip (compiled without SLP vectorisation)
-extern template __global__ void k_trace_shadow_fast<false, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast<false, true>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast<true, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast<true, true>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast_inst<false, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast_inst<false, true>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast_inst<true, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow_fast_inst<true, true>(DeviceScene, PathState, PassParams, uint32_t);
-// walk_shadow_tex.hip: the closest-hit shadow walk of scenes that hold a `disk` or `blade` texture
-extern template __global__ void k_trace_shadow<false, true, false, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<true, true, false, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<false, true, true, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<true, true, true, 0, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<false, true, false, 1, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<true, true, false, 1, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<false, true, false, 2, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_trace_shadow<true, true, false, 2, BSDF_MASK_ALL>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<MASK_TAIL, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<MASK_TAIL, true>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<(MASK_TAIL | FEAT_QMC), false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<(MASK_TAIL | FEAT_QMC), true>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<MASK_COAT, false>(DeviceScene, PathState, PassParams, uint32_t);
-extern template __global__ void k_tail<(MASK_COAT | FEAT_QMC), false>(DeviceScene, PathState, PassParams, uint32_t);
+// The kernels other units instantiate (pt_instances.h: which, and where): declared, so that this unit instantiates none of them again
+#define PT_KERNEL PT_DECLARE_KERNEL
+PT_ALL_UNITS
+#undef PT_KERNEL
 
 // CubemapCamera's layout tables (cameras/CubemapCamera.cpp:10-46), indexed by projection mode and face
 __device__ const int g_cubeResU[4] = {4, 3, 6, 1}, g_cubeResV[4] = {3, 4, 1, 6};
@@ -180,202 +105,9 @@ namespace {
 std::mutex g_errMutex;
 std::string g_createError = "no error";
 
-// The streams of a context, kept per device for the life of the process and handed from a destroyed context to the next one created:
-// HIP binds a stream to one of a few hardware queues when it is created (GPU_MAX_HW_QUEUES, 4 by default), and the streams of a context
-// created after another one was destroyed came out with a binding on which the four parts of the wavefront loop no longer ran side by
-// side (materialtest 1280x720x256: 840 Msamples/s in a process's first context, 675 in every later one; the 16-spp passes of the
-// as-shipped scene 24 ms against 35 ms).  A renderer that is opened once per frame or per scene keeps its first context's streams this way.
-struct StreamSet {
-    hipStream_t main = nullptr, part[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, abort = nullptr;
-};
 std::mutex g_streamMutex;
 std::map<int, std::vector<StreamSet>> g_freeStreams;   // device ordinal -> sets no context holds (never destroyed: they live as long as the process)
-
-struct DeviceBuffers {
-    std::vector<void *> allocs;
-    ~DeviceBuffers() { release(); }
-    void release() { for (void *p : allocs) (void)hipFree(p); allocs.clear(); }
-};
-
-// a launch of the plan: the kernel, its workgroup size and dynamic LDS bytes (the grid is the pool's, or a part of it)
-struct ResolvedLaunch { const void *fn = nullptr; int threads = 0; size_t lds = 0; };
-// what planLaunches made of the choice (csrc/host/LaunchChoice.hpp) on this device
-struct LaunchPlan {
-    PassKind kind;
-    LaunchChoice choice;
-    ResolvedLaunch closest, shadow, shade[2 + PT_NUM_CLASSES], tail;
-    int thrShade[3] = {192, 128, 256};    // workgroup sizes of the shading launches, by ShadeSize
-    bool tailFits = false;                // a workgroup of k_tail fits a CU
-};
-
-// Where a pass of the wavefront loop takes what a render pass takes from the context and its description: the framebuffer it resolves into, the tile
-// seeds of a Sobol' pass and -- tghip_query_radiance -- the rays that replace the camera's.
-struct PassTarget {
-    float *sum = nullptr;                 // W*H*3 floats and W*H counts on the device
-    uint32_t *count = nullptr;
-    const uint32_t *tileSeeds = nullptr;  // TGHIP_PASS_SOBOL: on the device already; nullptr = the description's host array, through ctx->dTileSeeds
-    const float4 *rays = nullptr;         // k_query_paths in front of every closest-hit launch (LaunchChoice::queryPaths): the caller's rays on the device ...
-    uint32_t numRays = 0;                 // ... and how many: the pixels from there on are padding
-    bool rayPaths = false;
-};
-
 } // namespace
-
-struct tghip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t partStream[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams of parts 1..3 of the split wavefront loop ("streams" option)
-    hipStream_t classStream[8][2] = {};   // per part: the streams of the shading classes that run beside the part's own ("class_streams" option)
-    hipEvent_t evFork[8] = {}, evJoin[8][2] = {};
-    hipStream_t launchStream = nullptr;   // where the launch helpers put their kernels (stream, or the stream of the part being launched)
-    hipEvent_t evPart[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, evMain = nullptr;
-    hipDeviceProp_t prop;
-    std::string error = "no error";
-
-    // scene
-    bool haveScene = false;
-    DeviceBuffers sceneMem;
-    DeviceScene scene;
-    SceneTraits sc;                       // what checkScene decided about it (csrc/host/SceneCheck.hpp): the facts the launch code branches on, the derived tables
-    LaunchOptions opt;                    // the options the choice of a pass's kernels reads (csrc/host/LaunchChoice.hpp) ...
-    LaunchPlan lp;                        // ... and what the last upload, option or pass of another kind made of them: choice, kernels, workgroup sizes, LDS bytes
-    std::map<std::tuple<const void *, int, size_t>, int> occupancy;   // residentBlocks: the runtime's answers, per kernel, workgroup size and LDS bytes
-    int instPhaseMin = 24;                // "inst_phase_min" / "inst_refill_at" (PathState::inst_*)
-    int instRefillAt = 48;
-    bool topTreeOpt = true;               // "top_tree": 0 = ignore TgHipSceneDesc::top_nodes at the next upload (flat lists walked in record order: faster, not the reference's ties)
-    long long tailThreshold = 8192;       // "tail_threshold" (LaunchOptions::tailOpt)
-    bool failReduce = false;              // "fail_reduce" option (fault injection for the reduce's callers)
-    int wideStride = int(PT_WIDE_NODE_BYTES);   // bytes per device node: 80 (TgHipWideNode), or 128 -- a cache line each ("wide_node_stride" option, at the next upload)
-    uint32_t width = 0, height = 0;
-
-    // framebuffer
-    float *fbSum = nullptr;
-    uint32_t *fbCount = nullptr;
-    float *extSum = nullptr;
-    uint32_t *extCount = nullptr;
-
-    // TGHIP_PASS_SOBOL / TGHIP_PASS_RECORDS state
-    DeviceBuffers extMem;                 // tile seeds + per-record pass arrays (sized at upload)
-    uint32_t *dTileSeeds = nullptr, *dRecIndex = nullptr, *dRecCount = nullptr, *dRecLum = nullptr;
-    TgHipSampleRecord *dRecords = nullptr;   // SampleRecords, ceil(W/4) x ceil(H/4)
-    float *lum = nullptr;                 // per-sample luminance of the running pass
-    size_t lumCap = 0;
-    PassPlan plan;                        // what planPass decided about the running pass (csrc/host/PassPlan.hpp); reused from pass to pass, with the shard's tile list
-    uint32_t *dSorted = nullptr, *dChunkStart = nullptr, *dHint = nullptr;   // gap-free item enumeration of record passes
-    size_t sortedCap = 0, chunkStartCap = 0, hintCap = 0;
-
-    // path pool
-    DeviceBuffers poolMem;
-    PathState pool;
-    uint32_t poolSlots = 0;
-    uint32_t poolGrid = 0;                // persistent workgroups the pool is laid out for
-    uint32_t poolWalkArrays = 0;          // walk arrays the pool carries behind the A_* ones (0: walks are never suspended)
-    uint32_t poolWalkWanted = 0;          // ... and how many the scene it was laid out for asked for (more than fit the 32-bit offsets: none)
-    uint32_t *hostLive = nullptr;         // pinned mirror of PathState::live for the loop condition
-    unsigned long long walkStats[2][PT_WALK_STATS] = {{0}, {0}};   // BlockStats::walk summed over workgroups and folds (tghip_get_walk_stats)
-    std::vector<BlockCtl> hostCtl;        // scratch for tghip_get_counters
-    std::vector<BlockStats> hostStats;
-
-    // options
-    // path pool size.  Every kernel of an iteration costs a fixed 140-180 us on top of the time that grows with its rays -- the
-    // longest walks / the latency of one shading turn, measured by doubling the pool: materialtest closest-hit 246 -> 348 us, shadow
-    // 347 -> 518 us, k_shade 421 -> 665 us per launch for twice the rays -- so the pool is as large as the 32-bit slot offsets allow
-    // (8 M slots x 272 B = 2.2 GB of the 288 GB): 1280x720x256 669 -> 745 (4 M) -> 818 (8 M) Msamples/s, mesh1m 404 -> 472 -> 507
-    long long maxSlots = 1ll << 23;
-    bool maxSlotsSet = false;             // "max_slots" was given explicitly
-    long long maxItems = 1ll << 26;       // work items per batch (partial-sum buffer = 16 B each)
-    int chunkSamples = 0;                 // "chunk_samples": samples per work item; 0 = 4, or one when the pass is short (csrc/host/PassPlan.cpp)
-    size_t partialCap = 0;
-    float4 *partial = nullptr;
-
-    // shading classes of the uploaded scene (rec_class) and the kernel variants chosen for them
-    TgHipAuxPixel *dAux = nullptr;        // auxiliary output buffers (allocated by the first TGHIP_PASS_AUX pass)
-    float *dSamples = nullptr;            // TGHIP_PASS_SAMPLES: per-sample radiance of the last such pass
-    // tghip_develop: where the kernels write when the caller's outputs are host memory (grown on demand), the depth output's maximum, the option
-    // that hands the work back to the caller's host code, the kernels' time
-    float *developHdr = nullptr;
-    uint8_t *developLdr = nullptr;
-    size_t developHdrCap = 0, developLdrCap = 0;
-    uint32_t *developMax = nullptr;
-    bool developHost = false;             // "develop_host"
-    double developMs = 0.0;
-    // tghip_nlmeans: the three input planes and the result on the device when they are not the caller's device memory (grown on demand), the
-    // "nlmeans_batch" option (0: the launcher's choice)
-    float *nlmBuf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t nlmCap[4] = {0, 0, 0, 0};
-    uint32_t nlmBatch = 0;
-    double nlmMs = 0.0;
-    // tghip_query_rays: the work counter the kernel's workgroups claim rays from (one word, reset in-stream before every launch), the rays and the
-    // answers on the device when they are the caller's host memory (grown on demand), the "query_blocks" / "query_refill_at" options (0: the
-    // measured defaults, RAY_QUERY_BLOCKS_PER_CU / RAY_QUERY_REFILL_AT), the kernel's time
-    uint32_t *queryCounter = nullptr;
-    float4 *queryRays = nullptr, *queryOut = nullptr;
-    size_t queryRaysCap = 0, queryOutCap = 0;
-    int queryBlocks = 0, queryRefillAt = 0;
-    double queryMs = 0.0;
-    // tghip_query_radiance: the plan of the query's pass (kept like `plan`), the framebuffer of its virtual image and that image's tile seeds -- all
-    // equal to radTileSeed where radTileSeedsSet entries are --, the rays on the device when they are the caller's host memory (all grown on demand),
-    // the time of the pass and the copy of its answers
-    PassPlan radPlan;
-    float *radSum = nullptr;
-    uint32_t *radCount = nullptr, *radTileSeeds = nullptr;
-    float4 *radRays = nullptr;
-    size_t radSumCap = 0, radCountCap = 0, radTileSeedsCap = 0, radRaysCap = 0, radTileSeedsSet = 0;
-    uint32_t radTileSeed = 0;
-    double radMs = 0.0;
-    void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context
-    int rankCount = 0, rankIndex = 0;
-    float *redSum = nullptr;              // tghip_reduce_framebuffers: where the reduced image lands when this context is the root
-    uint32_t *redCount = nullptr;
-    size_t redCap = 0;                    // pixels redSum / redCount were allocated for (a re-upload may change the resolution)
-    // the tiles of the shard the last pass rendered (plan.ownedList), on the device
-    uint32_t *dOwnedTiles = nullptr;
-    size_t ownedCap = 0;
-    size_t samplesCap = 0, samplesFloats = 0;
-    bool hoistOpt = true;                 // "hoist_quad": the scene's one quad tested before the decoupled walks instead of inside them (at the next upload)
-                                          // (scene.hoisted_rec and scene.env_tex are sc.hoisted.record / sc.env_tex unless "hoist_quad" / "env_lds" = 0 say -1)
-    bool countTraversal = false;
-    int checkInterval = 0;                // "check_interval": wavefront iterations between host-side liveness checks; 0 = 16 for batches that refill
-                                          // the pool several times (every check drains all streams: materialtest 825 / 835 / 845 Msamples/s for
-                                          // 4 / 8 / 16), 4 for short ones (the iterations after the last path ended are wasted)
-    int gridRounds = 1;                   // "grid_rounds": launch this many times the resident workgroups (each owns 1/rounds of the slots);
-                                          // the dispatcher starts the later ones as the first finish, filling the drain tail of a launch
-    // "suspend_lanes" / "suspend_turns" / "suspend_min_queue" (PathState::suspend_*): walk time-slicing of the wide traversal kernels
-    int suspendLanes = 12, suspendTurns = 16, suspendMinQueue = 1024;   // (measured, profiles/README.md: materialtest +0.5 %, mesh1m +4 % over none; round 5 on the final kernels, r5_sweep_final_kernels.txt: 12 lanes +0.5 % / +1 % over 16, 8 lanes +0.8 % / -3 %)
-    uint32_t numWideNodes = 0;
-    int leafBatch = 1;                    // "leaf_batch" (PathState::leaf_batch)
-    int leafBatchBvh2 = 0;                // "leaf_batch_bvh2" (PathState::leaf_batch_bvh2); 0 = leaf_batch, or the measured value for two-level scenes
-    long long poolPad = 9472;             // bytes between the per-slot arrays of the pool (multiple of 16)
-    bool timeKernels = false;             // HIP events around every launch of the wavefront loop (bench.py roofline)
-    std::vector<hipEvent_t> evPool;
-
-    // abort (PathTraceIntegrator::abortRender): a host-side request flag, mirrored into one device word the kernels poll.
-    // The word is allocated once per context (never with the reallocatable pool), so tghip_abort may write it from any
-    // thread at any time; the request is cleared by tghip_render_pass only, so one that lands before the pass's kernels
-    // have started is not lost.
-    std::atomic<bool> abortRequested{false};
-    uint32_t *abortFlagDev = nullptr;
-    hipStream_t abortStream = nullptr;
-    std::mutex abortMutex;                // serialises tghip_abort callers (they share abortStream)
-
-    // async pass state
-    bool passPending = false;
-    int passResult = TGHIP_OK;
-    TgHipPassDesc pendingPass;
-
-    // counters
-    TgHipCounters counters;
-    hipEvent_t evA = nullptr, evB = nullptr;
-};
-
-#define HIP_TRY(ctx, call)                                                                  \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            (ctx)->error = std::string(#call) + ": " + hipGetErrorString(e_);               \
-            return TGHIP_E_HIP;                                                             \
-        }                                                                                   \
-    } while (0)
 
 template<typename T, typename P>
 static int uploadArray(tghip_ctx *ctx, DeviceBuffers &mem, const T *src, size_t count, P *dst, size_t padBytes = 0)   // P = (restrict-qualified) const T *
@@ -400,21 +132,8 @@ static int allocArray(tghip_ctx *ctx, DeviceBuffers &mem, size_t count, T **dst)
     return TGHIP_OK;
 }
 
-// A device array of the context that grows on demand and is never shrunk: room for `need` elements.  (The old contents are dropped.  An allocation
-// is never empty: it happens only for need > cap >= 0.)
-template<typename T>
-static int growArray(tghip_ctx *ctx, T *&dev, size_t &cap, size_t need)
-{
-    if (cap >= need) return TGHIP_OK;
-    if (dev) (void)hipFree(dev);
-    dev = nullptr; cap = 0;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dev), need*sizeof(T)));
-    cap = need;
-    return TGHIP_OK;
-}
-
-// ---- Kernel identities (csrc/host/LaunchChoice.hpp) to kernels: per family the one place where run-time flags become template arguments.  What is
-// named here is what this translation unit instantiates (the k_shade, k_shade_fused, k_tail, k_trace_shadow_fast and <., BSDF_MASK_ALL> families: extern, above).
+// ---- Kernel identities (csrc/host/LaunchChoice.hpp) to kernels: per family the one place where run-time flags become template arguments.  What
+// walkKernelFn names is what this translation unit instantiates; the kernels of the other units are looked up in their list (pt_instances.h).
 #define KERNEL(...) reinterpret_cast<const void *>(&__VA_ARGS__)
 template<typename F>
 static const void *withBool(bool b, F f) { return b ? f(std::true_type()) : f(std::false_type()); }
@@ -433,9 +152,7 @@ static const void *walkKernelFn(const KernelId &k)
                                                                                                                   : KERNEL(k_trace_closest_wide<c, s, false, false>);
         case K_FINISH_CLOSEST_WIDE: return KERNEL(k_finish_trace_closest_wide<c, s>);
         case K_SHADOW:
-            if (k.mask == BSDF_MASK_ALL)      // walk_shadow_tex.hip: closest-hit shadow walks only
-                return k.inst == 1 ? KERNEL(k_trace_shadow<c, true, false, 1, BSDF_MASK_ALL>) : k.inst == 2 ? KERNEL(k_trace_shadow<c, true, false, 2, BSDF_MASK_ALL>)
-                     : k.flat ? KERNEL(k_trace_shadow<c, true, true, 0, BSDF_MASK_ALL>) : KERNEL(k_trace_shadow<c, true, false, 0, BSDF_MASK_ALL>);
+            if (k.mask == BSDF_MASK_ALL) return nullptr;   // (walk_shadow_tex.hip's, listed: never this unit's default-mask walk in their place)
             return withBool(k.forward, [&](auto FW) -> const void * {
                 constexpr bool fw = decltype(FW)::value;
                 return k.inst == 1 ? KERNEL(k_trace_shadow<c, fw, false, 1>) : k.inst == 2 ? KERNEL(k_trace_shadow<c, fw, false, 2>)
@@ -446,8 +163,6 @@ static const void *walkKernelFn(const KernelId &k)
         // latch the backend generates for the turn without PT_TURN_JOIN, pt_wavefront.h; "inst_shadow_join" = 0 launches that variant for tools/repro_latch_miscompile.py)
         case K_SHADOW_WIDE:         return !k.join ? KERNEL(k_trace_shadow_wide<false, false, true, false>)
                                          : k.inst ? KERNEL(k_trace_shadow_wide<c, s, true>) : KERNEL(k_trace_shadow_wide<c, s, false>);
-        case K_SHADOW_FAST:         return KERNEL(k_trace_shadow_fast<c, s>);
-        case K_SHADOW_FAST_INST:    return KERNEL(k_trace_shadow_fast_inst<c, s>);
         case K_TRACE_RAYS:          return k.decoupled ? KERNEL(k_trace_rays<c, false, 0, true>) : k.inst ? KERNEL(k_trace_rays<c, false, 1>)
                                          : k.flat ? KERNEL(k_trace_rays<c, true>) : KERNEL(k_trace_rays<c, false>);
         default:                    return nullptr;
@@ -455,37 +170,19 @@ static const void *walkKernelFn(const KernelId &k)
     }); });
 }
 
-// (mask, waves per SIMD, FUSE) of the k_shade instantiations that have a FEAT_QMC twin, and the further classes' families of k_shade_fused
-#define SHADE_KERNELS(X) \
-    X(MASK_LEAN, LEAN_WAVES, 0) X(MASK_LEAN, LEAN_WAVES, 3) X(MASK_LEAN, LEAN_WAVES, 7) \
-    X(MASK_SIMPLE, SIMPLE_WAVES, 0) X(MASK_SIMPLE, SIMPLE_WAVES, 3) X(MASK_SIMPLE, SIMPLE_WAVES, 7) X(MASK_SIMPLE_INST, SIMPLE_WAVES, 0) \
-    X(MASK_COAT, COAT_WAVES, 0) X(MASK_COAT, COAT_WAVES, 2) X(MASK_GLASS, 2, 0) X(MASK_GLASS, 2, 2) X(MASK_PLASTIC, 2, 0) X(MASK_PLASTIC, 2, 2) \
-    X(MASK_COAT_INST, 2, 0) X(MASK_GLASS_INST, 2, 0) X(MASK_PLASTIC_INST, 2, 0) X(MASK_FULL, 2, 0) X(MASK_FULL, 2, 2)
-#define SHADE_FUSED_KERNELS(X) X(MASK_COAT, COAT_WAVES) X(MASK_GLASS, 2) X(MASK_PLASTIC, 2)
-static const void *shadeKernelFn(const KernelId &k)
+// the explicitly instantiated kernels: every entry of every unit's list is one lookup
+static const void *explicitKernelFn(const KernelId &k)
 {
-    if (k.family == K_SHADE_FUSED) {
-#define X(M, W) if (k.mask == (M)) return KERNEL(k_shade_fused<M, MASK_SIMPLE, W>); \
-                if (k.mask == ((M) | FEAT_QMC)) return KERNEL(k_shade_fused<((M) | FEAT_QMC), (MASK_SIMPLE | FEAT_QMC), W>);
-        SHADE_FUSED_KERNELS(X)
-#undef X
-        return nullptr;
-    }
-    if (k.family == K_TAIL) {
-        if ((k.mask & ~FEAT_QMC) == MASK_COAT) return (k.mask & FEAT_QMC) ? KERNEL(k_tail<(MASK_COAT | FEAT_QMC), false>) : KERNEL(k_tail<MASK_COAT, false>);
-        if (k.mask & FEAT_QMC) return k.solids ? KERNEL(k_tail<(MASK_TAIL | FEAT_QMC), true>) : KERNEL(k_tail<(MASK_TAIL | FEAT_QMC), false>);
-        return k.solids ? KERNEL(k_tail<MASK_TAIL, true>) : KERNEL(k_tail<MASK_TAIL, false>);
-    }
-    if (k.globalTables) return KERNEL(k_shade<BSDF_MASK_ALL, 2, 0, true>);
-    if (k.mask == BSDF_MASK_ALL) return KERNEL(k_shade<BSDF_MASK_ALL, 2, 0>);   // the one variant with FEAT_MEDIA / FEAT_AUX / FEAT_CYLINDER; FEAT_QMC is in it
-    if (k.mask == MASK_MEDIA) return KERNEL(k_shade<MASK_MEDIA, 2, 0>);
-#define X(M, W, F) if (k.fuse == F && k.mask == (M)) return KERNEL(k_shade<M, W, F>); \
-                   if (k.fuse == F && k.mask == ((M) | FEAT_QMC)) return KERNEL(k_shade<((M) | FEAT_QMC), W, F>);
-    SHADE_KERNELS(X)
-#undef X
+#define PT_KERNEL(match, params, ...) if (match) return KERNEL(__VA_ARGS__);
+    PT_ALL_UNITS
+#undef PT_KERNEL
     return nullptr;
 }
-static const void *kernelFn(const KernelId &k) { return (k.family == K_SHADE || k.family == K_SHADE_FUSED || k.family == K_TAIL) ? shadeKernelFn(k) : walkKernelFn(k); }
+static const void *kernelFn(const KernelId &k)
+{
+    const void *fn = explicitKernelFn(k);
+    return fn ? fn : walkKernelFn(k);
+}
 
 // hipLaunchKernel takes the arguments by address and does not know the kernel's parameter list: every argument must HAVE the type of its parameter.  The
 // kernels launched through here take structs, pointers, `int` and `uint32_t`; a number of any other type is refused at compile time.
@@ -649,6 +346,9 @@ static int foldCounters(tghip_ctx *ctx)
     return TGHIP_OK;
 }
 
+// The pool goes: the next pass lays it out again (an option its layout depends on has changed, or ensurePool wants another one)
+static void dropPool(tghip_ctx *ctx) { ctx->poolMem.release(); ctx->poolSlots = 0; }
+
 // Pool layout: `grid` persistent workgroups x slotsPerBlock slots (a multiple of 64); queue segments and the
 // per-workgroup control records are laid out the same way.
 static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
@@ -672,8 +372,7 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     ctx->poolWalkWanted = walkArrays;
     int rc = foldCounters(ctx);                  // the per-workgroup statistics live in the pool
     if (rc != TGHIP_OK) return rc;
-    ctx->poolMem.release();
-    ctx->poolSlots = 0;
+    dropPool(ctx);
 #define POOL_ALLOC(field, n) do { std::remove_reference<decltype(*p.field)>::type *tmp_ = nullptr; \
         if ((rc = allocArray(ctx, ctx->poolMem, (n), &tmp_)) != TGHIP_OK) return rc; p.field = tmp_; } while (0)
     // arrays are skewed by an odd number of 256-byte units so that element i of different arrays does not map to
@@ -697,7 +396,7 @@ static int ensurePool(tghip_ctx *ctx, uint32_t wantSlots)
     HIP_TRY(ctx, hipMemsetAsync(p.ctl, 0, sizeof(BlockCtl)*grid, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(p.stats, 0, sizeof(BlockStats)*grid, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(p.live, 0, 4*sizeof(uint32_t), ctx->stream));
-    p.abort_flag = ctx->abortFlagDev;
+    p.abort_flag = ctx->abortFlagDev.get();
     p.num_slots = slots;
     p.slots_per_block = perBlock;
     ctx->poolSlots = slots;
@@ -775,8 +474,8 @@ tghip_ctx *tghip_create(int device_ordinal)
     if (e == hipSuccess) e = hipEventCreate(&ctx->evA);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evB);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&ctx->hostLive), 2*sizeof(uint32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->abortFlagDev), 64);
-    if (e == hipSuccess) e = hipMemset(ctx->abortFlagDev, 0, 64);
+    if (e == hipSuccess) e = ctx->abortFlagDev.once(16);
+    if (e == hipSuccess) e = hipMemset(ctx->abortFlagDev.get(), 0, 64);
     if (e != hipSuccess) {
         {
             std::lock_guard<std::mutex> lock(g_errMutex);
@@ -788,47 +487,18 @@ tghip_ctx *tghip_create(int device_ordinal)
     return ctx;
 }
 
-extern "C++" void tghipDestroyRankComm(void *comm);   // (defined with the RCCL loader below)
 void tghip_destroy(tghip_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    // every stream idle before the first buffer goes (the part / class streams join the main one at the end of a pass, an aborted or
-    // failed pass may have left them behind)
+    // every stream idle before the first buffer goes -- with the context, at the end: its arrays free themselves (device_array.h) -- (the part /
+    // class streams join the main one at the end of a pass, an aborted or failed pass may have left them behind)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 7; ++k) if (ctx->partStream[k]) (void)hipStreamSynchronize(ctx->partStream[k]);
     for (int k = 0; k < 8; ++k)
         for (int a = 0; a < 2; ++a) if (ctx->classStream[k][a]) (void)hipStreamSynchronize(ctx->classStream[k][a]);
     if (ctx->abortStream) (void)hipStreamSynchronize(ctx->abortStream);
-    ctx->sceneMem.release();
-    ctx->poolMem.release();
-    ctx->extMem.release();
-    if (ctx->lum) (void)hipFree(ctx->lum);
-    if (ctx->dSorted) (void)hipFree(ctx->dSorted);
-    if (ctx->dChunkStart) (void)hipFree(ctx->dChunkStart);
-    if (ctx->dHint) (void)hipFree(ctx->dHint);
-    if (ctx->fbSum) (void)hipFree(ctx->fbSum);
-    if (ctx->fbCount) (void)hipFree(ctx->fbCount);
-    if (ctx->dAux) (void)hipFree(ctx->dAux);
-    if (ctx->dSamples) (void)hipFree(ctx->dSamples);
-    if (ctx->developHdr) (void)hipFree(ctx->developHdr);
-    if (ctx->developLdr) (void)hipFree(ctx->developLdr);
-    if (ctx->developMax) (void)hipFree(ctx->developMax);
-    for (float *b : ctx->nlmBuf) if (b) (void)hipFree(b);
-    if (ctx->queryCounter) (void)hipFree(ctx->queryCounter);
-    if (ctx->queryRays) (void)hipFree(ctx->queryRays);
-    if (ctx->queryOut) (void)hipFree(ctx->queryOut);
-    if (ctx->radSum) (void)hipFree(ctx->radSum);
-    if (ctx->radCount) (void)hipFree(ctx->radCount);
-    if (ctx->radTileSeeds) (void)hipFree(ctx->radTileSeeds);
-    if (ctx->radRays) (void)hipFree(ctx->radRays);
-    if (ctx->dOwnedTiles) (void)hipFree(ctx->dOwnedTiles);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
-    if (ctx->redSum) (void)hipFree(ctx->redSum);
-    if (ctx->redCount) (void)hipFree(ctx->redCount);
-    if (ctx->partial) (void)hipFree(ctx->partial);
-    if (ctx->hostLive) (void)hipHostFree(ctx->hostLive);
-    if (ctx->abortFlagDev) (void)hipFree(ctx->abortFlagDev);
     if (ctx->evA) (void)hipEventDestroy(ctx->evA);
     if (ctx->evB) (void)hipEventDestroy(ctx->evB);
     for (hipEvent_t e : ctx->evPool) (void)hipEventDestroy(e);
@@ -856,7 +526,7 @@ void tghip_destroy(tghip_ctx *ctx)
             for (int k = 0; k < 7; ++k) if (set.part[k]) (void)hipStreamDestroy(set.part[k]);
         }
     }
-    delete ctx;
+    delete ctx;                                  // (and with it every device array it holds: the device is current, the streams are idle)
 }
 
 const char *tghip_last_error(tghip_ctx *ctx)
@@ -877,7 +547,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     // the options the choice of a pass's kernels reads: stored, and the plan of the uploaded scene made again
     if (k == "count_traversal" || setLaunchOption(ctx->opt, k, value)) {
         if (k == "count_traversal") ctx->countTraversal = value != 0;
-        if (k == "slots_per_block") { ctx->poolMem.release(); ctx->poolSlots = 0; }
+        if (k == "slots_per_block") dropPool(ctx);
         for (int kk = 0; kk < 8 && k == "class_streams" && value != 0; ++kk)     // (created when the option is first switched on: an experiment's streams)
             for (int a = 0; a < 2; ++a)
                 if (!ctx->classStream[kk][a]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->classStream[kk][a], hipStreamNonBlocking));
@@ -890,7 +560,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "time_kernels") ctx->timeKernels = value != 0;
     else if (k == "inst_phase_min") ctx->instPhaseMin = int(std::min<long long>(std::max<long long>(value, 1), 64));
     else if (k == "inst_refill_at") ctx->instRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 63));
-    else if (k == "grid_rounds") { ctx->gridRounds = int(std::min<long long>(std::max<long long>(value, 1), 8)); ctx->poolMem.release(); ctx->poolSlots = 0; }
+    else if (k == "grid_rounds") { ctx->gridRounds = int(std::min<long long>(std::max<long long>(value, 1), 8)); dropPool(ctx); }
     else if (k == "leaf_batch_bvh2") ctx->leafBatchBvh2 = int(std::min<long long>(std::max<long long>(value, 0), 64));
     else if (k == "suspend_lanes") ctx->suspendLanes = int(std::min<long long>(std::max<long long>(value, 0), 64));
     else if (k == "suspend_turns") ctx->suspendTurns = int(std::min<long long>(std::max<long long>(value, 1), 1 << 20));   // (>= 1: every launch advances every walk)
@@ -906,7 +576,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "nlmeans_batch") ctx->nlmBatch = uint32_t(std::min<long long>(std::max<long long>(value, 0), NLMEANS_MAX_BATCH));   // offsets box-filtered at once by tghip_nlmeans (0: the measured choice, denoise.hip)
     else if (k == "query_blocks") ctx->queryBlocks = int(std::min<long long>(std::max<long long>(value, 0), 1 << 16));       // workgroups of tghip_query_rays (0: the measured default)
     else if (k == "query_refill_at") ctx->queryRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 64));   // idle lanes of a wave at which it claims rays (0: the measured default)
-    else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; ctx->poolMem.release(); ctx->poolSlots = 0; }
+    else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; dropPool(ctx); }
     else if (k == "wide_node_stride") {
         if (value != 128 && value != 80) { ctx->error = "wide_node_stride is 80 or 128"; return TGHIP_E_INVALID; }
         ctx->wideStride = int(value);
@@ -1016,14 +686,11 @@ int tghip_upload_scene(tghip_ctx *ctx, const TgHipSceneDesc *sd)
 
     // framebuffer
     if (ctx->width != uint32_t(sd->camera.res_x) || ctx->height != uint32_t(sd->camera.res_y) || !ctx->fbSum) {
-        if (ctx->fbSum) (void)hipFree(ctx->fbSum);
-        if (ctx->fbCount) (void)hipFree(ctx->fbCount);
-        if (ctx->dAux) (void)hipFree(ctx->dAux);
-        ctx->fbSum = nullptr; ctx->fbCount = nullptr; ctx->dAux = nullptr;
+        ctx->fbSum.release(); ctx->fbCount.release(); ctx->dAux.release();
         ctx->width = uint32_t(sd->camera.res_x); ctx->height = uint32_t(sd->camera.res_y);
         size_t npix = size_t(ctx->width)*ctx->height;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->fbSum), npix*3*sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->fbCount), npix*sizeof(uint32_t)));
+        if ((rc = ctx->fbSum.grow(ctx, npix*3)) != TGHIP_OK) return rc;
+        if ((rc = ctx->fbCount.grow(ctx, npix)) != TGHIP_OK) return rc;
         // tile seeds, SampleRecords and the per-record pass arrays
         ctx->extMem.release();
         const size_t tiles = size_t((ctx->width + 15)/16)*((ctx->height + 15)/16);
@@ -1045,13 +712,13 @@ int tghip_clear_framebuffer(tghip_ctx *ctx)
     if (!ctx || !ctx->haveScene) return TGHIP_E_NOSCENE;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     size_t npix = size_t(ctx->width)*ctx->height;
-    float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    float *sum = ctx->frameSum();
+    uint32_t *cnt = ctx->frameCount();
     HIP_TRY(ctx, hipMemsetAsync(sum, 0, npix*3*sizeof(float), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(cnt, 0, npix*sizeof(uint32_t), ctx->stream));
     const size_t recs = size_t((ctx->width + 3)/4)*((ctx->height + 3)/4);
     HIP_TRY(ctx, hipMemsetAsync(ctx->dRecords, 0, recs*sizeof(TgHipSampleRecord), ctx->stream));
-    if (ctx->dAux) HIP_TRY(ctx, hipMemsetAsync(ctx->dAux, 0, npix*sizeof(TgHipAuxPixel), ctx->stream));
+    if (ctx->dAux) HIP_TRY(ctx, hipMemsetAsync(ctx->dAux.get(), 0, npix*sizeof(TgHipAuxPixel), ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TGHIP_OK;
 }
@@ -1072,8 +739,8 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp, const PassTarget &targ
     if (ctx->abortRequested.load(std::memory_order_acquire))
         return TGHIP_E_ABORTED;                  // aborted before this batch started: nothing to drain
     PathState st = ctx->pool;
-    st.partial = ctx->partial;
-    st.abort_flag = ctx->abortFlagDev;
+    st.partial = ctx->partial.get();
+    st.abort_flag = ctx->abortFlagDev.get();
     st.leaf_batch = uint32_t(ctx->leafBatch);
     const LaunchPlan &lp = ctx->lp;              // (tghip_wait planned the pass's kind)
     const LaunchChoice &choice = lp.choice;
@@ -1222,7 +889,7 @@ static int runBatch(tghip_ctx *ctx, const PassParams &pp, const PassTarget &targ
                 HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->evPart[k - 1], 0));
             }
             if (ctx->abortRequested.load(std::memory_order_acquire))
-                HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev, 0xFF, sizeof(uint32_t), ctx->stream));
+                HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev.get(), 0xFF, sizeof(uint32_t), ctx->stream));
             if (tailEligible) hipLaunchKernelGGL(k_live_slots, dim3(1), dim3(256), 0, ctx->stream, st, uint32_t(grid));
             HIP_TRY(ctx, hipMemcpyAsync(ctx->hostLive, st.live, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1357,11 +1024,11 @@ static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32
         return rc;
 
     // the device arrays the plan names
-    auto upload = [&](uint32_t *&dev, size_t &cap, const std::vector<uint32_t> &src) -> int {
-        const int grc = growArray(ctx, dev, cap, src.size());
+    auto upload = [&](DeviceArray<uint32_t> &dev, const std::vector<uint32_t> &src) -> int {
+        const int grc = dev.grow(ctx, src.size());
         if (grc != TGHIP_OK) return grc;
         if (!src.empty())
-            HIP_TRY(ctx, hipMemcpyAsync(dev, src.data(), src.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(dev.get(), src.data(), src.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         return TGHIP_OK;
     };
     PassParams base{};
@@ -1374,11 +1041,11 @@ static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32
     base.variance_w = plan.varianceW;
     if (plan.shardCount > 1) {
         if (plan.ownedStale) {                   // the shard's tile list changed: rare
-            if ((rc = upload(ctx->dOwnedTiles, ctx->ownedCap, plan.ownedList)) != TGHIP_OK) return rc;
+            if ((rc = upload(ctx->dOwnedTiles, plan.ownedList)) != TGHIP_OK) return rc;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             plan.ownedStale = false;
         }
-        base.owned_tiles = ctx->dOwnedTiles;
+        base.owned_tiles = ctx->dOwnedTiles.get();
     }
     if ((pass.flags & TGHIP_PASS_SOBOL) && target.tileSeeds) {
         base.tile_seeds = target.tileSeeds;
@@ -1388,34 +1055,34 @@ static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32
     }
     if (plan.recordPass) {
         const size_t recBytes = size_t(plan.numRecords)*sizeof(uint32_t);
-        if ((rc = growArray(ctx, ctx->lum, ctx->lumCap, size_t(plan.lumFloats))) != TGHIP_OK) return rc;
+        if ((rc = ctx->lum.grow(ctx, size_t(plan.lumFloats))) != TGHIP_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecIndex, plan.recIndex.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecCount, plan.recCount.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dRecLum, plan.recLum.data(), recBytes, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = upload(ctx->dSorted, ctx->sortedCap, plan.sorted)) != TGHIP_OK) return rc;
-        if ((rc = upload(ctx->dChunkStart, ctx->chunkStartCap, plan.chunkStart)) != TGHIP_OK) return rc;
+        if ((rc = upload(ctx->dSorted, plan.sorted)) != TGHIP_OK) return rc;
+        if ((rc = upload(ctx->dChunkStart, plan.chunkStart)) != TGHIP_OK) return rc;
         // the hint table -- for every 64 items the chunk their first one lies in -- is filled by a launch from the chunk starts
-        if ((rc = growArray(ctx, ctx->dHint, ctx->hintCap, plan.hintEntries)) != TGHIP_OK) return rc;
-        hipLaunchKernelGGL(k_record_hints, dim3(uint32_t((plan.hintEntries + 255)/256)), dim3(256), 0, ctx->stream, ctx->dChunkStart, plan.chunksAll, ctx->dHint, uint32_t(plan.hintEntries));
+        if ((rc = ctx->dHint.grow(ctx, plan.hintEntries)) != TGHIP_OK) return rc;
+        hipLaunchKernelGGL(k_record_hints, dim3(uint32_t((plan.hintEntries + 255)/256)), dim3(256), 0, ctx->stream, ctx->dChunkStart.get(), plan.chunksAll, ctx->dHint.get(), uint32_t(plan.hintEntries));
         HIP_TRY(ctx, hipGetLastError());
         base.rec_index = ctx->dRecIndex; base.rec_count = ctx->dRecCount; base.rec_lum = ctx->dRecLum;
-        base.lum = ctx->lum;
-        base.rec_sorted = ctx->dSorted; base.rec_chunk_start = ctx->dChunkStart; base.rec_hint = ctx->dHint;
+        base.lum = ctx->lum.get();
+        base.rec_sorted = ctx->dSorted.get(); base.rec_chunk_start = ctx->dChunkStart.get(); base.rec_hint = ctx->dHint.get();
         base.num_sorted = uint32_t(plan.sorted.size());
         base.num_chunks = plan.chunksAll;
     }
     if (plan.auxPass && !ctx->dAux) {
         const size_t npix = size_t(w)*h;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dAux), npix*sizeof(TgHipAuxPixel)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dAux, 0, npix*sizeof(TgHipAuxPixel), ctx->stream));
+        if ((rc = ctx->dAux.grow(ctx, npix)) != TGHIP_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dAux.get(), 0, npix*sizeof(TgHipAuxPixel), ctx->stream));
     }
-    base.aux = ctx->dAux;
+    base.aux = ctx->dAux.get();
     if (pass.flags & TGHIP_PASS_SAMPLES) {
         const size_t need = size_t(w)*h*plan.spp*3u;
-        if ((rc = growArray(ctx, ctx->dSamples, ctx->samplesCap, need)) != TGHIP_OK) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dSamples, 0, need*sizeof(float), ctx->stream));
+        if ((rc = ctx->dSamples.grow(ctx, need)) != TGHIP_OK) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dSamples.get(), 0, need*sizeof(float), ctx->stream));
         ctx->samplesFloats = need;
-        base.samples = ctx->dSamples; base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
+        base.samples = ctx->dSamples.get(); base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
     }
 
     uint64_t wantSlots = std::min<uint64_t>(uint64_t(ctx->maxSlots), plan.batchItems);
@@ -1424,9 +1091,9 @@ static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32
     if (ctx->lp.choice.oneLaunch && !ctx->maxSlotsSet)
         wantSlots = std::min<uint64_t>(wantSlots, uint64_t(launchGrid(ctx))*uint64_t(ctx->lp.thrShade[SIZE_SIMPLE]));
     if ((rc = ensurePool(ctx, uint32_t(wantSlots))) != TGHIP_OK) return rc;
-    if ((rc = growArray(ctx, ctx->partial, ctx->partialCap, size_t(plan.batchItems))) != TGHIP_OK) return rc;
+    if ((rc = ctx->partial.grow(ctx, size_t(plan.batchItems))) != TGHIP_OK) return rc;
     // the device word still holds the previous pass's abort, if any; a request for THIS pass is re-mirrored by runBatch
-    HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev, 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev.get(), 0, sizeof(uint32_t), ctx->stream));
 
     const double msSetup = msSince(tWait0);
     const unsigned long long itersBefore = ctx->counters.iterations;
@@ -1461,6 +1128,30 @@ static int runPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32
     return rc;
 }
 
+// The launches of `launch` between the context's two timing events, `after` -- the copies back into host memory -- behind them and, once the stream
+// has run dry, the launches' milliseconds in `ms`.
+template<typename Launch, typename After>
+static int timedLaunches(tghip_ctx *ctx, double &ms, Launch launch, After after)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    int rc = launch();
+    if (rc != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    if ((rc = after()) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float elapsed = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&elapsed, ctx->evA, ctx->evB));
+    ms = elapsed;
+    return TGHIP_OK;
+}
+// ... and what the tghip_*_kernel_time functions answer: the milliseconds the last such call stored
+static int kernelTime(const tghip_ctx *ctx, double tghip_ctx::*stored, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->*stored;
+    return TGHIP_OK;
+}
+
 extern "C" {
 
 int tghip_wait(tghip_ctx *ctx)
@@ -1477,8 +1168,8 @@ int tghip_wait(tghip_ctx *ctx)
     if (rc != TGHIP_OK || ctx->plan.empty)
         return ctx->passResult = rc;
     PassTarget target;
-    target.sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    target.count = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    target.sum = ctx->frameSum();
+    target.count = ctx->frameCount();
     return ctx->passResult = runPass(ctx, pass, ctx->width, ctx->height, ctx->plan, target);
 }
 
@@ -1492,7 +1183,7 @@ int tghip_abort(tghip_ctx *ctx)
     std::lock_guard<std::mutex> lock(ctx->abortMutex);
     static const uint32_t one = 1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipError_t e = hipMemcpyAsync(ctx->abortFlagDev, &one, sizeof(one), hipMemcpyHostToDevice, ctx->abortStream);
+    hipError_t e = hipMemcpyAsync(ctx->abortFlagDev.get(), &one, sizeof(one), hipMemcpyHostToDevice, ctx->abortStream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->abortStream);
     if (e != hipSuccess) return TGHIP_E_HIP;    // (ctx->error belongs to the thread driving the pass)
     return TGHIP_OK;
@@ -1505,8 +1196,8 @@ int tghip_download_framebuffer(tghip_ctx *ctx, float *rgb_sum, uint32_t *count, 
     int rc = tghip_wait(ctx);
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    const uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    const float *sum = ctx->frameSum();
+    const uint32_t *cnt = ctx->frameCount();
     if (rgb_sum) HIP_TRY(ctx, hipMemcpyAsync(rgb_sum, sum, npixels*3*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (count) HIP_TRY(ctx, hipMemcpyAsync(count, cnt, npixels*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1520,8 +1211,8 @@ int tghip_upload_framebuffer(tghip_ctx *ctx, const float *rgb_sum, const uint32_
     int rc = tghip_wait(ctx);
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    float *sum = ctx->frameSum();
+    uint32_t *cnt = ctx->frameCount();
     HIP_TRY(ctx, hipMemcpyAsync(sum, rgb_sum, npixels*3*sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(cnt, count, npixels*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1560,7 +1251,7 @@ int tghip_download_aux(tghip_ctx *ctx, TgHipAuxPixel *out, size_t npixels)
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     if (!ctx->dAux) { std::memset(out, 0, npixels*sizeof(TgHipAuxPixel)); return TGHIP_OK; }   // no TGHIP_PASS_AUX pass yet
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->dAux, npixels*sizeof(TgHipAuxPixel), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->dAux.get(), npixels*sizeof(TgHipAuxPixel), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TGHIP_OK;
 }
@@ -1572,8 +1263,8 @@ int tghip_upload_aux(tghip_ctx *ctx, const TgHipAuxPixel *in, size_t npixels)
     int rc = tghip_wait(ctx);
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->dAux) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->dAux), npixels*sizeof(TgHipAuxPixel)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dAux, in, npixels*sizeof(TgHipAuxPixel), hipMemcpyHostToDevice, ctx->stream));
+    if (!ctx->dAux && (rc = ctx->dAux.grow(ctx, npixels)) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dAux.get(), in, npixels*sizeof(TgHipAuxPixel), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TGHIP_OK;
 }
@@ -1585,7 +1276,7 @@ int tghip_download_samples(tghip_ctx *ctx, float *rgb, size_t nfloats)
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     if (!rgb || !ctx->dSamples || nfloats != ctx->samplesFloats) { ctx->error = "no TGHIP_PASS_SAMPLES pass of that size has been rendered"; return TGHIP_E_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(rgb, ctx->dSamples, nfloats*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rgb, ctx->dSamples.get(), nfloats*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TGHIP_OK;
 }
@@ -1605,42 +1296,29 @@ int tghip_develop(tghip_ctx *ctx, const TgHipDevelopDesc *desc, float *hdr_out, 
     int rc = tghip_wait(ctx);
     if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
     if (!frame && !ctx->dAux) { ctx->error = "tghip_develop: no auxiliary output buffers yet (no TGHIP_PASS_AUX pass, no tghip_upload_aux)"; return TGHIP_E_INVALID; }
-    const float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    const uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
+    const float *sum = ctx->frameSum();
+    const uint32_t *cnt = ctx->frameCount();
     if (frame && ((reinterpret_cast<uintptr_t>(sum) | reinterpret_cast<uintptr_t>(cnt)) & 15u)) { ctx->error = "tghip_develop: the bound framebuffer is not 16-byte aligned"; return TGHIP_E_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t hdrFloats = npixels*(frame || (desc->source != TGHIP_AUX_DEPTH && desc->source != TGHIP_AUX_VISIBILITY) ? 3 : 1);
-    float *hdr = hdr_out;
-    uint8_t *ldr = ldr_out;
-    if (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) {
-        if ((reinterpret_cast<uintptr_t>(hdr) & 15u) || (reinterpret_cast<uintptr_t>(ldr) & 3u)) { ctx->error = "tghip_develop: device outputs must be aligned (hdr_out to 16 bytes, ldr_out to 4)"; return TGHIP_E_INVALID; }
-    } else {
-        int grc;
-        if (hdr_out && (grc = growArray(ctx, ctx->developHdr, ctx->developHdrCap, hdrFloats)) != TGHIP_OK) return grc;
-        if (ldr_out && (grc = growArray(ctx, ctx->developLdr, ctx->developLdrCap, npixels*3)) != TGHIP_OK) return grc;
-        hdr = hdr_out ? ctx->developHdr : nullptr;
-        ldr = ldr_out ? ctx->developLdr : nullptr;
-    }
-    if (!ctx->developMax) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developMax), 64));
-    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
-    if (frame) HIP_TRY(ctx, developLaunchFrame(ctx->stream, sum, cnt, npixels, desc->tonemap, hdr, ldr));
-    else HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux, npixels, desc->source, desc->part, hdr, ldr, ctx->developMax));
-    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
-    if (hdr_out && hdr != hdr_out) HIP_TRY(ctx, hipMemcpyAsync(hdr_out, hdr, hdrFloats*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (ldr_out && ldr != ldr_out) HIP_TRY(ctx, hipMemcpyAsync(ldr_out, ldr, npixels*3, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
-    ctx->developMs = ms;
-    return TGHIP_OK;
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    if (device && ((reinterpret_cast<uintptr_t>(hdr_out) & 15u) || (reinterpret_cast<uintptr_t>(ldr_out) & 3u))) { ctx->error = "tghip_develop: device outputs must be aligned (hdr_out to 16 bytes, ldr_out to 4)"; return TGHIP_E_INVALID; }
+    float *hdr = nullptr;
+    uint8_t *ldr = nullptr;
+    if ((rc = stageOutput(ctx, device, hdr_out, hdrFloats*sizeof(float), ctx->developHdr, hdr)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, ldr_out, npixels*3, ctx->developLdr, ldr)) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, ctx->developMax.once(16));
+    return timedLaunches(ctx, ctx->developMs, [&]() -> int {
+        if (frame) HIP_TRY(ctx, developLaunchFrame(ctx->stream, sum, cnt, npixels, desc->tonemap, hdr, ldr));
+        else HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux.get(), npixels, desc->source, desc->part, hdr, ldr, ctx->developMax.get()));
+        return TGHIP_OK;
+    }, [&]() -> int {
+        const int crc = copyBack(ctx, hdr_out, hdr, hdrFloats*sizeof(float));
+        return crc != TGHIP_OK ? crc : copyBack(ctx, ldr_out, ldr, npixels*3);
+    });
 }
 
-int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms)
-{
-    if (!ctx || !ms) return TGHIP_E_INVALID;
-    *ms = ctx->developMs;
-    return TGHIP_OK;
-}
+int tghip_develop_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::developMs, ms); }
 
 int tghip_nlmeans(tghip_ctx *ctx, const TgHipNlMeansDesc *desc, const float *image, const float *guide, const float *variance, float *out)
 {
@@ -1674,148 +1352,27 @@ int tghip_nlmeans(tghip_ctx *ctx, const TgHipNlMeansDesc *desc, const float *ima
     const size_t npixels = size_t(desc->width)*desc->height, nfloats = npixels*channels, nbytes = nfloats*sizeof(float);
     // scratch planes 0..2: image, guide, variance (uploaded, or developed from the aux buffers); 3: the result of a call with host memory
     const float *in[3] = {image, guide, variance};
-    float *result = out;
-    for (int b = 0; b < 4; ++b) {
-        const bool needed = b < 3 ? (!pointers || !device) : !device;
-        int grc;
-        if (needed && (grc = growArray(ctx, ctx->nlmBuf[b], ctx->nlmCap[b], nfloats)) != TGHIP_OK) return grc;
+    float *result = nullptr;
+    for (int b = 0; b < 3; ++b) {
+        if (pointers) rc = stageInput(ctx, device, in[b], nbytes, ctx->nlmBuf[b], in[b]);
+        else { rc = ctx->nlmBuf[b].grow(ctx, nfloats); in[b] = ctx->nlmBuf[b].get(); }   // (developed below)
+        if (rc != TGHIP_OK) return rc;
     }
-    if (pointers && !device)
-        for (int b = 0; b < 3; ++b) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->nlmBuf[b], in[b], nbytes, hipMemcpyHostToDevice, ctx->stream));
-            in[b] = ctx->nlmBuf[b];
+    if ((rc = stageOutput(ctx, device, out, nbytes, ctx->nlmBuf[3], result)) != TGHIP_OK) return rc;
+    return timedLaunches(ctx, ctx->nlmMs, [&]() -> int {
+        if (!pointers) {
+            HIP_TRY(ctx, ctx->developMax.once(16));
+            const uint32_t parts[3] = {desc->image_part, desc->guide_part, TGHIP_DEVELOP_VARIANCE};
+            for (int b = 0; b < 3; ++b)
+                HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux.get(), npixels, desc->source, parts[b], ctx->nlmBuf[b].get(), nullptr, ctx->developMax.get()));
         }
-    if (!device) result = ctx->nlmBuf[3];
-    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
-    if (!pointers) {
-        if (!ctx->developMax) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->developMax), 64));
-        const uint32_t parts[3] = {desc->image_part, desc->guide_part, TGHIP_DEVELOP_VARIANCE};
-        for (int b = 0; b < 3; ++b) {
-            HIP_TRY(ctx, developLaunchAux(ctx->stream, ctx->dAux, npixels, desc->source, parts[b], ctx->nlmBuf[b], nullptr, ctx->developMax));
-            in[b] = ctx->nlmBuf[b];
-        }
-    }
-    HIP_TRY(ctx, nlMeansLaunch(ctx->stream, in[0], in[1], in[2], result, desc->width, desc->height, channels, desc->F, desc->R, desc->k,
-                               desc->variance_scale, ctx->nlmBatch));
-    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
-    if (result != out) HIP_TRY(ctx, hipMemcpyAsync(out, result, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
-    ctx->nlmMs = ms;
-    return TGHIP_OK;
+        HIP_TRY(ctx, nlMeansLaunch(ctx->stream, in[0], in[1], in[2], result, desc->width, desc->height, channels, desc->F, desc->R, desc->k,
+                                   desc->variance_scale, ctx->nlmBatch));
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, out, result, nbytes); });
 }
 
-int tghip_nlmeans_kernel_time(tghip_ctx *ctx, double *ms)
-{
-    if (!ctx || !ms) return TGHIP_E_INVALID;
-    *ms = ctx->nlmMs;
-    return TGHIP_OK;
-}
-
-extern "C++" {
-namespace {
-// RCCL through dlopen: single-GPU users of this library never load it
-struct RcclApi {
-    std::mutex mutex;
-    bool tried = false;
-    void *lib = nullptr;
-    decltype(&ncclCommInitAll) commInitAll = nullptr;
-    decltype(&ncclGetUniqueId) getUniqueId = nullptr;
-    decltype(&ncclCommInitRank) commInitRank = nullptr;
-    decltype(&ncclCommDestroy) commDestroy = nullptr;
-    decltype(&ncclReduce) reduce = nullptr;
-    decltype(&ncclGroupStart) groupStart = nullptr;
-    decltype(&ncclGroupEnd) groupEnd = nullptr;
-    decltype(&ncclGetErrorString) errorString = nullptr;
-    std::map<std::vector<int>, std::vector<ncclComm_t>> comms;   // one communicator set per device list, kept for the life of the process
-    bool load()
-    {
-        if (tried) return lib != nullptr;
-        tried = true;
-        // An RCCL the process already has comes first (RTLD_NOLOAD matches by SONAME): a host program that brought its own -- PyTorch-ROCm ships
-        // one next to libtorch -- and this library must not end up with two copies whose exported symbols resolve into each other.
-        lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-        if (!lib) lib = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-        if (!lib) lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-        if (!lib) return false;
-        commInitAll = reinterpret_cast<decltype(commInitAll)>(dlsym(lib, "ncclCommInitAll"));
-        reduce = reinterpret_cast<decltype(reduce)>(dlsym(lib, "ncclReduce"));
-        groupStart = reinterpret_cast<decltype(groupStart)>(dlsym(lib, "ncclGroupStart"));
-        groupEnd = reinterpret_cast<decltype(groupEnd)>(dlsym(lib, "ncclGroupEnd"));
-        errorString = reinterpret_cast<decltype(errorString)>(dlsym(lib, "ncclGetErrorString"));
-        getUniqueId = reinterpret_cast<decltype(getUniqueId)>(dlsym(lib, "ncclGetUniqueId"));
-        commInitRank = reinterpret_cast<decltype(commInitRank)>(dlsym(lib, "ncclCommInitRank"));
-        commDestroy = reinterpret_cast<decltype(commDestroy)>(dlsym(lib, "ncclCommDestroy"));
-        if (!commInitAll || !reduce || !groupStart || !groupEnd || !errorString || !getUniqueId || !commInitRank || !commDestroy) { dlclose(lib); lib = nullptr; }
-        return lib != nullptr;
-    }
-} g_rccl;
-} // namespace
-} // extern "C++"
-
-int tghip_reduce_framebuffers(tghip_ctx *const *ctxs, int n, int root, float *rgb_sum, uint32_t *count, size_t npixels)
-{
-    if (!ctxs || n < 1 || root < 0 || root >= n) return TGHIP_E_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!ctxs[i]) return TGHIP_E_INVALID;
-    tghip_ctx *rc = ctxs[root];
-    std::vector<int> devices;
-    for (int i = 0; i < n; ++i) {
-        tghip_ctx *c = ctxs[i];
-        if (c->failReduce) { rc->error = "tghip_reduce_framebuffers: forced failure (the \"fail_reduce\" option)"; return TGHIP_E_HIP; }
-        if (!c->haveScene) { rc->error = "tghip_reduce_framebuffers: a context has no scene"; return TGHIP_E_NOSCENE; }
-        if (c->width != rc->width || c->height != rc->height) { rc->error = "tghip_reduce_framebuffers: the contexts render different images"; return TGHIP_E_INVALID; }
-        for (int d : devices)
-            if (d == c->device) { rc->error = "tghip_reduce_framebuffers: two contexts on one device (RCCL wants one rank per device; sum on the host instead)"; return TGHIP_E_UNSUPPORTED; }
-        devices.push_back(c->device);
-        int w = tghip_wait(c);
-        if (w != TGHIP_OK && w != TGHIP_E_ABORTED) return w;
-    }
-    if (npixels != size_t(rc->width)*rc->height) { rc->error = "pixel count mismatch"; return TGHIP_E_INVALID; }
-    HIP_TRY(rc, hipSetDevice(rc->device));
-    if (rc->redCap < npixels) {                  // (first call, or the context was re-uploaded with a larger image since)
-        if (rc->redSum) (void)hipFree(rc->redSum);
-        if (rc->redCount) (void)hipFree(rc->redCount);
-        rc->redSum = nullptr; rc->redCount = nullptr; rc->redCap = 0;
-        HIP_TRY(rc, hipMalloc(reinterpret_cast<void **>(&rc->redSum), npixels*3*sizeof(float)));
-        HIP_TRY(rc, hipMalloc(reinterpret_cast<void **>(&rc->redCount), npixels*sizeof(uint32_t)));
-        rc->redCap = npixels;
-    }
-
-    std::lock_guard<std::mutex> lock(g_rccl.mutex);
-    if (!g_rccl.load()) { rc->error = "tghip_reduce_framebuffers: librccl.so could not be loaded"; return TGHIP_E_UNSUPPORTED; }
-    auto ncclTry = [&](ncclResult_t r, const char *what) {
-        if (r == ncclSuccess) return true;
-        rc->error = std::string(what) + ": " + g_rccl.errorString(r);
-        return false;
-    };
-    std::vector<ncclComm_t> &comms = g_rccl.comms[devices];
-    if (comms.empty()) {
-        comms.resize(size_t(n));
-        if (!ncclTry(g_rccl.commInitAll(comms.data(), n, devices.data()), "ncclCommInitAll")) { g_rccl.comms.erase(devices); return TGHIP_E_HIP; }
-    }
-    // two reductions per rank (radiance sums, sample counts) in one group; every rank's calls run on its own stream
-    if (!ncclTry(g_rccl.groupStart(), "ncclGroupStart")) { g_rccl.comms.erase(devices); return TGHIP_E_HIP; }
-    bool ok = true;
-    for (int i = 0; i < n && ok; ++i) {
-        tghip_ctx *c = ctxs[i];
-        const float *sum = c->extSum ? c->extSum : c->fbSum;
-        const uint32_t *cnt = c->extCount ? c->extCount : c->fbCount;
-        ok = ncclTry(g_rccl.reduce(sum, i == root ? rc->redSum : nullptr, npixels*3, ncclFloat32, ncclSum, root, comms[size_t(i)], c->stream), "ncclReduce")
-          && ncclTry(g_rccl.reduce(cnt, i == root ? rc->redCount : nullptr, npixels, ncclUint32, ncclSum, root, comms[size_t(i)], c->stream), "ncclReduce");
-    }
-    if (!ncclTry(g_rccl.groupEnd(), "ncclGroupEnd") || !ok) { g_rccl.comms.erase(devices); return TGHIP_E_HIP; }   // (a communicator set that failed is not reused)
-    for (int i = 0; i < n; ++i) {
-        HIP_TRY(rc, hipSetDevice(ctxs[i]->device));
-        HIP_TRY(rc, hipStreamSynchronize(ctxs[i]->stream));
-    }
-    HIP_TRY(rc, hipSetDevice(rc->device));
-    if (rgb_sum) HIP_TRY(rc, hipMemcpyAsync(rgb_sum, rc->redSum, npixels*3*sizeof(float), hipMemcpyDeviceToHost, rc->stream));
-    if (count) HIP_TRY(rc, hipMemcpyAsync(count, rc->redCount, npixels*sizeof(uint32_t), hipMemcpyDeviceToHost, rc->stream));
-    HIP_TRY(rc, hipStreamSynchronize(rc->stream));
-    return TGHIP_OK;
-}
+int tghip_nlmeans_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::nlmMs, ms); }
 
 // the libm restatements exactly as the shading kernels call them (pt_math.h)
 __global__ void k_debug_libm(int fn, const float *x, float *y, uint32_t n)
@@ -1859,21 +1416,19 @@ int tghip_debug_libm(tghip_ctx *ctx, int fn, const float *x, float *y, size_t n)
     if (n == 0) return TGHIP_OK;
     if (!x || !y || n > 0x3FFFFFFFu || fn < TGHIP_LIBM_SINF || fn > TGHIP_LIBM_SINHF) { ctx->error = "invalid libm self-test arguments"; return TGHIP_E_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *dx = nullptr, *dy = nullptr;
+    DeviceArray<float> dx, dy;
     const bool dbl = fn >= TGHIP_LIBM_EXPD && fn <= TGHIP_LIBM_SQRTD;   // n doubles in, n doubles out
     const size_t nx = (fn == TGHIP_LIBM_ATAN2F || fn == TGHIP_LIBM_POWF || dbl) ? 2*n : n, ny = dbl ? 2*n : n;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dx), nx*sizeof(float)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dy), ny*sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(dx, x, nx*sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    HIP_TRY(ctx, dx.once(nx));
+    hipError_t e = dy.once(ny);
+    if (e == hipSuccess) e = hipMemcpyAsync(dx.get(), x, nx*sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-        if (dbl) hipLaunchKernelGGL(k_debug_libmd, dim3(uint32_t((n + 255)/256)), dim3(256), 0, ctx->stream, fn, reinterpret_cast<const double *>(dx), reinterpret_cast<double *>(dy), uint32_t(n));
-        else     hipLaunchKernelGGL(k_debug_libm, dim3(uint32_t((n + 255)/256)), dim3(256), 0, ctx->stream, fn, dx, dy, uint32_t(n));
+        if (dbl) hipLaunchKernelGGL(k_debug_libmd, dim3(uint32_t((n + 255)/256)), dim3(256), 0, ctx->stream, fn, reinterpret_cast<const double *>(dx.get()), reinterpret_cast<double *>(dy.get()), uint32_t(n));
+        else     hipLaunchKernelGGL(k_debug_libm, dim3(uint32_t((n + 255)/256)), dim3(256), 0, ctx->stream, fn, static_cast<const float *>(dx.get()), dy.get(), uint32_t(n));
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(y, dy, ny*sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(y, dy.get(), ny*sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
     return TGHIP_OK;
 }
@@ -1893,17 +1448,15 @@ int tghip_debug_bsdf(tghip_ctx *ctx, const TgHipBsdfCase *cases, TgHipBsdfResult
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    TgHipBsdfCase *dc = nullptr;
-    TgHipBsdfResult *dr = nullptr;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dc), n*sizeof(TgHipBsdfCase)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dr), n*sizeof(TgHipBsdfResult));
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, cases, n*sizeof(TgHipBsdfCase), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dr, 0, n*sizeof(TgHipBsdfResult), ctx->stream);
-    if (e == hipSuccess) e = debugBsdfLaunch(ctx->stream, ctx->scene, dc, dr, uint32_t(n), variants);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, dr, n*sizeof(TgHipBsdfResult), hipMemcpyDeviceToHost, ctx->stream);
+    DeviceArray<TgHipBsdfCase> dc;
+    DeviceArray<TgHipBsdfResult> dr;
+    HIP_TRY(ctx, dc.once(n));
+    hipError_t e = dr.once(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc.get(), cases, n*sizeof(TgHipBsdfCase), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dr.get(), 0, n*sizeof(TgHipBsdfResult), ctx->stream);
+    if (e == hipSuccess) e = debugBsdfLaunch(ctx->stream, ctx->scene, dc.get(), dr.get(), uint32_t(n), variants);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dr.get(), n*sizeof(TgHipBsdfResult), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dc);
-    if (dr) (void)hipFree(dr);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
     return TGHIP_OK;
 }
@@ -1937,17 +1490,15 @@ int tghip_debug_light(tghip_ctx *ctx, const TgHipLightCase *cases, TgHipLightRes
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    TgHipLightCase *dc = nullptr;
-    TgHipLightResult *dr = nullptr;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dc), n*sizeof(TgHipLightCase)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dr), n*sizeof(TgHipLightResult));
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, cases, n*sizeof(TgHipLightCase), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dr, 0, n*sizeof(TgHipLightResult), ctx->stream);
-    if (e == hipSuccess) e = debugLightLaunch(ctx->stream, ctx->scene, dc, dr, uint32_t(n), variants);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, dr, n*sizeof(TgHipLightResult), hipMemcpyDeviceToHost, ctx->stream);
+    DeviceArray<TgHipLightCase> dc;
+    DeviceArray<TgHipLightResult> dr;
+    HIP_TRY(ctx, dc.once(n));
+    hipError_t e = dr.once(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc.get(), cases, n*sizeof(TgHipLightCase), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dr.get(), 0, n*sizeof(TgHipLightResult), ctx->stream);
+    if (e == hipSuccess) e = debugLightLaunch(ctx->stream, ctx->scene, dc.get(), dr.get(), uint32_t(n), variants);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dr.get(), n*sizeof(TgHipLightResult), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dc);
-    if (dr) (void)hipFree(dr);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
     return TGHIP_OK;
 }
@@ -1990,92 +1541,19 @@ int tghip_debug_launch_plan(tghip_ctx *ctx, const TgHipPassDesc *pass, TgHipLaun
     return TGHIP_OK;
 }
 
-extern "C++" void tghipDestroyRankComm(void *comm)
-{
-    std::lock_guard<std::mutex> lock(g_rccl.mutex);
-    if (comm && g_rccl.load()) (void)g_rccl.commDestroy(static_cast<ncclComm_t>(comm));
-}
-
-// ---- the same reduce between PROCESSES (one process per GPU, SURVEY.md 8e: torch.distributed.run, mpirun, ...) ----
-int tghip_comm_unique_id(void *id, size_t bytes)
-{
-    static_assert(sizeof(ncclUniqueId) == TGHIP_COMM_ID_BYTES, "TGHIP_COMM_ID_BYTES");
-    if (!id || bytes < sizeof(ncclUniqueId)) return TGHIP_E_INVALID;
-    std::lock_guard<std::mutex> lock(g_rccl.mutex);
-    if (!g_rccl.load()) return TGHIP_E_UNSUPPORTED;
-    ncclUniqueId u;
-    if (g_rccl.getUniqueId(&u) != ncclSuccess) return TGHIP_E_HIP;
-    std::memcpy(id, &u, sizeof(u));
-    return TGHIP_OK;
-}
-
-int tghip_comm_init_rank(tghip_ctx *ctx, const void *id, size_t bytes, int nranks, int rank)
-{
-    if (!ctx || !id || bytes < sizeof(ncclUniqueId) || nranks < 1 || rank < 0 || rank >= nranks) return TGHIP_E_INVALID;
-    if (ctx->failReduce) { ctx->error = "tghip_comm_init_rank: forced failure (the \"fail_reduce\" option)"; return TGHIP_E_HIP; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> lock(g_rccl.mutex);
-    if (!g_rccl.load()) { ctx->error = "tghip_comm_init_rank: librccl.so could not be loaded"; return TGHIP_E_UNSUPPORTED; }
-    if (ctx->rankComm) { (void)g_rccl.commDestroy(static_cast<ncclComm_t>(ctx->rankComm)); ctx->rankComm = nullptr; }
-    ncclUniqueId u;
-    std::memcpy(&u, id, sizeof(u));
-    ncclComm_t comm = nullptr;
-    const ncclResult_t r = g_rccl.commInitRank(&comm, nranks, u, rank);
-    if (r != ncclSuccess) { ctx->error = std::string("ncclCommInitRank: ") + g_rccl.errorString(r); return TGHIP_E_HIP; }
-    ctx->rankComm = comm; ctx->rankCount = nranks; ctx->rankIndex = rank;
-    return TGHIP_OK;
-}
-
-int tghip_reduce_framebuffer_rank(tghip_ctx *ctx, int root, float *rgb_sum, uint32_t *count, size_t npixels)
-{
-    if (!ctx) return TGHIP_E_INVALID;
-    if (!ctx->haveScene) return TGHIP_E_NOSCENE;
-    if (!ctx->rankComm) { ctx->error = "tghip_reduce_framebuffer_rank: no communicator (tghip_comm_init_rank)"; return TGHIP_E_INVALID; }
-    if (root < 0 || root >= ctx->rankCount || npixels != size_t(ctx->width)*ctx->height) { ctx->error = "tghip_reduce_framebuffer_rank: root / pixel count mismatch"; return TGHIP_E_INVALID; }
-    if (ctx->failReduce) { ctx->error = "tghip_reduce_framebuffer_rank: forced failure (the \"fail_reduce\" option)"; return TGHIP_E_HIP; }
-    int w = tghip_wait(ctx);
-    if (w != TGHIP_OK && w != TGHIP_E_ABORTED) return w;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool isRoot = ctx->rankIndex == root;
-    if (isRoot && ctx->redCap < npixels) {
-        if (ctx->redSum) (void)hipFree(ctx->redSum);
-        if (ctx->redCount) (void)hipFree(ctx->redCount);
-        ctx->redSum = nullptr; ctx->redCount = nullptr; ctx->redCap = 0;
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->redSum), npixels*3*sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->redCount), npixels*sizeof(uint32_t)));
-        ctx->redCap = npixels;
-    }
-    const float *sum = ctx->extSum ? ctx->extSum : ctx->fbSum;
-    const uint32_t *cnt = ctx->extCount ? ctx->extCount : ctx->fbCount;
-    ncclComm_t comm = static_cast<ncclComm_t>(ctx->rankComm);
-    ncclResult_t r;
-    {
-        std::lock_guard<std::mutex> lock(g_rccl.mutex);
-        r = g_rccl.groupStart();
-        if (r == ncclSuccess) r = g_rccl.reduce(sum, isRoot ? ctx->redSum : nullptr, npixels*3, ncclFloat32, ncclSum, root, comm, ctx->stream);
-        if (r == ncclSuccess) r = g_rccl.reduce(cnt, isRoot ? ctx->redCount : nullptr, npixels, ncclUint32, ncclSum, root, comm, ctx->stream);
-        const ncclResult_t e = g_rccl.groupEnd();
-        if (r == ncclSuccess) r = e;
-    }
-    if (r != ncclSuccess) { ctx->error = std::string("ncclReduce: ") + g_rccl.errorString(r); return TGHIP_E_HIP; }
-    if (isRoot && rgb_sum) HIP_TRY(ctx, hipMemcpyAsync(rgb_sum, ctx->redSum, npixels*3*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (isRoot && count) HIP_TRY(ctx, hipMemcpyAsync(count, ctx->redCount, npixels*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TGHIP_OK;
-}
-
 int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_t n, int repeats, double *ms_per_launch)
 {
     if (!ctx || !ctx->haveScene) return TGHIP_E_NOSCENE;
     if (n == 0) return TGHIP_OK;
     if (!rays || !hits || n > 0x7FFFFFFFu) { ctx->error = "invalid ray batch"; return TGHIP_E_INVALID; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float4 *dRays = nullptr, *dHits = nullptr;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&dRays), n*sizeof(TgHipRay)));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dHits), n*sizeof(TgHipHit));
-    if (e != hipSuccess) { (void)hipFree(dRays); ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    DeviceArray<float4> rayMem, hitMem;          // (a ray is two float4, a hit one)
+    HIP_TRY(ctx, rayMem.once(n*sizeof(TgHipRay)/sizeof(float4)));
+    hipError_t e = hitMem.once(n*sizeof(TgHipHit)/sizeof(float4));
+    if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    float4 *dRays = rayMem.get(), *dHits = hitMem.get();
     int rc = ensurePool(ctx, ctx->poolSlots ? ctx->pool.num_slots : 256);   // the traversal statistics live in the pool
-    if (rc != TGHIP_OK) { (void)hipFree(dRays); (void)hipFree(dHits); return rc; }
+    if (rc != TGHIP_OK) return rc;
     (void)hipMemcpyAsync(dRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream);
     const int grid = int(std::min<size_t>(size_t(launchGrid(ctx)), (n + 255)/256));
     // the walk of the choice (csrc/host/LaunchChoice.cpp); the wide one keeps no queue in LDS, only its group stack
@@ -2094,7 +1572,6 @@ int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_
     e = hipStreamSynchronize(ctx->stream);
     float ms = 0.0f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->evA, ctx->evB);
-    (void)hipFree(dRays); (void)hipFree(dHits);
     if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
     if (ms_per_launch) *ms_per_launch = double(ms)/repeats;
     return TGHIP_OK;
@@ -2116,17 +1593,11 @@ int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipR
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool occluded = desc->mode == TGHIP_QUERY_OCCLUDED, device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
     const size_t outBytes = occluded ? n : n*sizeof(TgHipHit);
-    if (!ctx->queryCounter) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->queryCounter), 64));
-    const float4 *dRays = reinterpret_cast<const float4 *>(rays);
-    void *dOut = out;
-    if (!device) {
-        int grc;
-        if ((grc = growArray(ctx, ctx->queryRays, ctx->queryRaysCap, n*2)) != TGHIP_OK) return grc;
-        if ((grc = growArray(ctx, ctx->queryOut, ctx->queryOutCap, (outBytes + sizeof(float4) - 1)/sizeof(float4))) != TGHIP_OK) return grc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->queryRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream));
-        dRays = ctx->queryRays;
-        dOut = ctx->queryOut;
-    }
+    HIP_TRY(ctx, ctx->queryCounter.once(16));
+    const float4 *dRays = nullptr;
+    float4 *dOut = nullptr;
+    if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->queryOut, dOut)) != TGHIP_OK) return rc;
     // the walk tghip_trace_rays answers with on this scene, and its stack
     const LaunchChoice &choice = ctx->lp.choice;
     const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE;
@@ -2138,24 +1609,14 @@ int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipR
     const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
                                                  : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
     const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter, 0, sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
-    HIP_TRY(ctx, rayQueryLaunch(ctx->stream, ctx->scene, walk, occluded, dRays, dOut, uint32_t(n), ctx->queryCounter, blocks, refillAt, lds));
-    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
-    if (!device) HIP_TRY(ctx, hipMemcpyAsync(out, dOut, outBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0.0f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
-    ctx->queryMs = ms;
-    return TGHIP_OK;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter.get(), 0, sizeof(uint32_t), ctx->stream));
+    return timedLaunches(ctx, ctx->queryMs, [&]() -> int {
+        HIP_TRY(ctx, rayQueryLaunch(ctx->stream, ctx->scene, walk, occluded, dRays, dOut, uint32_t(n), ctx->queryCounter.get(), blocks, refillAt, lds));
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, out, dOut, outBytes); });
 }
 
-int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms)
-{
-    if (!ctx || !ms) return TGHIP_E_INVALID;
-    *ms = ctx->queryMs;
-    return TGHIP_OK;
-}
+int tghip_query_rays_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::queryMs, ms); }
 
 int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, const TgHipRay *rays, float *rgb_sum, uint32_t *count, size_t n)
 {
@@ -2178,31 +1639,25 @@ int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, con
     // the scratch: the image's framebuffer (zero: k_resolve adds), its tile seeds, the rays when they are host memory
     const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
     const size_t npix = size_t(im.width)*im.height;
-    if ((rc = growArray(ctx, ctx->radSum, ctx->radSumCap, npix*3)) != TGHIP_OK) return rc;
-    if ((rc = growArray(ctx, ctx->radCount, ctx->radCountCap, npix)) != TGHIP_OK) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->radSum, 0, npix*3*sizeof(float), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->radCount, 0, npix*sizeof(uint32_t), ctx->stream));
+    if ((rc = ctx->radSum.grow(ctx, npix*3)) != TGHIP_OK) return rc;
+    if ((rc = ctx->radCount.grow(ctx, npix)) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->radSum.get(), 0, npix*3*sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->radCount.get(), 0, npix*sizeof(uint32_t), ctx->stream));
     PassTarget target;
-    target.sum = ctx->radSum; target.count = ctx->radCount;
+    target.sum = ctx->radSum.get(); target.count = ctx->radCount.get();
     target.rayPaths = true;
     target.numRays = uint32_t(n);
     if (pass.flags & TGHIP_PASS_SOBOL) {
-        const size_t had = ctx->radTileSeedsCap;
-        if ((rc = growArray(ctx, ctx->radTileSeeds, ctx->radTileSeedsCap, size_t(plan.numTiles))) != TGHIP_OK) return rc;
-        if (ctx->radTileSeedsCap != had) ctx->radTileSeedsSet = 0;
+        bool fresh = false;
+        if ((rc = ctx->radTileSeeds.grow(ctx, size_t(plan.numTiles), &fresh)) != TGHIP_OK) return rc;
+        if (fresh) ctx->radTileSeedsSet = 0;
         if (ctx->radTileSeedsSet < plan.numTiles || ctx->radTileSeed != desc->sobol_seed) {
-            HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->radTileSeeds), int(desc->sobol_seed), size_t(plan.numTiles), ctx->stream));
+            HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctx->radTileSeeds.get()), int(desc->sobol_seed), size_t(plan.numTiles), ctx->stream));
             ctx->radTileSeedsSet = plan.numTiles; ctx->radTileSeed = desc->sobol_seed;
         }
-        target.tileSeeds = ctx->radTileSeeds;
+        target.tileSeeds = ctx->radTileSeeds.get();
     }
-    if (device) {
-        target.rays = reinterpret_cast<const float4 *>(rays);
-    } else {
-        if ((rc = growArray(ctx, ctx->radRays, ctx->radRaysCap, n*2)) != TGHIP_OK) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->radRays, rays, n*sizeof(TgHipRay), hipMemcpyHostToDevice, ctx->stream));
-        target.rays = ctx->radRays;
-    }
+    if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->radRays, target.rays)) != TGHIP_OK) return rc;
     // what the pass borrows of the context and gets back: the launch plan of the last render pass's kind (so that the next one plans nothing anew).
     // An abort request left over from an earlier pass -- tghip_wait above has honoured it -- is cleared and NOT put back, as tghip_render_pass clears
     // it where a pass begins; an abort DURING the query ends the query like a pass (TGHIP_E_ABORTED) and stays set until the next pass or query.
@@ -2213,29 +1668,19 @@ int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, con
     ctx->lp = lpBefore;
     ctx->radMs = ctx->counters.ms_total - msTotalBefore;
     if (rc != TGHIP_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
-    if (device) {
-        HIP_TRY(ctx, radianceQueryLaunchResults(ctx->stream, ctx->radSum, ctx->radCount, rgb_sum, count, uint32_t(n)));
-    } else {                                     // (the first n pixels of the image are the n rays)
-        HIP_TRY(ctx, hipMemcpyAsync(rgb_sum, ctx->radSum, n*3*sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (count) HIP_TRY(ctx, hipMemcpyAsync(count, ctx->radCount, n*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (device) {
-        float ms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evA, ctx->evB));
-        ctx->radMs += double(ms);
-    }
-    return TGHIP_OK;
+    // the answers: a launch into the caller's device memory, whose time counts with the pass's, or copies of the image's first n pixels -- the n rays
+    double msCopy = 0.0;
+    rc = timedLaunches(ctx, msCopy, [&]() -> int {
+        if (device) HIP_TRY(ctx, radianceQueryLaunchResults(ctx->stream, ctx->radSum.get(), ctx->radCount.get(), rgb_sum, count, uint32_t(n)));
+        if (device) return TGHIP_OK;
+        const int crc = copyBack(ctx, rgb_sum, ctx->radSum.get(), n*3*sizeof(float));
+        return crc != TGHIP_OK ? crc : copyBack(ctx, count, ctx->radCount.get(), n*sizeof(uint32_t));
+    }, []() { return TGHIP_OK; });
+    if (rc == TGHIP_OK && device) ctx->radMs += msCopy;
+    return rc;
 }
 
-int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms)
-{
-    if (!ctx || !ms) return TGHIP_E_INVALID;
-    *ms = ctx->radMs;
-    return TGHIP_OK;
-}
+int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::radMs, ms); }
 
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out)
 {
