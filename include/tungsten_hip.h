@@ -16,6 +16,8 @@
  *   tghip_download_framebuffer <- OutputBuffer<Vec3f>::addSample / operator[] (cameras/OutputBuffer.hpp:104-144).
  *   tghip_trace_rays        <- TraceableScene::intersect (renderer/TraceableScene.hpp:170-192), batched.
  *   tghip_query_rays        <- TraceableScene::intersect and ::occluded (renderer/TraceableScene.hpp:170-223), batched, on host or device memory.
+ *   tghip_query_surface     <- TraceableScene::intersect + Primitive::intersectionInfo (renderer/TraceableScene.hpp:170-192), the albedo and emission
+ *                              of PathTracer.cpp:83-88 and TraceableScene::intersectInfinites (:194-209) for a miss, batched, on host or device memory.
  *   tghip_reduce_framebuffers <- the merge of per-machine partial renders the reference does offline on the host
  *                              (src/hdrmanip/hdrmanip.cpp:69-112: load N HDR images, add, divide); here the tile shards of
  *                              one frame, summed on the device side by RCCL over xGMI.
@@ -704,6 +706,49 @@ int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, con
 /* Instrumentation: HIP-event time of the launches of the context's last tghip_query_radiance -- the pass and the copy of its answers --, in
  * milliseconds (profiles/radiance_query/bench.txt) */
 int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms);
+/* What is at the closest hit of caller-supplied rays: position, geometric and shading normal, texture coordinates, primitive, instance and material, the
+ * material's albedo and the emitted radiance -- the question between tghip_query_rays (where) and tghip_query_radiance (what arrives).  Two launches
+ * on the context's stream (csrc/hip/surface_query.hip): tghip_query_rays' closest-hit walk, which keeps the hit and the instance it was reached
+ * through in scratch of the context, and a dense launch, one lane per ray, that describes the hit and writes the answer.
+ *   the hit      rec and t are bit for bit what tghip_query_rays (TGHIP_QUERY_CLOSEST) returns for the same ray on the same context, in every kind of
+ *                scene and at the edge of [tmin, tmax) alike: the walk is that call's.
+ *   its fields   ng, ns, uv: IntersectionInfo::Ng, ::Ns, ::uv of the primitive (Primitive::intersectionInfo; through an instance the normals rotated to
+ *                world space, primitives/Instance.cpp:337-346) -- the primitive's own values, the ones the normal output buffer records: nothing is
+ *                flipped for two-sided shading, no bump map is applied.  p = ray.o + ray.d*t in float32, unfused (TraceableScene.hpp:184), for an
+ *                instanced hit too.  albedo = (*bsdf->albedo())[info] as PathTracer.cpp:83-88 takes it: a `transparency` material gives its base's.
+ *                emission = Primitive::evalDirect at the hit when the primitive is emissive (zero from its back side), else zero.  object: the
+ *                primitive, for an instanced hit the `instances` object; bsdf: the global index of the hit's material; instance: the record index of
+ *                the TGHIP_REC_INSTANCE record the hit was reached through, -1 = none.
+ *   a miss       rec, instance, object and bsdf are -1 and every other word is zero -- unless TraceableScene::intersectInfinites
+ *                (TraceableScene.hpp:194-209) finds an emitter along d (the last infinite light wins; a cap only inside its angle): then flags =
+ *                TGHIP_SURFACE_INFINITE, object is the emitter, uv its direction's (0, 0 for a cap) and emission its texture there.
+ *   arithmetic   one instantiation under the all-features family's mask (every record kind and texture type, the reference's tie rule on a cube's
+ *                edges): an answer never depends on which shading family the scene's passes use.
+ *   memory       flags 0: rays and out are host memory, staged through buffers of the context that only grow; TGHIP_DEVELOP_DEVICE_POINTERS: both are
+ *                memory of the context's device, 16-byte aligned.  Nothing is allocated per call once the scratch has grown.
+ * Runs on the context's stream, waits for a running pass like tghip_query_rays, returns when the answers are complete and leaves the framebuffer, the
+ * SampleRecords, the auxiliary and the per-sample buffers as they were.  "query_blocks" and "query_refill_at" steer the walk as they steer
+ * tghip_query_rays' and never change an answer.  A ray with a non-finite component or a zero direction gets an unspecified answer; the call returns.
+ * n == 0 succeeds.  TGHIP_E_NOSCENE without an upload.  TGHIP_E_INVALID, the context still usable (tghip_last_error says which): no description, NULL
+ * rays or out with n > 0, unknown flag bits, non-zero reserved words, n > 2^31 - 1, misaligned device pointers (tungsten_host.h:
+ * tgh_query_surface_check is the same check on its own). */
+#define TGHIP_SURFACE_HIT       1u   /* a finite primitive was hit: every field below is filled */
+#define TGHIP_SURFACE_BACK_SIDE 2u   /* IntersectionTemporary's back-side answer of the primitive (Info::backSide) */
+#define TGHIP_SURFACE_EMISSIVE  4u   /* the primitive hit has an emission (Primitive::isEmissive) */
+#define TGHIP_SURFACE_INFINITE  8u   /* no hit; an infinite emitter lies along the ray: object, uv, emission are its */
+typedef struct TgHipSurface {
+    float p[3];   float t;           /* ray.o + ray.d*t (TraceableScene.hpp:184), float32, unfused */
+    float ng[3];  int32_t rec;       /* IntersectionInfo::Ng; the record, as TgHipHit::rec */
+    float ns[3];  int32_t instance;  /* IntersectionInfo::Ns; record index of the TGHIP_REC_INSTANCE record the hit was reached through, -1 = none */
+    float uv[2];  int32_t object, bsdf;   /* IntersectionInfo::uv; the primitive (for an instanced hit the `instances` object); global bsdf index */
+    float albedo[3];   uint32_t flags;
+    float emission[3]; uint32_t reserved; /* 0 */
+} TgHipSurface;                      /* 96 B */
+typedef struct TgHipSurfaceQueryDesc { uint32_t flags, reserved[3]; } TgHipSurfaceQueryDesc;   /* flags: TGHIP_DEVELOP_DEVICE_POINTERS */
+int tghip_query_surface(tghip_ctx *ctx, const TgHipSurfaceQueryDesc *desc, const TgHipRay *rays, TgHipSurface *out, size_t n);
+/* Instrumentation: HIP-event time of the two launches of the context's last tghip_query_surface, in milliseconds; with the option
+ * "surface_time_stage" = 1 that of its dense launch alone (profiles/surface_query/bench.txt).  The option changes no answer. */
+int tghip_query_surface_kernel_time(tghip_ctx *ctx, double *ms);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

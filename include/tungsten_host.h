@@ -249,6 +249,10 @@ int tgh_query_rays_check(const TgHipRayQueryDesc *desc, const void *rays, const 
 int tgh_query_radiance_check(const TgHipRadianceQueryDesc *desc, const void *rays, const void *rgb_sum, const void *count, size_t n, int scene_has_sobol,
                              char *err, size_t errlen);
 
+/* What tghip_query_surface decides about a call before it touches the device (csrc/host/SurfaceQuery.cpp), on its own, no device and no scene: TGHIP_OK,
+ * or TGHIP_E_INVALID and in `err` the refusal's message.  Only the pointers' values are looked at, nothing is read through them. */
+int tgh_query_surface_check(const TgHipSurfaceQueryDesc *desc, const void *rays, const void *out, size_t n, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

@@ -33,6 +33,10 @@ LIGHT_RESULT_DTYPE = np.dtype([("chosen", np.int32), ("choose_weight", np.float3
                                ("pdf", np.float32), ("approx", np.float32), ("hit", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
                                ("back_side", np.uint32), ("emission", np.float32, 3), ("direct_pdf", np.float32), ("choose_next", np.float32),
                                ("sample_next", np.float32), ("reserved", np.uint32, 4)])
+# capi.TgHipSurface (Renderer.query_surface)
+SURFACE_DTYPE = np.dtype([("p", np.float32, 3), ("t", np.float32), ("ng", np.float32, 3), ("rec", np.int32), ("ns", np.float32, 3), ("instance", np.int32),
+                          ("uv", np.float32, 2), ("object", np.int32), ("bsdf", np.int32), ("albedo", np.float32, 3), ("flags", np.uint32),
+                          ("emission", np.float32, 3), ("reserved", np.uint32)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 QUERY_MODE_NAMES = ("closest", "occluded")                                  # capi.TGHIP_QUERY_*
@@ -225,6 +229,35 @@ class Renderer(object):
         desc = self._radiance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, spp_begin, spp_end, seed, sobol_seed)
         ctx = self.context(device)
         if lib.tghip_query_radiance(ctx, C.byref(desc), rays.data_ptr(), out_sum.data_ptr(), out_count.data_ptr(), n) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+
+    def query_surface(self, rays, device=0):
+        """What is at the closest hit of every ray (tghip_query_surface): rays [N,8] float32 (o, tmin, d, tmax) -> a structured array [N] of
+        SURFACE_DTYPE: position, t, geometric and shading normal, record, instance, uv, object, bsdf, albedo, flags (capi.TGHIP_SURFACE_*) and
+        emission; for a miss the infinite emitter along the ray, if there is one."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.empty(rays.shape[0], SURFACE_DTYPE)
+        desc = capi.TgHipSurfaceQueryDesc(0)
+        ctx = self.context(device)
+        if lib.tghip_query_surface(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def query_surface_into(self, rays, out, device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 24
+        elements -- the words of SURFACE_DTYPE, the integer ones as their bits --, both contiguous.  The answers are complete when the call
+        returns."""
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        for name, t, size in (("rays", rays, 8), ("out", out, 24)):
+            if str(t.dtype) != "torch.float32":
+                raise TungstenError("query_surface_into: %s must be torch.float32, not %s" % (name, t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("query_surface_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("query_surface_into: rays must be contiguous [N, 8] and out contiguous with N x 24 elements")
+        desc = capi.TgHipSurfaceQueryDesc(capi.TGHIP_DEVELOP_DEVICE_POINTERS)
+        ctx = self.context(device)
+        if lib.tghip_query_surface(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
             raise TungstenError(lib.tghip_last_error(ctx).decode())
 
     def debug_libm(self, fn, x, device=0):

@@ -214,6 +214,18 @@ class TgHipRadianceQueryDesc(C.Structure):
     _fields_ = [("flags", u32), ("seed", u32), ("spp_begin", u32), ("spp_end", u32), ("sobol_seed", u32), ("reserved", u32*3)]
 
 
+TGHIP_SURFACE_HIT, TGHIP_SURFACE_BACK_SIDE, TGHIP_SURFACE_EMISSIVE, TGHIP_SURFACE_INFINITE = 1, 2, 4, 8
+
+
+class TgHipSurface(C.Structure):
+    _fields_ = [("p", f32*3), ("t", f32), ("ng", f32*3), ("rec", i32), ("ns", f32*3), ("instance", i32), ("uv", f32*2), ("object", i32), ("bsdf", i32),
+                ("albedo", f32*3), ("flags", u32), ("emission", f32*3), ("reserved", u32)]
+
+
+class TgHipSurfaceQueryDesc(C.Structure):
+    _fields_ = [("flags", u32), ("reserved", u32*3)]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -322,6 +334,8 @@ PROTOTYPES = {
     "tghip_query_rays_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_query_radiance": (C.c_int, [VP, C.POINTER(TgHipRadianceQueryDesc), VP, VP, VP, C.c_size_t]),
     "tghip_query_radiance_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_query_surface": (C.c_int, [VP, C.POINTER(TgHipSurfaceQueryDesc), VP, VP, C.c_size_t]),
+    "tghip_query_surface_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -399,6 +413,7 @@ PROTOTYPES = {
     "tgh_pass_plan_free": (None, [VP]),
     "tgh_query_rays_check": (C.c_int, [C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_query_radiance_check": (C.c_int, [C.POINTER(TgHipRadianceQueryDesc), VP, VP, VP, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]),
+    "tgh_query_surface_check": (C.c_int, [C.POINTER(TgHipSurfaceQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

@@ -151,6 +151,14 @@ struct tghip_ctx {
     size_t radTileSeedsSet = 0;
     uint32_t radTileSeed = 0;
     double radMs = 0.0;
+    // tghip_query_surface: per ray the hit its walk left and -- instanced scenes -- the instance it was reached through, the answers on the device when
+    // the caller's are host memory (all grown on demand; the counter, the staged rays and the two options are tghip_query_rays'), the event between
+    // the two launches, their time and the dense launch's share of it, the "surface_time_stage" option (1: the getter answers with the share)
+    DeviceArray<float4> surfHits, surfOut;
+    DeviceArray<int> surfInst;
+    hipEvent_t evSurfMid = nullptr;
+    double surfMs = 0.0, surfDenseMs = 0.0;
+    bool surfTimeDense = false;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context (tghipDestroyRankComm)
     int rankCount = 0, rankIndex = 0;
     DeviceArray<float> redSum;            // the reduces (reduce.hip): where the reduced image lands when this context is the root (grown: a re-upload

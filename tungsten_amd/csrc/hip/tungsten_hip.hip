@@ -9,8 +9,10 @@
 #include "develop.h"
 #include "ray_query.h"
 #include "radiance_query.h"
+#include "surface_query.h"
 #include "../host/RayQuery.hpp"
 #include "../host/RadianceQuery.hpp"
+#include "../host/SurfaceQuery.hpp"
 
 #include <chrono>
 
@@ -473,6 +475,7 @@ tghip_ctx *tghip_create(int device_ordinal)
     ctx->launchStream = ctx->stream;
     if (e == hipSuccess) e = hipEventCreate(&ctx->evA);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evB);
+    if (e == hipSuccess) e = hipEventCreate(&ctx->evSurfMid);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&ctx->hostLive), 2*sizeof(uint32_t), hipHostMallocDefault);
     if (e == hipSuccess) e = ctx->abortFlagDev.once(16);
     if (e == hipSuccess) e = hipMemset(ctx->abortFlagDev.get(), 0, 64);
@@ -501,6 +504,7 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
     if (ctx->evA) (void)hipEventDestroy(ctx->evA);
     if (ctx->evB) (void)hipEventDestroy(ctx->evB);
+    if (ctx->evSurfMid) (void)hipEventDestroy(ctx->evSurfMid);
     for (hipEvent_t e : ctx->evPool) (void)hipEventDestroy(e);
     for (int k = 0; k < 7; ++k) if (ctx->evPart[k]) (void)hipEventDestroy(ctx->evPart[k]);
     if (ctx->evMain) (void)hipEventDestroy(ctx->evMain);
@@ -576,6 +580,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     else if (k == "nlmeans_batch") ctx->nlmBatch = uint32_t(std::min<long long>(std::max<long long>(value, 0), NLMEANS_MAX_BATCH));   // offsets box-filtered at once by tghip_nlmeans (0: the measured choice, denoise.hip)
     else if (k == "query_blocks") ctx->queryBlocks = int(std::min<long long>(std::max<long long>(value, 0), 1 << 16));       // workgroups of tghip_query_rays (0: the measured default)
     else if (k == "query_refill_at") ctx->queryRefillAt = int(std::min<long long>(std::max<long long>(value, 0), 64));   // idle lanes of a wave at which it claims rays (0: the measured default)
+    else if (k == "surface_time_stage") ctx->surfTimeDense = value == 1;   // tghip_query_surface_kernel_time: 0 = both launches, 1 = the dense one alone (instrumentation)
     else if (k == "pool_pad") { ctx->poolPad = std::max<long long>(value, 0)/16*16; dropPool(ctx); }
     else if (k == "wide_node_stride") {
         if (value != 128 && value != 80) { ctx->error = "wide_node_stride is 80 or 128"; return TGHIP_E_INVALID; }
@@ -1681,6 +1686,55 @@ int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, con
 }
 
 int tghip_query_radiance_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::radMs, ms); }
+
+int tghip_query_surface(tghip_ctx *ctx, const TgHipSurfaceQueryDesc *desc, const TgHipRay *rays, TgHipSurface *out, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    int rc = checkSurfaceQuery(desc, rays, out, n, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    if (!ctx->haveScene) { ctx->error = "tghip_query_surface before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    if (n == 0) return TGHIP_OK;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    const size_t outBytes = n*sizeof(TgHipSurface);
+    HIP_TRY(ctx, ctx->queryCounter.once(16));
+    const float4 *dRays = nullptr;
+    float4 *dOut = nullptr;
+    if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->surfOut, dOut)) != TGHIP_OK) return rc;
+    // the walk and the workgroups of tghip_query_rays on this scene, and what the walk leaves for the dense launch
+    const LaunchChoice &choice = ctx->lp.choice;
+    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
+    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
+                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
+    const size_t perWave = (n + 63)/64;
+    const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
+                                                 : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
+    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    if ((rc = ctx->surfHits.grow(ctx, n)) != TGHIP_OK) return rc;
+    if (inst && (rc = ctx->surfInst.grow(ctx, n)) != TGHIP_OK) return rc;
+    int *dInst = inst ? ctx->surfInst.get() : nullptr;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter.get(), 0, sizeof(uint32_t), ctx->stream));
+    rc = timedLaunches(ctx, ctx->surfMs, [&]() -> int {
+        HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays, ctx->surfHits.get(), dInst, uint32_t(n), ctx->queryCounter.get(), blocks, refillAt, lds));
+        HIP_TRY(ctx, hipEventRecord(ctx->evSurfMid, ctx->stream));
+        HIP_TRY(ctx, surfaceQueryLaunchDescribe(ctx->stream, ctx->scene, dRays, ctx->surfHits.get(), dInst, dOut, uint32_t(n)));
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, out, dOut, outBytes); });
+    if (rc != TGHIP_OK) return rc;
+    float dense = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&dense, ctx->evSurfMid, ctx->evB));
+    ctx->surfDenseMs = dense;
+    return TGHIP_OK;
+}
+
+int tghip_query_surface_kernel_time(tghip_ctx *ctx, double *ms)
+{
+    return kernelTime(ctx, ctx && ctx->surfTimeDense ? &tghip_ctx::surfDenseMs : &tghip_ctx::surfMs, ms);
+}
 
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out)
 {
