@@ -31,6 +31,8 @@
  *                              BSDF code on caller-supplied cases, per shading family, for the parity tests.
  *   tghip_debug_light / tghip_debug_light_info <- TraceBase::chooseLight (integrators/TraceBase.cpp:416-459) and Primitive::sampleDirect / approximateRadiance /
  *                              intersect + intersectionInfo / evalDirect / directPdf of single calls: the shading kernels' light code, the same way.
+ *   tghip_debug_medium      <- Medium::sampleDistance / transmittance (media/Medium.hpp:63-67) and PhaseFunction::eval / sample of single calls: the
+ *                              shading and shadow kernels' medium code, the same way.
  *
  * Ownership: the caller owns every host array (borrowed for the duration of the call; the
  * shim copies with hipMemcpyAsync); the shim owns device memory behind the opaque handle.
@@ -833,6 +835,41 @@ int tghip_debug_light(tghip_ctx *ctx, const TgHipLightCase *cases, TgHipLightRes
  * the bits are those of csrc/hip/pt_variants.h: FEAT_SOLIDS, FEAT_INFINITE, FEAT_BITMAP, FEAT_MESHLIGHT, FEAT_CYLINDER, the four bits of FEAT_FAMILY_ALL
  * together, FEAT_MULTILIGHT), covered = 1 when the variant's mask holds them all.  variant_mask (one word): the mask the variant's kernel is compiled for. */
 int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
+/* Self-test of the device's medium code (csrc/hip/pt_scene.h: mediumSampleDistance / mediumTransmittance / phaseEval / phaseSample) on caller-supplied
+ * cases against the uploaded scene's media, one thread per case (csrc/hip/debug_units.hip), host pointers; the calls are made as k_shade and the shadow
+ * walks make them, under the feature mask of family `variant` (no Sobol' sampler) -- which must be one that carries the media code (FEAT_MEDIA:
+ * tghip_debug_bsdf_info's variant_mask says which; today TGHIP_BSDF_VARIANT_MEDIA and TGHIP_BSDF_VARIANT_ALL).  Per case:
+ *   distance  mediumSampleDistance along the ray (p, d) up to max_t (+inf: the segment left the scene) with the medium's bounce count state_bounce
+ *             (firstScatter = state_bounce == 0), drawing from the stream (seed, stream, 0): ok (0: the path ends here), t, weight, exited, the bounce
+ *             count afterwards, and the stream's next number;
+ *   tr        mediumTransmittance of the same ray with farT = max_t for (startOnSurface, endOnSurface) = (1,1), (1,0), (0,1), (0,0);
+ *   phase     phaseEval(d, wo), then phaseSample(d) drawing from the stream (seed, stream, 1): w, pdf and the stream's next number.
+ * Outputs behind a refused sampleDistance are unspecified.  TGHIP_E_INVALID (context left usable, nothing launched) for null pointers with n > 0, a
+ * medium index outside TgHipSceneDesc::media, an index that names an operand entry of an `interpolated` medium (no medium of the scene: the entries
+ * behind it do not exist for it to interpolate), a variant that is unknown or lacks the media code, a scene without media, or no scene; n == 0 succeeds
+ * and launches nothing, as for the sibling entries. */
+typedef struct TgHipMediumCase {
+    int32_t  medium;          /* index in TgHipSceneDesc::media */
+    uint32_t variant;         /* TGHIP_BSDF_VARIANT_* */
+    uint32_t seed, stream;    /* the samplers: rngStart(seed, stream, 0) and (seed, stream, 1) */
+    uint32_t state_bounce;    /* MediumState::bounce before the call */
+    float    p[3], d[3];      /* the ray: origin, unit direction */
+    float    max_t;           /* its far end; +inf allowed */
+    float    wo[3];           /* a second unit direction, for phaseEval */
+    uint32_t reserved;
+} TgHipMediumCase;            /* 64 B */
+typedef struct TgHipMediumResult {
+    uint32_t ok;              /* mediumSampleDistance's return */
+    float    t, weight[3];
+    uint32_t exited;
+    uint32_t bounce_after;
+    float    tr[4][3];        /* [2*!startOnSurface + !endOnSurface][channel] */
+    float    phase_f;
+    float    w[3], phase_pdf;
+    float    dist_next, phase_next;   /* the two streams' next numbers after the calls returned */
+    uint32_t reserved[2];
+} TgHipMediumResult;          /* 112 B */
+int tghip_debug_medium(tghip_ctx *ctx, const TgHipMediumCase *cases, TgHipMediumResult *results, size_t n);
 /* Which kernels a pass runs on a scene, as the context decides it once per upload, option and kind of pass (csrc/host/LaunchChoice.cpp; tungsten_host.h:
  * tgh_launch_choice answers the same without a device and documents the fields). */
 #define TGHIP_KERNEL_NAME_LEN 80

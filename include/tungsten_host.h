@@ -188,6 +188,9 @@ int tgh_scene_check(const TgHipSceneDesc *scene, TgHostSceneTraits *out /* may b
  * (csrc/host/SceneCheck.cpp: lightNeeds) and whether the mask of shading family `variant` (TGHIP_BSDF_VARIANT_*, without the Sobol' sampler's bit) holds
  * them; variant_mask: that mask.  Any output pointer may be NULL.  TGHIP_E_INVALID for no scene, an unknown variant or a description tgh_scene_check refuses. */
 int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, uint32_t *covered, uint32_t *variant_mask);
+/* What tghip_debug_medium decides about a call before it launches anything (tungsten_hip.h), on its own, no device: TGHIP_OK, or TGHIP_E_INVALID with
+ * the refusal in err (csrc/host/SceneCheck.cpp: checkMediumCases).  Also TGHIP_E_INVALID for no scene or a description tgh_scene_check refuses. */
+int tgh_medium_cases_check(const TgHipSceneDesc *scene, const TgHipMediumCase *cases, const TgHipMediumResult *results, size_t n, char *err, size_t errlen);
 
 /* Which kernels a pass runs on a scene (csrc/host/LaunchChoice.cpp), on its own, no device: the choice tghip_wait makes for a pass with the flags `pass_flags`
  * (TGHIP_PASS_*), short or not (TgHostPassPlan::short_batch), under the options keys[i] = values[i] (tghip_set_option's keys; "count_traversal" among them)

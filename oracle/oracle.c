@@ -4708,6 +4708,56 @@ void oracle_light_cases(const TgHipSceneDesc *s, int n, const int32_t *light, co
     }
 }
 
+/* The medium calls of the path tracer on n caller-supplied cases (tests/medium_cases.py), as the device's tghip_debug_medium makes them: per case the
+ * medium (index into s->media; never an operand entry of an interpolated one), MediumState::bounce before the call (firstScatter = bounce == 0), a ray
+ * (p, unit d, farT = max_t, which may be +inf) and a second unit direction wo; nxd replay numbers for sampleDistance and nxp for the phase sample.
+ * out: 26 words per case, the layout of TgHipMediumResult's first 24 and of ref_harness medium-cases --
+ *   ok, t, weight[3], exited, bounce_after | tr[4][3]: transmittance(ray, startOnSurface, endOnSurface) for (1,1), (1,0), (0,1), (0,0) |
+ *   phase_f = eval(d, wo) | w[3], phase_pdf of sample(d) | numbers consumed by sampleDistance, by the phase sample.
+ * Words behind a refused sampleDistance ("the path ends here") are zero. */
+void oracle_medium_cases(const TgHipSceneDesc *s, int n, const int32_t *medium, const int32_t *state_bounce, const float *p, const float *d,
+                         const float *max_t, const float *wo, const float *xi_dist, int nxd, const float *xi_phase, int nxp, uint32_t *out)
+{
+    #pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; ++i) {
+        union { float f; uint32_t u; int32_t i; } r[26];
+        memset(r, 0, sizeof(r));
+        uint32_t *o = out + 26*(size_t)i;
+        if (medium[i] < 0 || (uint32_t)medium[i] >= s->num_media) { memcpy(o, r, sizeof(r)); continue; }
+        const TgHipMedium *m = &s->media[medium[i]];
+        Ray ray = {ld3(p + 3*(size_t)i), ld3(d + 3*(size_t)i), 0.0f, max_t[i]};
+        const v3 wwo = ld3(wo + 3*(size_t)i);
+        Sampler smp;
+        memset(&smp, 0, sizeof(smp));
+        smp.replay = xi_dist + (size_t)nxd*(size_t)i; smp.replay_n = nxd;
+        MediumState state = {state_bounce[i] == 0, state_bounce[i]};
+        MediumSample ms;
+        memset(&ms, 0, sizeof(ms));
+        if (medium_sampleDistance(s, medium[i], &smp, &ray, &state, &ms)) {
+            r[0].u = 1u;
+            r[1].f = ms.t;
+            r[2].f = ms.weight.x; r[3].f = ms.weight.y; r[4].f = ms.weight.z;
+            r[5].u = ms.exited ? 1u : 0u;
+            r[6].i = state.bounce;
+        }
+        r[24].u = (uint32_t)smp.replay_pos;
+        for (int k = 0; k < 4; ++k) {
+            v3 tr = medium_transmittance(s, medium[i], &ray, ray.tmax, k < 2, (k & 1) == 0);
+            r[7 + 3*k].f = tr.x; r[8 + 3*k].f = tr.y; r[9 + 3*k].f = tr.z;
+        }
+        r[19].f = phase_eval(m, ray.d, wwo);
+        Sampler smp2;
+        memset(&smp2, 0, sizeof(smp2));
+        smp2.replay = xi_phase + (size_t)nxp*(size_t)i; smp2.replay_n = nxp;
+        v3 w = vs(0.0f);
+        float pdf = 0.0f;
+        phase_sample(m, &smp2, ray.d, &w, &pdf);
+        r[20].f = w.x; r[21].f = w.y; r[22].f = w.z; r[23].f = pdf;
+        r[25].u = (uint32_t)smp2.replay_pos;
+        memcpy(o, r, sizeof(r));
+    }
+}
+
 void oracle_texture_eval(const TgHipSceneDesc *s, int tex, float u, float v, float *rgb)
 {
     v3 r = texture_eval(s, tex, u, v);

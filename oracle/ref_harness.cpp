@@ -28,6 +28,8 @@
 //       eval / pdf / sample of the scene's bsdfs on caller-supplied cases, raw float32 / uint32 in and out.
 //   ref_harness light-cases <scene.json> <cases.bin> <out.bin>
 //       chooseLight and sampleDirect / approximateRadiance / intersect / evalDirect / directPdf of the scene's lights on caller-supplied cases, likewise.
+//   ref_harness medium-cases <scene.json> <cases.bin> <out.bin>
+//       sampleDistance and transmittance of the scene's media and eval / sample of their phase functions on caller-supplied cases, likewise.
 //
 // Nothing here is copied from the reference; it only calls its public classes.
 #include <atomic>
@@ -73,6 +75,10 @@
 #include "primitives/InfiniteSphere.hpp"
 #include "primitives/TriangleMesh.hpp"
 #include "integrators/TraceBase.hpp"
+#include "media/Medium.hpp"
+#include "phasefunctions/PhaseFunction.hpp"
+#include "samplerecords/MediumSample.hpp"
+#include "samplerecords/PhaseSample.hpp"
 #include "renderer/TraceableScene.hpp"
 #include "sampling/PathSampleGenerator.hpp"
 #include "sampling/UniformSampler.hpp"
@@ -757,6 +763,87 @@ static int cmdLightCases(int argc, char **argv)
     return os ? 0 : 1;
 }
 
+// ref_harness medium-cases <scene.json> <cases.bin> <out.bin>: the medium calls of the path tracer on caller-supplied cases, binary in and out.
+// cases.bin: u32 n, nxd, nxp, names; `names` medium names of 64 bytes each (zero padded): the media are found in Scene::media() by name; per case
+// i32 medium (index into the names), i32 bounce (MediumState::bounce before the call; firstScatter = bounce == 0), f32 p[3], d[3], max_t (the ray's
+// farT; may be +inf), wo[3], xi_dist[nxd], xi_phase[nxp] (the numbers the two samplers replay).  out.bin: 26 words per case -- u32 ok, f32 t,
+// weight[3], u32 exited, i32 bounce afterwards (all zero where sampleDistance returned false); f32 tr[4][3] = transmittance(ray, startOnSurface,
+// endOnSurface) for (1,1), (1,0), (0,1), (0,0); f32 phase_f = eval(d, wo).x; f32 w[3], pdf of sample(d); u32 numbers consumed by sampleDistance,
+// by the phase sample -- from Medium::sampleDistance, Medium::transmittance, PhaseFunction::eval and PhaseFunction::sample
+// (tools/make_medium_golden.py -> tests/golden/medium_corners.npz).
+static int cmdMediumCases(int argc, char **argv)
+{
+    if (argc < 5) return 2;
+    ThreadUtils::startThreads(1);
+    Loaded L;
+    const uint32 seed = 0xBA5EBA11u;
+    if (!loadScene(argv[2], seed, L)) return 1;
+    std::ifstream in(argv[3], std::ios::binary);
+    uint32 header[4] = {0, 0, 0, 0};
+    in.read(reinterpret_cast<char *>(header), sizeof(header));
+    if (!in || header[1] > 64 || header[2] > 64 || header[3] > 4096) { std::fprintf(stderr, "ref_harness: bad case file\n"); return 1; }
+    const uint32 n = header[0], nxd = header[1], nxp = header[2], names = header[3];
+    std::vector<const Medium *> media;
+    for (uint32 k = 0; k < names; ++k) {
+        char name[65] = {0};
+        in.read(name, 64);
+        const Medium *found = nullptr;
+        for (const std::shared_ptr<Medium> &m : L.scene->media())
+            if (m->name() == name) found = m.get();
+        if (!in || !found) { std::fprintf(stderr, "ref_harness: the scene has no medium '%s'\n", name); return 1; }
+        media.push_back(found);
+    }
+    std::vector<uint32> out(size_t(n)*26, 0u);
+    std::vector<float> rec(12 + nxd + nxp);
+    for (uint32 c = 0; c < n; ++c) {
+        in.read(reinterpret_cast<char *>(rec.data()), std::streamsize(rec.size()*sizeof(float)));
+        if (!in) { std::fprintf(stderr, "ref_harness: case file ends at case %u\n", c); return 1; }
+        int32 mi, bounce;
+        std::memcpy(&mi, &rec[0], 4); std::memcpy(&bounce, &rec[1], 4);
+        if (mi < 0 || size_t(mi) >= media.size()) { std::fprintf(stderr, "ref_harness: case %u names medium %d\n", c, mi); return 1; }
+        const Medium &medium = *media[size_t(mi)];
+        const Vec3f p(rec[2], rec[3], rec[4]), d(rec[5], rec[6], rec[7]), wo(rec[9], rec[10], rec[11]);
+        const Ray ray(p, d, 0.0f, rec[8]);
+        float f[26] = {0.0f};
+        auto word = [&](int k, uint32 v) { std::memcpy(&f[k], &v, 4); };
+
+        GraftPathSampler sd(seed);
+        sd.setReplay(std::vector<float>(rec.begin() + 12, rec.begin() + 12 + nxd));
+        Medium::MediumState state;
+        state.reset();
+        state.component = 0;
+        state.firstScatter = bounce == 0;
+        state.bounce = bounce;
+        MediumSample ms;
+        ms.t = 0.0f; ms.weight = Vec3f(0.0f); ms.exited = false;
+        if (medium.sampleDistance(sd, ray, state, ms)) {
+            word(0, 1u);
+            f[1] = ms.t; f[2] = ms.weight.x(); f[3] = ms.weight.y(); f[4] = ms.weight.z();
+            word(5, ms.exited ? 1u : 0u);
+            word(6, uint32(state.bounce));
+        }
+        word(24, uint32(sd.consumed()));
+        for (int k = 0; k < 4; ++k) {
+            const Vec3f tr = medium.transmittance(sd, ray, k < 2, (k & 1) == 0);
+            f[7 + 3*k] = tr.x(); f[8 + 3*k] = tr.y(); f[9 + 3*k] = tr.z();
+        }
+        const PhaseFunction *phase = medium.phaseFunction(p);
+        f[19] = phase->eval(d, wo).x();
+        GraftPathSampler sp(seed);
+        sp.setReplay(std::vector<float>(rec.begin() + 12 + nxd, rec.end()));
+        PhaseSample ps;
+        ps.w = Vec3f(0.0f); ps.weight = Vec3f(0.0f); ps.pdf = 0.0f;
+        phase->sample(sp, d, ps);
+        f[20] = ps.w.x(); f[21] = ps.w.y(); f[22] = ps.w.z(); f[23] = ps.pdf;
+        word(25, uint32(sp.consumed()));
+        std::memcpy(&out[size_t(c)*26], f, sizeof(f));
+    }
+    std::ofstream os(argv[4], std::ios::binary);
+    os.write(reinterpret_cast<const char *>(out.data()), std::streamsize(out.size()*4));
+    std::fprintf(stderr, "ref_harness: %u medium cases on %zu media\n", n, media.size());
+    return os ? 0 : 1;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) {
@@ -776,6 +863,7 @@ int main(int argc, char **argv)
     else if (cmd == "bounds") rc = cmdBounds(argc, argv);
     else if (cmd == "bsdf-cases") rc = cmdBsdfCases(argc, argv);
     else if (cmd == "light-cases") rc = cmdLightCases(argc, argv);
+    else if (cmd == "medium-cases") rc = cmdMediumCases(argc, argv);
     if (rc == 2) std::fprintf(stderr, "ref_harness: bad arguments\n");
     return rc;
 }

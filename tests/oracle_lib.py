@@ -239,6 +239,25 @@ def light_cases(desc, light, p, w, xi_choose, xi_sample):
     return out
 
 
+_lib.oracle_medium_cases.argtypes = [DESC_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_int, C.c_void_p]
+
+
+def medium_cases(desc, medium, state_bounce, p, d, max_t, wo, xi_dist, xi_phase):
+    """sampleDistance, the four transmittances, the phase function's eval and sample over n cases at once: [n, 26] uint32 words -- ok, t, weight[3],
+    exited, bounce_after, tr[4][3], phase_f, w[3], phase_pdf, then the numbers sampleDistance and the phase sample consumed (the floats as bit
+    patterns) -- the layout the reference harness writes for the same cases.  medium: indices into desc.media."""
+    medium, state_bounce = np.ascontiguousarray(medium, np.int32), np.ascontiguousarray(state_bounce, np.int32)
+    p, d, max_t, wo, xi_dist, xi_phase = [np.ascontiguousarray(v, np.float32) for v in (p, d, max_t, wo, xi_dist, xi_phase)]
+    n = medium.size
+    assert p.shape == (n, 3) and d.shape == (n, 3) and wo.shape == (n, 3) and max_t.shape == (n,) and state_bounce.shape == (n,)
+    assert xi_dist.shape[0] == n and xi_phase.shape[0] == n
+    out = np.zeros((n, 26), np.uint32)
+    _lib.oracle_medium_cases(desc, n, medium.ctypes.data, state_bounce.ctypes.data, p.ctypes.data, d.ctypes.data, max_t.ctypes.data, wo.ctypes.data,
+                             xi_dist.ctypes.data, xi_dist.shape[1], xi_phase.ctypes.data, xi_phase.shape[1], out.ctypes.data)
+    return out
+
+
 def light_sample(desc, light, p, xi0, xi1):
     p = np.ascontiguousarray(p, np.float32)
     d = np.empty(3, np.float32)

@@ -1192,3 +1192,81 @@ def light_corners(tmpdir, which="all", **kw):
     kw.setdefault("resolution", (32, 18))
     kw.setdefault("spp", 2)
     return cornell(tmpdir, name=kw.pop("name", "light_corners_%s.json" % which), edit=both, **kw)
+
+
+# ---- the scene of the per-call medium comparisons (tests/medium_cases.py) ----
+_CORNER_SIGMA = {"sigma_a": [0.02, 0.03, 0.05], "sigma_s": [0.25, 0.22, 0.2]}        # the golden fog's coefficients
+
+
+def medium_corner_list():
+    """The media of scenes.medium_corners() in scene order, as (name, json).  Both loaders keep every medium the scene file lists, referenced or not
+    (the reference: Scene.cpp reads the whole `media` array and prunes nothing on load), so none of them needs a primitive; the camera sits in the first."""
+    out = []
+
+    def add(name, **kw):
+        out.append((name, dict(dict({"type": "homogeneous"}, **_CORNER_SIGMA), name=name, **kw)))
+    # homogeneous and scattering: one medium per transmittance with the parameters of test_media.TRANSMITTANCES ...
+    add("t_exponential")
+    add("t_linear", transmittance={"type": "linear", "max_t": 0.75})
+    add("t_quadratic", transmittance={"type": "quadratic", "max_t": 0.75})
+    add("t_double_exponential", transmittance={"type": "double_exponential", "sigma_a": 1.0, "sigma_b": 10.0})
+    add("t_pulse", transmittance={"type": "pulse", "min": 0.0, "max": 1.0, "num_pulses": 4})
+    add("t_erlang", transmittance={"type": "erlang", "rate": 3.0})
+    add("t_davis", transmittance={"type": "davis", "alpha": 1.6})
+    add("t_davis_weinstein", transmittance={"type": "davis_weinstein", "h": 0.8, "c": 1.2})
+    add("t_interpolated", transmittance={"type": "interpolated", "ratio": 0.35, "tr_a": {"type": "linear", "max_t": 2.0}, "tr_b": {"type": "erlang", "rate": 2.0}})
+    # ... and their corners: more and narrower pulses off the origin, davis below its clamp, davis_weinstein at beta = 0, a Dirac operand against a
+    # smooth one, two equal rates
+    add("t_pulse_7", transmittance={"type": "pulse", "min": 0.5, "max": 3.0, "num_pulses": 7})
+    add("t_davis_clamped", transmittance={"type": "davis", "alpha": 0.3})
+    add("t_davis_weinstein_half", transmittance={"type": "davis_weinstein", "h": 0.5, "c": 1.2})
+    add("t_interpolated_dirac", transmittance={"type": "interpolated", "ratio": 0.6, "tr_a": {"type": "pulse"}, "tr_b": {"type": "davis", "alpha": 1.6}})
+    add("t_double_equal", transmittance={"type": "double_exponential", "sigma_a": 2.0, "sigma_b": 2.0})
+    # absorption only
+    add("a_exponential", sigma_s=0.0)
+    add("a_linear", sigma_s=0.0, transmittance={"type": "linear", "max_t": 0.75})
+    add("a_pulse", sigma_s=0.0, transmittance={"type": "pulse", "min": 0.0, "max": 1.0, "num_pulses": 4})
+    add("a_interpolated", sigma_s=0.0, transmittance={"type": "interpolated", "ratio": 0.35, "tr_a": {"type": "linear", "max_t": 2.0}, "tr_b": {"type": "erlang", "rate": 2.0}})
+    # coefficients: a channel that never scatters, extinctions three orders of magnitude apart, a thin and a thick density
+    add("c_zero_channel", sigma_s=[0.3, 0.0, 0.2])
+    add("c_wide", sigma_a=[5e-4, 0.5, 25.0], sigma_s=[5e-4, 0.5, 25.0])
+    add("c_thin", density=0.01)
+    add("c_dense", density=40.0)
+    # the medium's own bounce limit
+    for b in (0, 1, 3):
+        add("b_%d" % b, max_bounces=b, transmittance={"type": "quadratic", "max_t": 0.75})
+    # phase functions (isotropic: every medium above)
+    add("p_rayleigh", phase_function={"type": "rayleigh"})
+    for tag, g in (("0", 0.0), ("+1e-4", 1e-4), ("-1e-4", -1e-4), ("+0.3", 0.3), ("-0.7", -0.7), ("+0.99", 0.99), ("-0.99", -0.99)):
+        add("p_hg_" + tag, phase_function={"type": "henyey_greenstein", "g": g})
+    # the exponential medium: the golden's parameters, no falloff at all, a falloff along an axis (dx == 0 exactly for rays across it), absorption only
+    add("e_golden", type="exponential", falloff_scale=1.2, unit_point=[0.0, 0.3, 0.0], falloff_direction=[0.0, 1.0, 0.2], density=1.6)
+    add("e_flat", type="exponential", falloff_scale=0.0, unit_point=[0.0, 0.3, 0.0], falloff_direction=[0.0, 1.0, 0.2])
+    add("e_axis", type="exponential", falloff_scale=0.8, unit_point=[0.0, 1.0, 0.0], falloff_direction=[0.0, -1.0, 0.0])
+    add("e_absorbing", type="exponential", sigma_a=[2.0, 0.6, 0.3], sigma_s=0.0, falloff_scale=2.0, unit_point=[0.3, 0.0, 0.3], falloff_direction=[0.0, 1.0, 0.0])
+    # the atmosphere: the golden's parameters (a centre, no pivot), a small steep ball, a wide shallow one, absorption only
+    add("h_golden", type="atmosphere", falloff_scale=0.9, radius=1.2, center=[0.1, 0.8, -0.2])
+    add("h_small", type="atmosphere", falloff_scale=3.0, radius=0.05, center=[0.1, 0.8, -0.2])
+    add("h_wide", type="atmosphere", falloff_scale=0.2, radius=5.0, center=[0.1, 0.8, -0.2])
+    add("h_absorbing", type="atmosphere", sigma_a=[2.0, 0.6, 0.3], sigma_s=0.0, falloff_scale=1.0, radius=0.3, center=[0.33, 0.3, 0.37])
+    # ... and a ball so steep (exp(-49) of the centre's density at its rim) that for a ray starting outside it erf(s t0) alone decides the argument of
+    # the inverse error function: the only way to its branches next to -1 (tests/medium_cases.py)
+    add("h_steep", type="atmosphere", falloff_scale=7.0, radius=0.5, center=[0.125, 0.75, -0.25])
+    return out
+
+
+def medium_corners(tmpdir, **kw):
+    """The Cornell box with the media of medium_corner_list() (none of them on a primitive; the camera sits in the first): the scene of the per-call
+    medium comparisons (tests/medium_cases.py)."""
+    def edit(scene):
+        scene["media"] = scene.get("media", []) + [m for _, m in medium_corner_list()]
+        scene["camera"]["medium"] = medium_corner_list()[0][0]
+    user = kw.pop("edit", None)
+
+    def both(scene):
+        edit(scene)
+        if user:
+            user(scene)
+    kw.setdefault("resolution", (32, 18))
+    kw.setdefault("spp", 2)
+    return cornell(str(tmpdir), name=kw.pop("name", "medium_corners.json"), edit=both, **kw)

@@ -44,7 +44,7 @@ def test_product_library_does_not_link_the_oracle():
 def test_ctypes_layout_matches_the_headers(tmp_path):
     structs = ["TgHipBvhNode", "TgHipWideNode", "TgHipPrimRec", "TgHipTriAttr", "TgHipObject", "TgHipBsdf", "TgHipTexture", "TgHipMedium", "TgHipCamera",
                "TgHipSettings", "TgHipSceneDesc", "TgHipPassDesc", "TgHipAuxPixel", "TgHipCounters", "TgHipRay", "TgHipHit", "TgHostSceneInfo",
-               "TgHipBsdfCase", "TgHipBsdfResult", "TgHipLightCase", "TgHipLightResult", "TgHostSceneTraits", "TgHostPassPlan", "TgHostPassBatch",
+               "TgHipBsdfCase", "TgHipBsdfResult", "TgHipLightCase", "TgHipLightResult", "TgHipMediumCase", "TgHipMediumResult", "TgHostSceneTraits", "TgHostPassPlan", "TgHostPassBatch",
                "TgHipWalkLaunch", "TgHipShadeLaunch", "TgHipShadeSize", "TgHipLaunchChoice", "TgHipLaunchPlan"]
     src = '#include <stdio.h>\n#include "tungsten_host.h"\nint main(void){\n'
     for s in structs:
@@ -115,6 +115,33 @@ def test_ctypes_layout_of_the_light_cases(tmp_path):
     assert tg.LIGHT_RESULT_DTYPE.fields["choose_next"][1] == 18*4
 
 
+def test_ctypes_layout_of_the_medium_cases(tmp_path):
+    """TgHipMediumCase / TgHipMediumResult (tghip_debug_medium): every field of the ctypes mirror and of the numpy record type at the C offset."""
+    fields = {"TgHipMediumCase": ["medium", "variant", "seed", "stream", "state_bounce", "p", "d", "max_t", "wo", "reserved"],
+              "TgHipMediumResult": ["ok", "t", "weight", "exited", "bounce_after", "tr", "phase_f", "w", "phase_pdf", "dist_next", "phase_next", "reserved"]}
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "tungsten_hip.h"\nint main(void){\n'
+    for s, names in fields.items():
+        src += 'printf("%s %%zu\\n", sizeof(%s));\n' % (s, s)
+        for n in names:
+            src += 'printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (s, n, s, n)
+    src += 'return 0;}\n'
+    c = tmp_path/"medium.c"
+    c.write_text(src)
+    exe = str(tmp_path/"medium")
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", exe])
+    got = dict(l.split() for l in subprocess.check_output([exe]).decode().splitlines())
+    for s, names in fields.items():
+        ct, dt = getattr(capi, s), {"TgHipMediumCase": tg.MEDIUM_CASE_DTYPE, "TgHipMediumResult": tg.MEDIUM_RESULT_DTYPE}[s]
+        assert int(got[s]) == C.sizeof(ct) == dt.itemsize, s
+        assert [f[0] for f in ct._fields_] == names == list(dt.names)
+        for n in names:
+            assert int(got["%s.%s" % (s, n)]) == getattr(ct, n).offset == dt.fields[n][1], (s, n)
+    # both are whole multiples of 16 bytes
+    assert C.sizeof(capi.TgHipMediumCase) == 64 and C.sizeof(capi.TgHipMediumResult) == 112
+    # the first 24 words of a result are the words the oracle and the reference harness write for the same case (tests/medium_cases.py: WORDS)
+    assert tg.MEDIUM_RESULT_DTYPE.fields["dist_next"][1] == 24*4 and tg.MEDIUM_RESULT_DTYPE.fields["tr"][1] == 7*4
+
+
 def test_error_paths_without_arguments():
     lib = tg.lib
     assert lib.tghip_upload_scene(None, None) == -1
@@ -126,6 +153,8 @@ def test_error_paths_without_arguments():
     assert lib.tghip_debug_light(None, None, None, 0) == -1
     assert lib.tghip_debug_light_info(None, 0, None, None, None) == -1
     assert lib.tgh_light_needs(None, 0, None, None, None) == -1
+    assert lib.tghip_debug_medium(None, None, None, 0) == -1
+    assert lib.tgh_medium_cases_check(None, None, None, 0, None, 0) == -1
     lib.tghip_destroy(None)   # no-op
     with pytest.raises(tg.TungstenError):
         tg.FlattenedScene("/nonexistent/scene.json")

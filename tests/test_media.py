@@ -1,6 +1,8 @@
 """Participating media: analytic properties of the homogeneous medium that hold at any size, checked on
 the oracle (CPU) and on the HIP path (gpu).  The per-sample parity with the reference is in test_oracle_golden.py /
-test_gpu_parity.py (cases cornell_fog, cornell_smoke, cornell_fog_smoke_sobol)."""
+test_gpu_parity.py (cases cornell_fog, cornell_smoke, cornell_fog_smoke_sobol); the per-CALL parity -- every sampleDistance, transmittance and
+phase-function call of the oracle against the reference's recorded answers and of the device against the oracle, word for word -- in
+tests/medium_cases.py, tests/test_medium_units_cpu.py and tests/test_gpu_medium_units.py."""
 import numpy as np
 import pytest
 

@@ -218,6 +218,8 @@ MUTATIONS = {
     "no_nodes": ("cornell", _set("num_nodes", 0), INVALID, "no BVH"),
     "res_x_zero": ("cornell", _set("camera.res_x", 0), INVALID, "invalid camera resolution"),
     "seventeen_lights": ("cornell", _seventeen_lights, UNSUPPORTED, "more than 16 sampled lights"),
+    # a path's bounce lives in 8 bits of the slot flags (csrc/hip/pt_kernels.h: FLAG_BOUNCE); 255 is the last the device can count to
+    "max_bounces_256": ("cornell", _set("settings.max_bounces", 256), UNSUPPORTED, "max_bounces above 255"),
     "light_out_of_range": ("cornell", _elem("lights", "num_lights", 0, None, lambda d: d.num_objects), INVALID, "lights[] entry out of range"),
     "record_kind_the_scene_cannot_hold": ("cornell", _elem("recs", "num_recs", 0, "meta", lambda d: d.recs[0].meta | (7 << 29)), INVALID, "malformed or too deep BVH"),
     "record_object": ("cornell", _elem("recs", "num_recs", 0, "meta", lambda d: (d.recs[0].meta & (7 << 29)) | d.num_objects), INVALID, "refers to an object out of range"),
@@ -269,6 +271,14 @@ def test_one_mutation_gives_the_uploads_refusal(name, base):
     mutate(bad, keep)
     rc, _, msg = check(C.byref(bad))
     assert (rc, text in msg) == (code, True), (rc, msg)
+
+
+def test_the_last_bounce_count_the_flags_hold_passes(base):
+    """settings.max_bounces of 255 is accepted (256 is the mutation "max_bounces_256" above): FLAG_BOUNCE is 8 bits."""
+    ok = tg.TgHipSceneDesc.from_buffer_copy(base("cornell"))
+    ok.settings.max_bounces = 255
+    rc, _, msg = check(C.byref(ok))
+    assert rc == 0, msg
 
 
 def test_null_arguments(base):

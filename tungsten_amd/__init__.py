@@ -33,6 +33,12 @@ LIGHT_RESULT_DTYPE = np.dtype([("chosen", np.int32), ("choose_weight", np.float3
                                ("pdf", np.float32), ("approx", np.float32), ("hit", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
                                ("back_side", np.uint32), ("emission", np.float32, 3), ("direct_pdf", np.float32), ("choose_next", np.float32),
                                ("sample_next", np.float32), ("reserved", np.uint32, 4)])
+# capi.TgHipMediumCase / TgHipMediumResult (Renderer.debug_medium)
+MEDIUM_CASE_DTYPE = np.dtype([("medium", np.int32), ("variant", np.uint32), ("seed", np.uint32), ("stream", np.uint32), ("state_bounce", np.uint32),
+                              ("p", np.float32, 3), ("d", np.float32, 3), ("max_t", np.float32), ("wo", np.float32, 3), ("reserved", np.uint32)])
+MEDIUM_RESULT_DTYPE = np.dtype([("ok", np.uint32), ("t", np.float32), ("weight", np.float32, 3), ("exited", np.uint32), ("bounce_after", np.uint32),
+                                ("tr", np.float32, (4, 3)), ("phase_f", np.float32), ("w", np.float32, 3), ("phase_pdf", np.float32),
+                                ("dist_next", np.float32), ("phase_next", np.float32), ("reserved", np.uint32, 2)])
 # capi.TgHipSurface (Renderer.query_surface)
 SURFACE_DTYPE = np.dtype([("p", np.float32, 3), ("t", np.float32), ("ng", np.float32, 3), ("rec", np.int32), ("ns", np.float32, 3), ("instance", np.int32),
                           ("uv", np.float32, 2), ("object", np.int32), ("bsdf", np.int32), ("albedo", np.float32, 3), ("flags", np.uint32),
@@ -311,6 +317,16 @@ class Renderer(object):
         if rc != 0:
             raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
         return needs, cov.astype(bool), int(mask.value)
+
+    def debug_medium(self, cases, device=0):
+        """The shading and shadow kernels' medium code on caller-supplied cases (tghip_debug_medium): `cases` an array of MEDIUM_CASE_DTYPE, the result
+        an array of MEDIUM_RESULT_DTYPE of the same length."""
+        cases = np.ascontiguousarray(cases, MEDIUM_CASE_DTYPE).reshape(-1)
+        out = np.zeros(cases.size, MEDIUM_RESULT_DTYPE)
+        rc = lib.tghip_debug_medium(self.context(device), cases.ctypes.data if cases.size else None, out.ctypes.data if cases.size else None, cases.size)
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        return out
 
     def trace_samples(self, spp_begin, spp_end, seed=DEFAULT_SEED, tile_seeds=None, device=0):
         """One TGHIP_PASS_SAMPLES pass on the device (into a cleared framebuffer): the radiance of every individual sample,

@@ -167,6 +167,16 @@ class TgHipLightResult(C.Structure):
                 ("choose_next", f32), ("sample_next", f32), ("reserved", u32*4)]
 
 
+class TgHipMediumCase(C.Structure):
+    _fields_ = [("medium", i32), ("variant", u32), ("seed", u32), ("stream", u32), ("state_bounce", u32), ("p", f32*3), ("d", f32*3), ("max_t", f32),
+                ("wo", f32*3), ("reserved", u32)]
+
+
+class TgHipMediumResult(C.Structure):
+    _fields_ = [("ok", u32), ("t", f32), ("weight", f32*3), ("exited", u32), ("bounce_after", u32), ("tr", (f32*3)*4), ("phase_f", f32), ("w", f32*3),
+                ("phase_pdf", f32), ("dist_next", f32), ("phase_next", f32), ("reserved", u32*2)]
+
+
 class TgHipPassDesc(C.Structure):
     _fields_ = [("spp_begin", u32), ("spp_end", u32), ("seed", u32), ("shard_index", u32), ("shard_count", u32),
                 ("flags", u32),
@@ -341,6 +351,7 @@ PROTOTYPES = {
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
     "tghip_debug_light": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_light_info": (C.c_int, [VP, C.c_int, VP, VP, VP]),
+    "tghip_debug_medium": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_launch_plan": (C.c_int, [VP, C.POINTER(TgHipPassDesc), C.POINTER(TgHipLaunchPlan)]),
     "tghip_set_option": (C.c_int, [VP, C.c_char_p, C.c_longlong]),
     "tghip_get_counters": (C.c_int, [VP, C.POINTER(TgHipCounters)]),
@@ -399,6 +410,7 @@ PROTOTYPES = {
     "tgh_leaf_bounds": (C.c_int, [VP, C.c_uint32, VP, VP]),
     "tgh_scene_check": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(TgHostSceneTraits), C.c_char_p, C.c_size_t]),
     "tgh_light_needs": (C.c_int, [C.POINTER(TgHipSceneDesc), C.c_int, VP, VP, VP]),
+    "tgh_medium_cases_check": (C.c_int, [C.POINTER(TgHipSceneDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_launch_choice": (C.c_int, [C.POINTER(TgHipSceneDesc), C.POINTER(C.c_char_p), C.POINTER(C.c_longlong), u32, u32, C.c_int,
                                     C.POINTER(TgHipLaunchChoice), C.c_char_p, C.c_size_t]),
     "tgh_pass_plan_create": (VP, [C.POINTER(TgHipPassDesc), u32, u32, C.c_int, u64, u64, u32, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]),

@@ -3,6 +3,8 @@
 // (tests/test_gpu_bsdf_units.py compares every word with the oracle and the reference's recorded answers); no render launches these.
 // Likewise tghip_debug_light: chooseLight / lightSampleDirect / lightApproximateRadiance / lightIntersect / lightEvalDirect / lightDirectPdf in the
 // order and with the arguments of k_shade's next-event estimation (tests/test_gpu_light_units.py).
+// Likewise tghip_debug_medium: mediumSampleDistance / mediumTransmittance / phaseEval / phaseSample, for the two families that carry the media code
+// (tests/test_gpu_medium_units.py).
 #include "pt_wavefront.h"
 #include "debug_units.h"
 
@@ -103,6 +105,51 @@ __global__ void __launch_bounds__(64) k_debug_light(DeviceScene s, const TgHipLi
     results[i] = r;
 }
 
+// One medium case (TgHipMediumCase): the calls k_shade makes on a path inside a medium and the shadow walks make segment by segment (pt_wavefront.h),
+// each on the unstaged scene in global memory.
+template<uint32_t M>
+__global__ void __launch_bounds__(64) k_debug_medium(DeviceScene s, const TgHipMediumCase *cases, TgHipMediumResult *results, uint32_t n, uint32_t variant)
+{
+    static_assert((M & FEAT_QMC) == 0, "the debug kernels draw from the counter-based stream only");
+    static_assert((M & FEAT_MEDIA) != 0, "the medium code is compiled into the FEAT_MEDIA families only");
+    const uint32_t i = blockIdx.x*blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const TgHipMediumCase c = cases[i];
+    if (c.variant != variant || c.medium < 0 || (uint32_t)c.medium >= s.num_media) return;     // (the shim has refused such an index already)
+    const f3 p = mk3(c.p[0], c.p[1], c.p[2]), d = mk3(c.d[0], c.d[1], c.d[2]), wo = mk3(c.wo[0], c.wo[1], c.wo[2]);
+    const TgHipMedium &mm = s.media[c.medium];
+    TgHipMediumResult r;
+    // Medium::sampleDistance on the case's first stream
+    Rng rng = rngStart(c.seed, c.stream, 0u);
+    uint32_t medBounce = c.state_bounce;
+    f3 weight = splat3(0.0f);
+    float t = 0.0f;
+    bool exited = false;
+    const bool ok = mediumSampleDistance<M>(s, c.medium, rng, p, d, c.max_t, medBounce, weight, t, exited);
+    r.ok = ok ? 1u : 0u;
+    r.t = t;
+    r.weight[0] = weight.x; r.weight[1] = weight.y; r.weight[2] = weight.z;
+    r.exited = exited ? 1u : 0u;
+    r.bounce_after = medBounce;
+    r.dist_next = rngNext1D(rng);
+    // Medium::transmittance for the four (startOnSurface, endOnSurface) pairs
+    for (int k = 0; k < 4; ++k) {
+        const f3 tr = mediumTransmittance(s, c.medium, p, d, c.max_t, k < 2, (k & 1) == 0);
+        r.tr[k][0] = tr.x; r.tr[k][1] = tr.y; r.tr[k][2] = tr.z;
+    }
+    // the phase function: eval for the given pair, sample on the second stream
+    r.phase_f = phaseEval(mm, d, wo);
+    Rng rng2 = rngStart(c.seed, c.stream, 1u);
+    f3 w = splat3(0.0f);
+    float pdf = 0.0f;
+    phaseSample<M>(mm, rng2, d, w, pdf);
+    r.w[0] = w.x; r.w[1] = w.y; r.w[2] = w.z;
+    r.phase_pdf = pdf;
+    r.phase_next = rngNext1D(rng2);
+    r.reserved[0] = r.reserved[1] = 0u;
+    results[i] = r;
+}
+
 hipError_t debugBsdfLaunch(hipStream_t stream, const DeviceScene &scene, const TgHipBsdfCase *cases, TgHipBsdfResult *results, uint32_t n,
                            uint32_t variants)
 {
@@ -120,6 +167,24 @@ hipError_t debugLightLaunch(hipStream_t stream, const DeviceScene &scene, const 
     const dim3 grid((n + 63u)/64u), block(64);
 #define DEBUG_LAUNCH(V, MASK) \
     if (variants & (1u << (V))) hipLaunchKernelGGL(k_debug_light<DEBUG_MASK(MASK)>, grid, block, 0, stream, scene, cases, results, n, uint32_t(V));
+    PT_FAMILY_VARIANTS(DEBUG_LAUNCH)
+#undef DEBUG_LAUNCH
+    return hipGetLastError();
+}
+
+// (only the families whose mask carries FEAT_MEDIA have the medium code: the others are not instantiated, and the shim refuses their cases)
+template<uint32_t M>
+static void debugMediumLaunchOne(hipStream_t stream, const DeviceScene &scene, const TgHipMediumCase *cases, TgHipMediumResult *results, uint32_t n, uint32_t variant)
+{
+    if constexpr ((M & FEAT_MEDIA) != 0u)
+        hipLaunchKernelGGL(k_debug_medium<M>, dim3((n + 63u)/64u), dim3(64), 0, stream, scene, cases, results, n, variant);
+}
+
+hipError_t debugMediumLaunch(hipStream_t stream, const DeviceScene &scene, const TgHipMediumCase *cases, TgHipMediumResult *results, uint32_t n,
+                             uint32_t variants)
+{
+#define DEBUG_LAUNCH(V, MASK) \
+    if (variants & (1u << (V))) debugMediumLaunchOne<DEBUG_MASK(MASK)>(stream, scene, cases, results, n, uint32_t(V));
     PT_FAMILY_VARIANTS(DEBUG_LAUNCH)
 #undef DEBUG_LAUNCH
     return hipGetLastError();

@@ -1522,6 +1522,31 @@ int tghip_debug_light_info(tghip_ctx *ctx, int variant, uint32_t *needs, uint32_
     return TGHIP_OK;
 }
 
+// the medium functions exactly as k_shade and the shadow walks call them, for the two families that carry them (debug_units.hip); the refusals
+// are csrc/host/SceneCheck.cpp's checkMediumCases, made before anything is launched
+int tghip_debug_medium(tghip_ctx *ctx, const TgHipMediumCase *cases, TgHipMediumResult *results, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (n == 0) return TGHIP_OK;
+    if (!ctx->haveScene) { ctx->error = "medium self-test without an uploaded scene"; return TGHIP_E_INVALID; }
+    uint32_t variants = 0;
+    const int rc = checkMediumCases(ctx->sc, cases, results, n, variants, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    DeviceArray<TgHipMediumCase> dc;
+    DeviceArray<TgHipMediumResult> dr;
+    HIP_TRY(ctx, dc.once(n));
+    hipError_t e = dr.once(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc.get(), cases, n*sizeof(TgHipMediumCase), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dr.get(), 0, n*sizeof(TgHipMediumResult), ctx->stream);
+    if (e == hipSuccess) e = debugMediumLaunch(ctx->stream, ctx->scene, dc.get(), dr.get(), uint32_t(n), variants);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, dr.get(), n*sizeof(TgHipMediumResult), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return TGHIP_E_HIP; }
+    return TGHIP_OK;
+}
+
 int tghip_debug_launch_plan(tghip_ctx *ctx, const TgHipPassDesc *pass, TgHipLaunchPlan *out)
 {
     if (!ctx || !pass || !out) return TGHIP_E_INVALID;

@@ -75,6 +75,22 @@ uint32_t familyMask(uint32_t variant)
     }
 }
 
+int checkMediumCases(const SceneTraits &t, const TgHipMediumCase *cases, const TgHipMediumResult *results, size_t n, uint32_t &variants, std::string &error)
+{
+    variants = 0u;
+    if (n == 0) return TGHIP_OK;
+    if (!cases || !results || n > 0x3FFFFFFFu) { error = "invalid medium self-test arguments"; return TGHIP_E_INVALID; }
+    if (!t.haveMedia || t.mediumOperand.empty()) { error = "medium self-test: the scene has no media"; return TGHIP_E_INVALID; }
+    for (size_t i = 0; i < n; ++i) {
+        if (cases[i].medium < 0 || size_t(cases[i].medium) >= t.mediumOperand.size()) { error = "medium self-test: medium index outside the scene's table"; return TGHIP_E_INVALID; }
+        if (t.mediumOperand[size_t(cases[i].medium)]) { error = "medium self-test: the entry is an operand of an interpolated transmittance, not a medium"; return TGHIP_E_INVALID; }
+        if (cases[i].variant >= TGHIP_BSDF_VARIANT_COUNT) { error = "medium self-test: unknown variant"; return TGHIP_E_INVALID; }
+        if (!(familyMask(cases[i].variant) & FEAT_MEDIA)) { error = "medium self-test: the variant's kernels carry no medium code"; return TGHIP_E_INVALID; }
+        variants |= 1u << cases[i].variant;
+    }
+    return TGHIP_OK;
+}
+
 uint32_t lightNeeds(const TgHipSceneDesc *s, uint32_t slot)
 {
     if (slot >= s->num_lights || s->lights[slot] < 0 || uint32_t(s->lights[slot]) >= s->num_objects) return 0u;
@@ -311,6 +327,9 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
     if (sd->num_nodes == 0 || !sd->nodes) return fail(TGHIP_E_INVALID, "scene has no BVH");
     if (sd->camera.res_x <= 0 || sd->camera.res_y <= 0) return fail(TGHIP_E_INVALID, "invalid camera resolution");
     if (sd->num_lights > 16) return fail(TGHIP_E_UNSUPPORTED, "more than 16 sampled lights are not supported");
+    // a path's bounce lives in 8 bits of its slot's flags, in 8 bits of a media scene's shadow tag, and bounds the 8 bits of the medium's own count
+    // (pt_kernels.h: FLAG_BOUNCE, SHADOW_TAG_MEDIA, FLAG_MEDIUM_BOUNCE): bounce 256 would read as bounce 0 with the specular flag set
+    if (sd->settings.max_bounces > 255) return fail(TGHIP_E_UNSUPPORTED, "integrator max_bounces above 255 are not supported");
     if (sd->num_objects >= (1u << 24)) return fail(TGHIP_E_UNSUPPORTED, "too many objects");
     if (sd->num_recs >= (1u << 26) || sd->num_nodes >= (1u << 26))   // 64-B attribute / node records behind 32-bit byte offsets (at32)
         return fail(TGHIP_E_UNSUPPORTED, "more than 2^26 primitive records or BVH nodes are not supported");
@@ -406,6 +425,7 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
     if (t.haveMedia) {
         if (!sd->media || sd->num_media > PT_MAX_MEDIA) return fail(TGHIP_E_UNSUPPORTED, "more than 126 media are not supported");
         if (sd->num_objects >= (1u << 16)) return fail(TGHIP_E_UNSUPPORTED, "media scenes support at most 65535 primitives");
+        t.mediumOperand.assign(sd->num_media, 0);
         for (uint32_t i = 0; i < sd->num_media; ++i) {
             const TgHipMedium &m = sd->media[i];
             if (m.phase_type < TGHIP_PHASE_ISOTROPIC || m.phase_type > TGHIP_PHASE_RAYLEIGH) return fail(TGHIP_E_UNSUPPORTED, "unknown phase function");
@@ -418,6 +438,7 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
             if (m.trans_type == TGHIP_TRANS_INTERPOLATED &&
                 (i + 2 >= sd->num_media || sd->media[i + 1].trans_type == TGHIP_TRANS_INTERPOLATED || sd->media[i + 2].trans_type == TGHIP_TRANS_INTERPOLATED))
                 return fail(TGHIP_E_INVALID, "an interpolated transmittance needs its two (non-interpolated) operands in the media entries behind it");
+            if (m.trans_type == TGHIP_TRANS_INTERPOLATED) t.mediumOperand[i + 1] = t.mediumOperand[i + 2] = 1;
         }
     }
     const TgHipCamera &cam = sd->camera;

@@ -31,6 +31,7 @@ struct SceneTraits {
                                           // transmittance segment by segment (the closest-hit shadow walk)
     std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex or haveFibre (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
+    std::vector<uint8_t> mediumOperand;   // per entry of media[]: 1 = an operand of the interpolated transmittance in front of it, no medium of its own (tghip_debug_medium)
     std::vector<uint32_t> lightNeeds;     // per slot of lights[]: the feature bits its light code needs (lightNeeds below; tghip_debug_light_info)
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
@@ -96,6 +97,10 @@ uint32_t familyMask(uint32_t variant);
 // light: a branch that folds away leaves the light to the next one that compiles -- a cube sampled as a quad --, silently.  FEAT_FAMILY_ALL stands for
 // "all four bits" (HAS_PROCTEX): a disk or blade emission, a sampled checker environment.  FEAT_MULTILIGHT whenever the scene has a second light.
 uint32_t lightNeeds(const TgHipSceneDesc *s, uint32_t slot);
+// What tghip_debug_medium decides about a call before anything touches the device: TGHIP_OK with the set of variants to launch (bit = 1 << variant;
+// none for n == 0), or TGHIP_E_INVALID with the refusal in `error` -- null pointers, a scene without media, a medium index outside media[] or one that
+// names an operand entry, a variant that is unknown or whose mask lacks FEAT_MEDIA.  t: checkScene's answer for the uploaded scene.
+int checkMediumCases(const SceneTraits &t, const TgHipMediumCase *cases, const TgHipMediumResult *results, size_t n, uint32_t &variants, std::string &error);
 // Depth of the subtree under `root` (also validates child references).  `level`: 0 = the scene's tree (leaves: non-instance records and
 // instance-set records, which are collected in `found`), 1 = the reference's tree behind a set record (leaves: one or two slots of
 // inst_prims; the instance records behind them are collected in `found`), 2 = a master's subtree (triangles and the like only).

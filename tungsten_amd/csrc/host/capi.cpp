@@ -534,6 +534,18 @@ int tgh_light_needs(const TgHipSceneDesc *scene, int variant, uint32_t *needs, u
     return TGHIP_OK;
 }
 
+int tgh_medium_cases_check(const TgHipSceneDesc *scene, const TgHipMediumCase *cases, const TgHipMediumResult *results, size_t n, char *err, size_t errlen)
+{
+    if (!scene) { setErr(err, errlen, "no scene description"); return TGHIP_E_INVALID; }
+    SceneTraits t;
+    std::string error;
+    if (checkScene(scene, SceneCheckOptions(), t, error) != TGHIP_OK) { setErr(err, errlen, error); return TGHIP_E_INVALID; }
+    uint32_t variants = 0;
+    const int rc = checkMediumCases(t, cases, results, n, variants, error);
+    if (rc != TGHIP_OK) setErr(err, errlen, error);
+    return rc;
+}
+
 int tgh_launch_choice(const TgHipSceneDesc *scene, const char *const *keys, const long long *values, uint32_t num_options,
                       uint32_t pass_flags, int short_batch, TgHipLaunchChoice *out, char *err, size_t errlen)
 {
