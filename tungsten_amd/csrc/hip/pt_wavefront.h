@@ -730,6 +730,38 @@ __global__ __launch_bounds__(512) void k_trace_closest_inst(DeviceScene s, PathS
 #ifndef PT_REFILL_AT
 #define PT_REFILL_AT 40
 #endif
+// The scene's hoisted quad (DeviceScene::hoisted_rec) as values: the three rows of its record and its object's normal, loaded ONCE per kernel with
+// uniform loads, before the walk's loop -- inside it they were two dependent scalar round trips (the record's meta word, then the object it names) behind
+// every refill's wait.  hoistedQuadTest is testRecord<true, KIND_BIT(TGHIP_REC_QUAD)> on these values: the same test, operands and rounding.
+struct HoistedQuad { float4 r0, r1, r2; f3 n; };
+PT_DEV HoistedQuad hoistedQuadLoad(const DeviceScene &s)
+{
+    HoistedQuad q;
+    q.r0 = q.r1 = q.r2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    q.n = splat3(0.0f);
+    if (s.hoisted_rec >= 0) {
+        const PT_CONST_AS float *rp = asConst(reinterpret_cast<const float *>(s.recs)) + (uint32_t)s.hoisted_rec*12;
+        q.r0 = make_float4(rp[0], rp[1], rp[2], rp[3]);
+        q.r1 = make_float4(rp[4], rp[5], rp[6], rp[7]);
+        q.r2 = make_float4(rp[8], rp[9], rp[10], rp[11]);
+        const uint32_t meta = __float_as_uint(q.r0.w);
+        if (TGHIP_REC_KIND(meta) == TGHIP_REC_QUAD)
+            q.n = ld3(asConst(s.objects)[TGHIP_REC_OBJECT(meta)].normal);
+    }
+    return q;
+}
+PT_DEV bool hoistedQuadTest(const HoistedQuad &q, uint32_t ri, const RayD &ray, float &tmax, float4 &hit, uint32_t &hitMeta)
+{
+    const uint32_t meta = __float_as_uint(q.r0.w);
+    float t, u = 0.0f, v = 0.0f;
+    const bool ok = TGHIP_REC_KIND(meta) == TGHIP_REC_QUAD && quadTest(xyz(q.r0), xyz(q.r1), xyz(q.r2), q.r1.w, q.r2.w, q.n, ray, tmax, t, u, v);
+    if (ok) {
+        tmax = t;
+        hit = make_float4(t, u, v, __int_as_float((int)ri));
+        hitMeta = meta;
+    }
+    return ok;
+}
 // DECOUPLED (single-level scenes): a turn tests the lane's next pending record AND visits its next node -- the walk does not wait for
 // the records of the node visited last before it moves on (their outcome only tightens tmax, never what is visited next), so a ray
 // needs about max(nodes, records) turns instead of their sum; a node visited before an earlier node's records have shortened the ray
@@ -759,31 +791,157 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
     float tmax = 0.0f;
     float4 hit = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
     int hitInst = -1;
-    bool pendingPublish = false;                 // DECOUPLED: the walk is over, its hit is published at the next refill (below)
     bool exhausted = false;                      // wave-uniform: the queue has been handed out completely
     uint32_t age = 0;                            // turns this lane's walk has had in this launch (PathState::suspend_turns)
     const bool maySuspend = !INST && st.suspend_lanes != 0u && n >= st.suspend_min_queue;
     WALK_PROF_DECL;
-    for (;;) {
-        unsigned long long busyMask = __ballot(busy);
-        if constexpr (DECOUPLED) {
-            // Finished walks publish their hit -- and bin their path by the shading class of the record hit, a dependent load -- together,
-            // right before the lanes are refilled (once the queue is dry: in the turn they finish): one memory round trip per refill
-            // instead of one in nearly every turn, sat out by the whole wave.
-            // (round 6: once the queue is dry the finished walks wait until more than eight of them can publish together, or nothing else is
-            // left -- eight or fewer enabled lanes issue VALU instructions at a quarter of the rate, profiles/r6_ubench_lane_masks.txt)
+    if constexpr (!INST && DECOUPLED) {
+        // The decoupled turn, with ONE memory wait for everything the wave asks for in it.  In program order:
+        //   publish, first half   finished walks store their hit and ASK for the shading class of the record hit -- together, right before the
+        //                         lanes are refilled (once the queue is dry: when more than eight of them can publish together, or nothing else is
+        //                         left -- eight or fewer enabled lanes issue VALU instructions at a quarter of the rate, profiles/r6_ubench_lane_masks.txt)
+        //   refill, first half    idle lanes claim slots and ASK for their rays, into the ray registers they no longer need
+        //   the walk's fetch      busy lanes their next record and node; a lane that has just claimed a slot the ROOT -- node 0, whatever its ray is
+        //   -- the wait --
+        //   publish, second half  the path goes on its class's queue (the slot index kept from before the refill)
+        //   refill, second half   the fresh lanes set their rays up and test the hoisted quad; a walk an earlier launch suspended (about 1 % of the
+        //                         rays) restores its state with a wait of its own and drops the root it asked for -- it walks on in the next turn
+        //   record test, node visit, as before: the fresh lanes visit their root with the other lanes' nodes
+        // The same turns as with the refill and the publish waited for on their own (three dependent round trips in a turn that refills), and in
+        // each of them the same records and nodes: a ray's walk is a pure function of the ray.
+        const HoistedQuad hq = hoistedQuadLoad(s);   // the scene's one quad, tested before the walk (DeviceScene::hoisted_rec), loaded once
+        bool pendingPublish = false;             // the walk is over, its hit is published at the next refill
+        for (;;) {
+            unsigned long long busyMask = __ballot(busy);
+            const bool refill = !exhausted && __popcll(busyMask) <= PT_REFILL_AT;
             const unsigned long long pendMask = __ballot(pendingPublish);
-            if (pendMask != 0ull && ((!exhausted && __popcll(busyMask) <= PT_REFILL_AT) || (exhausted && (__popcll(pendMask) > 8 || busyMask == 0ull)))) {
+            bool pushing = false;                // this lane's publish is under way: the class has been asked for
+            uint32_t pushLocal = 0u;
+            uint8_t pushCls = (uint8_t)CLS_MISS;
+            if (pendMask != 0ull && (refill || (exhausted && (__popcll(pendMask) > 8 || busyMask == 0ull)))) {
                 WALK_SECTION(wpPubs, wpPubLanes, pendingPublish);
                 if (pendingPublish) {
                     slotF4<NTS>(st, A_HIT, slot) = hit;
                     const int ri = __float_as_int(hit.w);
-                    const int cls = ri < 0 ? CLS_MISS : (int)at32(s.rec_class, (uint32_t)ri);
-                    queuePush(true, local, L, shadeQueue(cls));
+                    if (ri >= 0) pushCls = at32(s.rec_class, (uint32_t)ri);
+                    pushLocal = local;
+                    pushing = true;
                     pendingPublish = false;
                 }
             }
+            auto finishPublish = [&]() { if (pushing) queuePush(true, pushLocal, L, shadeQueue((int)pushCls)); };
+            bool fresh = false;                  // the lane has claimed a slot in this turn: its ray is on its way
+            if (refill) {
+                unsigned long long want = ~busyMask;
+                uint32_t lane = laneId();
+                uint32_t base = 0;
+                if (lane == 0)
+                    base = atomicAdd(&fetchNext, (uint32_t)__popcll(want));
+                base = __shfl(base, 0);
+                const uint32_t i = base + __popcll(want & ((1ull << lane) - 1ull));
+                WALK_SECTION(wpRefills, wpRefillLanes, !busy && i < n);
+                if (!busy && i < n) {
+                    local = order[i];
+                    slot = first + local;
+                    const float4 ro = slotF4<NTS>(st, A_RAY_O, slot), rd = slotF4<NTS>(st, A_RAY_D, slot);   // (not looked at before the wait)
+                    ray.o = xyz(ro); ray.d = xyz(rd); ray.tmin = ro.w; ray.tmax = rd.w;
+                    age = 0;
+                    busy = true;
+                    fresh = true;
+                }
+                if (base + (uint32_t)__popcll(want) >= n) {
+                    exhausted = true;
+                    if (COUNT) wpDry = wall_clock64();
+                }
+                busyMask = __ballot(busy);
+            }
+            // The queue is dry and this wave is down to its last, longest walks: those that have had their turns in this launch are
+            // suspended -- state to the slot's walk arrays, the ray back on the extension queue -- and continue in the next launch
+            // in a full wave (PathState::suspend_*).  (Never a fresh lane: suspend_turns >= 1.)
+            if (maySuspend && exhausted && (uint32_t)__popcll(busyMask) <= st.suspend_lanes) {
+                if (busy && age >= st.suspend_turns) {
+                    walkSave(st, slot, w, stack, stride);
+                    if (COUNT) wpSuspended++;
+                    slotF4<NTS>(st, A_HIT, slot) = hit;
+                    slotW(st, A_RAY_O, slot, 3u) = __uint_as_float(__float_as_uint(ray.tmin) | WALK_SUSPENDED_BIT);
+                    queuePush(true, local, L, Q_EXT);
+                    busy = false;
+                }
+                busyMask = __ballot(busy);
+            }
+            if (busyMask == 0ull) {
+                finishPublish();                 // (a turn without busy lanes just waits for the classes)
+                if (__ballot(pendingPublish) != 0ull)
+                    continue;                    // (the walks that ended in the last turn: published at the top of the loop)
+                break;
+            }
+            age++;
+            if (COUNT) { turns++; dryTurns += exhausted ? 1u : 0u; if (exhausted) wpBusyDry += (uint32_t)__popcll(busyMask); else wpBusy += (uint32_t)__popcll(busyMask); }
+            uint32_t recIdx = 0, nodeIdx = 0;
+            bool hasRec = false, hasNode = fresh;    // (a fresh lane: node 0)
+            if (busy && !fresh) {
+                if (w.triMask == 0u && w.tri2Mask != 0u) { w.triBase = w.tri2Base; w.triMask = w.tri2Mask; w.triValid = w.tri2Valid; w.tri2Mask = 0u; }
+                if (w.triMask) {
+                    const uint32_t b = (uint32_t)__ffs((int)w.triMask) - 1u;
+                    recIdx = w.triBase + (uint32_t)__popc(w.triValid & ((1u << b) - 1u));
+                    w.triMask &= w.triMask - 1u;
+                    hasRec = true;
+                }
+                if (w.tri2Mask == 0u)            // (room for the records of the node visited now)
+                    hasNode = wideNextNode(w, wr.octInv, stack, stride, nodeIdx);
+            }
+            float4 r0, r1, r2;
+            WideNodeRegs nd;
+            PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
+            finishPublish();
+            if (fresh) {
+                const bool resumed = (__float_as_uint(ray.tmin) & WALK_SUSPENDED_BIT) != 0u;   // a walk an earlier launch suspended (above)
+                ray.tmin = __uint_as_float(__float_as_uint(ray.tmin) & ~WALK_SUSPENDED_BIT);
+                wr = wideRaySetup(ray);
+                if (!resumed) {
+                    wideStart(w);
+                    w.node = -1;                 // (the root is here)
+                    tmax = ray.tmax;
+                    hit = make_float4(tmax, 0.0f, 0.0f, __int_as_float(-1));
+                    if (s.hoisted_rec >= 0) {
+                        uint32_t meta;
+                        if (COUNT) prims++;
+                        (void)hoistedQuadTest(hq, (uint32_t)s.hoisted_rec, ray, tmax, hit, meta);
+                    }
+                    rays++;
+                    if (COUNT) wpRays++;
+                } else {
+                    hasNode = false;
+                    age = 0;                     // (this turn is not one of the walk's: suspended again before it had one, it would never end)
+                    walkRestore(st, slot, w, stack, stride);
+                    if (COUNT) wpResumed++;
+                    hit = slotF4<NTS>(st, A_HIT, slot);                      // the best hit so far
+                    tmax = hit.x;
+                    slotW(st, A_RAY_O, slot, 3u) = ray.tmin;             // (the ray is an ordinary one again)
+                }
+            }
+            WALK_SECTION(wpRecTurns, wpRecLanes, hasRec);
+            WALK_SECTION(wpNodeTurns, wpNodeLanes, hasNode);
+            if (hasRec) {
+                if (COUNT) prims++;
+                uint32_t meta;
+                const bool accepted = testRecordLoaded<false, SOLIDS ? KINDS_ALL : KINDS_MESH>(s, recIdx, r0, r1, r2, ray, tmax, hit, meta);
+                if (COUNT && accepted) wpHits++;
+            }
+            if (hasNode) {
+                if (COUNT) nodes++;
+                const uint32_t ob = w.triBase, om = w.triMask, ov = w.triValid;
+                wideVisit(w, nd, ray.o, wr, ray.tmin, tmax, s.hoisted_rec >= 0);
+                if (om) { w.tri2Base = w.triBase; w.tri2Mask = w.triMask; w.tri2Valid = w.triValid; w.triBase = ob; w.triMask = om; w.triValid = ov; }
+            }
+            if (busy && wideWalkOver(w)) {       // (in the turn that looked at the walk's last record / node)
+                busy = false;
+                pendingPublish = true;
+            }
         }
+    } else           // the sequential walk (decouple=0) and the two-level one: a lane's ray is waited for where it is taken
+    for (;;) {
+        unsigned long long busyMask = __ballot(busy);
         if (!exhausted && __popcll(busyMask) <= PT_REFILL_AT) {
             unsigned long long want = ~busyMask;
             uint32_t lane = laneId();
@@ -809,13 +967,6 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
                         wideStart(w);
                         tmax = ray.tmax;
                         hit = make_float4(tmax, 0.0f, 0.0f, __int_as_float(-1));
-                        if constexpr (DECOUPLED && !INST) {
-                            if (s.hoisted_rec >= 0) {            // the scene's one quad, before the walk (DeviceScene::hoisted_rec; uniform loads)
-                                uint32_t meta;
-                                if (COUNT) prims++;
-                                (void)testRecord<true, KIND_BIT(TGHIP_REC_QUAD)>(s, (uint32_t)s.hoisted_rec, ray, tmax, hit, meta);
-                            }
-                        }
                         rays++;
                         if (COUNT) wpRays++;
                     } else {
@@ -852,50 +1003,11 @@ PT_DEV void traceClosestWideBody(const DeviceScene &s, const PathState &st, Bloc
                 busyMask = __ballot(busy);
             }
         }
-        if (busyMask == 0ull) {
-            if (DECOUPLED && __ballot(pendingPublish) != 0ull)
-                continue;                        // (the walks that ended in the last turn: published at the top of the loop)
+        if (busyMask == 0ull)
             break;
-        }
         age++;
         if (COUNT) { turns++; dryTurns += exhausted ? 1u : 0u; if (exhausted) wpBusyDry += (uint32_t)__popcll(busyMask); else wpBusy += (uint32_t)__popcll(busyMask); }
-        if constexpr (!INST && DECOUPLED) {
-            uint32_t recIdx = 0, nodeIdx = 0;
-            bool hasRec = false, hasNode = false, finished = false;
-            if (busy) {
-                if (w.triMask == 0u && w.tri2Mask != 0u) { w.triBase = w.tri2Base; w.triMask = w.tri2Mask; w.triValid = w.tri2Valid; w.tri2Mask = 0u; }
-                if (w.triMask) {
-                    const uint32_t b = (uint32_t)__ffs((int)w.triMask) - 1u;
-                    recIdx = w.triBase + (uint32_t)__popc(w.triValid & ((1u << b) - 1u));
-                    w.triMask &= w.triMask - 1u;
-                    hasRec = true;
-                }
-                if (w.tri2Mask == 0u)            // (room for the records of the node visited now)
-                    hasNode = wideNextNode(w, wr.octInv, stack, stride, nodeIdx);
-            }
-            float4 r0, r1, r2;
-            WideNodeRegs nd;
-            PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
-            WALK_SECTION(wpRecTurns, wpRecLanes, hasRec);
-            WALK_SECTION(wpNodeTurns, wpNodeLanes, hasNode);
-            if (hasRec) {
-                if (COUNT) prims++;
-                uint32_t meta;
-                const bool accepted = testRecordLoaded<false, SOLIDS ? KINDS_ALL : KINDS_MESH>(s, recIdx, r0, r1, r2, ray, tmax, hit, meta);
-                if (COUNT && accepted) wpHits++;
-            }
-            if (hasNode) {
-                if (COUNT) nodes++;
-                const uint32_t ob = w.triBase, om = w.triMask, ov = w.triValid;
-                wideVisit(w, nd, ray.o, wr, ray.tmin, tmax, s.hoisted_rec >= 0);
-                if (om) { w.tri2Base = w.triBase; w.tri2Mask = w.triMask; w.tri2Valid = w.triValid; w.triBase = ob; w.triMask = om; w.triValid = ov; }
-            }
-            if (busy && wideWalkOver(w)) {       // (in the turn that looked at the walk's last record / node)
-                busy = false;
-                pendingPublish = true;
-            }
-            (void)finished;
-        } else if constexpr (!INST) {
+        if constexpr (!INST) {
             // What the lane looks at this turn: its next record, its next node, or -- when that record is the last one of the node
             // visited before -- BOTH: the node to visit next does not depend on the record's outcome (the group's order is fixed),
             // only its slab tests do, and they run after the record test; so the walk is the one wideNext defines, a record-bearing
