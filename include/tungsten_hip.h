@@ -18,6 +18,7 @@
  *   tghip_query_rays        <- TraceableScene::intersect and ::occluded (renderer/TraceableScene.hpp:170-223), batched, on host or device memory.
  *   tghip_query_surface     <- TraceableScene::intersect + Primitive::intersectionInfo (renderer/TraceableScene.hpp:170-192), the albedo and emission
  *                              of PathTracer.cpp:83-88 and TraceableScene::intersectInfinites (:194-209) for a miss, batched, on host or device memory.
+ *   tghip_query_transmittance <- TraceBase::generalizedShadowRay (integrators/TraceBase.cpp:62-133), batched, on host or device memory.
  *   tghip_reduce_framebuffers <- the merge of per-machine partial renders the reference does offline on the host
  *                              (src/hdrmanip/hdrmanip.cpp:69-112: load N HDR images, add, divide); here the tile shards of
  *                              one frame, summed on the device side by RCCL over xGMI.
@@ -751,6 +752,58 @@ int tghip_query_surface(tghip_ctx *ctx, const TgHipSurfaceQueryDesc *desc, const
 /* Instrumentation: HIP-event time of the two launches of the context's last tghip_query_surface, in milliseconds; with the option
  * "surface_time_stage" = 1 that of its dense launch alone (profiles/surface_query/bench.txt).  The option changes no answer. */
 int tghip_query_surface_kernel_time(tghip_ctx *ctx, double *ms);
+/* How much light gets along caller-supplied rays: TraceBase::generalizedShadowRay (integrators/TraceBase.cpp:62-133, generalizedShadowRayImpl<false>) on
+ * the segment [tmin, tmax) of every ray -- the visibility the path tracer's own shadow rays see: `forward` boundaries and `transparency` cut-outs let light
+ * through, participating media attenuate it, the primitive the rays are aimed at is left out.  (TGHIP_QUERY_OCCLUDED is geometry only.)  A small wavefront
+ * of its own on the context's stream (csrc/hip/transmittance_query.hip): per round a closest-hit walk -- tghip_query_rays' -- over the rays still under
+ * way, and a dense launch, one lane per such ray, that does the rest of the round and either writes the ray's answer or hands it to the next round.
+ *   closest hit  every round takes the closest hit of the current segment: bit for bit what tghip_query_rays (TGHIP_QUERY_CLOSEST) answers for the segment's
+ *                (o, d, tmin, tmax) on the same context, in every kind of scene.  Infinite emitters are never hit.
+ *   a hit that   the material has no TGHIP_LOBE_FORWARD: rgb = 0.  Otherwise transparency = bsdf->eval(forward event) (the frame flipped for two-sided
+ *   is not the   shading exactly as the path tracer's shadow walk flips it, all-features arithmetic); transparency == 0: rgb = 0; throughput *= transparency,
+ *   end cap      bounce++, and bounce >= max_bounces: rgb = 0.
+ *   medium       then, if the ray is in a medium: throughput *= transmittance(the ray up to the hit, or up to tmax on a miss; startsOnSurface;
+ *                endsOnSurface) -- AFTER the transparency, the reference's order (:97, 104-112), and with the caller's endsOnSurface for EVERY
+ *                segment (:111), not the constant `true` of a pass's shadow rays.
+ *   the end      on a miss, or when the hit is the end cap: rgb = throughput if bounce >= min_bounces, else 0.  A quad end cap is only found when
+ *                Embree's slab test lets the ray into its flat box: culled, the walk ends as at the end cap but the segment's medium length is tmax.
+ *   otherwise    medium = selectMedium(hit primitive, medium, !backSide), startsOnSurface = true, o = o + d*t (float32, unfused), remaining -= t,
+ *                tmin = 5e-4, tmax = remaining, and the next round.
+ *   crossed      the number of times `bounce++` above ran, whatever ended the walk.
+ *   media        NULL: every ray starts in desc->medium; else n words, ray i starts in media[i] (an index in TgHipSceneDesc::media, TGHIP_MEDIUM_NONE or
+ *                TGHIP_MEDIUM_OF_CAMERA) and desc->medium is only checked.
+ *   memory       flags without TGHIP_DEVELOP_DEVICE_POINTERS: rays, media and out are host memory, staged through buffers of the context that only
+ *                grow; with it: memory of the context's device, rays and out 16-byte aligned, media 4-byte aligned.  Nothing is allocated per call
+ *                once the scratch has grown.
+ * The pdfs (generalizedShadowRayAndPdfs), the emission at the end cap with a mesh light's distance test (attenuatedEmission) and per-ray end caps are not
+ * part of the call.  Runs on the context's stream, waits for a running pass like tghip_query_rays, returns when the answers are complete and leaves the
+ * framebuffer, the SampleRecords, the auxiliary and the per-sample buffers as they were.  "query_blocks" and "query_refill_at" steer the walk and never
+ * change an answer.  A per-ray media[i] out of range, a non-finite ray component or a zero direction gives that ray an unspecified answer; the call
+ * returns.  n == 0 succeeds.  TGHIP_E_NOSCENE without an upload -- decided before the arguments are looked at, a missing description apart: the check
+ * reads the uploaded scene's tables, so on a context without a scene a malformed call answers TGHIP_E_NOSCENE too (its siblings, whose checks need
+ * no scene, answer TGHIP_E_INVALID there).  TGHIP_E_INVALID, the context still usable (tghip_last_error says which): no description,
+ * NULL rays or out with n > 0, unknown flag bits, non-zero reserved words, n > 2^31 - 1, misaligned device pointers, desc->medium below -2 or >=
+ * num_media or naming an operand entry of an `interpolated` medium (tghip_debug_medium's rule), end_cap outside the objects or naming an `instances`
+ * object or an infinite emitter, bounce > 255 (tungsten_host.h: tgh_query_transmittance_check is the same check on its own). */
+#define TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE 2u   /* flags; bit 0 stays TGHIP_DEVELOP_DEVICE_POINTERS */
+#define TGHIP_TRANSMITTANCE_ENDS_ON_SURFACE   4u
+#define TGHIP_MEDIUM_NONE      (-1)
+#define TGHIP_MEDIUM_OF_CAMERA (-2)                /* the medium the scene's camera is in, as tghip_query_radiance starts */
+typedef struct TgHipTransmittanceQueryDesc {
+    uint32_t flags;
+    int32_t  medium;      /* medium every ray starts in when `media` is NULL: index in TgHipSceneDesc::media, or one of the two above */
+    int32_t  end_cap;     /* object index of the primitive the rays are aimed at (generalizedShadowRay's endCap), -1 = none */
+    uint32_t bounce;      /* the bounce count the walk starts with */
+    uint32_t reserved[4]; /* zero */
+} TgHipTransmittanceQueryDesc;                     /* 32 B */
+typedef struct TgHipTransmittance { float rgb[3]; uint32_t crossed; } TgHipTransmittance;   /* 16 B */
+int tghip_query_transmittance(tghip_ctx *ctx, const TgHipTransmittanceQueryDesc *desc, const TgHipRay *rays,
+                              const int32_t *media /* n start media, may be NULL */, TgHipTransmittance *out, size_t n);
+/* Instrumentation: HIP-event time from the first launch to the last of the context's last tghip_query_transmittance, in milliseconds -- every round's two
+ * launches and the one-word read-backs between the rounds (profiles/transmittance_query/bench.txt) */
+int tghip_query_transmittance_kernel_time(tghip_ctx *ctx, double *ms);
+/* ... and the rounds that call ran: 1 + the most surfaces a ray of the batch went on behind, 1 in a scene without a forward-lobe BSDF */
+int tghip_query_transmittance_rounds(tghip_ctx *ctx, uint32_t *rounds);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

@@ -256,6 +256,17 @@ int tgh_query_radiance_check(const TgHipRadianceQueryDesc *desc, const void *ray
  * or TGHIP_E_INVALID and in `err` the refusal's message.  Only the pointers' values are looked at, nothing is read through them. */
 int tgh_query_surface_check(const TgHipSurfaceQueryDesc *desc, const void *rays, const void *out, size_t n, char *err, size_t errlen);
 
+/* What tghip_query_transmittance decides about a call before it touches the device (csrc/host/TransmittanceQuery.cpp), on its own, no device: TGHIP_OK,
+ * or TGHIP_E_INVALID and in `err` the refusal's message.  `scene`: what the refusals that depend on the uploaded scene read -- per entry of media[]
+ * whether it is an operand of an `interpolated` medium (NULL: none is), per object its TGHIP_OBJ_* type; NULL checks a call against a scene without
+ * media and without objects.  Only the pointers' values of rays, media and out are looked at, nothing is read through them. */
+typedef struct TgHostTransmittanceScene {
+    uint32_t num_media;   const uint8_t *medium_operand;   /* num_media bytes, or NULL */
+    uint32_t num_objects; const int32_t *object_type;      /* num_objects words */
+} TgHostTransmittanceScene;
+int tgh_query_transmittance_check(const TgHipTransmittanceQueryDesc *desc, const void *rays, const void *media, const void *out, size_t n,
+                                  const TgHostTransmittanceScene *scene, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

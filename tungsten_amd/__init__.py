@@ -43,6 +43,8 @@ MEDIUM_RESULT_DTYPE = np.dtype([("ok", np.uint32), ("t", np.float32), ("weight",
 SURFACE_DTYPE = np.dtype([("p", np.float32, 3), ("t", np.float32), ("ng", np.float32, 3), ("rec", np.int32), ("ns", np.float32, 3), ("instance", np.int32),
                           ("uv", np.float32, 2), ("object", np.int32), ("bsdf", np.int32), ("albedo", np.float32, 3), ("flags", np.uint32),
                           ("emission", np.float32, 3), ("reserved", np.uint32)])
+# capi.TgHipTransmittance (Renderer.query_transmittance)
+TRANSMITTANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("crossed", np.uint32)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 QUERY_MODE_NAMES = ("closest", "occluded")                                  # capi.TGHIP_QUERY_*
@@ -264,6 +266,55 @@ class Renderer(object):
         desc = capi.TgHipSurfaceQueryDesc(capi.TGHIP_DEVELOP_DEVICE_POINTERS)
         ctx = self.context(device)
         if lib.tghip_query_surface(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+
+    def _transmittance_desc(self, flags, medium, end_cap, bounce, starts_on_surface, ends_on_surface):
+        if medium == "camera":
+            medium = capi.TGHIP_MEDIUM_OF_CAMERA
+        elif medium is None:
+            medium = capi.TGHIP_MEDIUM_NONE
+        if starts_on_surface:
+            flags |= capi.TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE
+        if ends_on_surface:
+            flags |= capi.TGHIP_TRANSMITTANCE_ENDS_ON_SURFACE
+        return capi.TgHipTransmittanceQueryDesc(flags, int(medium), int(end_cap), int(bounce))
+
+    def query_transmittance(self, rays, media=None, medium="camera", end_cap=-1, bounce=0, starts_on_surface=False, ends_on_surface=False, device=0):
+        """How much light gets along every ray (tghip_query_transmittance, TraceBase::generalizedShadowRay): rays [N,8] float32 (o, tmin, d, tmax)
+        -> a structured array [N] of TRANSMITTANCE_DTYPE: rgb, and crossed, the see-through surfaces the walk went through.  medium: the medium
+        every ray starts in -- an index, None, or "camera" for the one the scene's camera is in; media: int32 [N], per ray instead.  end_cap: the
+        object index of the primitive the rays are aimed at, -1 = none; bounce: the bounce count the walk starts with."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.empty(rays.shape[0], TRANSMITTANCE_DTYPE)
+        if media is not None:
+            media = np.ascontiguousarray(media, np.int32).reshape(-1)
+            if media.size != rays.shape[0]:
+                raise TungstenError("query_transmittance: media must hold one entry per ray")
+        desc = self._transmittance_desc(0, medium, end_cap, bounce, starts_on_surface, ends_on_surface)
+        ctx = self.context(device)
+        if lib.tghip_query_transmittance(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None, out.ctypes.data,
+                                         rays.shape[0]) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def query_transmittance_into(self, rays, out, media=None, medium="camera", end_cap=-1, bounce=0, starts_on_surface=False, ends_on_surface=False,
+                                 device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 4
+        elements -- rgb and crossed's bits --, media None or int32 [N], all contiguous.  The answers are complete when the call returns."""
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        tensors = [("rays", rays, "torch.float32", 8), ("out", out, "torch.float32", 4)]
+        if media is not None:
+            tensors.append(("media", media, "torch.int32", 1))
+        for name, t, dtype, size in tensors:
+            if str(t.dtype) != dtype:
+                raise TungstenError("query_transmittance_into: %s must be %s, not %s" % (name, dtype, t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("query_transmittance_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("query_transmittance_into: rays must be contiguous [N, 8], out contiguous with N x 4 and media with N elements")
+        desc = self._transmittance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, medium, end_cap, bounce, starts_on_surface, ends_on_surface)
+        ctx = self.context(device)
+        if lib.tghip_query_transmittance(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None, out.data_ptr(), n) != 0:
             raise TungstenError(lib.tghip_last_error(ctx).decode())
 
     def debug_libm(self, fn, x, device=0):

@@ -236,6 +236,25 @@ class TgHipSurfaceQueryDesc(C.Structure):
     _fields_ = [("flags", u32), ("reserved", u32*3)]
 
 
+# TgHipObject::type
+(TGHIP_OBJ_MESH, TGHIP_OBJ_QUAD, TGHIP_OBJ_CUBE, TGHIP_OBJ_SPHERE, TGHIP_OBJ_INFINITE_SPHERE, TGHIP_OBJ_INSTANCES, TGHIP_OBJ_DISK,
+ TGHIP_OBJ_INFINITE_SPHERE_CAP, TGHIP_OBJ_POINT, TGHIP_OBJ_CYLINDER) = range(10)
+TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE, TGHIP_TRANSMITTANCE_ENDS_ON_SURFACE = 2, 4
+TGHIP_MEDIUM_NONE, TGHIP_MEDIUM_OF_CAMERA = -1, -2
+
+
+class TgHipTransmittanceQueryDesc(C.Structure):
+    _fields_ = [("flags", u32), ("medium", i32), ("end_cap", i32), ("bounce", u32), ("reserved", u32*4)]
+
+
+class TgHipTransmittance(C.Structure):
+    _fields_ = [("rgb", f32*3), ("crossed", u32)]
+
+
+class TgHostTransmittanceScene(C.Structure):
+    _fields_ = [("num_media", u32), ("medium_operand", C.POINTER(C.c_uint8)), ("num_objects", u32), ("object_type", C.POINTER(i32))]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -346,6 +365,9 @@ PROTOTYPES = {
     "tghip_query_radiance_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_query_surface": (C.c_int, [VP, C.POINTER(TgHipSurfaceQueryDesc), VP, VP, C.c_size_t]),
     "tghip_query_surface_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_query_transmittance": (C.c_int, [VP, C.POINTER(TgHipTransmittanceQueryDesc), VP, VP, VP, C.c_size_t]),
+    "tghip_query_transmittance_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_query_transmittance_rounds": (C.c_int, [VP, C.POINTER(C.c_uint32)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -426,6 +448,8 @@ PROTOTYPES = {
     "tgh_query_rays_check": (C.c_int, [C.POINTER(TgHipRayQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_query_radiance_check": (C.c_int, [C.POINTER(TgHipRadianceQueryDesc), VP, VP, VP, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]),
     "tgh_query_surface_check": (C.c_int, [C.POINTER(TgHipSurfaceQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "tgh_query_transmittance_check": (C.c_int, [C.POINTER(TgHipTransmittanceQueryDesc), VP, VP, VP, C.c_size_t, C.POINTER(TgHostTransmittanceScene),
+                                                C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

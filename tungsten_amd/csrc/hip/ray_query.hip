@@ -3,6 +3,9 @@
 // leave out).  Persistent workgroups claim rays from ONE global counter: the idle lanes of a wave are counted with a ballot, one lane adds the count and
 // broadcasts the base, each idle lane takes base + its rank.  Nothing waits for another workgroup and nothing spins: a wave leaves once it holds no
 // ray and the counter has passed n.  The shim resets the counter in-stream before every launch (tungsten_hip.hip: tghip_query_rays).
+// The two loops below exist twice more with another load and another store -- surface_query.hip (k_surface_walk*) and transmittance_query.hip
+// (k_transmittance_walk*): instantiated there again because as a shared template these kernels did not come out instruction for instruction
+// (profiles/surface_query/kernel_resources_diff.txt).  A change to a turn of the walk is made in all three.
 #include "ray_query.h"
 #include "pt_wavefront.h"
 

@@ -159,6 +159,16 @@ struct tghip_ctx {
     hipEvent_t evSurfMid = nullptr;
     double surfMs = 0.0, surfDenseMs = 0.0;
     bool surfTimeDense = false;
+    // tghip_query_transmittance: the rays' state between the rounds of its wavefront (csrc/hip/transmittance_query.h: TransmittanceState), the two
+    // index lists the rounds alternate between, the start media and the answers on the device when the caller's are host memory (all grown on demand;
+    // the two counter words -- the walk's claims, the survivors -- are queryCounter's first two, the staged rays and the two options
+    // tghip_query_rays'), the time of the last call's rounds and how many it ran
+    DeviceArray<float4> trO, trD, trT, trHits, trOut;
+    DeviceArray<uint2> trB;
+    DeviceArray<int> trInst, trMedia;
+    DeviceArray<uint32_t> trList[2];
+    double trMs = 0.0;
+    uint32_t trRounds = 0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context (tghipDestroyRankComm)
     int rankCount = 0, rankIndex = 0;
     DeviceArray<float> redSum;            // the reduces (reduce.hip): where the reduced image lands when this context is the root (grown: a re-upload

@@ -10,9 +10,11 @@
 #include "ray_query.h"
 #include "radiance_query.h"
 #include "surface_query.h"
+#include "transmittance_query.h"
 #include "../host/RayQuery.hpp"
 #include "../host/RadianceQuery.hpp"
 #include "../host/SurfaceQuery.hpp"
+#include "../host/TransmittanceQuery.hpp"
 
 #include <chrono>
 
@@ -1759,6 +1761,86 @@ int tghip_query_surface(tghip_ctx *ctx, const TgHipSurfaceQueryDesc *desc, const
 int tghip_query_surface_kernel_time(tghip_ctx *ctx, double *ms)
 {
     return kernelTime(ctx, ctx && ctx->surfTimeDense ? &tghip_ctx::surfDenseMs : &tghip_ctx::surfMs, ms);
+}
+
+int tghip_query_transmittance(tghip_ctx *ctx, const TgHipTransmittanceQueryDesc *desc, const TgHipRay *rays, const int32_t *media, TgHipTransmittance *out, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_query_transmittance: no description"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "tghip_query_transmittance before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    const TgHostTransmittanceScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), uint32_t(ctx->sc.objectType.size()), ctx->sc.objectType.data()};
+    int rc = checkTransmittanceQuery(desc, rays, media, out, n, &facts, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    if (n == 0) return TGHIP_OK;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
+    const size_t outBytes = n*sizeof(TgHipTransmittance);
+    HIP_TRY(ctx, ctx->queryCounter.once(16));
+    const float4 *dRays = nullptr;
+    const int *dMedia = nullptr;
+    float4 *dOut = nullptr;
+    if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
+    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->trMedia, dMedia)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->trOut, dOut)) != TGHIP_OK) return rc;
+    // the walk and the workgroups of tghip_query_rays on this scene
+    const LaunchChoice &choice = ctx->lp.choice;
+    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
+    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
+                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
+    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    // the state between the rounds.  A scene without a forward-lobe BSDF ends every ray in round 0: nothing but the hits is ever stored.
+    const bool oneRound = !ctx->sc.haveForwardBsdf;
+    if ((rc = ctx->trHits.grow(ctx, n)) != TGHIP_OK) return rc;
+    if (inst && (rc = ctx->trInst.grow(ctx, n)) != TGHIP_OK) return rc;
+    if (!oneRound) {
+        if ((rc = ctx->trO.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trD.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trT.grow(ctx, n)) != TGHIP_OK ||
+            (rc = ctx->trB.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trList[0].grow(ctx, n)) != TGHIP_OK || (rc = ctx->trList[1].grow(ctx, n)) != TGHIP_OK)
+            return rc;
+    }
+    const TransmittanceState st = {ctx->trO.get(), ctx->trD.get(), ctx->trT.get(), ctx->trB.get(), ctx->trHits.get(), inst ? ctx->trInst.get() : nullptr};
+    TransmittanceParams p;
+    p.cameraMedium = ctx->sc.cameraMedium;
+    p.medium = desc->medium == TGHIP_MEDIUM_OF_CAMERA ? p.cameraMedium : desc->medium;
+    p.endCap = desc->end_cap;
+    p.bounce = desc->bounce;
+    p.startsOnSurface = (desc->flags & TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE) ? 1u : 0u;
+    p.endsOnSurface = (desc->flags & TGHIP_TRANSMITTANCE_ENDS_ON_SURFACE) ? 1u : 0u;
+    // A ray that goes on has crossed a surface: bounce < max_bounces bounds the rounds whatever the rays do
+    const long long maxRounds = oneRound ? 1 : std::max<long long>(1, (long long)ctx->scene.settings.max_bounces - (long long)desc->bounce);
+    uint32_t *counters = ctx->queryCounter.get();
+    ctx->trRounds = 0;
+    return timedLaunches(ctx, ctx->trMs, [&]() -> int {
+        uint32_t live = uint32_t(n);
+        for (long long round = 0; round < maxRounds && live > 0; ++round) {
+            // workgroups: as many as stay resident, no more than the round has waves for (a workgroup without a ray only reads the counter)
+            const size_t perWave = (size_t(live) + 63)/64;
+            const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
+                                                         : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
+            const uint32_t *list = round == 0 ? nullptr : ctx->trList[(round - 1) & 1].get();
+            uint32_t *next = ctx->trList[round & 1].get();
+            HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
+            HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays, st, list, live, counters, blocks, refillAt, lds));
+            HIP_TRY(ctx, transmittanceQueryLaunchSegment(ctx->stream, ctx->scene, p, dRays, dMedia, st, list, live, dOut, next, counters + 1));
+            ctx->trRounds++;
+            if (oneRound) break;
+            // the one word a round hands back: how many rays the next one has
+            HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, out, dOut, outBytes); });
+}
+
+int tghip_query_transmittance_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::trMs, ms); }
+
+int tghip_query_transmittance_rounds(tghip_ctx *ctx, uint32_t *rounds)
+{
+    if (!ctx || !rounds) return TGHIP_E_INVALID;
+    *rounds = ctx->trRounds;
+    return TGHIP_OK;
 }
 
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out)

@@ -501,6 +501,10 @@ int checkScene(const TgHipSceneDesc *sd, const SceneCheckOptions &opt, SceneTrai
         allTypes |= tm;
         if (c != 0) { t.haveComplex = true; t.complexMask |= tm; }
     }
+    t.haveForwardBsdf = t.haveForward;
+    t.objectType.assign(sd->num_objects, 0);
+    for (uint32_t i = 0; i < sd->num_objects; ++i) t.objectType[i] = sd->objects[i].type;
+    t.cameraMedium = sd->camera.medium;
     t.mediaSimple = t.haveMedia && !t.haveInstances && familyCovers(TGHIP_BSDF_VARIANT_MEDIA, allTypes, false);
     if (t.haveMedia) t.haveForward = true;   // shadow rays pick up transmittance segment by segment: the closest-hit walk
     t.leanScene = sd->num_infinite_lights == 0 && sd->num_lights <= 1;

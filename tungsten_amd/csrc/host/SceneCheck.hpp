@@ -32,6 +32,11 @@ struct SceneTraits {
     std::vector<uint32_t> bsdfTypes;      // per bsdf: bsdfTypeMask, plus FEAT_BITMAP when a texture inside is a bitmap and FEAT_FAMILY_ALL when haveProcTex or haveFibre (tghip_debug_bsdf_info)
     std::vector<uint8_t> bsdfForward;     // ... and whether it has a forward lobe
     std::vector<uint8_t> mediumOperand;   // per entry of media[]: 1 = an operand of the interpolated transmittance in front of it, no medium of its own (tghip_debug_medium)
+    // what tghip_query_transmittance reads: whether some BSDF has a forward lobe (haveForward without the media's share of it), per object its
+    // TGHIP_OBJ_* type, the medium the camera is in
+    bool haveForwardBsdf = false;
+    std::vector<int32_t> objectType;
+    int32_t cameraMedium = -1;
     std::vector<uint32_t> lightNeeds;     // per slot of lights[]: the feature bits its light code needs (lightNeeds below; tghip_debug_light_info)
     bool haveMeshLight = false;           // a triangle mesh is a sampled light: closest-hit shadow walk, MASK_FULL shading
     bool thinlens = false;                // thin-lens camera: passes run the EXT kernel variants (PT_PASS_THINLENS)
