@@ -24,11 +24,12 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 # + radiance_query.hip, the ray source and the result copy of tghip_query_radiance (its check and virtual image, csrc/host/RadianceQuery.cpp, likewise)
 # + surface_query.hip, the walk and the dense launch of tghip_query_surface (its argument check, csrc/host/SurfaceQuery.cpp, likewise)
 # + transmittance_query.hip, the walk and the dense launch of a round of tghip_query_transmittance (its argument check, csrc/host/TransmittanceQuery.cpp, likewise)
+# + direct_query.hip, the three dense launches of tghip_query_direct around those two units' walks (its argument check, csrc/host/DirectQuery.cpp, likewise)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
 # (the shim reads what csrc/host/SceneCheck.cpp decided about a scene, SceneTraits, what csrc/host/PassPlan.cpp decided about a pass, PassPlan, what
 # csrc/host/LaunchChoice.cpp decided about the pass's kernels, LaunchChoice, and calls csrc/host/RayQuery.cpp's check of a query)
-HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp tungsten_amd/csrc/host/RayQuery.hpp tungsten_amd/csrc/host/RadianceQuery.hpp tungsten_amd/csrc/host/SurfaceQuery.hpp tungsten_amd/csrc/host/TransmittanceQuery.hpp tungsten_amd/csrc/host/LaunchChoice.hpp
+HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp tungsten_amd/csrc/host/RayQuery.hpp tungsten_amd/csrc/host/RadianceQuery.hpp tungsten_amd/csrc/host/SurfaceQuery.hpp tungsten_amd/csrc/host/TransmittanceQuery.hpp tungsten_amd/csrc/host/DirectQuery.hpp tungsten_amd/csrc/host/LaunchChoice.hpp
 # -ffp-contract=off: no FMA contraction, so device arithmetic rounds like the CPU reference/oracle
 # (DESIGN.md "Numerics"); TG_FAST=1 allows contraction.
 FPFLAGS  := $(if $(TG_FAST),-ffp-contract=fast,-ffp-contract=off)

@@ -19,6 +19,7 @@
  *   tghip_query_surface     <- TraceableScene::intersect + Primitive::intersectionInfo (renderer/TraceableScene.hpp:170-192), the albedo and emission
  *                              of PathTracer.cpp:83-88 and TraceableScene::intersectInfinites (:194-209) for a miss, batched, on host or device memory.
  *   tghip_query_transmittance <- TraceBase::generalizedShadowRay (integrators/TraceBase.cpp:62-133), batched, on host or device memory.
+ *   tghip_query_direct      <- TraceBase::estimateDirect / volumeEstimateDirect (integrators/TraceBase.cpp:470-494), batched, on host or device memory.
  *   tghip_reduce_framebuffers <- the merge of per-machine partial renders the reference does offline on the host
  *                              (src/hdrmanip/hdrmanip.cpp:69-112: load N HDR images, add, divide); here the tile shards of
  *                              one frame, summed on the device side by RCCL over xGMI.
@@ -776,7 +777,7 @@ int tghip_query_surface_kernel_time(tghip_ctx *ctx, double *ms);
  *                grow; with it: memory of the context's device, rays and out 16-byte aligned, media 4-byte aligned.  Nothing is allocated per call
  *                once the scratch has grown.
  * The pdfs (generalizedShadowRayAndPdfs), the emission at the end cap with a mesh light's distance test (attenuatedEmission) and per-ray end caps are not
- * part of the call.  Runs on the context's stream, waits for a running pass like tghip_query_rays, returns when the answers are complete and leaves the
+ * part of the call (tghip_query_direct below has the latter two).  Runs on the context's stream, waits for a running pass like tghip_query_rays, returns when the answers are complete and leaves the
  * framebuffer, the SampleRecords, the auxiliary and the per-sample buffers as they were.  "query_blocks" and "query_refill_at" steer the walk and never
  * change an answer.  A per-ray media[i] out of range, a non-finite ray component or a zero direction gives that ray an unspecified answer; the call
  * returns.  n == 0 succeeds.  TGHIP_E_NOSCENE without an upload -- decided before the arguments are looked at, a missing description apart: the check
@@ -804,6 +805,71 @@ int tghip_query_transmittance(tghip_ctx *ctx, const TgHipTransmittanceQueryDesc 
 int tghip_query_transmittance_kernel_time(tghip_ctx *ctx, double *ms);
 /* ... and the rounds that call ran: 1 + the most surfaces a ray of the batch went on behind, 1 in a scene without a forward-lobe BSDF */
 int tghip_query_transmittance_rounds(tghip_ctx *ctx, uint32_t *rounds);
+/* How much light the scene's emitters send DIRECTLY to the closest hit of caller-supplied rays -- or to their origins inside a medium: the path tracer's
+ * next-event estimation, TraceBase::estimateDirect (integrators/TraceBase.cpp:483-494) and volumeEstimateDirect (:470-481), sample by sample.  A small
+ * wavefront of its own on the context's stream (csrc/hip/direct_query.hip): the closest-hit walk of tghip_query_surface, a dense launch, one lane per
+ * (ray, sample), that draws the samples and decides what needs no walk, rounds of tghip_query_transmittance's walk over the shadow rays still under way
+ * with a dense launch each, and a launch that adds every ray's samples up.
+ *   surface      (no TGHIP_DIRECT_VOLUME)  the point is the closest hit of ray i in [tmin, tmax): bit for bit tghip_query_surface's on the same context;
+ *   mode         `rec` is its TgHipHit::rec.  A miss answers zeros with rec = -1 and count = 0.  At a hit every sample s is one
+ *                estimateDirect(event, medium, desc->bounce, ray, &transmittance), event = makeLocalScatterEvent(data, info, ray, sampler)
+ *                (TraceBase.cpp:24-51: the frame flipped for two-sided shading), medium the one the ray travels in, transmittance initialised to -1
+ *                as PathTracer.cpp:70 does.  Inside, operation for operation: chooseLight; sampleDirect's early return for pure-specular and forward
+ *                materials; lightSample and -- not for a Dirac light -- bsdfSample (:246-321) with isConsistent, selectMedium by the geometric side of
+ *                each shadow ray, attenuatedEmission (:144-174: the light's own intersect, the 1 + 1e-3 distance test, a Dirac light's ray cut at the
+ *                sampled distance, generalizedShadowRay with the light as end cap, startsOnSurface = endsOnSurface = true), evalDirect, directPdf and
+ *                the power heuristic.  A triangle-mesh emitter's own intersect is the scene walk, as in a pass: its hit is the first one of the shadow
+ *                walk that is the mesh.
+ *   volume mode  (TGHIP_DIRECT_VOLUME)  the point is rays[i].o, rays[i].d the direction the path arrived along (parentRay.dir()); tmin and tmax are
+ *                ignored and no walk precedes the estimate.  Every sample is one volumeEstimateDirect (:470-481, 323-381, 402-414) with the phase
+ *                function of the start medium: shadow rays with epsilon 0, startsOnSurface = false, no selectMedium.  A ray that starts in no medium
+ *                answers zeros with count = 0.  rec = -1, and visibility_count stays 0: the reference passes no `transmittance` there.
+ *   rgb          the float32 sum of the samples' estimates, added one by one in sample-index order from zero.  Multiplied by no throughput; nothing is
+ *                added for an emissive hit.  The conditions around the call in handleSurface (enable_light_sampling, bounce < max_bounces - 1) are
+ *                the caller's business; min_bounces and max_bounces act only where generalizedShadowRay reads them.  A scene without lights answers
+ *                zeros.  No option and no internal division of the work changes a bit of it.
+ *   visibility   the sum, in the same order, of transmittance.avg() over the samples whose light sample got as far as its shadow ray, and
+ *   .._count     how many those were: what PathTracer.cpp:93-94 feeds the visibility output with.
+ *   count        the samples taken: spp_end - spp_begin at a hit (in a medium), 0 otherwise.
+ *   numbers      ray i, sample s draws from the counter-based stream keyed (seed, i, s) (csrc/hip/pt_math.h: rngStart), s in [spp_begin, spp_end); after
+ *                `skip` numbers drawn and thrown away, in the reference's order: chooseLight's one number when it is called (light = -1) and the
+ *                scene has more than one light, then sampleDirect's, then the BSDF's or the phase function's.  There is no Sobol' form.
+ *   light        -1: chooseLight.  k >= 0: the light in slot k of TgHipSceneDesc::lights with weight 1 and no chooseLight draw.
+ *   medium,      as tghip_query_transmittance's: media NULL, every ray starts in desc->medium; else n words, ray i starts in media[i] and desc->medium
+ *   media        is only checked.
+ *   memory       flags without TGHIP_DEVELOP_DEVICE_POINTERS: rays, media and out are host memory, staged through buffers of the context that only
+ *                grow; with it: memory of the context's device, rays and out 16-byte aligned, media 4-byte aligned.  Nothing is allocated per call
+ *                once the scratch has grown (it grows to a fixed number of items; larger calls run in parts).
+ * All-features arithmetic, so an answer never depends on the scene's shading family.  Runs on the context's stream, waits for a running pass like
+ * tghip_query_rays, returns when the answers are complete and leaves the framebuffer, the SampleRecords, the auxiliary and the per-sample buffers as
+ * they were.  "query_blocks" and "query_refill_at" steer the walks and never change an answer.  n == 0 succeeds.  TGHIP_E_NOSCENE without an upload,
+ * decided before the arguments are looked at, a missing description apart, as tghip_query_transmittance.  TGHIP_E_INVALID, the context still usable:
+ * no description, NULL rays or out with n > 0, unknown flag bits, n > 2^31 - 1, misaligned device pointers, desc->medium below -2 or >= num_media or
+ * naming an operand entry of an `interpolated` medium, spp_end <= spp_begin, skip > 1024, light below -1 or >= num_lights, bounce > 255, volume mode
+ * with media == NULL and a desc->medium that resolves to no medium.  TGHIP_E_UNSUPPORTED: n (spp_end - spp_begin) >= 2^32 (tungsten_host.h:
+ * tgh_query_direct_check is the same check on its own). */
+#define TGHIP_DIRECT_VOLUME 2u           /* flags; bit 0 stays TGHIP_DEVELOP_DEVICE_POINTERS */
+typedef struct TgHipDirectQueryDesc {
+    uint32_t flags;
+    uint32_t seed;
+    uint32_t spp_begin, spp_end;         /* sample indices [spp_begin, spp_end) of every ray */
+    int32_t  medium;                     /* as TgHipTransmittanceQueryDesc::medium: index, TGHIP_MEDIUM_NONE, TGHIP_MEDIUM_OF_CAMERA */
+    uint32_t bounce;                     /* the `bounce` handed to estimateDirect (a pass's camera vertex hands 1) */
+    int32_t  light;                      /* -1: chooseLight; k >= 0: slot k of TgHipSceneDesc::lights, weight 1, no chooseLight draw */
+    uint32_t skip;                       /* numbers of the stream drawn and thrown away first, <= 1024 */
+} TgHipDirectQueryDesc;                  /* 32 B */
+typedef struct TgHipDirect {
+    float    rgb[3];                     /* float32 sum of the samples' estimates, added one by one in sample-index order from zero */
+    float    visibility;                 /* sum of transmittance.avg() over the samples that recorded one */
+    uint32_t count, visibility_count;
+    int32_t  rec;                        /* surface mode: TgHipHit::rec of the hit, -1 = miss; volume mode: -1 */
+    uint32_t reserved;                   /* 0 */
+} TgHipDirect;                           /* 32 B */
+int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const TgHipRay *rays,
+                       const int32_t *media /* n start media, may be NULL */, TgHipDirect *out, size_t n);
+/* Instrumentation: HIP-event time from the first launch to the last of the context's last tghip_query_direct, in milliseconds -- the walks, the dense
+ * launches and the one-word read-backs between the rounds (profiles/direct_query/bench.txt) */
+int tghip_query_direct_kernel_time(tghip_ctx *ctx, double *ms);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

@@ -267,6 +267,19 @@ typedef struct TgHostTransmittanceScene {
 int tgh_query_transmittance_check(const TgHipTransmittanceQueryDesc *desc, const void *rays, const void *media, const void *out, size_t n,
                                   const TgHostTransmittanceScene *scene, char *err, size_t errlen);
 
+/* What tghip_query_direct decides about a call before it touches the device (csrc/host/DirectQuery.cpp), on its own, no device: TGHIP_OK, or the
+ * call's refusal -- TGHIP_E_INVALID, or TGHIP_E_UNSUPPORTED for n (spp_end - spp_begin) >= 2^32 items -- and in `err` its message.  `scene`: what the
+ * refusals that depend on the uploaded scene read -- per entry of media[] whether it is an operand of an `interpolated` medium (NULL: none is), the
+ * number of sampled lights, the medium the camera is in (-1: none); NULL checks a call against a scene without media and lights.  Only the pointers'
+ * values of rays, media and out are looked at, nothing is read through them. */
+typedef struct TgHostDirectScene {
+    uint32_t num_media;   const uint8_t *medium_operand;   /* num_media bytes, or NULL */
+    uint32_t num_lights;
+    int32_t  camera_medium;
+} TgHostDirectScene;
+int tgh_query_direct_check(const TgHipDirectQueryDesc *desc, const void *rays, const void *media, const void *out, size_t n,
+                           const TgHostDirectScene *scene, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

@@ -45,6 +45,9 @@ SURFACE_DTYPE = np.dtype([("p", np.float32, 3), ("t", np.float32), ("ng", np.flo
                           ("emission", np.float32, 3), ("reserved", np.uint32)])
 # capi.TgHipTransmittance (Renderer.query_transmittance)
 TRANSMITTANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("crossed", np.uint32)])
+# capi.TgHipDirect (Renderer.query_direct)
+DIRECT_DTYPE = np.dtype([("rgb", np.float32, 3), ("visibility", np.float32), ("count", np.uint32), ("visibility_count", np.uint32), ("rec", np.int32),
+                         ("reserved", np.uint32)])
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 QUERY_MODE_NAMES = ("closest", "occluded")                                  # capi.TGHIP_QUERY_*
@@ -315,6 +318,57 @@ class Renderer(object):
         desc = self._transmittance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, medium, end_cap, bounce, starts_on_surface, ends_on_surface)
         ctx = self.context(device)
         if lib.tghip_query_transmittance(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None, out.data_ptr(), n) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+
+    def _direct_desc(self, flags, spp, seed, medium, bounce, light, skip, volume):
+        if medium == "camera":
+            medium = capi.TGHIP_MEDIUM_OF_CAMERA
+        elif medium is None:
+            medium = capi.TGHIP_MEDIUM_NONE
+        if volume:
+            flags |= capi.TGHIP_DIRECT_VOLUME
+        begin, end = (0, spp) if np.isscalar(spp) else spp
+        return capi.TgHipDirectQueryDesc(flags, int(seed) & 0xFFFFFFFF, int(begin), int(end), int(medium), int(bounce), int(light), int(skip))
+
+    def query_direct(self, rays, spp=1, seed=DEFAULT_SEED, medium="camera", media=None, bounce=1, light=-1, skip=0, volume=False, device=0):
+        """Direct lighting at the closest hit of every ray (tghip_query_direct, TraceBase::estimateDirect), or with volume=True at the rays' origins
+        inside a medium (volumeEstimateDirect): rays [N,8] float32 (o, tmin, d, tmax) -> a structured array [N] of DIRECT_DTYPE: rgb, the sum of the
+        estimates of the sample indices spp (a number: 0 .. spp - 1, or a pair (begin, end)) drawn from the stream keyed (seed, ray index, sample
+        index) behind `skip` discarded numbers; visibility and visibility_count, the light samples' shadow-ray transmittance as the visibility
+        output takes it; count, the samples taken; rec, the hit's record.  medium: the medium every ray travels in -- an index, None, or "camera" for
+        the one the scene's camera is in; media: int32 [N], per ray instead.  bounce: the bounce handed to estimateDirect; light: -1 for
+        chooseLight, or a slot of the scene's lights."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.empty(rays.shape[0], DIRECT_DTYPE)
+        if media is not None:
+            media = np.ascontiguousarray(media, np.int32).reshape(-1)
+            if media.size != rays.shape[0]:
+                raise TungstenError("query_direct: media must hold one entry per ray")
+        desc = self._direct_desc(0, spp, seed, medium, bounce, light, skip, volume)
+        ctx = self.context(device)
+        if lib.tghip_query_direct(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None, out.ctypes.data,
+                                  rays.shape[0]) != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        return out
+
+    def query_direct_into(self, rays, out, spp=1, seed=DEFAULT_SEED, medium="camera", media=None, bounce=1, light=-1, skip=0, volume=False, device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 8
+        elements -- the words of DIRECT_DTYPE, the integer ones as their bits --, media None or int32 [N], all contiguous.  The answers are complete
+        when the call returns."""
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        tensors = [("rays", rays, "torch.float32", 8), ("out", out, "torch.float32", 8)]
+        if media is not None:
+            tensors.append(("media", media, "torch.int32", 1))
+        for name, t, dtype, size in tensors:
+            if str(t.dtype) != dtype:
+                raise TungstenError("query_direct_into: %s must be %s, not %s" % (name, dtype, t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("query_direct_into: %s must live on the context's device (cuda:%d)" % (name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("query_direct_into: rays must be contiguous [N, 8], out contiguous with N x 8 and media with N elements")
+        desc = self._direct_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, spp, seed, medium, bounce, light, skip, volume)
+        ctx = self.context(device)
+        if lib.tghip_query_direct(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None, out.data_ptr(), n) != 0:
             raise TungstenError(lib.tghip_last_error(ctx).decode())
 
     def debug_libm(self, fn, x, device=0):

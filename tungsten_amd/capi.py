@@ -255,6 +255,21 @@ class TgHostTransmittanceScene(C.Structure):
     _fields_ = [("num_media", u32), ("medium_operand", C.POINTER(C.c_uint8)), ("num_objects", u32), ("object_type", C.POINTER(i32))]
 
 
+TGHIP_DIRECT_VOLUME = 2
+
+
+class TgHipDirectQueryDesc(C.Structure):
+    _fields_ = [("flags", u32), ("seed", u32), ("spp_begin", u32), ("spp_end", u32), ("medium", i32), ("bounce", u32), ("light", i32), ("skip", u32)]
+
+
+class TgHipDirect(C.Structure):
+    _fields_ = [("rgb", f32*3), ("visibility", f32), ("count", u32), ("visibility_count", u32), ("rec", i32), ("reserved", u32)]
+
+
+class TgHostDirectScene(C.Structure):
+    _fields_ = [("num_media", u32), ("medium_operand", C.POINTER(C.c_uint8)), ("num_lights", u32), ("camera_medium", i32)]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -368,6 +383,8 @@ PROTOTYPES = {
     "tghip_query_transmittance": (C.c_int, [VP, C.POINTER(TgHipTransmittanceQueryDesc), VP, VP, VP, C.c_size_t]),
     "tghip_query_transmittance_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_query_transmittance_rounds": (C.c_int, [VP, C.POINTER(C.c_uint32)]),
+    "tghip_query_direct": (C.c_int, [VP, C.POINTER(TgHipDirectQueryDesc), VP, VP, VP, C.c_size_t]),
+    "tghip_query_direct_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -450,6 +467,7 @@ PROTOTYPES = {
     "tgh_query_surface_check": (C.c_int, [C.POINTER(TgHipSurfaceQueryDesc), VP, VP, C.c_size_t, C.c_char_p, C.c_size_t]),
     "tgh_query_transmittance_check": (C.c_int, [C.POINTER(TgHipTransmittanceQueryDesc), VP, VP, VP, C.c_size_t, C.POINTER(TgHostTransmittanceScene),
                                                 C.c_char_p, C.c_size_t]),
+    "tgh_query_direct_check": (C.c_int, [C.POINTER(TgHipDirectQueryDesc), VP, VP, VP, C.c_size_t, C.POINTER(TgHostDirectScene), C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

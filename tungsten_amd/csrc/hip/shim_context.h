@@ -169,6 +169,16 @@ struct tghip_ctx {
     DeviceArray<uint32_t> trList[2];
     double trMs = 0.0;
     uint32_t trRounds = 0;
+    // tghip_query_direct: the items and shadow segments of the chunk under way (csrc/hip/direct_query.h: DirectState), the hits of the chunk's rays,
+    // the two index lists the rounds alternate between, the start media and the answers on the device when the caller's are host memory (all grown
+    // on demand, the state to at most DIRECT_QUERY_CHUNK items; the counter words, the staged rays and the two options are tghip_query_rays'), the time
+    // of the last call's launches
+    DeviceArray<float4> dqOrigin, dqO, dqD, dqHits, dqT, dqC, dqE, dqRes, dqRayHits, dqOut;
+    DeviceArray<uint4> dqB;
+    DeviceArray<float> dqWeight;
+    DeviceArray<int> dqInst, dqRayInst, dqMedia;
+    DeviceArray<uint32_t> dqStatus, dqList[2];
+    double dqMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context (tghipDestroyRankComm)
     int rankCount = 0, rankIndex = 0;
     DeviceArray<float> redSum;            // the reduces (reduce.hip): where the reduced image lands when this context is the root (grown: a re-upload

@@ -11,10 +11,12 @@
 #include "radiance_query.h"
 #include "surface_query.h"
 #include "transmittance_query.h"
+#include "direct_query.h"
 #include "../host/RayQuery.hpp"
 #include "../host/RadianceQuery.hpp"
 #include "../host/SurfaceQuery.hpp"
 #include "../host/TransmittanceQuery.hpp"
+#include "../host/DirectQuery.hpp"
 
 #include <chrono>
 
@@ -1842,6 +1844,106 @@ int tghip_query_transmittance_rounds(tghip_ctx *ctx, uint32_t *rounds)
     *rounds = ctx->trRounds;
     return TGHIP_OK;
 }
+
+// (ray, sample) items of tghip_query_direct that are under way at once: what its scratch grows to at most (about 300 bytes an item); a larger call
+// runs in parts, whole rays where a ray's samples fit and runs of one ray's samples where they do not.  A part changes no bit of an answer: a ray's
+// samples are added in sample order, a later part going on from the sums the earlier ones stored.
+#define DIRECT_QUERY_CHUNK (1u << 20)
+// rounds of shadow walks per part, whatever the scene's max_bounces
+#define DIRECT_QUERY_MAX_ROUNDS 257
+
+int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const TgHipRay *rays, const int32_t *media, TgHipDirect *out, size_t n)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_query_direct: no description"; return TGHIP_E_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "tghip_query_direct before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
+    const TgHostDirectScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), ctx->scene.num_lights, ctx->sc.cameraMedium};
+    int rc = checkDirectQuery(desc, rays, media, out, n, &facts, ctx->error);
+    if (rc != TGHIP_OK) return rc;
+    if (n == 0) return TGHIP_OK;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0, volume = (desc->flags & TGHIP_DIRECT_VOLUME) != 0;
+    const size_t outBytes = n*sizeof(TgHipDirect);
+    HIP_TRY(ctx, ctx->queryCounter.once(16));
+    const float4 *dRays = nullptr;
+    const int *dMedia = nullptr;
+    float4 *dOut = nullptr;
+    if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
+    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->dqMedia, dMedia)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->dqOut, dOut)) != TGHIP_OK) return rc;
+    // the walk and the workgroups of tghip_query_rays on this scene
+    const LaunchChoice &choice = ctx->lp.choice;
+    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
+    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
+                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
+    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    auto blocksFor = [&](uint32_t live) {
+        // workgroups: as many as stay resident, no more than there are waves for (a workgroup without a ray only reads the counter)
+        const size_t perWave = (size_t(live) + 63)/64;
+        return ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
+                                    : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
+    };
+    // the parts: raysPer rays by samplesPer samples, at most DIRECT_QUERY_CHUNK items
+    const uint64_t spp = uint64_t(desc->spp_end) - desc->spp_begin;
+    const uint64_t samplesPer = std::min<uint64_t>(spp, DIRECT_QUERY_CHUNK);
+    const uint64_t raysPer = std::min<uint64_t>(n, std::max<uint64_t>(1, DIRECT_QUERY_CHUNK/samplesPer));
+    const size_t items = size_t(raysPer*samplesPer);
+    if ((rc = ctx->dqStatus.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqWeight.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqOrigin.grow(ctx, items)) != TGHIP_OK ||
+        (rc = ctx->dqO.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqD.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqHits.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqT.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqB.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqC.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK)
+        return rc;
+    if (inst && (rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK) return rc;
+    if (!volume && (rc = ctx->dqRayHits.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
+    if (!volume && inst && (rc = ctx->dqRayInst.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
+    const DirectState st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
+                            inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
+    // (the shadow walks are tghip_query_transmittance's, reading segments through a list: of its state they touch o, d, hits and inst)
+    const TransmittanceState walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
+    const float4 *rayHits = volume ? nullptr : ctx->dqRayHits.get();
+    int *rayInst = !volume && inst ? ctx->dqRayInst.get() : nullptr;
+    DirectParams p;
+    p.seed = desc->seed; p.skip = desc->skip; p.bounce = desc->bounce; p.light = desc->light;
+    p.cameraMedium = ctx->sc.cameraMedium;
+    p.medium = desc->medium == TGHIP_MEDIUM_OF_CAMERA ? p.cameraMedium : desc->medium;
+    uint32_t *counters = ctx->queryCounter.get();
+    return timedLaunches(ctx, ctx->dqMs, [&]() -> int {
+        for (uint64_t r0 = 0; r0 < n; r0 += raysPer) {
+            for (uint64_t s0 = desc->spp_begin; s0 < desc->spp_end; s0 += samplesPer) {
+                p.ray0 = uint32_t(r0); p.rays = uint32_t(std::min<uint64_t>(raysPer, n - r0));
+                p.sample0 = uint32_t(s0); p.samples = uint32_t(std::min<uint64_t>(samplesPer, desc->spp_end - s0));
+                p.first = s0 == desc->spp_begin ? 1u : 0u;
+                HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
+                if (!volume && p.first)      // the point: tghip_query_surface's walk as it is (the hits stay for the ray's later parts)
+                    HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays + r0*2u, ctx->dqRayHits.get(), rayInst, p.rays, counters, blocksFor(p.rays), refillAt, lds));
+                HIP_TRY(ctx, directQueryLaunchSetup(ctx->stream, ctx->scene, p, volume, dRays, dMedia, rayHits, rayInst, st, ctx->dqList[1].get(), counters + 1));
+                uint32_t live = 0;
+                HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                // A segment that goes on has crossed a surface (bounce++) and bounce >= max_bounces ends it: the rounds are bounded whatever the rays do
+                for (int round = 0; live > 0; ++round) {
+                    if (round >= DIRECT_QUERY_MAX_ROUNDS) { ctx->error = "tghip_query_direct: shadow rays still under way after 257 rounds"; return TGHIP_E_UNSUPPORTED; }
+                    const uint32_t *list = ctx->dqList[(round + 1) & 1].get();
+                    uint32_t *next = ctx->dqList[round & 1].get();
+                    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
+                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, walk, nullptr, walkState, list, live, counters, blocksFor(live), refillAt, lds));
+                    HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, list, live, next, counters + 1));
+                    // the one word a round hands back: how many segments the next one has
+                    HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                }
+                HIP_TRY(ctx, directQueryLaunchFinish(ctx->stream, p, volume, dMedia, ctx->scene.num_media, rayHits, st, dOut));
+            }
+        }
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, out, dOut, outBytes); });
+}
+
+int tghip_query_direct_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::dqMs, ms); }
 
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out)
 {
