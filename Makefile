@@ -20,9 +20,11 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 # the shim (tungsten_hip.hip; its context: shim_context.h, device_array.h) + reduce.hip, its RCCL reduces (host code only) + one translation unit per family of
 # explicit instantiations (pt_instances.h lists each unit's; they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
-# + ray_query.hip, the kernels of tghip_query_rays (its argument check csrc/host/RayQuery.cpp comes in through HOSTSRC)
+# + ray_query.hip, the kernels of tghip_query_rays (its argument check csrc/host/RayQuery.cpp comes in through HOSTSRC; the claim, the ray load and the
+#   8-wide loop it shares with the units below: query_walk.h, query_walk_wide.h; the clauses the five checks share: csrc/host/QueryCheck.hpp)
 # + radiance_query.hip, the ray source and the result copy of tghip_query_radiance (its check and virtual image, csrc/host/RadianceQuery.cpp, likewise)
-# + surface_query.hip, the walk and the dense launch of tghip_query_surface (its argument check, csrc/host/SurfaceQuery.cpp, likewise)
+# + surface_query.hip, the instanced walk and the dense launch of tghip_query_surface -- its other walks are ray_query.hip's kernels -- (its argument check,
+#   csrc/host/SurfaceQuery.cpp, likewise)
 # + transmittance_query.hip, the walk and the dense launch of a round of tghip_query_transmittance (its argument check, csrc/host/TransmittanceQuery.cpp, likewise)
 # + direct_query.hip, the three dense launches of tghip_query_direct around those two units' walks (its argument check, csrc/host/DirectQuery.cpp, likewise)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)

@@ -194,6 +194,37 @@ def test_options_change_no_byte(name, leg, scene):
     assert same_bytes(s.ask(g, 65), full[:65])
 
 
+def test_queries_that_share_scratch_leave_nothing_stale(scene):
+    """tghip_query_transmittance and tghip_query_direct stage a caller's host arrays in the same device scratch, the answers and the per-ray start
+    media: a transmittance query of 129 rays, a direct query of 65 with other media, the transmittance query again, on one context -- each answer is
+    the bytes of the same call on a context that has answered nothing else."""
+    s, g = scene("dq_fog_smoke"), group("media_per_ray")
+    kw = s.params(g)
+    at = np.arange(129) % len(g["rays"])
+    rays, media = np.ascontiguousarray(g["rays"][at]), np.ascontiguousarray(kw["media"][at])
+    short = rays.copy()
+    short[:, 7] = 0.25                               # (segments that mostly end in the medium they start in, not on a wall)
+
+    def transmittance(r):
+        return r.query_transmittance(short, media=media)
+
+    def direct(r):
+        return r.query_direct(rays[:65], **dict(kw, media=np.ascontiguousarray(media[::-1][:65])))
+
+    got = [transmittance(s.renderer), direct(s.renderer), transmittance(s.renderer)]
+    want = []
+    for call in (transmittance, direct):
+        fresh = tg.Renderer(s.path)
+        try:
+            want.append(call(fresh))
+        finally:
+            fresh.close()
+    print("transmittance: %d of 129 rays let light through, %d different answers; direct: %d of 65 rays lit"
+          % ((got[0]["rgb"] > 0).any(axis=1).sum(), len(np.unique(got[0]["rgb"], axis=0)), (got[1]["rgb"] != 0).any(axis=1).sum()))
+    assert same_bytes(got[0], want[0]) and same_bytes(got[1], want[1]) and same_bytes(got[2], want[0])
+    assert (got[0]["rgb"] > 0).any() and (got[1]["count"] > 0).any()
+
+
 @pytest.mark.skipif(not scenes.have_materialtest(), reason="materialtest assets (assets/) not present")
 def test_the_wide_walk(tmp_path):
     """materialtest walks the 8-wide BVH: prefixes, repeated calls and the walk's options give the same bytes there too"""

@@ -168,6 +168,27 @@ def test_the_batches_cover_the_walks(batch):
     assert need <= set(walks.values()), walks
 
 
+@pytest.mark.parametrize("scene, options, walk", [("cornell", {}, 0), ("terraces", {"wide_bvh": 0}, 1), ("terraces", {}, 3)])
+def test_the_walks_without_instances_are_query_rays_walks(scene, options, walk, batch):
+    """On the flat list, the BVH2 and the 8-wide BVH the surface query walks with tghip_query_rays' own closest-hit kernels: record and t are that
+    query's, at one ray, one wave plus one and more than one workgroup."""
+    b = batch(scene)
+    r = b.renderer
+    try:
+        for k, v in options.items():
+            r.set_option(k, v)
+        assert ray_walk(r) == walk
+        for n in (1, 65, 257):
+            got, closest = r.query_surface(b.rays[:n]), r.query_rays(b.rays[:n], "closest")
+            hit = closest["rec"] >= 0
+            assert (got["rec"] == closest["rec"]).all(), (scene, walk, n)
+            assert same_bytes(got["t"][hit], closest["t"][hit]) and (got["t"][~hit].view(np.uint32) == 0).all(), (scene, walk, n)
+        assert hit.any()
+    finally:
+        for k in options:
+            r.set_option(k, 1)
+
+
 def quat_rotate(q, v):
     """Quaternions [n, 4] (w, x, y, z) times vectors [n, 3], float64 (math/Quaternion.hpp:78-88)"""
     w, qv = q[:, 0:1], q[:, 1:4]

@@ -165,25 +165,58 @@ class Renderer(object):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         hits = np.empty(rays.shape[0], dtype=[("t", np.float32), ("u", np.float32), ("v", np.float32), ("rec", np.int32)])
         ms = C.c_double(0.0)
-        rc = lib.tghip_trace_rays(self.context(device), rays.ctypes.data, hits.ctypes.data, rays.shape[0], int(repeats), C.byref(ms))
-        if rc != 0:
-            raise TungstenError(lib.tghip_last_error(self.context(device)).decode())
+        self._raise_last(self.context(device), lib.tghip_trace_rays(self.context(device), rays.ctypes.data, hits.ctypes.data, rays.shape[0], int(repeats), C.byref(ms)))
         return hits, ms.value
+
+    def _raise_last(self, ctx, rc):
+        if rc != 0:
+            raise TungstenError(lib.tghip_last_error(ctx).decode())
+
+    @staticmethod
+    def _query_arrays(fn, rays, media=None):
+        """The host arrays of a query: rays as float32 [N,8] and, where given, media as int32 [N]."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if media is not None:
+            media = np.ascontiguousarray(media, np.int32).reshape(-1)
+            if media.size != rays.shape[0]:
+                raise TungstenError("%s: media must hold one entry per ray" % fn)
+        return rays, media
+
+    @staticmethod
+    def _query_tensors(fn, device, tensors, shapes):
+        """The torch tensors of a query_*_into: (name, tensor or None, dtypes, elements per ray), the rays first -- each of one of its dtypes, on the
+        context's device, contiguous and of N x elements, which `shapes` says in words.  Returns N."""
+        rays = tensors[0][1]
+        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        for name, t, dtypes, size in tensors:
+            if t is None:
+                continue
+            if str(t.dtype) not in dtypes:
+                raise TungstenError("%s: %s must be %s, not %s" % (fn, name, " or ".join(dtypes), t.dtype))
+            if not t.is_cuda or t.get_device() != device:
+                raise TungstenError("%s: %s must live on the context's device (cuda:%d)" % (fn, name, device))
+            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
+                raise TungstenError("%s: %s" % (fn, shapes))
+        return n
+
+    @staticmethod
+    def _query_medium(medium):
+        """An index, or "camera" / None as the C interface spells them"""
+        return capi.TGHIP_MEDIUM_OF_CAMERA if medium == "camera" else capi.TGHIP_MEDIUM_NONE if medium is None else int(medium)
 
     def query_rays(self, rays, mode="closest", device=0):
         """Batched TraceableScene::intersect / ::occluded (tghip_query_rays): rays [N,8] float32 (o, tmin, d, tmax) -> with mode "closest" the
         structured hits of trace_rays (t, u, v, rec; the same bits), with "occluded" uint8 [N]: 1 where the closest-hit query has a hit."""
         if mode not in QUERY_MODE_NAMES:
             raise TungstenError("query_rays: mode must be 'closest' or 'occluded', not %r" % (mode,))
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        rays, _ = self._query_arrays("query_rays", rays)
         if mode == "closest":
             out = np.empty(rays.shape[0], dtype=[("t", np.float32), ("u", np.float32), ("v", np.float32), ("rec", np.int32)])
         else:
             out = np.empty(rays.shape[0], np.uint8)
         desc = capi.TgHipRayQueryDesc(QUERY_MODE_NAMES.index(mode), 0)
         ctx = self.context(device)
-        if lib.tghip_query_rays(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_rays(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]))
         return out
 
     def query_rays_into(self, rays, out, mode="closest", device=0):
@@ -193,18 +226,12 @@ class Renderer(object):
         if mode not in QUERY_MODE_NAMES:
             raise TungstenError("query_rays_into: mode must be 'closest' or 'occluded', not %r" % (mode,))
         closest = mode == "closest"
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
-        for name, t, dtype, size in (("rays", rays, "torch.float32", 8), ("out", out, "torch.float32" if closest else "torch.uint8", 4 if closest else 1)):
-            if str(t.dtype) != dtype:
-                raise TungstenError("query_rays_into: %s must be %s, not %s" % (name, dtype, t.dtype))
-            if not t.is_cuda or t.get_device() != device:
-                raise TungstenError("query_rays_into: %s must live on the context's device (cuda:%d)" % (name, device))
-            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
-                raise TungstenError("query_rays_into: rays must be contiguous [N, 8] and out contiguous with N x %d elements" % (4 if closest else 1))
+        n = self._query_tensors("query_rays_into", device, (("rays", rays, ("torch.float32",), 8),
+                                                            ("out", out, ("torch.float32" if closest else "torch.uint8",), 4 if closest else 1)),
+                                "rays must be contiguous [N, 8] and out contiguous with N x %d elements" % (4 if closest else 1))
         desc = capi.TgHipRayQueryDesc(QUERY_MODE_NAMES.index(mode), capi.TGHIP_DEVELOP_DEVICE_POINTERS)
         ctx = self.context(device)
-        if lib.tghip_query_rays(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_rays(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n))
 
     def _radiance_desc(self, flags, spp_begin, spp_end, seed, sobol_seed):
         if sobol_seed is not None:
@@ -216,119 +243,82 @@ class Renderer(object):
         for every ray the sum of PathTracer::traceSample over the sample indices [spp_begin, spp_end), each path starting on the ray behind the
         camera, and the samples counted.  sobol_seed: the SobolPathSampler seed of every ray's "tile" (the scene needs its Sobol' matrices); None
         draws from the counter-based stream keyed (seed, ray index, sample index)."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        rays, _ = self._query_arrays("query_radiance", rays)
         ssum, count = np.empty((rays.shape[0], 3), np.float32), np.empty(rays.shape[0], np.uint32)
         desc = self._radiance_desc(0, spp_begin, spp_end, seed, sobol_seed)
         ctx = self.context(device)
-        if lib.tghip_query_radiance(ctx, C.byref(desc), rays.ctypes.data, ssum.ctypes.data, count.ctypes.data, rays.shape[0]) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_radiance(ctx, C.byref(desc), rays.ctypes.data, ssum.ctypes.data, count.ctypes.data, rays.shape[0]))
         return ssum, count
 
     def query_radiance_into(self, rays, out_sum, out_count, spp_begin=0, spp_end=1, seed=DEFAULT_SEED, sobol_seed=None, device=0):
         """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out_sum float32 with N x 3
         elements, out_count int32 or uint32 with N elements (the counts' bits either way), all contiguous.  The answers are complete when
         the call returns."""
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
-        for name, t, dtype, size in (("rays", rays, ("torch.float32",), 8), ("out_sum", out_sum, ("torch.float32",), 3),
-                                     ("out_count", out_count, ("torch.int32", "torch.uint32"), 1)):
-            if str(t.dtype) not in dtype:
-                raise TungstenError("query_radiance_into: %s must be %s, not %s" % (name, " or ".join(dtype), t.dtype))
-            if not t.is_cuda or t.get_device() != device:
-                raise TungstenError("query_radiance_into: %s must live on the context's device (cuda:%d)" % (name, device))
-            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
-                raise TungstenError("query_radiance_into: rays must be contiguous [N, 8], out_sum contiguous with N x 3 and out_count with N elements")
+        n = self._query_tensors("query_radiance_into", device, (("rays", rays, ("torch.float32",), 8), ("out_sum", out_sum, ("torch.float32",), 3),
+                                                                ("out_count", out_count, ("torch.int32", "torch.uint32"), 1)),
+                                "rays must be contiguous [N, 8], out_sum contiguous with N x 3 and out_count with N elements")
         desc = self._radiance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, spp_begin, spp_end, seed, sobol_seed)
         ctx = self.context(device)
-        if lib.tghip_query_radiance(ctx, C.byref(desc), rays.data_ptr(), out_sum.data_ptr(), out_count.data_ptr(), n) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_radiance(ctx, C.byref(desc), rays.data_ptr(), out_sum.data_ptr(), out_count.data_ptr(), n))
 
     def query_surface(self, rays, device=0):
         """What is at the closest hit of every ray (tghip_query_surface): rays [N,8] float32 (o, tmin, d, tmax) -> a structured array [N] of
         SURFACE_DTYPE: position, t, geometric and shading normal, record, instance, uv, object, bsdf, albedo, flags (capi.TGHIP_SURFACE_*) and
         emission; for a miss the infinite emitter along the ray, if there is one."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        rays, _ = self._query_arrays("query_surface", rays)
         out = np.empty(rays.shape[0], SURFACE_DTYPE)
         desc = capi.TgHipSurfaceQueryDesc(0)
         ctx = self.context(device)
-        if lib.tghip_query_surface(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_surface(ctx, C.byref(desc), rays.ctypes.data, out.ctypes.data, rays.shape[0]))
         return out
 
     def query_surface_into(self, rays, out, device=0):
         """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 24
         elements -- the words of SURFACE_DTYPE, the integer ones as their bits --, both contiguous.  The answers are complete when the call
         returns."""
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
-        for name, t, size in (("rays", rays, 8), ("out", out, 24)):
-            if str(t.dtype) != "torch.float32":
-                raise TungstenError("query_surface_into: %s must be torch.float32, not %s" % (name, t.dtype))
-            if not t.is_cuda or t.get_device() != device:
-                raise TungstenError("query_surface_into: %s must live on the context's device (cuda:%d)" % (name, device))
-            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
-                raise TungstenError("query_surface_into: rays must be contiguous [N, 8] and out contiguous with N x 24 elements")
+        n = self._query_tensors("query_surface_into", device, (("rays", rays, ("torch.float32",), 8), ("out", out, ("torch.float32",), 24)),
+                                "rays must be contiguous [N, 8] and out contiguous with N x 24 elements")
         desc = capi.TgHipSurfaceQueryDesc(capi.TGHIP_DEVELOP_DEVICE_POINTERS)
         ctx = self.context(device)
-        if lib.tghip_query_surface(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_surface(ctx, C.byref(desc), rays.data_ptr(), out.data_ptr(), n))
 
     def _transmittance_desc(self, flags, medium, end_cap, bounce, starts_on_surface, ends_on_surface):
-        if medium == "camera":
-            medium = capi.TGHIP_MEDIUM_OF_CAMERA
-        elif medium is None:
-            medium = capi.TGHIP_MEDIUM_NONE
         if starts_on_surface:
             flags |= capi.TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE
         if ends_on_surface:
             flags |= capi.TGHIP_TRANSMITTANCE_ENDS_ON_SURFACE
-        return capi.TgHipTransmittanceQueryDesc(flags, int(medium), int(end_cap), int(bounce))
+        return capi.TgHipTransmittanceQueryDesc(flags, self._query_medium(medium), int(end_cap), int(bounce))
 
     def query_transmittance(self, rays, media=None, medium="camera", end_cap=-1, bounce=0, starts_on_surface=False, ends_on_surface=False, device=0):
         """How much light gets along every ray (tghip_query_transmittance, TraceBase::generalizedShadowRay): rays [N,8] float32 (o, tmin, d, tmax)
         -> a structured array [N] of TRANSMITTANCE_DTYPE: rgb, and crossed, the see-through surfaces the walk went through.  medium: the medium
         every ray starts in -- an index, None, or "camera" for the one the scene's camera is in; media: int32 [N], per ray instead.  end_cap: the
         object index of the primitive the rays are aimed at, -1 = none; bounce: the bounce count the walk starts with."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        rays, media = self._query_arrays("query_transmittance", rays, media)
         out = np.empty(rays.shape[0], TRANSMITTANCE_DTYPE)
-        if media is not None:
-            media = np.ascontiguousarray(media, np.int32).reshape(-1)
-            if media.size != rays.shape[0]:
-                raise TungstenError("query_transmittance: media must hold one entry per ray")
         desc = self._transmittance_desc(0, medium, end_cap, bounce, starts_on_surface, ends_on_surface)
         ctx = self.context(device)
-        if lib.tghip_query_transmittance(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None, out.ctypes.data,
-                                         rays.shape[0]) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_transmittance(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None,
+                                                            out.ctypes.data, rays.shape[0]))
         return out
 
     def query_transmittance_into(self, rays, out, media=None, medium="camera", end_cap=-1, bounce=0, starts_on_surface=False, ends_on_surface=False,
                                  device=0):
         """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 4
         elements -- rgb and crossed's bits --, media None or int32 [N], all contiguous.  The answers are complete when the call returns."""
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
-        tensors = [("rays", rays, "torch.float32", 8), ("out", out, "torch.float32", 4)]
-        if media is not None:
-            tensors.append(("media", media, "torch.int32", 1))
-        for name, t, dtype, size in tensors:
-            if str(t.dtype) != dtype:
-                raise TungstenError("query_transmittance_into: %s must be %s, not %s" % (name, dtype, t.dtype))
-            if not t.is_cuda or t.get_device() != device:
-                raise TungstenError("query_transmittance_into: %s must live on the context's device (cuda:%d)" % (name, device))
-            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
-                raise TungstenError("query_transmittance_into: rays must be contiguous [N, 8], out contiguous with N x 4 and media with N elements")
+        n = self._query_tensors("query_transmittance_into", device, (("rays", rays, ("torch.float32",), 8), ("out", out, ("torch.float32",), 4),
+                                                                     ("media", media, ("torch.int32",), 1)),
+                                "rays must be contiguous [N, 8], out contiguous with N x 4 and media with N elements")
         desc = self._transmittance_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, medium, end_cap, bounce, starts_on_surface, ends_on_surface)
         ctx = self.context(device)
-        if lib.tghip_query_transmittance(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None, out.data_ptr(), n) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_transmittance(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None,
+                                                            out.data_ptr(), n))
 
     def _direct_desc(self, flags, spp, seed, medium, bounce, light, skip, volume):
-        if medium == "camera":
-            medium = capi.TGHIP_MEDIUM_OF_CAMERA
-        elif medium is None:
-            medium = capi.TGHIP_MEDIUM_NONE
         if volume:
             flags |= capi.TGHIP_DIRECT_VOLUME
         begin, end = (0, spp) if np.isscalar(spp) else spp
-        return capi.TgHipDirectQueryDesc(flags, int(seed) & 0xFFFFFFFF, int(begin), int(end), int(medium), int(bounce), int(light), int(skip))
+        return capi.TgHipDirectQueryDesc(flags, int(seed) & 0xFFFFFFFF, int(begin), int(end), self._query_medium(medium), int(bounce), int(light), int(skip))
 
     def query_direct(self, rays, spp=1, seed=DEFAULT_SEED, medium="camera", media=None, bounce=1, light=-1, skip=0, volume=False, device=0):
         """Direct lighting at the closest hit of every ray (tghip_query_direct, TraceBase::estimateDirect), or with volume=True at the rays' origins
@@ -338,38 +328,25 @@ class Renderer(object):
         output takes it; count, the samples taken; rec, the hit's record.  medium: the medium every ray travels in -- an index, None, or "camera" for
         the one the scene's camera is in; media: int32 [N], per ray instead.  bounce: the bounce handed to estimateDirect; light: -1 for
         chooseLight, or a slot of the scene's lights."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        rays, media = self._query_arrays("query_direct", rays, media)
         out = np.empty(rays.shape[0], DIRECT_DTYPE)
-        if media is not None:
-            media = np.ascontiguousarray(media, np.int32).reshape(-1)
-            if media.size != rays.shape[0]:
-                raise TungstenError("query_direct: media must hold one entry per ray")
         desc = self._direct_desc(0, spp, seed, medium, bounce, light, skip, volume)
         ctx = self.context(device)
-        if lib.tghip_query_direct(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None, out.ctypes.data,
-                                  rays.shape[0]) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_direct(ctx, C.byref(desc), rays.ctypes.data, media.ctypes.data if media is not None else None,
+                                                     out.ctypes.data, rays.shape[0]))
         return out
 
     def query_direct_into(self, rays, out, spp=1, seed=DEFAULT_SEED, medium="camera", media=None, bounce=1, light=-1, skip=0, volume=False, device=0):
         """The same on torch tensors of the context's device, without a copy through the host: rays float32 [N,8], out float32 with N x 8
         elements -- the words of DIRECT_DTYPE, the integer ones as their bits --, media None or int32 [N], all contiguous.  The answers are complete
         when the call returns."""
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
-        tensors = [("rays", rays, "torch.float32", 8), ("out", out, "torch.float32", 8)]
-        if media is not None:
-            tensors.append(("media", media, "torch.int32", 1))
-        for name, t, dtype, size in tensors:
-            if str(t.dtype) != dtype:
-                raise TungstenError("query_direct_into: %s must be %s, not %s" % (name, dtype, t.dtype))
-            if not t.is_cuda or t.get_device() != device:
-                raise TungstenError("query_direct_into: %s must live on the context's device (cuda:%d)" % (name, device))
-            if n < 0 or not t.is_contiguous() or t.numel() != n*size:
-                raise TungstenError("query_direct_into: rays must be contiguous [N, 8], out contiguous with N x 8 and media with N elements")
+        n = self._query_tensors("query_direct_into", device, (("rays", rays, ("torch.float32",), 8), ("out", out, ("torch.float32",), 8),
+                                                              ("media", media, ("torch.int32",), 1)),
+                                "rays must be contiguous [N, 8], out contiguous with N x 8 and media with N elements")
         desc = self._direct_desc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, spp, seed, medium, bounce, light, skip, volume)
         ctx = self.context(device)
-        if lib.tghip_query_direct(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None, out.data_ptr(), n) != 0:
-            raise TungstenError(lib.tghip_last_error(ctx).decode())
+        self._raise_last(ctx, lib.tghip_query_direct(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None,
+                                                     out.data_ptr(), n))
 
     def debug_libm(self, fn, x, device=0):
         """The device's restatement of a host libm function (capi.TGHIP_LIBM_*) evaluated on the device: float32 in, float32 out."""

@@ -134,11 +134,13 @@ struct tghip_ctx {
     DeviceArray<float> nlmBuf[4];
     uint32_t nlmBatch = 0;
     double nlmMs = 0.0;
-    // tghip_query_rays: the work counter the kernel's workgroups claim rays from (one word, reset in-stream before every launch), the rays and the
-    // answers on the device when they are the caller's host memory (grown on demand), the "query_blocks" / "query_refill_at" options (0: the
-    // measured defaults, RAY_QUERY_BLOCKS_PER_CU / RAY_QUERY_REFILL_AT), the kernel's time
+    // What tghip_query_rays, _surface, _transmittance and _direct share (no two run at once: each drains the stream before it returns): the counter
+    // words the walks claim rays from and the dense launches count survivors in (reset in-stream before every launch that reads them); the rays, the
+    // start media and the answers on the device when they are the caller's host memory (grown on demand; a query writes all n of its answers); the
+    // "query_blocks" / "query_refill_at" options (0: the measured defaults, RAY_QUERY_BLOCKS_PER_CU / RAY_QUERY_REFILL_AT); tghip_query_rays' time
     DeviceArray<uint32_t> queryCounter;
     DeviceArray<float4> queryRays, queryOut;
+    DeviceArray<int> queryMedia;
     int queryBlocks = 0, queryRefillAt = 0;
     double queryMs = 0.0;
     // tghip_query_radiance: the plan of the query's pass (kept like `plan`), the framebuffer of its virtual image and that image's tile seeds -- all
@@ -151,32 +153,28 @@ struct tghip_ctx {
     size_t radTileSeedsSet = 0;
     uint32_t radTileSeed = 0;
     double radMs = 0.0;
-    // tghip_query_surface: per ray the hit its walk left and -- instanced scenes -- the instance it was reached through, the answers on the device when
-    // the caller's are host memory (all grown on demand; the counter, the staged rays and the two options are tghip_query_rays'), the event between
-    // the two launches, their time and the dense launch's share of it, the "surface_time_stage" option (1: the getter answers with the share)
-    DeviceArray<float4> surfHits, surfOut;
+    // tghip_query_surface: per ray the hit its walk left and -- instanced scenes -- the instance it was reached through (grown on demand), the event
+    // between the two launches, their time and the dense launch's share of it, the "surface_time_stage" option (1: the getter answers with the share)
+    DeviceArray<float4> surfHits;
     DeviceArray<int> surfInst;
     hipEvent_t evSurfMid = nullptr;
     double surfMs = 0.0, surfDenseMs = 0.0;
     bool surfTimeDense = false;
     // tghip_query_transmittance: the rays' state between the rounds of its wavefront (csrc/hip/transmittance_query.h: TransmittanceState), the two
-    // index lists the rounds alternate between, the start media and the answers on the device when the caller's are host memory (all grown on demand;
-    // the two counter words -- the walk's claims, the survivors -- are queryCounter's first two, the staged rays and the two options
-    // tghip_query_rays'), the time of the last call's rounds and how many it ran
-    DeviceArray<float4> trO, trD, trT, trHits, trOut;
+    // index lists the rounds alternate between (all grown on demand), the time of the last call's rounds and how many it ran
+    DeviceArray<float4> trO, trD, trT, trHits;
     DeviceArray<uint2> trB;
-    DeviceArray<int> trInst, trMedia;
+    DeviceArray<int> trInst;
     DeviceArray<uint32_t> trList[2];
     double trMs = 0.0;
     uint32_t trRounds = 0;
     // tghip_query_direct: the items and shadow segments of the chunk under way (csrc/hip/direct_query.h: DirectState), the hits of the chunk's rays,
-    // the two index lists the rounds alternate between, the start media and the answers on the device when the caller's are host memory (all grown
-    // on demand, the state to at most DIRECT_QUERY_CHUNK items; the counter words, the staged rays and the two options are tghip_query_rays'), the time
-    // of the last call's launches
-    DeviceArray<float4> dqOrigin, dqO, dqD, dqHits, dqT, dqC, dqE, dqRes, dqRayHits, dqOut;
+    // the two index lists the rounds alternate between (all grown on demand, the state to at most DIRECT_QUERY_CHUNK items), the time of the last
+    // call's launches
+    DeviceArray<float4> dqOrigin, dqO, dqD, dqHits, dqT, dqC, dqE, dqRes, dqRayHits;
     DeviceArray<uint4> dqB;
     DeviceArray<float> dqWeight;
-    DeviceArray<int> dqInst, dqRayInst, dqMedia;
+    DeviceArray<int> dqInst, dqRayInst;
     DeviceArray<uint32_t> dqStatus, dqList[2];
     double dqMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context (tghipDestroyRankComm)

@@ -1,8 +1,7 @@
 // What is at the closest hit of caller rays (tghip_query_surface), in two launches on the context's stream.
-//   k_surface_walk*     the closest-hit walks of tghip_query_rays (ray_query.hip: the claim loop, the decoupled loop of the 8-wide BVH, the per-ray
-//                       machines) once more, storing per ray the hit and -- instanced scenes -- the record of the instance it was reached through,
-//                       which k_query_rays computes and drops.  A second instantiation, not a template shared with ray_query.hip: shared, that unit's
-//                       kernels did not come out instruction for instruction as they were (profiles/surface_query/kernel_resources_diff.txt).
+//   the walk            tghip_query_rays' closest-hit kernels themselves (ray_query.hip, through rayQueryLaunch), the hits left in scratch; on
+//                       instanced scenes k_surface_walk<RAY_QUERY_INST>, that unit's per-ray loop storing the record of the instance a hit was
+//                       reached through as well, which k_query_rays computes and drops (the claim and the ray load: query_walk.h).
 //   k_surface_describe  dense, one lane per ray in ray order: IntersectionInfo of the hit (pt_scene.h: intersectionInfo, all seven record kinds and
 //                       through instances), the material's albedo and the primitive's emission as the path tracer's output buffers take them
 //                       (PathTracer.cpp:83-88), or for a miss the infinite emitter along the ray (TraceableScene.hpp:194-209), and the 96 bytes, staged
@@ -12,107 +11,16 @@
 // One instantiation, under the all-features family's mask: every record kind, every texture type, cubeSurface with the reference's tie rule -- an
 // answer never depends on which shading family the scene's passes use.  (FEAT_QMC cleared as in debug_units.hip: nothing here draws a number.)
 #include "surface_query.h"
-#include "pt_wavefront.h"
+#include "query_walk.h"
 
 #define SURFACE_MASK (BSDF_MASK_ALL & ~FEAT_QMC)
 
-namespace {
-
-// The wave's claim: every lane with `idle` set gets the index of a ray of the batch, or one >= n when the batch has been handed out.
-// `exhausted` (wave-uniform) is set by the claim that reaches n.  Called by all 64 lanes.
-PT_DEV uint32_t claimRays(uint32_t *counter, bool idle, uint32_t n, bool &exhausted)
-{
-    const unsigned long long want = __ballot(idle);
-    const uint32_t lane = laneId(), count = (uint32_t)__popcll(want);
-    uint32_t base = 0;
-    if (lane == 0)
-        base = atomicAdd(counter, count);
-    base = __shfl(base, 0);
-    // (the counter cannot wrap: n < 2^31, and every wave adds at most 64 once it has seen n passed)
-    exhausted = base + count >= n;
-    return base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
-}
-
-PT_DEV RayD loadRay(const float4 *rays, uint32_t i)
-{
-    const float4 ro = rays[(size_t)i*2u + 0u], rd = rays[(size_t)i*2u + 1u];
-    RayD ray;
-    ray.o = xyz(ro); ray.d = xyz(rd); ray.tmin = ro.w; ray.tmax = rd.w;
-    return ray;
-}
-
-}  // namespace
-
-// Scenes on the 8-wide BVH: k_query_rays_wide<false>'s loop (ray_query.hip) -- per turn a lane tests at most one pending record and visits at most one
-// node; a lane whose walk is over stores its hit and is idle; the wave claims once `refillAt` of its lanes are.  The closest hit is traverseClosestWide's
-// whatever the turn order, as there.  (These scenes hold no instance.)
-__global__ __launch_bounds__(RAY_QUERY_THREADS) void k_surface_walk_wide(DeviceScene s, const float4 *rays, float4 *hits, uint32_t n, uint32_t *counter, uint32_t refillAt)
-{
-    extern __shared__ int ldsStack[];
-    uint2 *stack = reinterpret_cast<uint2 *>(ldsStack) + threadIdx.x;
-    const int stride = RAY_QUERY_THREADS;
-    bool busy = false, exhausted = false;
-    uint32_t index = 0;
-    RayD ray; ray.o = splat3(0.0f); ray.d = splat3(1.0f); ray.tmin = 0.0f; ray.tmax = 0.0f;
-    WideRay wr; wr.idir = splat3(1.0f); wr.octInv = 0u;
-    WideState w;
-    wideStart(w);
-    float tmax = 0.0f;
-    float4 hit = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-    for (;;) {
-        unsigned long long busyMask = __ballot(busy);
-        if (!exhausted && 64u - (uint32_t)__popcll(busyMask) >= refillAt) {
-            const uint32_t i = claimRays(counter, !busy, n, exhausted);
-            if (!busy && i < n) {
-                index = i;
-                ray = loadRay(rays, i);
-                wr = wideRaySetup(ray);
-                wideStart(w);
-                tmax = ray.tmax;
-                hit = make_float4(tmax, 0.0f, 0.0f, __int_as_float(-1));
-                busy = true;
-            }
-            busyMask = __ballot(busy);
-        }
-        if (busyMask == 0ull)
-            break;                               // (an idle wave has claimed above, refillAt <= 64: the counter has passed n)
-        uint32_t recIdx = 0, nodeIdx = 0;
-        bool hasRec = false, hasNode = false;
-        if (busy) {
-            if (w.triMask == 0u && w.tri2Mask != 0u) { w.triBase = w.tri2Base; w.triMask = w.tri2Mask; w.triValid = w.tri2Valid; w.tri2Mask = 0u; }
-            if (w.triMask) {
-                const uint32_t b = (uint32_t)__ffs((int)w.triMask) - 1u;
-                recIdx = w.triBase + (uint32_t)__popc(w.triValid & ((1u << b) - 1u));
-                w.triMask &= w.triMask - 1u;
-                hasRec = true;
-            }
-            if (w.tri2Mask == 0u)                // (room for the records of the node visited now)
-                hasNode = wideNextNode(w, wr.octInv, stack, stride, nodeIdx);
-        }
-        float4 r0, r1, r2;
-        WideNodeRegs nd;
-        PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
-        if (hasRec) {
-            uint32_t meta;
-            (void)testRecordLoaded<false, KINDS_ALL>(s, recIdx, r0, r1, r2, ray, tmax, hit, meta);
-        }
-        if (hasNode) {
-            const uint32_t ob = w.triBase, om = w.triMask, ov = w.triValid;
-            wideVisit(w, nd, ray.o, wr, ray.tmin, tmax);
-            if (om) { w.tri2Base = w.triBase; w.tri2Mask = w.triMask; w.tri2Valid = w.triValid; w.triBase = ob; w.triMask = om; w.triValid = ov; }
-        }
-        if (busy && wideWalkOver(w)) {    // (in the turn that looked at the walk's last record / node)
-            hits[index] = hit;
-            busy = false;
-        }
-    }
-}
-
-// Flat-list, BVH2 and instanced scenes: k_query_rays<WALK, false>'s loop -- tghip_trace_rays' per-ray functions, claims at ray granularity.  The instanced
-// walk's hitInst, which that kernel drops, is kept.
+// Instanced scenes: k_query_rays<RAY_QUERY_INST, false>'s loop (ray_query.hip) -- tghip_trace_rays' per-ray function, claims at ray granularity -- with
+// the walk's hitInst, which that kernel drops, kept.  (WALK stays a parameter for the kernel's name; the other walks are ray_query.hip's kernels.)
 template<int WALK>
 __global__ __launch_bounds__(RAY_QUERY_THREADS) void k_surface_walk(DeviceScene s, const float4 *rays, float4 *hits, int *inst, uint32_t n, uint32_t *counter)
 {
+    static_assert(WALK == RAY_QUERY_INST, "the walks without instances are rayQueryLaunch's");
     extern __shared__ int ldsStack[];
     int *stack = ldsStack + threadIdx.x;
     const int stride = RAY_QUERY_THREADS;
@@ -123,10 +31,8 @@ __global__ __launch_bounds__(RAY_QUERY_THREADS) void k_surface_walk(DeviceScene 
             const RayD ray = loadRay(rays, i);
             uint32_t nodes = 0, prims = 0;
             int hitInst = -1;
-            const float4 hit = WALK == RAY_QUERY_INST ? traverseClosestInst<false, KINDS_ALL>(s, ray, stack, stride, nodes, prims, hitInst)
-                                                      : traverseClosest<false, WALK == RAY_QUERY_FLAT>(s, ray, stack, stride, nodes, prims);
-            hits[i] = hit;
-            if (WALK == RAY_QUERY_INST) inst[i] = hitInst;
+            hits[i] = traverseClosestInst<false, KINDS_ALL>(s, ray, stack, stride, nodes, prims, hitInst);
+            inst[i] = hitInst;
         }
     }
 }
@@ -208,13 +114,10 @@ __global__ __launch_bounds__(SURFACE_QUERY_THREADS) void k_surface_describe(Devi
 hipError_t surfaceQueryLaunchWalk(hipStream_t stream, const DeviceScene &scene, RayQueryWalk walk, const float4 *rays, float4 *hits, int *inst, uint32_t n,
                                   uint32_t *counter, uint32_t blocks, uint32_t refillAt, size_t ldsBytes)
 {
-    const dim3 grid(blocks), block(RAY_QUERY_THREADS);
-    switch (walk) {
-    case RAY_QUERY_FLAT: hipLaunchKernelGGL((k_surface_walk<RAY_QUERY_FLAT>), grid, block, ldsBytes, stream, scene, rays, hits, inst, n, counter); break;
-    case RAY_QUERY_BVH2: hipLaunchKernelGGL((k_surface_walk<RAY_QUERY_BVH2>), grid, block, ldsBytes, stream, scene, rays, hits, inst, n, counter); break;
-    case RAY_QUERY_INST: hipLaunchKernelGGL((k_surface_walk<RAY_QUERY_INST>), grid, block, ldsBytes, stream, scene, rays, hits, inst, n, counter); break;
-    case RAY_QUERY_WIDE: hipLaunchKernelGGL(k_surface_walk_wide, grid, block, ldsBytes, stream, scene, rays, hits, n, counter, refillAt); break;
-    }
+    // no instance in the scene: the hit is all the walk leaves, and tghip_query_rays' closest-hit kernels leave it
+    if (walk != RAY_QUERY_INST)
+        return rayQueryLaunch(stream, scene, walk, false, rays, hits, n, counter, blocks, refillAt, ldsBytes);
+    hipLaunchKernelGGL((k_surface_walk<RAY_QUERY_INST>), dim3(blocks), dim3(RAY_QUERY_THREADS), ldsBytes, stream, scene, rays, hits, inst, n, counter);
     return hipGetLastError();
 }
 

@@ -1,10 +1,9 @@
 // How much light gets along caller rays (tghip_query_transmittance): TraceBase::generalizedShadowRayImpl<false> (TraceBase.cpp:62-125) as a small
 // wavefront on the context's stream.  Per round two launches:
-//   k_transmittance_walk*     the closest-hit walks of tghip_query_rays (ray_query.hip: the claim loop, the decoupled loop of the 8-wide BVH, the
-//                             per-ray machines) over the rays still under way, read through the round's index list from the SoA state -- round 0
-//                             reads the caller's rays directly --, storing per ray the hit and, instanced scenes, the instance record.  A further
-//                             instantiation of those loops like surface_query.hip's, not a template shared with them: shared, ray_query.hip's
-//                             kernels did not come out instruction for instruction as they were (profiles/surface_query/kernel_resources_diff.txt).
+//   k_transmittance_walk*     the closest-hit walks of tghip_query_rays (the claim and the decoupled loop of the 8-wide BVH: query_walk.h, shared
+//                             with ray_query.hip; the per-ray machines: that unit's loop once more) over the rays still under way, read through
+//                             the round's index list from the SoA state -- round 0 reads the caller's rays directly --, storing per ray the hit
+//                             and, instanced scenes, the instance record.
 //   k_transmittance_segment   dense, one lane per ray of the round: the end-cap test with Embree's box cull for a quad, intersectionInfo and the
 //                             forward-lobe bsdfEval of a see-through surface under the all-features mask, the segment's medium transmittance AFTER the
 //                             transparency (the reference's order), the bounce limits, selectMedium and the step to the hit.  A ray whose walk is
@@ -14,27 +13,14 @@
 // occupancy of whichever lanes of a walking wave just finished -- what k_trace_shadow<., FORWARD>, the per-ray loop of the same function, pays.
 // (FEAT_QMC cleared as in debug_units.hip: nothing here draws a number.)
 #include "transmittance_query.h"
-#include "pt_wavefront.h"
+#include "query_walk.h"
 
 #define TRANSMITTANCE_MASK (BSDF_MASK_ALL & ~FEAT_QMC)
 
 namespace {
 
-// The wave's claim (ray_query.hip): every lane with `idle` set gets a place of the round's list, or one >= n when the list has been handed out.
-PT_DEV uint32_t claimRays(uint32_t *counter, bool idle, uint32_t n, bool &exhausted)
-{
-    const unsigned long long want = __ballot(idle);
-    const uint32_t lane = laneId(), count = (uint32_t)__popcll(want);
-    uint32_t base = 0;
-    if (lane == 0)
-        base = atomicAdd(counter, count);
-    base = __shfl(base, 0);
-    // (the counter cannot wrap: n < 2^31, and every wave adds at most 64 once it has seen n passed)
-    exhausted = base + count >= n;
-    return base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
-}
-
-// Place j of the round: the ray's index in the batch and its current segment
+// Place j of the round: the ray's index in the batch and its current segment.  (The direct case is loadRay's two loads, written out: through
+// loadRay every kernel of this unit came out a few instructions different, profiles/query_walk/kernel_resources_diff.txt.)
 PT_DEV RayD loadSegment(const float4 *rays, const TransmittanceState &st, const uint32_t *list, uint32_t j, uint32_t &i)
 {
     float4 ro, rd;
@@ -47,67 +33,14 @@ PT_DEV RayD loadSegment(const float4 *rays, const TransmittanceState &st, const 
 
 }  // namespace
 
-// Scenes on the 8-wide BVH: k_query_rays_wide<false>'s loop (ray_query.hip).  (These scenes hold no instance.)
+// Scenes on the 8-wide BVH: k_query_rays_wide<false>'s loop (query_walk_wide.h) over the round's segments.  (These scenes hold no instance.)
 __global__ __launch_bounds__(RAY_QUERY_THREADS) void k_transmittance_walk_wide(DeviceScene s, const float4 *rays, TransmittanceState st, const uint32_t *list, uint32_t n,
                                                                                uint32_t *counter, uint32_t refillAt)
 {
-    extern __shared__ int ldsStack[];
-    uint2 *stack = reinterpret_cast<uint2 *>(ldsStack) + threadIdx.x;
-    const int stride = RAY_QUERY_THREADS;
-    bool busy = false, exhausted = false;
-    uint32_t index = 0;
-    RayD ray; ray.o = splat3(0.0f); ray.d = splat3(1.0f); ray.tmin = 0.0f; ray.tmax = 0.0f;
-    WideRay wr; wr.idir = splat3(1.0f); wr.octInv = 0u;
-    WideState w;
-    wideStart(w);
-    float tmax = 0.0f;
-    float4 hit = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-    for (;;) {
-        unsigned long long busyMask = __ballot(busy);
-        if (!exhausted && 64u - (uint32_t)__popcll(busyMask) >= refillAt) {
-            const uint32_t j = claimRays(counter, !busy, n, exhausted);
-            if (!busy && j < n) {
-                ray = loadSegment(rays, st, list, j, index);
-                wr = wideRaySetup(ray);
-                wideStart(w);
-                tmax = ray.tmax;
-                hit = make_float4(tmax, 0.0f, 0.0f, __int_as_float(-1));
-                busy = true;
-            }
-            busyMask = __ballot(busy);
-        }
-        if (busyMask == 0ull)
-            break;                               // (an idle wave has claimed above, refillAt <= 64: the counter has passed n)
-        uint32_t recIdx = 0, nodeIdx = 0;
-        bool hasRec = false, hasNode = false;
-        if (busy) {
-            if (w.triMask == 0u && w.tri2Mask != 0u) { w.triBase = w.tri2Base; w.triMask = w.tri2Mask; w.triValid = w.tri2Valid; w.tri2Mask = 0u; }
-            if (w.triMask) {
-                const uint32_t b = (uint32_t)__ffs((int)w.triMask) - 1u;
-                recIdx = w.triBase + (uint32_t)__popc(w.triValid & ((1u << b) - 1u));
-                w.triMask &= w.triMask - 1u;
-                hasRec = true;
-            }
-            if (w.tri2Mask == 0u)                // (room for the records of the node visited now)
-                hasNode = wideNextNode(w, wr.octInv, stack, stride, nodeIdx);
-        }
-        float4 r0, r1, r2;
-        WideNodeRegs nd;
-        PT_WALK_FETCH(s, r0, r1, r2, nd, hasRec, recIdx, hasNode, nodeIdx);
-        if (hasRec) {
-            uint32_t meta;
-            (void)testRecordLoaded<false, KINDS_ALL>(s, recIdx, r0, r1, r2, ray, tmax, hit, meta);
-        }
-        if (hasNode) {
-            const uint32_t ob = w.triBase, om = w.triMask, ov = w.triValid;
-            wideVisit(w, nd, ray.o, wr, ray.tmin, tmax);
-            if (om) { w.tri2Base = w.triBase; w.tri2Mask = w.triMask; w.tri2Valid = w.triValid; w.triBase = ob; w.triMask = om; w.triValid = ov; }
-        }
-        if (busy && wideWalkOver(w)) {    // (in the turn that looked at the walk's last record / node)
-            st.hits[index] = hit;
-            busy = false;
-        }
-    }
+#define QUERY_WALK_OCCLUDED false
+#define QUERY_WALK_LOAD(j, index) loadSegment(rays, st, list, j, index)
+#define QUERY_WALK_STORE(index, hit, found) st.hits[index] = hit
+#include "query_walk_wide.h"
 }
 
 // Flat-list, BVH2 and instanced scenes: k_query_rays<WALK, false>'s loop, the instanced walk's hitInst kept

@@ -1161,6 +1161,62 @@ static int kernelTime(const tghip_ctx *ctx, double tghip_ctx::*stored, double *m
     return TGHIP_OK;
 }
 
+// Idle lanes of a wave at which the wide walk of tghip_query_rays claims new rays, and its workgroups per CU (swept: profiles/ray_query_ab.txt)
+#define RAY_QUERY_REFILL_AT 48
+#define RAY_QUERY_BLOCKS_PER_CU 2
+
+// How tghip_query_rays, _surface, _transmittance and _direct walk on the uploaded scene: the walk tghip_trace_rays answers with, its stack in LDS,
+// the refill threshold, whether hits are reached through instances, and the workgroups of a launch over `live` rays -- "query_blocks", or as many as
+// stay resident, no more than there are waves for (a workgroup without a ray only reads the counter).
+struct QueryWalk {
+    RayQueryWalk walk;
+    size_t lds;
+    uint32_t refillAt, fixedBlocks, residentBlocks;
+    bool inst;
+    uint32_t blocks(size_t live) const { return fixedBlocks ? fixedBlocks : uint32_t(std::min<size_t>(residentBlocks, ((live + 63)/64 + 3)/4)); }
+};
+static QueryWalk queryWalk(const tghip_ctx *ctx)
+{
+    const LaunchChoice &choice = ctx->lp.choice;
+    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE;
+    QueryWalk q;
+    q.inst = choice.rayWalk == LaunchChoice::RAYS_INST;
+    q.walk = wide ? RAY_QUERY_WIDE : q.inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
+    q.lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
+                 : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
+    q.refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    q.fixedBlocks = uint32_t(std::max(ctx->queryBlocks, 0));
+    q.residentBlocks = uint32_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU;
+    return q;
+}
+
+// A query needs a scene ...
+static int queryScene(tghip_ctx *ctx, const char *fn)
+{
+    if (!ctx->haveScene) ctx->error = std::string(fn) + " before tghip_upload_scene";
+    return ctx->haveScene ? TGHIP_OK : TGHIP_E_NOSCENE;
+}
+// ... and, behind its own argument check, begins like this: the scene; for a batch that is not empty -- the caller answers an empty one -- the pass
+// under way run out (one that was aborted is no error of the query's), the device, the counter words.
+static int queryBegin(tghip_ctx *ctx, const char *fn, size_t n)
+{
+    int rc = queryScene(ctx, fn);
+    if (rc != TGHIP_OK || n == 0) return rc;
+    rc = tghip_wait(ctx);
+    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, ctx->queryCounter.once(16));
+    return TGHIP_OK;
+}
+
+// The start medium of a description: TGHIP_MEDIUM_OF_CAMERA is the camera's
+template<typename Params>
+static void queryStartMedium(const tghip_ctx *ctx, int32_t medium, Params &p)
+{
+    p.cameraMedium = ctx->sc.cameraMedium;
+    p.medium = medium == TGHIP_MEDIUM_OF_CAMERA ? p.cameraMedium : medium;
+}
+
 extern "C" {
 
 int tghip_wait(tghip_ctx *ctx)
@@ -1611,41 +1667,22 @@ int tghip_trace_rays(tghip_ctx *ctx, const TgHipRay *rays, TgHipHit *hits, size_
     return TGHIP_OK;
 }
 
-// Idle lanes of a wave at which the wide walk of tghip_query_rays claims new rays, and its workgroups per CU (swept: profiles/ray_query_ab.txt)
-#define RAY_QUERY_REFILL_AT 48
-#define RAY_QUERY_BLOCKS_PER_CU 2
-
 int tghip_query_rays(tghip_ctx *ctx, const TgHipRayQueryDesc *desc, const TgHipRay *rays, void *out, size_t n)
 {
     if (!ctx) return TGHIP_E_INVALID;
     int rc = checkRayQuery(desc, rays, out, n, ctx->error);
     if (rc != TGHIP_OK) return rc;
-    if (!ctx->haveScene) { ctx->error = "tghip_query_rays before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
-    if (n == 0) return TGHIP_OK;
-    rc = tghip_wait(ctx);
-    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = queryBegin(ctx, "tghip_query_rays", n)) != TGHIP_OK || n == 0) return rc;
     const bool occluded = desc->mode == TGHIP_QUERY_OCCLUDED, device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
     const size_t outBytes = occluded ? n : n*sizeof(TgHipHit);
-    HIP_TRY(ctx, ctx->queryCounter.once(16));
     const float4 *dRays = nullptr;
     float4 *dOut = nullptr;
     if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
     if ((rc = stageOutput(ctx, device, out, outBytes, ctx->queryOut, dOut)) != TGHIP_OK) return rc;
-    // the walk tghip_trace_rays answers with on this scene, and its stack
-    const LaunchChoice &choice = ctx->lp.choice;
-    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE;
-    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : choice.rayWalk == LaunchChoice::RAYS_INST ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
-    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
-                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
-    // workgroups: as many as stay resident, no more than the batch has waves for (a workgroup without a ray only reads the counter)
-    const size_t perWave = (n + 63)/64;
-    const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
-                                                 : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
-    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    const QueryWalk q = queryWalk(ctx);
     HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter.get(), 0, sizeof(uint32_t), ctx->stream));
     return timedLaunches(ctx, ctx->queryMs, [&]() -> int {
-        HIP_TRY(ctx, rayQueryLaunch(ctx->stream, ctx->scene, walk, occluded, dRays, dOut, uint32_t(n), ctx->queryCounter.get(), blocks, refillAt, lds));
+        HIP_TRY(ctx, rayQueryLaunch(ctx->stream, ctx->scene, q.walk, occluded, dRays, dOut, uint32_t(n), ctx->queryCounter.get(), q.blocks(n), q.refillAt, q.lds));
         return TGHIP_OK;
     }, [&]() { return copyBack(ctx, out, dOut, outBytes); });
 }
@@ -1656,13 +1693,10 @@ int tghip_query_radiance(tghip_ctx *ctx, const TgHipRadianceQueryDesc *desc, con
 {
     if (!ctx) return TGHIP_E_INVALID;
     if (!desc) { ctx->error = "tghip_query_radiance: no description"; return TGHIP_E_INVALID; }
-    if (!ctx->haveScene) { ctx->error = "tghip_query_radiance before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
-    int rc = checkRadianceQuery(desc, rays, rgb_sum, count, n, ctx->scene.sobol != nullptr, ctx->error);
+    int rc = queryScene(ctx, "tghip_query_radiance");
     if (rc != TGHIP_OK) return rc;
-    if (n == 0) return TGHIP_OK;
-    rc = tghip_wait(ctx);
-    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = checkRadianceQuery(desc, rays, rgb_sum, count, n, ctx->scene.sobol != nullptr, ctx->error)) != TGHIP_OK) return rc;
+    if ((rc = queryBegin(ctx, "tghip_query_radiance", n)) != TGHIP_OK || n == 0) return rc;
     // the pass over the virtual image (csrc/host/RadianceQuery.cpp).  Its work items hold ONE sample each, whatever "chunk_samples" says, and k_resolve
     // adds them to the ray's sum one by one (runPass: group 1): the order of the additions is part of the answer, not a matter of options.
     const RadianceQueryImage im = radianceQueryImage(n);
@@ -1721,34 +1755,21 @@ int tghip_query_surface(tghip_ctx *ctx, const TgHipSurfaceQueryDesc *desc, const
     if (!ctx) return TGHIP_E_INVALID;
     int rc = checkSurfaceQuery(desc, rays, out, n, ctx->error);
     if (rc != TGHIP_OK) return rc;
-    if (!ctx->haveScene) { ctx->error = "tghip_query_surface before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
-    if (n == 0) return TGHIP_OK;
-    rc = tghip_wait(ctx);
-    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = queryBegin(ctx, "tghip_query_surface", n)) != TGHIP_OK || n == 0) return rc;
     const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
     const size_t outBytes = n*sizeof(TgHipSurface);
-    HIP_TRY(ctx, ctx->queryCounter.once(16));
     const float4 *dRays = nullptr;
     float4 *dOut = nullptr;
     if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
-    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->surfOut, dOut)) != TGHIP_OK) return rc;
-    // the walk and the workgroups of tghip_query_rays on this scene, and what the walk leaves for the dense launch
-    const LaunchChoice &choice = ctx->lp.choice;
-    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
-    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
-    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
-                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
-    const size_t perWave = (n + 63)/64;
-    const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
-                                                 : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
-    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->queryOut, dOut)) != TGHIP_OK) return rc;
+    // what the walk leaves for the dense launch
+    const QueryWalk q = queryWalk(ctx);
     if ((rc = ctx->surfHits.grow(ctx, n)) != TGHIP_OK) return rc;
-    if (inst && (rc = ctx->surfInst.grow(ctx, n)) != TGHIP_OK) return rc;
-    int *dInst = inst ? ctx->surfInst.get() : nullptr;
+    if (q.inst && (rc = ctx->surfInst.grow(ctx, n)) != TGHIP_OK) return rc;
+    int *dInst = q.inst ? ctx->surfInst.get() : nullptr;
     HIP_TRY(ctx, hipMemsetAsync(ctx->queryCounter.get(), 0, sizeof(uint32_t), ctx->stream));
     rc = timedLaunches(ctx, ctx->surfMs, [&]() -> int {
-        HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays, ctx->surfHits.get(), dInst, uint32_t(n), ctx->queryCounter.get(), blocks, refillAt, lds));
+        HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, dRays, ctx->surfHits.get(), dInst, uint32_t(n), ctx->queryCounter.get(), q.blocks(n), q.refillAt, q.lds));
         HIP_TRY(ctx, hipEventRecord(ctx->evSurfMid, ctx->stream));
         HIP_TRY(ctx, surfaceQueryLaunchDescribe(ctx->stream, ctx->scene, dRays, ctx->surfHits.get(), dInst, dOut, uint32_t(n)));
         return TGHIP_OK;
@@ -1769,43 +1790,32 @@ int tghip_query_transmittance(tghip_ctx *ctx, const TgHipTransmittanceQueryDesc 
 {
     if (!ctx) return TGHIP_E_INVALID;
     if (!desc) { ctx->error = "tghip_query_transmittance: no description"; return TGHIP_E_INVALID; }
-    if (!ctx->haveScene) { ctx->error = "tghip_query_transmittance before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
-    const TgHostTransmittanceScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), uint32_t(ctx->sc.objectType.size()), ctx->sc.objectType.data()};
-    int rc = checkTransmittanceQuery(desc, rays, media, out, n, &facts, ctx->error);
+    int rc = queryScene(ctx, "tghip_query_transmittance");
     if (rc != TGHIP_OK) return rc;
-    if (n == 0) return TGHIP_OK;
-    rc = tghip_wait(ctx);
-    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const TgHostTransmittanceScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), uint32_t(ctx->sc.objectType.size()), ctx->sc.objectType.data()};
+    if ((rc = checkTransmittanceQuery(desc, rays, media, out, n, &facts, ctx->error)) != TGHIP_OK) return rc;
+    if ((rc = queryBegin(ctx, "tghip_query_transmittance", n)) != TGHIP_OK || n == 0) return rc;
     const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0;
     const size_t outBytes = n*sizeof(TgHipTransmittance);
-    HIP_TRY(ctx, ctx->queryCounter.once(16));
     const float4 *dRays = nullptr;
     const int *dMedia = nullptr;
     float4 *dOut = nullptr;
     if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
-    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->trMedia, dMedia)) != TGHIP_OK) return rc;
-    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->trOut, dOut)) != TGHIP_OK) return rc;
-    // the walk and the workgroups of tghip_query_rays on this scene
-    const LaunchChoice &choice = ctx->lp.choice;
-    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
-    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
-    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
-                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
-    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
+    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->queryMedia, dMedia)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->queryOut, dOut)) != TGHIP_OK) return rc;
+    const QueryWalk q = queryWalk(ctx);
     // the state between the rounds.  A scene without a forward-lobe BSDF ends every ray in round 0: nothing but the hits is ever stored.
     const bool oneRound = !ctx->sc.haveForwardBsdf;
     if ((rc = ctx->trHits.grow(ctx, n)) != TGHIP_OK) return rc;
-    if (inst && (rc = ctx->trInst.grow(ctx, n)) != TGHIP_OK) return rc;
+    if (q.inst && (rc = ctx->trInst.grow(ctx, n)) != TGHIP_OK) return rc;
     if (!oneRound) {
         if ((rc = ctx->trO.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trD.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trT.grow(ctx, n)) != TGHIP_OK ||
             (rc = ctx->trB.grow(ctx, n)) != TGHIP_OK || (rc = ctx->trList[0].grow(ctx, n)) != TGHIP_OK || (rc = ctx->trList[1].grow(ctx, n)) != TGHIP_OK)
             return rc;
     }
-    const TransmittanceState st = {ctx->trO.get(), ctx->trD.get(), ctx->trT.get(), ctx->trB.get(), ctx->trHits.get(), inst ? ctx->trInst.get() : nullptr};
+    const TransmittanceState st = {ctx->trO.get(), ctx->trD.get(), ctx->trT.get(), ctx->trB.get(), ctx->trHits.get(), q.inst ? ctx->trInst.get() : nullptr};
     TransmittanceParams p;
-    p.cameraMedium = ctx->sc.cameraMedium;
-    p.medium = desc->medium == TGHIP_MEDIUM_OF_CAMERA ? p.cameraMedium : desc->medium;
+    queryStartMedium(ctx, desc->medium, p);
     p.endCap = desc->end_cap;
     p.bounce = desc->bounce;
     p.startsOnSurface = (desc->flags & TGHIP_TRANSMITTANCE_STARTS_ON_SURFACE) ? 1u : 0u;
@@ -1817,14 +1827,10 @@ int tghip_query_transmittance(tghip_ctx *ctx, const TgHipTransmittanceQueryDesc 
     return timedLaunches(ctx, ctx->trMs, [&]() -> int {
         uint32_t live = uint32_t(n);
         for (long long round = 0; round < maxRounds && live > 0; ++round) {
-            // workgroups: as many as stay resident, no more than the round has waves for (a workgroup without a ray only reads the counter)
-            const size_t perWave = (size_t(live) + 63)/64;
-            const uint32_t blocks = ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
-                                                         : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
             const uint32_t *list = round == 0 ? nullptr : ctx->trList[(round - 1) & 1].get();
             uint32_t *next = ctx->trList[round & 1].get();
             HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
-            HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays, st, list, live, counters, blocks, refillAt, lds));
+            HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, dRays, st, list, live, counters, q.blocks(live), q.refillAt, q.lds));
             HIP_TRY(ctx, transmittanceQueryLaunchSegment(ctx->stream, ctx->scene, p, dRays, dMedia, st, list, live, dOut, next, counters + 1));
             ctx->trRounds++;
             if (oneRound) break;
@@ -1856,36 +1862,20 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
 {
     if (!ctx) return TGHIP_E_INVALID;
     if (!desc) { ctx->error = "tghip_query_direct: no description"; return TGHIP_E_INVALID; }
-    if (!ctx->haveScene) { ctx->error = "tghip_query_direct before tghip_upload_scene"; return TGHIP_E_NOSCENE; }
-    const TgHostDirectScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), ctx->scene.num_lights, ctx->sc.cameraMedium};
-    int rc = checkDirectQuery(desc, rays, media, out, n, &facts, ctx->error);
+    int rc = queryScene(ctx, "tghip_query_direct");
     if (rc != TGHIP_OK) return rc;
-    if (n == 0) return TGHIP_OK;
-    rc = tghip_wait(ctx);
-    if (rc != TGHIP_OK && rc != TGHIP_E_ABORTED) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const TgHostDirectScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data(), ctx->scene.num_lights, ctx->sc.cameraMedium};
+    if ((rc = checkDirectQuery(desc, rays, media, out, n, &facts, ctx->error)) != TGHIP_OK) return rc;
+    if ((rc = queryBegin(ctx, "tghip_query_direct", n)) != TGHIP_OK || n == 0) return rc;
     const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0, volume = (desc->flags & TGHIP_DIRECT_VOLUME) != 0;
     const size_t outBytes = n*sizeof(TgHipDirect);
-    HIP_TRY(ctx, ctx->queryCounter.once(16));
     const float4 *dRays = nullptr;
     const int *dMedia = nullptr;
     float4 *dOut = nullptr;
     if ((rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
-    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->dqMedia, dMedia)) != TGHIP_OK) return rc;
-    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->dqOut, dOut)) != TGHIP_OK) return rc;
-    // the walk and the workgroups of tghip_query_rays on this scene
-    const LaunchChoice &choice = ctx->lp.choice;
-    const bool wide = choice.rayWalk == LaunchChoice::RAYS_WIDE, inst = choice.rayWalk == LaunchChoice::RAYS_INST;
-    const RayQueryWalk walk = wide ? RAY_QUERY_WIDE : inst ? RAY_QUERY_INST : choice.rayWalk == LaunchChoice::RAYS_FLAT ? RAY_QUERY_FLAT : RAY_QUERY_BVH2;
-    const size_t lds = wide ? size_t(std::max(ctx->sc.wideDepth, 1))*RAY_QUERY_THREADS*sizeof(uint2)
-                            : std::max<size_t>(ldsBytes(ctx->sc, choice, LDS_TRACE, RAY_QUERY_THREADS), sizeof(int));
-    const uint32_t refillAt = uint32_t(ctx->queryRefillAt > 0 ? ctx->queryRefillAt : RAY_QUERY_REFILL_AT);
-    auto blocksFor = [&](uint32_t live) {
-        // workgroups: as many as stay resident, no more than there are waves for (a workgroup without a ray only reads the counter)
-        const size_t perWave = (size_t(live) + 63)/64;
-        return ctx->queryBlocks > 0 ? uint32_t(ctx->queryBlocks)
-                                    : uint32_t(std::min<size_t>(size_t(ctx->prop.multiProcessorCount)*RAY_QUERY_BLOCKS_PER_CU, (perWave + 3)/4));
-    };
+    if (media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->queryMedia, dMedia)) != TGHIP_OK) return rc;
+    if ((rc = stageOutput(ctx, device, out, outBytes, ctx->queryOut, dOut)) != TGHIP_OK) return rc;
+    const QueryWalk q = queryWalk(ctx);
     // the parts: raysPer rays by samplesPer samples, at most DIRECT_QUERY_CHUNK items
     const uint64_t spp = uint64_t(desc->spp_end) - desc->spp_begin;
     const uint64_t samplesPer = std::min<uint64_t>(spp, DIRECT_QUERY_CHUNK);
@@ -1897,19 +1887,18 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
         (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
         (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK)
         return rc;
-    if (inst && (rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK) return rc;
+    if (q.inst && (rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK) return rc;
     if (!volume && (rc = ctx->dqRayHits.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
-    if (!volume && inst && (rc = ctx->dqRayInst.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
+    if (!volume && q.inst && (rc = ctx->dqRayInst.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
     const DirectState st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
-                            inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
+                            q.inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
     // (the shadow walks are tghip_query_transmittance's, reading segments through a list: of its state they touch o, d, hits and inst)
     const TransmittanceState walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
     const float4 *rayHits = volume ? nullptr : ctx->dqRayHits.get();
-    int *rayInst = !volume && inst ? ctx->dqRayInst.get() : nullptr;
+    int *rayInst = !volume && q.inst ? ctx->dqRayInst.get() : nullptr;
     DirectParams p;
     p.seed = desc->seed; p.skip = desc->skip; p.bounce = desc->bounce; p.light = desc->light;
-    p.cameraMedium = ctx->sc.cameraMedium;
-    p.medium = desc->medium == TGHIP_MEDIUM_OF_CAMERA ? p.cameraMedium : desc->medium;
+    queryStartMedium(ctx, desc->medium, p);
     uint32_t *counters = ctx->queryCounter.get();
     return timedLaunches(ctx, ctx->dqMs, [&]() -> int {
         for (uint64_t r0 = 0; r0 < n; r0 += raysPer) {
@@ -1919,7 +1908,7 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
                 p.first = s0 == desc->spp_begin ? 1u : 0u;
                 HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
                 if (!volume && p.first)      // the point: tghip_query_surface's walk as it is (the hits stay for the ray's later parts)
-                    HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, walk, dRays + r0*2u, ctx->dqRayHits.get(), rayInst, p.rays, counters, blocksFor(p.rays), refillAt, lds));
+                    HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, dRays + r0*2u, ctx->dqRayHits.get(), rayInst, p.rays, counters, q.blocks(p.rays), q.refillAt, q.lds));
                 HIP_TRY(ctx, directQueryLaunchSetup(ctx->stream, ctx->scene, p, volume, dRays, dMedia, rayHits, rayInst, st, ctx->dqList[1].get(), counters + 1));
                 uint32_t live = 0;
                 HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1930,7 +1919,7 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
                     const uint32_t *list = ctx->dqList[(round + 1) & 1].get();
                     uint32_t *next = ctx->dqList[round & 1].get();
                     HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
-                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, walk, nullptr, walkState, list, live, counters, blocksFor(live), refillAt, lds));
+                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, nullptr, walkState, list, live, counters, q.blocks(live), q.refillAt, q.lds));
                     HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, list, live, next, counters + 1));
                     // the one word a round hands back: how many segments the next one has
                     HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

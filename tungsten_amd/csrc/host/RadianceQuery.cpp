@@ -1,36 +1,24 @@
 #include "RadianceQuery.hpp"
+#include "QueryCheck.hpp"
 #include "../../../include/tungsten_host.h"
-
-#include <cstdint>
-#include <cstdio>
 
 int checkRadianceQuery(const TgHipRadianceQueryDesc *desc, const void *rays, const void *rgbSum, const void *count, size_t n, bool sceneHasSobol,
                        std::string &error)
 {
-    if (!desc) { error = "tghip_query_radiance: no description"; return TGHIP_E_INVALID; }
-    if (desc->flags & ~(TGHIP_DEVELOP_DEVICE_POINTERS | TGHIP_RADIANCE_SOBOL)) { error = "tghip_query_radiance: unknown flag bits"; return TGHIP_E_INVALID; }
-    if (desc->reserved[0] != 0u || desc->reserved[1] != 0u || desc->reserved[2] != 0u) { error = "tghip_query_radiance: the reserved words must be zero"; return TGHIP_E_INVALID; }
-    if (desc->spp_end <= desc->spp_begin) { error = "tghip_query_radiance: spp_end must be above spp_begin"; return TGHIP_E_INVALID; }
-    if ((desc->flags & TGHIP_RADIANCE_SOBOL) && !sceneHasSobol) {
-        error = "tghip_query_radiance: TGHIP_RADIANCE_SOBOL needs sobol_matrices in the scene description";
-        return TGHIP_E_INVALID;
-    }
-    if (uint64_t(n) > 0x7FFFFFFFull) { error = "tghip_query_radiance: more than 2^31 - 1 rays"; return TGHIP_E_INVALID; }
-    if (n == 0) return TGHIP_OK;                 // (an empty batch asks nothing of its arrays)
-    if (!rays || !rgbSum) { error = "tghip_query_radiance: rays and rgb_sum are needed for a batch that is not empty"; return TGHIP_E_INVALID; }
-    if (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) {
-        // k_query_paths reads a ray as two 16-byte vectors; the sums and counts are written word by word
-        if (reinterpret_cast<uintptr_t>(rays) & 15u) { error = "tghip_query_radiance: device rays must be 16-byte aligned"; return TGHIP_E_INVALID; }
-        if ((reinterpret_cast<uintptr_t>(rgbSum) | reinterpret_cast<uintptr_t>(count)) & 3u) {
-            error = "tghip_query_radiance: device rgb_sum and count must be 4-byte aligned";
-            return TGHIP_E_INVALID;
-        }
-    }
+    const QueryCheck c = {"tghip_query_radiance", error};
+    if (!desc) return c.refuse("no description");
+    int rc = c.words(desc->flags, TGHIP_DEVELOP_DEVICE_POINTERS | TGHIP_RADIANCE_SOBOL, desc->reserved, 3);
+    if (rc != TGHIP_OK) return rc;
+    if (desc->spp_end <= desc->spp_begin) return c.refuse("spp_end must be above spp_begin");
+    if ((desc->flags & TGHIP_RADIANCE_SOBOL) && !sceneHasSobol) return c.refuse("TGHIP_RADIANCE_SOBOL needs sobol_matrices in the scene description");
+    // k_query_paths reads a ray as two 16-byte vectors; the sums and counts are written word by word
+    if ((rc = c.rays(n)) == TGHIP_OK)
+        rc = c.arrays(n, (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0, rays, rgbSum, "rays and rgb_sum", queryAddress(rays), "device rays",
+                      queryAddress(rgbSum) | queryAddress(count), "device rgb_sum and count");
+    if (rc != TGHIP_OK) return rc;
     // the size planPass refuses a record pass at -- 2^32 samples on one device: a plain pass of that size it would cut into batches without end
-    if (uint64_t(n)*(desc->spp_end - desc->spp_begin) >= (1ull << 32)) {
-        error = "tghip_query_radiance: pass too large (2^32 samples or more per device): fewer rays or a shorter sample range per call";
-        return TGHIP_E_UNSUPPORTED;
-    }
+    if (uint64_t(n)*(desc->spp_end - desc->spp_begin) >= (1ull << 32))
+        return c.refuse("pass too large (2^32 samples or more per device): fewer rays or a shorter sample range per call", TGHIP_E_UNSUPPORTED);
     return TGHIP_OK;
 }
 
@@ -62,7 +50,5 @@ extern "C" int tgh_query_radiance_check(const TgHipRadianceQueryDesc *desc, cons
                                         int scene_has_sobol, char *err, size_t errlen)
 {
     std::string error;
-    const int rc = checkRadianceQuery(desc, rays, rgb_sum, count, n, scene_has_sobol != 0, error);
-    if (rc != TGHIP_OK && err && errlen) std::snprintf(err, errlen, "%s", error.c_str());
-    return rc;
+    return queryCheckAnswer(checkRadianceQuery(desc, rays, rgb_sum, count, n, scene_has_sobol != 0, error), error, err, errlen);
 }
