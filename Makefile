@@ -27,11 +27,13 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 #   csrc/host/SurfaceQuery.cpp, likewise)
 # + transmittance_query.hip, the walk and the dense launch of a round of tghip_query_transmittance (its argument check, csrc/host/TransmittanceQuery.cpp, likewise)
 # + direct_query.hip, the three dense launches of tghip_query_direct around those two units' walks (its argument check, csrc/host/DirectQuery.cpp, likewise)
+# + vertex_query.hip, the three dense launches of tghip_query_vertex around the surface query's walk and the direct query's shadow rounds (its argument
+#   check, csrc/host/VertexQuery.cpp, likewise; its stand-alone sanitizer run: tools/vertex_query_check.cpp, the command in its header)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
 # (the shim reads what csrc/host/SceneCheck.cpp decided about a scene, SceneTraits, what csrc/host/PassPlan.cpp decided about a pass, PassPlan, what
 # csrc/host/LaunchChoice.cpp decided about the pass's kernels, LaunchChoice, and calls csrc/host/RayQuery.cpp's check of a query)
-HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp tungsten_amd/csrc/host/RayQuery.hpp tungsten_amd/csrc/host/RadianceQuery.hpp tungsten_amd/csrc/host/SurfaceQuery.hpp tungsten_amd/csrc/host/TransmittanceQuery.hpp tungsten_amd/csrc/host/DirectQuery.hpp tungsten_amd/csrc/host/LaunchChoice.hpp
+HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp tungsten_amd/csrc/host/RayQuery.hpp tungsten_amd/csrc/host/RadianceQuery.hpp tungsten_amd/csrc/host/SurfaceQuery.hpp tungsten_amd/csrc/host/TransmittanceQuery.hpp tungsten_amd/csrc/host/DirectQuery.hpp tungsten_amd/csrc/host/VertexQuery.hpp tungsten_amd/csrc/host/LaunchChoice.hpp
 # -ffp-contract=off: no FMA contraction, so device arithmetic rounds like the CPU reference/oracle
 # (DESIGN.md "Numerics"); TG_FAST=1 allows contraction.
 FPFLAGS  := $(if $(TG_FAST),-ffp-contract=fast,-ffp-contract=off)

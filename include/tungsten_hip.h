@@ -20,6 +20,8 @@
  *                              of PathTracer.cpp:83-88 and TraceableScene::intersectInfinites (:194-209) for a miss, batched, on host or device memory.
  *   tghip_query_transmittance <- TraceBase::generalizedShadowRay (integrators/TraceBase.cpp:62-133), batched, on host or device memory.
  *   tghip_query_direct      <- TraceBase::estimateDirect / volumeEstimateDirect (integrators/TraceBase.cpp:470-494), batched, on host or device memory.
+ *   tghip_query_vertex      <- one turn of PathTracer::traceSample's loop (PathTracer.cpp:50-131) on paths whose state the caller holds, batched, on
+ *                              host or device memory.
  *   tghip_reduce_framebuffers <- the merge of per-machine partial renders the reference does offline on the host
  *                              (src/hdrmanip/hdrmanip.cpp:69-112: load N HDR images, add, divide); here the tile shards of
  *                              one frame, summed on the device side by RCCL over xGMI.
@@ -870,6 +872,85 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
 /* Instrumentation: HIP-event time from the first launch to the last of the context's last tghip_query_direct, in milliseconds -- the walks, the dense
  * launches and the one-word read-backs between the rounds (profiles/direct_query/bench.txt) */
 int tghip_query_direct_kernel_time(tghip_ctx *ctx, double *ms);
+/* Paths whose state the CALLER holds, advanced vertex by vertex: one call runs `turns` turns of PathTracer::traceSample's loop
+ * (integrators/path_tracer/PathTracer.cpp:50-131) on n states -- TraceBase::handleSurface (integrators/TraceBase.cpp:516-568), handleVolume (:496-514),
+ * Medium::sampleDistance, the roulette, the NaN guards and handleInfiniteLights (:570-578).  Chained until no path is alive it returns
+ * tghip_query_radiance's answer bit for bit; in between the caller may look at the throughput, end a path by its own rule, hand in a direction of
+ * its own, reorder, drop or split the batch: a turn is a pure function of (state, uploaded scene and its integrator settings), and a TgHipPath is the
+ * whole state.  A small wavefront of its own on the context's stream (csrc/hip/vertex_query.hip): the closest-hit walk of tghip_query_surface over the
+ * live paths' rays, a dense front stage, the shadow walks and rounds of tghip_query_direct, a dense back stage.
+ *   start        TGHIP_VERTEX_START: state i is made from rays[i] first -- throughput 1, emission 0, bounce 0, wasSpecular, medium media[i] (or
+ *                desc->medium where media is NULL), the medium's state reset, the stream rngStart(seed, first_index + i, sample) behind first_number
+ *                numbers (csrc/hip/pt_math.h).  first_number = 2 makes a pinhole camera's own rays give that camera's samples, as
+ *                tghip_query_radiance does.  `paths` is then written only.  Without the flag rays and media must be NULL and `paths` is read.
+ *   one turn     of a live path (status 0), operation for operation in the reference's order: the closest hit in [tmin, tmax) -- rec and t are bit for
+ *                bit tghip_query_rays' (TGHIP_QUERY_CLOSEST) on the same context, a hit counting when t < tmax; with no hit and no medium the
+ *                epilogue (:128-131: handleInfiniteLights under min_bounces <= bounce < max_bounces, the NaN guard, ESCAPED); otherwise
+ *                sampleDistance, and at a surface makeLocalScatterEvent and handleSurface with estimateDirect exactly as tghip_query_direct
+ *                computes it (bounce + 1, the path's medium, the path's stream), in a medium handleVolume with volumeEstimateDirect.
+ *                emission += estimateDirect*throughput comes before the emissive hit's term (TraceBase.cpp:537-543), the roulette (:111-117) draws
+ *                after the BSDF, the NaN guards (:119-122) read the emission after both additions.  The next ray is ray.scatter(hitpoint, wo,
+ *                epsilon) at a surface and (p, w, 0) in a medium, tmax infinite, the medium selected by the geometric side and its state reset at a
+ *                surface.  bounce++; at max_bounces the path ends in this turn, so a path never costs a walk the reference would not make.
+ *   turns        the call runs desc->turns turns, or stops earlier when no path is alive.  *alive: the paths still alive afterwards.
+ *   ended paths  a path that is not alive comes back byte for byte as it came in.
+ *   bad states   a state whose medium is out of range or whose ray has a non-finite component or a zero direction gets an unspecified answer; the
+ *                call returns and nothing outside the n states is written.
+ *   memory       flags without TGHIP_DEVELOP_DEVICE_POINTERS: rays, media, paths and alive are host memory, staged through buffers of the context
+ *                that only grow; with it: memory of the context's device, rays and paths 16-byte aligned, media and alive 4-byte aligned (alive,
+ *                one word copied once the turns are through, may be a word of host memory even then).  The
+ *                scratch grows to a fixed number of paths; larger calls run in parts, which changes no bit.
+ * All-features arithmetic and the keyed PCG stream only (no Sobol' form), as tghip_query_direct.  MediumState's mediumBounces is NOT part of the state:
+ * TgHipSettings::low_order_scattering and include_surfaces keep their defaults in every scene this library uploads, so nothing reads it.  Runs on the
+ * context's stream, waits for a running pass like tghip_query_rays, returns when the states are complete and leaves the framebuffer, the SampleRecords,
+ * the auxiliary and the per-sample buffers as they were.  "query_blocks" and "query_refill_at" steer the walks and never change an answer.  n == 0
+ * succeeds.  TGHIP_E_NOSCENE without an upload, decided as tghip_query_transmittance decides it.  TGHIP_E_INVALID, the context still usable: no
+ * description, NULL paths with n > 0, TGHIP_VERTEX_START without rays, rays or media without it, unknown flag bits, a non-zero reserved word,
+ * turns == 0, first_number > 1024, n > 2^31 - 1, misaligned device pointers, desc->medium below -2 or >= num_media or naming an operand entry of an
+ * `interpolated` medium (tungsten_host.h: tgh_query_vertex_check is the same check on its own). */
+#define TGHIP_VERTEX_START 2u            /* flags; bit 0 stays TGHIP_DEVELOP_DEVICE_POINTERS */
+typedef struct TgHipVertexQueryDesc {
+    uint32_t flags;
+    uint32_t seed;
+    uint32_t sample;                     /* the sample index of the stream's key */
+    uint32_t first_index;                /* ray i is keyed first_index + i */
+    uint32_t first_number;               /* numbers of the stream drawn and thrown away first, <= 1024 */
+    int32_t  medium;                     /* as TgHipTransmittanceQueryDesc::medium: index, TGHIP_MEDIUM_NONE, TGHIP_MEDIUM_OF_CAMERA */
+    uint32_t turns;                      /* >= 1 */
+    uint32_t reserved;                   /* 0 */
+} TgHipVertexQueryDesc;                  /* 32 B */
+/* TgHipPath::status: 0 = alive, else why the path ended */
+enum { TGHIP_PATH_ALIVE = 0,
+       TGHIP_PATH_END_ESCAPED = 1,          /* the loop's condition failed, or PathTracer.cpp:59-60: the epilogue ran */
+       TGHIP_PATH_END_MAX_BOUNCES = 2,      /* bounce reached max_bounces in this turn */
+       TGHIP_PATH_END_ABSORBED = 3,         /* sampleDistance, bsdf.sample, isConsistent or the phase sample failed (:54-55, 98-99, 103-105) */
+       TGHIP_PATH_END_ZERO_THROUGHPUT = 4,  /* :108-109, then the epilogue */
+       TGHIP_PATH_END_ROULETTE = 5,         /* :116 */
+       TGHIP_PATH_END_NAN = 6 };            /* :119-122, 130-131: the emission is zero, as the reference returns its NaN colours */
+#define TGHIP_PATH_WAS_SPECULAR 1u       /* TgHipPath::flags */
+typedef struct TgHipPath {
+    float    o[3], tmin, d[3], tmax;     /* the ray the next turn traces: laid out as a TgHipRay */
+    float    throughput[3];
+    float    emission[3];                /* what traceSample would return if the path ended now */
+    uint32_t status;                     /* TGHIP_PATH_ALIVE or a TGHIP_PATH_END_* */
+    int32_t  medium;                     /* the medium the ray travels in: an index in TgHipSceneDesc::media, or -1 */
+    uint32_t medium_state_bounce;        /* MediumState::bounce; firstScatter is medium_state_bounce == 0, as in TgHipMediumCase */
+    uint32_t bounce;
+    uint32_t flags;                      /* TGHIP_PATH_WAS_SPECULAR */
+    int32_t  rec;                        /* TgHipHit::rec of the last turn's walk, -1 = miss */
+    float    t;                          /* ... and its distance, 0 on a miss */
+    uint32_t rng_state[2];               /* the PCG state, low word first */
+    uint32_t key;                        /* the index the stream's increment is made of */
+    uint32_t drawn;                      /* numbers taken from the stream so far, first_number included */
+    uint32_t reserved[3];                /* carried along unchanged; TGHIP_VERTEX_START writes zeros */
+} TgHipPath;                             /* 112 B: seven 16-byte vectors */
+int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const TgHipRay *rays /* TGHIP_VERTEX_START only: n rays */,
+                       const int32_t *media /* TGHIP_VERTEX_START only: n start media, may be NULL */,
+                       TgHipPath *paths /* n states: read and written; with START written only */, size_t n,
+                       uint32_t *alive /* paths still alive afterwards, may be NULL */);
+/* Instrumentation: HIP-event time from the first launch to the last of the context's last tghip_query_vertex, in milliseconds -- the walks, the dense
+ * launches and the one-word read-backs between them (profiles/vertex_query/bench.txt) */
+int tghip_query_vertex_kernel_time(tghip_ctx *ctx, double *ms);
 /* Self-test of the device's libm restatements (csrc/hip/pt_libm.h: glibc's sinf / cosf / logf / expf / atan2f / powf / cbrtf as the shading
  * kernels call them, pt_math.h: acosf): y[i] = fn(x[i]) evaluated ON THE DEVICE, host pointers.  fn: TGHIP_LIBM_*.  The two-argument
  * functions read their operands interleaved from x (2 n floats): ATAN2F y[i] = atan2f(x[2i], x[2i+1]), POWF y[i] = powf(x[2i], x[2i+1]).

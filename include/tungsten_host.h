@@ -280,6 +280,16 @@ typedef struct TgHostDirectScene {
 int tgh_query_direct_check(const TgHipDirectQueryDesc *desc, const void *rays, const void *media, const void *out, size_t n,
                            const TgHostDirectScene *scene, char *err, size_t errlen);
 
+/* What tghip_query_vertex decides about a call before it touches the device (csrc/host/VertexQuery.cpp), on its own, no device: TGHIP_OK, or
+ * TGHIP_E_INVALID and in `err` the refusal's message.  `scene`: what the refusals that depend on the uploaded scene read -- per entry of media[] whether
+ * it is an operand of an `interpolated` medium (NULL: none is); NULL checks a call against a scene without media.  Only the pointers' values of rays,
+ * media, paths and alive are looked at, nothing is read through them. */
+typedef struct TgHostVertexScene {
+    uint32_t num_media;   const uint8_t *medium_operand;   /* num_media bytes, or NULL */
+} TgHostVertexScene;
+int tgh_query_vertex_check(const TgHipVertexQueryDesc *desc, const void *rays, const void *media, const void *paths, const void *alive, size_t n,
+                           const TgHostVertexScene *scene, char *err, size_t errlen);
+
 /* file-format helpers used by the tests */
 int tgh_save_pfm(const char *path, const float *rgb, int w, int h);
 int tgh_load_hdr(const char *path, float *rgb /* may be NULL to query size */, int *w, int *h);

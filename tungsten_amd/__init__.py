@@ -48,6 +48,12 @@ TRANSMITTANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("crossed", np.uint32)])
 # capi.TgHipDirect (Renderer.query_direct)
 DIRECT_DTYPE = np.dtype([("rgb", np.float32, 3), ("visibility", np.float32), ("count", np.uint32), ("visibility_count", np.uint32), ("rec", np.int32),
                          ("reserved", np.uint32)])
+# capi.TgHipPath (Renderer.start_paths / query_vertex): the whole state of one caller-held path, 112 B
+PATH_DTYPE = np.dtype([("o", np.float32, 3), ("tmin", np.float32), ("d", np.float32, 3), ("tmax", np.float32), ("throughput", np.float32, 3),
+                       ("emission", np.float32, 3), ("status", np.uint32), ("medium", np.int32), ("medium_state_bounce", np.uint32), ("bounce", np.uint32),
+                       ("flags", np.uint32), ("rec", np.int32), ("t", np.float32), ("rng_state", np.uint32, 2), ("key", np.uint32), ("drawn", np.uint32),
+                       ("reserved", np.uint32, 3)])
+PATH_END_NAMES = ("alive", "escaped", "max_bounces", "absorbed", "zero_throughput", "roulette", "nan")   # capi.TGHIP_PATH_*
 DEFAULT_SEED = 0xBA5EBA11  # src/tungsten/Shared.hpp:246
 TONEMAP_NAMES = ("linear", "gamma", "reinhard", "filmic", "pbrt")           # capi.TGHIP_TONEMAP_*
 QUERY_MODE_NAMES = ("closest", "occluded")                                  # capi.TGHIP_QUERY_*
@@ -183,11 +189,13 @@ class Renderer(object):
         return rays, media
 
     @staticmethod
-    def _query_tensors(fn, device, tensors, shapes):
+    def _query_tensors(fn, device, tensors, shapes, n=None):
         """The torch tensors of a query_*_into: (name, tensor or None, dtypes, elements per ray), the rays first -- each of one of its dtypes, on the
-        context's device, contiguous and of N x elements, which `shapes` says in words.  Returns N."""
-        rays = tensors[0][1]
-        n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
+        context's device, contiguous and of N x elements, which `shapes` says in words.  Returns N: the rays' [N,8], or, for a call without rays,
+        the n its caller took from another tensor (below zero: a tensor of no whole number of entries)."""
+        if n is None:
+            rays = tensors[0][1]
+            n = rays.numel()//8 if rays.dim() == 2 and rays.shape[1] == 8 else -1
         for name, t, dtypes, size in tensors:
             if t is None:
                 continue
@@ -347,6 +355,55 @@ class Renderer(object):
         ctx = self.context(device)
         self._raise_last(ctx, lib.tghip_query_direct(ctx, C.byref(desc), rays.data_ptr(), media.data_ptr() if media is not None else None,
                                                      out.data_ptr(), n))
+
+    def _vertex_call(self, device, desc, rays, media, paths, n):
+        ctx = self.context(device)
+        alive = C.c_uint32(0)
+        self._raise_last(ctx, lib.tghip_query_vertex(ctx, C.byref(desc), rays, media, paths, n, C.addressof(alive)))
+        return int(alive.value)
+
+    def start_paths(self, rays, sample=0, seed=DEFAULT_SEED, first_index=0, first_number=2, medium="camera", media=None, turns=1, device=0):
+        """Paths the caller holds, begun on its rays (tghip_query_vertex with TGHIP_VERTEX_START): rays [N,8] float32 (o, tmin, d, tmax) -> (paths,
+        alive): a structured array [N] of PATH_DTYPE -- the state of PathTracer::traceSample behind the camera: throughput 1, wasSpecular, the stream
+        keyed (seed, first_index + i, sample) behind first_number discarded numbers (2: what a pinhole camera spends) -- advanced by `turns` turns
+        of the loop, and how many of them are still alive.  medium: the medium every path starts in -- an index, None, or "camera"; media: int32
+        [N], per ray instead."""
+        rays, media = self._query_arrays("start_paths", rays, media)
+        paths = np.empty(rays.shape[0], PATH_DTYPE)
+        desc = capi.TgHipVertexQueryDesc(capi.TGHIP_VERTEX_START, int(seed) & 0xFFFFFFFF, int(sample), int(first_index), int(first_number),
+                                         self._query_medium(medium), int(turns), 0)
+        alive = self._vertex_call(device, desc, rays.ctypes.data, media.ctypes.data if media is not None else None, paths.ctypes.data,
+                                  rays.shape[0])
+        return paths, alive
+
+    def query_vertex(self, paths, turns=1, device=0):
+        """`turns` more turns of traceSample's loop on caller-held paths (tghip_query_vertex): paths a structured array [N] of PATH_DTYPE -> (paths,
+        alive): a new array -- a path that is not alive comes back byte for byte -- and how many are still alive.  Between calls the states may be
+        reordered, dropped, split into batches or edited field by field."""
+        paths = np.array(paths, PATH_DTYPE, copy=True, order="C").reshape(-1)
+        desc = capi.TgHipVertexQueryDesc(0, 0, 0, 0, 0, capi.TGHIP_MEDIUM_NONE, int(turns), 0)
+        alive = self._vertex_call(device, desc, None, None, paths.ctypes.data, paths.size)
+        return paths, alive
+
+    def query_vertex_into(self, paths, rays=None, sample=0, seed=DEFAULT_SEED, first_index=0, first_number=2, medium="camera", media=None, turns=1, device=0):
+        """The same on torch tensors of the context's device, without a copy through the host: paths float32 (or int32) with N x 28 elements -- the words
+        of PATH_DTYPE, the integer ones as their bits --, advanced in place.  rays float32 [N,8] begins the paths on them first (start_paths; media
+        None or int32 [N]); None advances the states `paths` holds.  Returns how many paths are still alive; the states are complete when the call
+        returns."""
+        if rays is not None:
+            n = self._query_tensors("query_vertex_into", device, (("rays", rays, ("torch.float32",), 8), ("paths", paths, ("torch.float32", "torch.int32"), 28),
+                                                                  ("media", media, ("torch.int32",), 1)),
+                                    "rays must be contiguous [N, 8], paths contiguous with N x 28 and media with N elements")
+            desc = capi.TgHipVertexQueryDesc(capi.TGHIP_DEVELOP_DEVICE_POINTERS | capi.TGHIP_VERTEX_START, int(seed) & 0xFFFFFFFF, int(sample),
+                                             int(first_index), int(first_number), self._query_medium(medium), int(turns), 0)
+            return self._vertex_call(device, desc, rays.data_ptr(), media.data_ptr() if media is not None else None,
+                                     paths.data_ptr(), n)
+        if media is not None:
+            raise TungstenError("query_vertex_into: media belong to the rays that begin paths")
+        n = self._query_tensors("query_vertex_into", device, (("paths", paths, ("torch.float32", "torch.int32"), 28),),
+                                "paths must be contiguous with N x 28 elements", n=paths.numel()//28 if paths.numel() % 28 == 0 else -1)
+        desc = capi.TgHipVertexQueryDesc(capi.TGHIP_DEVELOP_DEVICE_POINTERS, 0, 0, 0, 0, capi.TGHIP_MEDIUM_NONE, int(turns), 0)
+        return self._vertex_call(device, desc, None, None, paths.data_ptr(), n)
 
     def debug_libm(self, fn, x, device=0):
         """The device's restatement of a host libm function (capi.TGHIP_LIBM_*) evaluated on the device: float32 in, float32 out."""

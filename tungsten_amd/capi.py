@@ -270,6 +270,27 @@ class TgHostDirectScene(C.Structure):
     _fields_ = [("num_media", u32), ("medium_operand", C.POINTER(C.c_uint8)), ("num_lights", u32), ("camera_medium", i32)]
 
 
+TGHIP_VERTEX_START = 2
+# TgHipPath::status
+(TGHIP_PATH_ALIVE, TGHIP_PATH_END_ESCAPED, TGHIP_PATH_END_MAX_BOUNCES, TGHIP_PATH_END_ABSORBED, TGHIP_PATH_END_ZERO_THROUGHPUT, TGHIP_PATH_END_ROULETTE,
+ TGHIP_PATH_END_NAN) = range(7)
+TGHIP_PATH_WAS_SPECULAR = 1
+
+
+class TgHipVertexQueryDesc(C.Structure):
+    _fields_ = [("flags", u32), ("seed", u32), ("sample", u32), ("first_index", u32), ("first_number", u32), ("medium", i32), ("turns", u32), ("reserved", u32)]
+
+
+class TgHipPath(C.Structure):
+    _fields_ = [("o", f32*3), ("tmin", f32), ("d", f32*3), ("tmax", f32), ("throughput", f32*3), ("emission", f32*3), ("status", u32), ("medium", i32),
+                ("medium_state_bounce", u32), ("bounce", u32), ("flags", u32), ("rec", i32), ("t", f32), ("rng_state", u32*2), ("key", u32),
+                ("drawn", u32), ("reserved", u32*3)]
+
+
+class TgHostVertexScene(C.Structure):
+    _fields_ = [("num_media", u32), ("medium_operand", C.POINTER(C.c_uint8))]
+
+
 class TgHostSceneInfo(C.Structure):
     _fields_ = [("width", u32), ("height", u32), ("spp", u32), ("spp_step", u32),
                 ("num_nodes", u32), ("num_recs", u32), ("num_objects", u32), ("num_lights", u32),
@@ -385,6 +406,8 @@ PROTOTYPES = {
     "tghip_query_transmittance_rounds": (C.c_int, [VP, C.POINTER(C.c_uint32)]),
     "tghip_query_direct": (C.c_int, [VP, C.POINTER(TgHipDirectQueryDesc), VP, VP, VP, C.c_size_t]),
     "tghip_query_direct_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
+    "tghip_query_vertex": (C.c_int, [VP, C.POINTER(TgHipVertexQueryDesc), VP, VP, VP, C.c_size_t, VP]),
+    "tghip_query_vertex_kernel_time": (C.c_int, [VP, C.POINTER(C.c_double)]),
     "tghip_debug_libm": (C.c_int, [VP, C.c_int, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf": (C.c_int, [VP, VP, VP, C.c_size_t]),
     "tghip_debug_bsdf_info": (C.c_int, [VP, C.c_int, VP, VP, VP, VP]),
@@ -468,6 +491,7 @@ PROTOTYPES = {
     "tgh_query_transmittance_check": (C.c_int, [C.POINTER(TgHipTransmittanceQueryDesc), VP, VP, VP, C.c_size_t, C.POINTER(TgHostTransmittanceScene),
                                                 C.c_char_p, C.c_size_t]),
     "tgh_query_direct_check": (C.c_int, [C.POINTER(TgHipDirectQueryDesc), VP, VP, VP, C.c_size_t, C.POINTER(TgHostDirectScene), C.c_char_p, C.c_size_t]),
+    "tgh_query_vertex_check": (C.c_int, [C.POINTER(TgHipVertexQueryDesc), VP, VP, VP, VP, C.c_size_t, C.POINTER(TgHostVertexScene), C.c_char_p, C.c_size_t]),
     "tgh_save_pfm": (C.c_int, [C.c_char_p, VP, C.c_int, C.c_int]),
     "tgh_load_hdr": (C.c_int, [C.c_char_p, VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

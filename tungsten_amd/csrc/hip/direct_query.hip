@@ -18,6 +18,10 @@
 // finish adds in sample order whatever order the segments ended in.
 // One instantiation, under the all-features family's mask, so an answer never depends on which shading family the scene's passes use (FEAT_QMC
 // cleared: the stream is the keyed PCG one, there is no Sobol' form).
+// k_direct_setup's two bodies are restated in vertex_query.hip (k_vertex_front: the direct estimate of a caller-held path's vertex, on the path's own
+// stream, medium and bounce + 1).  One difference is meant: that copy queues no light-sample segment for an emitter's black side, as k_shade does
+// without the visibility output.  Whatever else changes here changes there; tests/test_gpu_vertex_query.py holds the two to each other on the camera
+// vertex of three scenes.
 #include "direct_query.h"
 #include "pt_wavefront.h"
 

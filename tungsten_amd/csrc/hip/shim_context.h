@@ -177,6 +177,14 @@ struct tghip_ctx {
     DeviceArray<int> dqInst, dqRayInst;
     DeviceArray<uint32_t> dqStatus, dqList[2];
     double dqMs = 0.0;
+    // tghip_query_vertex: the states on the device when they are the caller's host memory, per live path of the part under way its ray for the walk,
+    // the walk's hit and instance and what the front stage leaves the back stage (csrc/hip/vertex_query.h: VertexState), the two index lists the turns
+    // alternate between (all grown on demand, to at most VERTEX_QUERY_CHUNK paths); the shadow segments are tghip_query_direct's scratch above.  The
+    // time of the last call's launches
+    DeviceArray<float4> vqPaths, vqWalkRays, vqHits, vqW, vqP;
+    DeviceArray<int> vqInst;
+    DeviceArray<uint32_t> vqList[2];
+    double vqMs = 0.0;
     void *rankComm = nullptr;             // tghip_comm_init_rank: this process's ncclComm_t (one process per GPU); destroyed with the context (tghipDestroyRankComm)
     int rankCount = 0, rankIndex = 0;
     DeviceArray<float> redSum;            // the reduces (reduce.hip): where the reduced image lands when this context is the root (grown: a re-upload

@@ -12,11 +12,13 @@
 #include "surface_query.h"
 #include "transmittance_query.h"
 #include "direct_query.h"
+#include "vertex_query.h"
 #include "../host/RayQuery.hpp"
 #include "../host/RadianceQuery.hpp"
 #include "../host/SurfaceQuery.hpp"
 #include "../host/TransmittanceQuery.hpp"
 #include "../host/DirectQuery.hpp"
+#include "../host/VertexQuery.hpp"
 
 #include <chrono>
 
@@ -1933,6 +1935,108 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
 }
 
 int tghip_query_direct_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::dqMs, ms); }
+
+// Paths of tghip_query_vertex that are under way at once: what its scratch grows to at most; a larger call runs in parts, each through all its turns.
+// A part changes no bit of an answer: a path's turn reads nothing but its own state and the scene.  The shadow segments use tghip_query_direct's
+// scratch, one item per live path.
+#define VERTEX_QUERY_CHUNK (1u << 20)
+
+int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const TgHipRay *rays, const int32_t *media, TgHipPath *paths, size_t n, uint32_t *alive)
+{
+    if (!ctx) return TGHIP_E_INVALID;
+    if (!desc) { ctx->error = "tghip_query_vertex: no description"; return TGHIP_E_INVALID; }
+    int rc = queryScene(ctx, "tghip_query_vertex");
+    if (rc != TGHIP_OK) return rc;
+    const TgHostVertexScene facts = {uint32_t(ctx->sc.mediumOperand.size()), ctx->sc.mediumOperand.data()};
+    if ((rc = checkVertexQuery(desc, rays, media, paths, alive, n, &facts, ctx->error)) != TGHIP_OK) return rc;
+    if ((rc = queryBegin(ctx, "tghip_query_vertex", n)) != TGHIP_OK) return rc;
+    const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0, start = (desc->flags & TGHIP_VERTEX_START) != 0;
+    if (n == 0) {
+        const uint32_t none = 0;
+        if (alive && device) HIP_TRY(ctx, hipMemcpy(alive, &none, sizeof none, hipMemcpyDefault));   // (device memory, or a host word: see the header)
+        else if (alive) *alive = 0;
+        return TGHIP_OK;
+    }
+    const size_t pathBytes = n*sizeof(TgHipPath);
+    const float4 *dRays = nullptr;
+    const int *dMedia = nullptr;
+    float4 *dPaths = nullptr;
+    if (start && (rc = stageInput(ctx, device, rays, n*sizeof(TgHipRay), ctx->queryRays, dRays)) != TGHIP_OK) return rc;
+    if (start && media && (rc = stageInput(ctx, device, media, n*sizeof(int32_t), ctx->queryMedia, dMedia)) != TGHIP_OK) return rc;
+    if (start || device) {
+        if ((rc = stageOutput(ctx, device, paths, pathBytes, ctx->vqPaths, dPaths)) != TGHIP_OK) return rc;
+    } else {
+        const float4 *staged = nullptr;
+        if ((rc = stageInput(ctx, false, paths, pathBytes, ctx->vqPaths, staged)) != TGHIP_OK) return rc;
+        dPaths = ctx->vqPaths.get();
+    }
+    const QueryWalk q = queryWalk(ctx);
+    const size_t items = std::min<size_t>(n, VERTEX_QUERY_CHUNK);
+    if ((rc = ctx->dqStatus.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqWeight.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqOrigin.grow(ctx, items)) != TGHIP_OK ||
+        (rc = ctx->dqO.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqD.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqHits.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqT.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqB.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqC.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->vqWalkRays.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->vqHits.grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqW.grow(ctx, items)) != TGHIP_OK ||
+        (rc = ctx->vqP.grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqList[0].grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqList[1].grow(ctx, items)) != TGHIP_OK)
+        return rc;
+    if (q.inst && ((rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->vqInst.grow(ctx, items)) != TGHIP_OK)) return rc;
+    const DirectState st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
+                            q.inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
+    const TransmittanceState walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
+    const VertexState vs = {ctx->vqW.get(), ctx->vqP.get()};
+    int *pathInst = q.inst ? ctx->vqInst.get() : nullptr;
+    VertexParams p;
+    p.seed = desc->seed; p.sample = desc->sample; p.firstIndex = desc->first_index; p.firstNumber = desc->first_number;
+    p.start = start ? 1u : 0u;
+    queryStartMedium(ctx, desc->medium, p);
+    uint32_t *counters = ctx->queryCounter.get();
+    uint32_t aliveTotal = 0;
+    rc = timedLaunches(ctx, ctx->vqMs, [&]() -> int {
+        for (size_t p0 = 0; p0 < n; p0 += VERTEX_QUERY_CHUNK) {
+            p.path0 = uint32_t(p0); p.paths = uint32_t(std::min<size_t>(VERTEX_QUERY_CHUNK, n - p0));
+            HIP_TRY(ctx, hipMemsetAsync(counters, 0, 3*sizeof(uint32_t), ctx->stream));
+            HIP_TRY(ctx, vertexQueryLaunchBegin(ctx->stream, p, ctx->scene.num_media, dRays, dMedia, dPaths, ctx->vqList[0].get(), ctx->vqWalkRays.get(), counters + 2));
+            uint32_t live = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            for (uint32_t turn = 0; turn < desc->turns && live > 0; ++turn) {
+                const uint32_t *list = ctx->vqList[turn & 1].get();
+                uint32_t *next = ctx->vqList[(turn + 1) & 1].get();
+                HIP_TRY(ctx, hipMemsetAsync(counters, 0, 3*sizeof(uint32_t), ctx->stream));
+                // the closest hit: tghip_query_surface's walk as it is, over the live paths' rays
+                HIP_TRY(ctx, surfaceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, ctx->vqWalkRays.get(), ctx->vqHits.get(), pathInst, live, counters, q.blocks(live), q.refillAt, q.lds));
+                HIP_TRY(ctx, vertexQueryLaunchFront(ctx->stream, ctx->scene, dPaths, list, live, ctx->vqHits.get(), pathInst, st, vs, ctx->dqList[1].get(), counters + 1));
+                uint32_t segments = 0;
+                HIP_TRY(ctx, hipMemcpyAsync(&segments, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                // the shadow segments: tghip_query_direct's rounds as they are (a segment that goes on has crossed a surface: bounded by max_bounces)
+                for (int round = 0; segments > 0; ++round) {
+                    if (round >= DIRECT_QUERY_MAX_ROUNDS) { ctx->error = "tghip_query_vertex: shadow rays still under way after 257 rounds"; return TGHIP_E_UNSUPPORTED; }
+                    const uint32_t *segList = ctx->dqList[(round + 1) & 1].get();
+                    uint32_t *segNext = ctx->dqList[round & 1].get();
+                    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
+                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, nullptr, walkState, segList, segments, counters, q.blocks(segments), q.refillAt, q.lds));
+                    HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, segList, segments, segNext, counters + 1));
+                    HIP_TRY(ctx, hipMemcpyAsync(&segments, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                }
+                HIP_TRY(ctx, vertexQueryLaunchBack(ctx->stream, dPaths, list, live, st, vs, next, ctx->vqWalkRays.get(), counters + 2));
+                // the one word a turn hands back: how many paths the next one has
+                HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            aliveTotal += live;
+        }
+        return TGHIP_OK;
+    }, [&]() { return copyBack(ctx, paths, dPaths, pathBytes); });
+    if (rc != TGHIP_OK) return rc;
+    if (alive && device) HIP_TRY(ctx, hipMemcpy(alive, &aliveTotal, sizeof aliveTotal, hipMemcpyDefault));
+    else if (alive) *alive = aliveTotal;
+    return TGHIP_OK;
+}
+
+int tghip_query_vertex_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::vqMs, ms); }
 
 int tghip_get_counters(tghip_ctx *ctx, TgHipCounters *out)
 {
