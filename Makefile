@@ -21,12 +21,13 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 # explicit instantiations (pt_instances.h lists each unit's; they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 # + ray_query.hip, the kernels of tghip_query_rays (its argument check csrc/host/RayQuery.cpp comes in through HOSTSRC; the claim, the ray load and the
-#   8-wide loop it shares with the units below: query_walk.h, query_walk_wide.h; the clauses the five checks share: csrc/host/QueryCheck.hpp)
+#   8-wide loop it shares with the units below, their ballot-append, start medium and far distance: query_walk.h, query_walk_wide.h; the clauses the five checks share: csrc/host/QueryCheck.hpp)
 # + radiance_query.hip, the ray source and the result copy of tghip_query_radiance (its check and virtual image, csrc/host/RadianceQuery.cpp, likewise)
 # + surface_query.hip, the instanced walk and the dense launch of tghip_query_surface -- its other walks are ray_query.hip's kernels -- (its argument check,
 #   csrc/host/SurfaceQuery.cpp, likewise)
 # + transmittance_query.hip, the walk and the dense launch of a round of tghip_query_transmittance (its argument check, csrc/host/TransmittanceQuery.cpp, likewise)
 # + direct_query.hip, the three dense launches of tghip_query_direct around those two units' walks (its argument check, csrc/host/DirectQuery.cpp, likewise)
+# + direct_estimate.h, the direct estimate at one point -- surface and volume body, once -- for direct_query.hip's setup and vertex_query.hip's front stage
 # + vertex_query.hip, the three dense launches of tghip_query_vertex around the surface query's walk and the direct query's shadow rounds (its argument
 #   check, csrc/host/VertexQuery.cpp, likewise; its stand-alone sanitizer run: tools/vertex_query_check.cpp, the command in its header)
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 import scenes
-from scenes import (_area_lights, _atmosphere, _expfog, _fog, _fog_and_smoke, _point_lights, _rayleigh_fog, _sun_and_sky, _two_lights)
+from scenes import (_area_lights, _atmosphere, _checker_light, _expfog, _fog, _fog_and_smoke, _point_lights, _rayleigh_fog, _sun_and_sky, _two_lights)
 from transmittance_cases import _box, _caps, _panes, _segments, _veil, _with, names_of
 
 GOLDEN = os.path.join(scenes.GOLDEN, "direct_cases.npz")
@@ -68,6 +68,7 @@ SCENES = {
     "dq_fog_rayleigh": lambda t, n: scenes.cornell(t, name=n, **SMALL, edit=_rayleigh_fog),
     "dq_expfog": lambda t, n: scenes.cornell(t, name=n, **SMALL, edit=_expfog),
     "dq_atmosphere": lambda t, n: scenes.cornell(t, name=n, **SMALL, edit=_atmosphere),
+    "dq_checker_light": lambda t, n: scenes.cornell(t, name=n, **SMALL, edit=_checker_light),
 }
 
 
@@ -161,6 +162,8 @@ def make_groups():
     rays = in_the_box(rs, 64)
     g.append(_group("dq_caps", "volume_caps", rays, medium="fog", volume=True, media=[("fog", "-")[i % 4 == 3] for i in range(len(rays))]))
     g.append(_group("dq_point_lights", "volume_dirac", in_the_box(rs, 64), medium=None, volume=True, media=["-"]*64))      # no medium: nothing is taken
+    # the floor under the checkered light: half of the light samples end on a black square -- a transmittance is recorded, no light comes
+    g.append(_group("dq_checker_light", "black_light_sample", at_region(rs, 128, (-0.4, 0.0, -0.4), (0.4, 0.0, 0.4)), spp=(0, 3)))
     return g
 
 
@@ -223,6 +226,7 @@ def census(groups, primitives):
             add("sun_cap", (kind == "infinite_sphere_cap") & lit)
         if g["scene"] == "dq_light_corners":
             add("choose_among_16", g["light"] >= 0)
+        add("black_light_sample", (g["recorded"] != 0) & (g["transmittance"].view(np.float32) > 0) & ((legs & LEG_LIGHT_TERM) == 0))
         add("unknown_weight", legs & LEG_UNKNOWN_WEIGHT)
         add("pure_specular_return", legs & LEG_PURE_SPECULAR)
         add("forward_return", legs & LEG_FORWARD)
@@ -252,4 +256,4 @@ LEGS = ["light_term", "bsdf_term", "dirac_light", "mesh_accepted", "mesh_rejecte
         "sun_cap", "choose_among_16", "unknown_weight", "pure_specular_return", "forward_return", "inconsistent", "flipped_frame", "rough_material",
         "coated_material", "transparency_material", "shadow_crosses_forward", "shadow_crosses_fractional", "shadow_ends_at_max_bounces",
         "through_instance", "select_medium", "volume_isotropic", "volume_henyey_greenstein", "volume_rayleigh", "volume_exponential",
-        "volume_atmosphere", "fixed_light", "skip", "media_per_ray"]
+        "volume_atmosphere", "fixed_light", "skip", "media_per_ray", "black_light_sample"]

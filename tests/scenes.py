@@ -138,6 +138,13 @@ def _two_lights(scene):
                                 "transform": {"position": [-0.98, 0.6, 0.2], "scale": [0.3, 0.3, 0.3], "rotation": [0, 0, -90]}})
 
 
+def _checker_light(scene):
+    """The quad light's emission a 4 x 4 checker whose off colour is exactly 0: a light sample on a black square has a shadow ray -- and, where the
+    ray gets there, a transmittance -- but no emission (TraceBase::attenuatedEmission, TraceBase.cpp:167-173)."""
+    light = next(p for p in scene["primitives"] if p["name"] == "light")
+    light["emission"] = {"type": "checker", "on_color": [34, 24, 8], "off_color": 0.0, "res_u": 4, "res_v": 4}
+
+
 def _speck_lights(scene):
     """Two more quad emitters a quarter of a millimetre across, next to `light2`: from most of the box their solid angle (1e-8 sr) is
     below the last bit of the 2 pi that Quad::approximateRadiance subtracts four arc cosines from (Quad.cpp:253-281), so the weight

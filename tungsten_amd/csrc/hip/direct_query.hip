@@ -16,240 +16,41 @@
 // Separate launches because the setup carries BSDF, texture, light and medium code at once and must not share registers with a walk, because a round's
 // lanes are the segments still alive and not the items they came from, and because the order of a ray's float additions is part of the answer: the
 // finish adds in sample order whatever order the segments ended in.
-// One instantiation, under the all-features family's mask, so an answer never depends on which shading family the scene's passes use (FEAT_QMC
-// cleared: the stream is the keyed PCG one, there is no Sobol' form).
-// k_direct_setup's two bodies are restated in vertex_query.hip (k_vertex_front: the direct estimate of a caller-held path's vertex, on the path's own
-// stream, medium and bounce + 1).  One difference is meant: that copy queues no light-sample segment for an emitter's black side, as k_shade does
-// without the visibility output.  Whatever else changes here changes there; tests/test_gpu_vertex_query.py holds the two to each other on the camera
-// vertex of three scenes.
-#include "direct_query.h"
-#include "pt_wavefront.h"
-
-#define DIRECT_MASK (BSDF_MASK_ALL & ~FEAT_QMC)
-
-namespace {
-
-PT_DEV RayD loadRay(const float4 *rays, uint32_t i)
-{
-    const float4 ro = rays[(size_t)i*2u + 0u], rd = rays[(size_t)i*2u + 1u];
-    RayD ray;
-    ray.o = xyz(ro); ray.d = xyz(rd); ray.tmin = ro.w; ray.tmax = rd.w;
-    return ray;
-}
-
-// The medium ray i starts in: the call's, or its own (out of range: an unspecified answer, no read outside the table)
-PT_DEV int startMedium(const DirectParams &p, const int *media, uint32_t numMedia, uint32_t i)
-{
-    int medium = p.medium;
-    if (media) {
-        medium = media[i];
-        if (medium == TGHIP_MEDIUM_OF_CAMERA) medium = p.cameraMedium;
-        if (medium < 0 || (uint32_t)medium >= numMedia) medium = -1;
-    }
-    return medium;
-}
-
-// The segments of this wave that are alive, appended in lane order.  Called by all 64 lanes.
-PT_DEV void appendLive(bool alive, uint32_t g, uint32_t *list, uint32_t *count)
-{
-    const unsigned long long on = __ballot(alive);
-    if (on != 0ull) {
-        const uint32_t lane = laneId();
-        uint32_t base = 0;
-        if (lane == 0)
-            base = atomicAdd(count, (uint32_t)__popcll(on));
-        base = __shfl(base, 0);
-        if (alive) list[base + (uint32_t)__popcll(on & ((1ull << lane) - 1ull))] = g;
-    }
-}
-
-PT_DEV void putSegment(const DirectState &st, uint32_t g, f3 o, float tmin, f3 d, float tmax, int medium, uint32_t bounce, int endCap, float mis,
-                       f3 c, float cw, f3 e, float ew)
-{
-    st.o[g] = mk4(o, tmin);
-    st.d[g] = mk4(d, tmax);
-    st.t[g] = mk4(splat3(1.0f), __int_as_float(medium));
-    st.b[g] = make_uint4(bounce, (uint32_t)endCap, __float_as_uint(0.0f), __float_as_uint(mis));
-    st.c[g] = mk4(c, cw);
-    st.e[g] = mk4(e, ew);
-}
-
-}  // namespace
+// The setup's two bodies -- the estimate at one point -- and the helpers around them are direct_estimate.h's, shared with vertex_query.hip's front
+// stage (the direct estimate of a caller-held path's vertex); here with KEEP_BLACK set, for the visibility output.
+#include "direct_estimate.h"
 
 template<bool VOLUME>
 __global__ __launch_bounds__(DIRECT_QUERY_THREADS) void k_direct_setup(DeviceScene s, DirectParams p, const float4 *rays, const int *media, const float4 *hits,
                                                                       const int *inst, DirectState st, uint32_t *list, uint32_t *count)
 {
-    constexpr uint32_t M = DIRECT_MASK;
     const uint32_t k = blockIdx.x*DIRECT_QUERY_THREADS + threadIdx.x;
-    bool q0 = false, q1 = false;
+    uint32_t status = 0u;
     if (k < p.rays*p.samples) {
         const uint32_t lr = k/p.samples, ls = k - lr*p.samples;
         const uint32_t i = p.ray0 + lr;
-        const int medium = startMedium(p, media, s.num_media, i);
+        const int medium = rayStartMedium(p, media, s.num_media, i);
         const RayD ray = loadRay(rays, i);
         const float4 hit = VOLUME ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : hits[lr];
         if (VOLUME ? medium >= 0 : __float_as_int(hit.w) >= 0) {
-            uint32_t status = 0u;
             float lightWeight = 1.0f;
             Rng rng = rngStart(p.seed, i, p.sample0 + ls);
             for (uint32_t j = 0; j < p.skip; ++j) (void)rngNextI(rng);
             if (VOLUME) {
-                // volumeEstimateDirect / volumeSampleDirect / volumeLightSample / volumePhaseSample (TraceBase.cpp:323-381, 402-414, 470-481) at
-                // mediumSample.p = ray.o with parentRay.dir() = ray.d: shadow rays start at tmin = 0, the medium is not re-selected
-                const TgHipMedium &mm = s.media[medium];
-                const f3 volP = ray.o;
-                const int light = p.light >= 0 ? s.lights[p.light] : chooseLight<M>(s, rng, volP, lightWeight);
-                if (light >= 0) {
-                    status |= DIRECT_ITEM_ESTIMATE;
-                    const bool meshLight = s.objects[light].type == TGHIP_OBJ_MESH;
-                    const bool diracLight = s.objects[light].type == TGHIP_OBJ_POINT;
-                    if (diracLight) status |= DIRECT_ITEM_DIRAC;
-                    {
-                        f3 d; float dist, pdf;
-                        if (lightSampleDirect<M>(s, light, volP, rng, d, dist, pdf)) {
-                            const float f = phaseEval(mm, ray.d, d);
-                            if (f != 0.0f && meshLight) {
-                                putSegment(st, k*2u, volP, 0.0f, d, PT_INF, medium, p.bounce, light, powerHeuristic(pdf, f), splat3(f), dist, splat3(0.0f), pdf);
-                                q0 = true;
-                            } else if (f != 0.0f) {
-                                RayD sr; sr.o = volP; sr.d = d; sr.tmin = 0.0f; sr.tmax = PT_INF;   // parentRay.scatter(p, d, 0.0f)
-                                LightHit lh;
-                                bool reached;
-                                if (diracLight) { lh.t = dist; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f); reached = true; }
-                                else reached = lightIntersect<M>(s, light, sr, lh) && !(lh.t*(1.0f + 1e-3f) < dist);
-                                if (reached) {
-                                    const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                    if (!isZero(e)) {      // (no transmittance is reported here: a black side needs no shadow ray)
-                                        putSegment(st, k*2u, volP, 0.0f, d, lh.t, medium, p.bounce, light, diracLight ? 1.0f : powerHeuristic(pdf, f), splat3(f), 0.0f, e, pdf);
-                                        q0 = true;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    if (!diracLight) {
-                        f3 w; float ppdf;
-                        phaseSample<M>(mm, rng, ray.d, w, ppdf);
-                        if (meshLight) {
-                            putSegment(st, k*2u + 1u, volP, 0.0f, w, PT_INF, medium, p.bounce, light, 1.0f, splat3(1.0f), ppdf, splat3(0.0f), 0.0f);   // directPdf needs the hit
-                            q1 = true;
-                        } else {
-                            RayD sr; sr.o = volP; sr.d = w; sr.tmin = 0.0f; sr.tmax = PT_INF;
-                            LightHit lh;
-                            if (lightIntersect<M>(s, light, sr, lh)) {
-                                const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                if (!isZero(e)) {
-                                    const float mis1 = powerHeuristic(ppdf, lightDirectPdf<M>(s, light, w, volP, lh));
-                                    putSegment(st, k*2u + 1u, volP, 0.0f, w, lh.t, medium, p.bounce, light, mis1, splat3(1.0f), 0.0f, e, 0.0f);   // phaseSample.weight = 1
-                                    q1 = true;
-                                }
-                            }
-                        }
-                    }
-                    st.origin[k] = mk4(volP, 0.0f);
-                }
+                // at mediumSample.p = ray.o with parentRay.dir() = ray.d
+                status = estimateDirectVolume(s, st, k, rng, ray.o, ray.d, medium, p.bounce, p.light, lightWeight);
             } else {
-                Info info;
-                intersectionInfo<M>(s, ray, hit, info, inst ? inst[lr] : -1);
-                const uint32_t lobes = s.bsdfs[info.bsdf].lobes;
-                // TraceBase::makeLocalScatterEvent (TraceBase.cpp:24-51)
-                Frame frame = shadingFrame<M>(s, info);
-                const bool hitBackside = dot(frame.normal, ray.d) > 0.0f;
-                const bool flipped = s.settings.enable_two_sided_shading && hitBackside && !(lobes & LOBE_TRANSMISSIVE);
-                if (flipped) {
-                    frame.normal = -frame.normal;
-                    frame.tangent = -frame.tangent;
-                }
+                ScatterPoint pt;
                 Event ev;
-                ev.wi = toLocal(frame, -ray.d);
-                ev.u = info.u; ev.v = info.v; ev.rng = &rng;
-                const bool consistency = s.settings.enable_consistency_checks != 0;
-                auto isConsistent = [&](f3 woLocal, f3 w) {      // TraceBase.cpp:53-60
-                    if (!consistency) return true;
-                    const bool geometricBackside = dot(w, info.Ng) < 0.0f;
-                    const bool shadingBackside = (woLocal.z < 0.0f) != flipped;
-                    return geometricBackside == shadingBackside;
-                };
-                // each shadow ray starts in the medium on its side of the surface (TraceBase.cpp:260-261, 302-303)
-                auto sideMedium = [&](f3 dir) {
-                    return s.num_media ? selectMedium(s.objects[info.object], medium, dot(dir, info.Ng) < 0.0f) : medium;
-                };
-                // estimateDirect (TraceBase.cpp:483-494): chooseLight draws whatever sampleDirect then does
-                const int light = p.light >= 0 ? s.lights[p.light] : chooseLight<M>(s, rng, info.p, lightWeight);
-                const bool pureSpecular = lobes != 0 && (lobes & ~(uint32_t)LOBE_SPECULAR) == 0;
-                if (light >= 0 && !pureSpecular && lobes != TGHIP_LOBE_FORWARD) {
-                    status |= DIRECT_ITEM_ESTIMATE;
-                    const bool meshLight = s.objects[light].type == TGHIP_OBJ_MESH;
-                    const bool diracLight = s.objects[light].type == TGHIP_OBJ_POINT;
-                    if (diracLight) status |= DIRECT_ITEM_DIRAC;
-                    // lightSample (TraceBase.cpp:246-285)
-                    {
-                        f3 d; float dist, pdf;
-                        if (lightSampleDirect<M>(s, light, info.p, rng, d, dist, pdf)) {
-                            ev.wo = toLocal(frame, d);
-                            ev.requested = LOBE_ALL_BUT_SPECULAR;
-                            if (isConsistent(ev.wo, d)) {
-                                const f3 f = bsdfEval<M>(s, info.bsdf, ev);
-                                if (!isZero(f) && meshLight) {
-                                    // whether the ray reaches a mesh emitter, and with which emission, is known after the walk (TriangleMesh::intersect
-                                    // is a tree query): the round stage completes the term
-                                    putSegment(st, k*2u, info.p, 5e-4f, d, PT_INF, sideMedium(d), p.bounce, light, powerHeuristic(pdf, bsdfPdf<M>(s, info.bsdf, ev)), f, dist,
-                                               splat3(0.0f), pdf);
-                                    q0 = true;
-                                } else if (!isZero(f)) {
-                                    RayD sr; sr.o = info.p; sr.d = d; sr.tmin = 5e-4f; sr.tmax = PT_INF;
-                                    LightHit lh;
-                                    // attenuatedEmission's own hit and distance test (TraceBase.cpp:155-162); a Dirac light is not intersected: the
-                                    // shadow ray ends at the sampled distance
-                                    bool reached;
-                                    if (diracLight) { lh.t = dist; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f); reached = true; }
-                                    else reached = lightIntersect<M>(s, light, sr, lh) && !(lh.t*(1.0f + 1e-3f) < dist);
-                                    if (reached) {
-                                        // (a black side too: attenuatedEmission reports the shadow ray's transmittance before it looks at the emission, :167-171)
-                                        const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                        const float mis0 = diracLight ? 1.0f : powerHeuristic(pdf, bsdfPdf<M>(s, info.bsdf, ev));   // no MIS against a Dirac light (:281-282)
-                                        putSegment(st, k*2u, info.p, 5e-4f, d, lh.t, sideMedium(d), p.bounce, light, mis0, f, 0.0f, e, pdf);
-                                        q0 = true;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    // bsdfSample (TraceBase.cpp:287-321); not for Dirac lights (:396-397)
-                    if (!diracLight) {
-                        ev.requested = LOBE_ALL_BUT_SPECULAR;
-                        ev.weight = splat3(1.0f); ev.pdf = 1.0f;
-                        if (bsdfSample<M>(s, info.bsdf, ev) && !isZero(ev.weight)) {
-                            const f3 wog = toGlobal(frame, ev.wo);
-                            if (isConsistent(ev.wo, wog)) {
-                                if (meshLight) {
-                                    putSegment(st, k*2u + 1u, info.p, 5e-4f, wog, PT_INF, sideMedium(wog), p.bounce, light, 1.0f, ev.weight, ev.pdf, splat3(0.0f), 0.0f);   // directPdf needs the hit
-                                    q1 = true;
-                                } else {
-                                    RayD sr; sr.o = info.p; sr.d = wog; sr.tmin = 5e-4f; sr.tmax = PT_INF;
-                                    LightHit lh;
-                                    if (lightIntersect<M>(s, light, sr, lh)) {
-                                        const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                        if (!isZero(e)) {
-                                            const float mis1 = powerHeuristic(ev.pdf, lightDirectPdf<M>(s, light, wog, info.p, lh));
-                                            putSegment(st, k*2u + 1u, info.p, 5e-4f, wog, lh.t, sideMedium(wog), p.bounce, light, mis1, ev.weight, 0.0f, e, 0.0f);
-                                            q1 = true;
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    st.origin[k] = mk4(info.p, 0.0f);
-                }
+                makeScatterPoint(s, ray, hit, inst ? inst[lr] : -1, rng, pt, ev);
+                status = estimateDirectSurface<true>(s, st, k, rng, pt, ev, medium, p.bounce, p.light, lightWeight);
             }
-            st.status[k] = status | (q0 ? DIRECT_ITEM_SEG0 : 0u) | (q1 ? DIRECT_ITEM_SEG1 : 0u);
+            st.status[k] = status;
             st.weight[k] = lightWeight;
         }
     }
-    appendLive(q0, k*2u, list, count);
-    appendLive(q1, k*2u + 1u, list, count);
+    appendLive((status & DIRECT_ITEM_SEG0) != 0u, k*2u, list, count);
+    appendLive((status & DIRECT_ITEM_SEG1) != 0u, k*2u + 1u, list, count);
 }
 
 // One turn of generalizedShadowRayImpl<false>'s loop for one segment, behind its `_scene->intersect` (the walk's launch), with endsOnSurface = true:
@@ -384,7 +185,7 @@ __global__ __launch_bounds__(DIRECT_QUERY_THREADS) void k_direct_finish(DirectPa
     int rec = -1;
     bool active;
     if (volume) {
-        active = startMedium(p, media, numMedia, i) >= 0;
+        active = rayStartMedium(p, media, numMedia, i) >= 0;
     } else {
         rec = __float_as_int(hits[lr].w);
         active = rec >= 0;
@@ -404,15 +205,10 @@ __global__ __launch_bounds__(DIRECT_QUERY_THREADS) void k_direct_finish(DirectPa
             const uint32_t status = st.status[k];
             count++;
             if (!(status & DIRECT_ITEM_ESTIMATE)) continue;
-            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0x7FC00000u));
-            const float4 r0 = (status & DIRECT_ITEM_SEG0) ? st.res[k*2u] : zero;
-            f3 result = splat3(0.0f) + xyz(r0);
-            if (!(status & DIRECT_ITEM_DIRAC)) {
-                const float4 r1 = (status & DIRECT_ITEM_SEG1) ? st.res[k*2u + 1u] : zero;
-                result = result + xyz(r1);
-            }
+            float shadowT;
+            const f3 result = directItemResult(st, k, status, shadowT);
             rgb = rgb + result*st.weight[k];
-            if (!volume && !isnan(r0.w)) { visibility += r0.w; visibilityCount++; }
+            if (!volume && !isnan(shadowT)) { visibility += shadowT; visibilityCount++; }
         }
     }
     out[(size_t)i*2u + 0u] = mk4(rgb, visibility);

@@ -2,13 +2,7 @@
 // gfx950 (MI355X) only.  The pass itself is the one tghip_wait drives -- k_start, the walks, the shading launches, k_finish, k_resolve, untouched --
 // over a virtual image whose row-major pixel index is the ray index (csrc/host/RadianceQuery.cpp); what is new is here.
 #include "radiance_query.h"
-
-// The far distance the closest-hit walk of a first segment [tmin, tmax) starts with.  The walks are the reference's: a quad accepts t <= far, and a
-// leaf is skipped by its BOX's entry distance, which lies up to a few ulps to either side of the t the primitive's own test reports (TgHipTopNode,
-// include/tungsten_hip.h) -- so a walk that starts with far = tmax answers for hits within a few ulps of tmax by its own arithmetic, not by the
-// segment.  It starts 2^-10 further instead, far beyond that slack, and k_query_clip below turns every hit with t >= tmax into the miss it is.
-// An infinite tmax (the camera's) and the -1 of a padding pixel stay what they are.
-PT_DEV float queryWalkFar(float tmax) { return (tmax > 0.0f && tmax < PT_INF) ? tmax*1.0009765625f : tmax; }
+#include "query_walk.h"      // queryWalkFar: the far distance the walk of the first segment starts with; k_query_clip below ends the segment exactly
 
 // The ray source.  nextPath has written every fresh path with the pinhole ray of its virtual pixel and left the path's stream behind the two numbers
 // a pinhole camera spends on its pixel filter (Sobol': at dimension 2), throughput 1, bounce 0, wasSpecular, the camera's medium: the state of

@@ -156,15 +156,7 @@ __global__ __launch_bounds__(TRANSMITTANCE_QUERY_THREADS) void k_transmittance_s
         }
     }
     // the rays of this wave that go on, appended to the next round's list in lane order
-    const unsigned long long on = __ballot(goesOn);
-    if (on != 0ull) {
-        const uint32_t lane = laneId();
-        uint32_t base = 0;
-        if (lane == 0)
-            base = atomicAdd(nextCount, (uint32_t)__popcll(on));
-        base = __shfl(base, 0);
-        if (goesOn) next[base + (uint32_t)__popcll(on & ((1ull << lane) - 1ull))] = i;
-    }
+    appendLive(goesOn, i, next, nextCount);
 }
 
 hipError_t transmittanceQueryLaunchWalk(hipStream_t stream, const DeviceScene &scene, RayQueryWalk walk, const float4 *rays, const TransmittanceState &st,

@@ -1860,6 +1860,42 @@ int tghip_query_transmittance_rounds(tghip_ctx *ctx, uint32_t *rounds)
 // rounds of shadow walks per part, whatever the scene's max_bounces
 #define DIRECT_QUERY_MAX_ROUNDS 257
 
+// The scratch of `items` direct estimates under way at once (tghip_query_direct's items, tghip_query_vertex's live paths): st for the dense stages,
+// walkState for the shadow walks -- tghip_query_transmittance's, reading segments through a list: of its state they touch o, d, hits and inst
+static int directScratch(tghip_ctx *ctx, const QueryWalk &q, size_t items, DirectState &st, TransmittanceState &walkState)
+{
+    int rc;
+    if ((rc = ctx->dqStatus.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqWeight.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqOrigin.grow(ctx, items)) != TGHIP_OK ||
+        (rc = ctx->dqO.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqD.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqHits.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqT.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqB.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqC.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
+        (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK)
+        return rc;
+    if (q.inst && (rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK) return rc;
+    st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
+          q.inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
+    walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
+    return TGHIP_OK;
+}
+
+// The shadow rounds of the `live` segments a setup or front stage left in dqList[1]: per round the walk, k_direct_round and the one word it hands back,
+// how many segments the next one has.  A segment that goes on has crossed a surface (bounce++) and bounce >= max_bounces ends it: bounded.  fn: the caller.
+static int directShadowRounds(tghip_ctx *ctx, const char *fn, const QueryWalk &q, const DirectState &st, const TransmittanceState &walkState, uint32_t live)
+{
+    uint32_t *counters = ctx->queryCounter.get();
+    for (int round = 0; live > 0; ++round) {
+        if (round >= DIRECT_QUERY_MAX_ROUNDS) { ctx->error = std::string(fn) + ": shadow rays still under way after 257 rounds"; return TGHIP_E_UNSUPPORTED; }
+        const uint32_t *list = ctx->dqList[(round + 1) & 1].get();
+        uint32_t *next = ctx->dqList[round & 1].get();
+        HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, nullptr, walkState, list, live, counters, q.blocks(live), q.refillAt, q.lds));
+        HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, list, live, next, counters + 1));
+        HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TGHIP_OK;
+}
+
 int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const TgHipRay *rays, const int32_t *media, TgHipDirect *out, size_t n)
 {
     if (!ctx) return TGHIP_E_INVALID;
@@ -1882,20 +1918,11 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
     const uint64_t spp = uint64_t(desc->spp_end) - desc->spp_begin;
     const uint64_t samplesPer = std::min<uint64_t>(spp, DIRECT_QUERY_CHUNK);
     const uint64_t raysPer = std::min<uint64_t>(n, std::max<uint64_t>(1, DIRECT_QUERY_CHUNK/samplesPer));
-    const size_t items = size_t(raysPer*samplesPer);
-    if ((rc = ctx->dqStatus.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqWeight.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqOrigin.grow(ctx, items)) != TGHIP_OK ||
-        (rc = ctx->dqO.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqD.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqHits.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqT.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqB.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqC.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK)
-        return rc;
-    if (q.inst && (rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK) return rc;
+    DirectState st;
+    TransmittanceState walkState;
+    if ((rc = directScratch(ctx, q, size_t(raysPer*samplesPer), st, walkState)) != TGHIP_OK) return rc;
     if (!volume && (rc = ctx->dqRayHits.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
     if (!volume && q.inst && (rc = ctx->dqRayInst.grow(ctx, size_t(raysPer))) != TGHIP_OK) return rc;
-    const DirectState st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
-                            q.inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
-    // (the shadow walks are tghip_query_transmittance's, reading segments through a list: of its state they touch o, d, hits and inst)
-    const TransmittanceState walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
     const float4 *rayHits = volume ? nullptr : ctx->dqRayHits.get();
     int *rayInst = !volume && q.inst ? ctx->dqRayInst.get() : nullptr;
     DirectParams p;
@@ -1915,18 +1942,7 @@ int tghip_query_direct(tghip_ctx *ctx, const TgHipDirectQueryDesc *desc, const T
                 uint32_t live = 0;
                 HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                // A segment that goes on has crossed a surface (bounce++) and bounce >= max_bounces ends it: the rounds are bounded whatever the rays do
-                for (int round = 0; live > 0; ++round) {
-                    if (round >= DIRECT_QUERY_MAX_ROUNDS) { ctx->error = "tghip_query_direct: shadow rays still under way after 257 rounds"; return TGHIP_E_UNSUPPORTED; }
-                    const uint32_t *list = ctx->dqList[(round + 1) & 1].get();
-                    uint32_t *next = ctx->dqList[round & 1].get();
-                    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
-                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, nullptr, walkState, list, live, counters, q.blocks(live), q.refillAt, q.lds));
-                    HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, list, live, next, counters + 1));
-                    // the one word a round hands back: how many segments the next one has
-                    HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                }
+                if ((rc = directShadowRounds(ctx, "tghip_query_direct", q, st, walkState, live)) != TGHIP_OK) return rc;
                 HIP_TRY(ctx, directQueryLaunchFinish(ctx->stream, p, volume, dMedia, ctx->scene.num_media, rayHits, st, dOut));
             }
         }
@@ -1951,12 +1967,13 @@ int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const T
     if ((rc = checkVertexQuery(desc, rays, media, paths, alive, n, &facts, ctx->error)) != TGHIP_OK) return rc;
     if ((rc = queryBegin(ctx, "tghip_query_vertex", n)) != TGHIP_OK) return rc;
     const bool device = (desc->flags & TGHIP_DEVELOP_DEVICE_POINTERS) != 0, start = (desc->flags & TGHIP_VERTEX_START) != 0;
-    if (n == 0) {
-        const uint32_t none = 0;
-        if (alive && device) HIP_TRY(ctx, hipMemcpy(alive, &none, sizeof none, hipMemcpyDefault));   // (device memory, or a host word: see the header)
-        else if (alive) *alive = 0;
+    // *alive, where it is asked for: device memory, or a host word (see the header)
+    auto putAlive = [&](uint32_t count) -> int {
+        if (alive && device) HIP_TRY(ctx, hipMemcpy(alive, &count, sizeof count, hipMemcpyDefault));
+        else if (alive) *alive = count;
         return TGHIP_OK;
-    }
+    };
+    if (n == 0) return putAlive(0);
     const size_t pathBytes = n*sizeof(TgHipPath);
     const float4 *dRays = nullptr;
     const int *dMedia = nullptr;
@@ -1972,18 +1989,13 @@ int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const T
     }
     const QueryWalk q = queryWalk(ctx);
     const size_t items = std::min<size_t>(n, VERTEX_QUERY_CHUNK);
-    if ((rc = ctx->dqStatus.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqWeight.grow(ctx, items)) != TGHIP_OK || (rc = ctx->dqOrigin.grow(ctx, items)) != TGHIP_OK ||
-        (rc = ctx->dqO.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqD.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqHits.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqT.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqB.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqC.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqE.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqRes.grow(ctx, 2*items)) != TGHIP_OK ||
-        (rc = ctx->dqList[0].grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->dqList[1].grow(ctx, 2*items)) != TGHIP_OK ||
+    DirectState st;
+    TransmittanceState walkState;
+    if ((rc = directScratch(ctx, q, items, st, walkState)) != TGHIP_OK ||
         (rc = ctx->vqWalkRays.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->vqHits.grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqW.grow(ctx, items)) != TGHIP_OK ||
         (rc = ctx->vqP.grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqList[0].grow(ctx, items)) != TGHIP_OK || (rc = ctx->vqList[1].grow(ctx, items)) != TGHIP_OK)
         return rc;
-    if (q.inst && ((rc = ctx->dqInst.grow(ctx, 2*items)) != TGHIP_OK || (rc = ctx->vqInst.grow(ctx, items)) != TGHIP_OK)) return rc;
-    const DirectState st = {ctx->dqStatus.get(), ctx->dqWeight.get(), ctx->dqOrigin.get(), ctx->dqO.get(), ctx->dqD.get(), ctx->dqHits.get(),
-                            q.inst ? ctx->dqInst.get() : nullptr, ctx->dqT.get(), ctx->dqB.get(), ctx->dqC.get(), ctx->dqE.get(), ctx->dqRes.get()};
-    const TransmittanceState walkState = {st.o, st.d, nullptr, nullptr, st.hits, st.inst};
+    if (q.inst && (rc = ctx->vqInst.grow(ctx, items)) != TGHIP_OK) return rc;
     const VertexState vs = {ctx->vqW.get(), ctx->vqP.get()};
     int *pathInst = q.inst ? ctx->vqInst.get() : nullptr;
     VertexParams p;
@@ -2010,17 +2022,7 @@ int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const T
                 uint32_t segments = 0;
                 HIP_TRY(ctx, hipMemcpyAsync(&segments, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                // the shadow segments: tghip_query_direct's rounds as they are (a segment that goes on has crossed a surface: bounded by max_bounces)
-                for (int round = 0; segments > 0; ++round) {
-                    if (round >= DIRECT_QUERY_MAX_ROUNDS) { ctx->error = "tghip_query_vertex: shadow rays still under way after 257 rounds"; return TGHIP_E_UNSUPPORTED; }
-                    const uint32_t *segList = ctx->dqList[(round + 1) & 1].get();
-                    uint32_t *segNext = ctx->dqList[round & 1].get();
-                    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 2*sizeof(uint32_t), ctx->stream));
-                    HIP_TRY(ctx, transmittanceQueryLaunchWalk(ctx->stream, ctx->scene, q.walk, nullptr, walkState, segList, segments, counters, q.blocks(segments), q.refillAt, q.lds));
-                    HIP_TRY(ctx, directQueryLaunchRound(ctx->stream, ctx->scene, st, segList, segments, segNext, counters + 1));
-                    HIP_TRY(ctx, hipMemcpyAsync(&segments, counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                }
+                if ((rc = directShadowRounds(ctx, "tghip_query_vertex", q, st, walkState, segments)) != TGHIP_OK) return rc;   // tghip_query_direct's, as they are
                 HIP_TRY(ctx, vertexQueryLaunchBack(ctx->stream, dPaths, list, live, st, vs, next, ctx->vqWalkRays.get(), counters + 2));
                 // the one word a turn hands back: how many paths the next one has
                 HIP_TRY(ctx, hipMemcpyAsync(&live, counters + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -2030,10 +2032,7 @@ int tghip_query_vertex(tghip_ctx *ctx, const TgHipVertexQueryDesc *desc, const T
         }
         return TGHIP_OK;
     }, [&]() { return copyBack(ctx, paths, dPaths, pathBytes); });
-    if (rc != TGHIP_OK) return rc;
-    if (alive && device) HIP_TRY(ctx, hipMemcpy(alive, &aliveTotal, sizeof aliveTotal, hipMemcpyDefault));
-    else if (alive) *alive = aliveTotal;
-    return TGHIP_OK;
+    return rc != TGHIP_OK ? rc : putAlive(aliveTotal);
 }
 
 int tghip_query_vertex_kernel_time(tghip_ctx *ctx, double *ms) { return kernelTime(ctx, &tghip_ctx::vqMs, ms); }

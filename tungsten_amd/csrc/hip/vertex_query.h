@@ -37,7 +37,8 @@ struct VertexState {
 hipError_t vertexQueryLaunchBegin(hipStream_t stream, const VertexParams &p, uint32_t numMedia, const float4 *rays, const int *media, float4 *paths,
                                   uint32_t *list, float4 *walkRays, uint32_t *count);
 // The front stage, behind the closest-hit walk over walkRays (hits / inst, indexed like `list`): one lane per live path does everything of the turn
-// that needs no shadow walk and writes the path's new state but for the terms the back stage adds; item j of `st` is path list[j]'s direct estimate,
+// that needs no shadow walk and writes the path's new state but for the terms the back stage adds; item j of `st` is path list[j]'s direct estimate
+// (direct_estimate.h's bodies, as k_direct_setup calls them, but without the segment of a light sample whose emission is zero),
 // its live segments appended to segList, counted in *segCount (zero when the launch starts; segList holds two words per path).
 hipError_t vertexQueryLaunchFront(hipStream_t stream, const DeviceScene &scene, float4 *paths, const uint32_t *list, uint32_t live, const float4 *hits,
                                   const int *inst, const DirectState &st, const VertexState &vs, uint32_t *segList, uint32_t *segCount);

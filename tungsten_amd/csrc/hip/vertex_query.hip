@@ -6,62 +6,26 @@
 //   k_vertex_begin   one lane per path, once per call and part: TGHIP_VERTEX_START makes the state from the ray; the live paths are appended to the
 //                    first turn's list, their rays written next to it for the walk.
 //   k_vertex_front   one lane per live path behind the walk: the medium's distance sample, the transparency boolean, makeLocalScatterEvent, the
-//                    direct estimate's draws with everything that needs no shadow walk (k_direct_setup's surface and volume bodies, restated here on
-//                    the path's own stream, medium and bounce + 1: a second copy, so that k_direct_setup, k_direct_round and k_direct_finish keep
-//                    their code), the emissive term, the BSDF or phase sample, the roulette draw and the next ray.  The direct term's factors and
-//                    the emissive term stay apart; the rest of the new state is written.
+//                    direct estimate's draws with everything that needs no shadow walk (direct_estimate.h's surface and volume bodies, the ones
+//                    k_direct_setup calls, here on the path's own stream, medium and bounce + 1 and without the segment of a black light sample),
+//                    the emissive term, the BSDF or phase sample, the roulette draw and the next ray.  The direct term's factors and the emissive
+//                    term stay apart; the rest of the new state is written.
 //   k_vertex_back    one lane per live path behind the shadow rounds: emission += estimateDirect*throughput, then the emissive hit's term
 //                    (TraceBase.cpp:537-543), the NaN guards on the emission after both, the status; 16-byte accesses.  The survivors are appended to
 //                    the next turn's list with their rays: one atomicAdd per wave (ballot, popcount, rank).
 // Separate launches for the reasons direct_query.hip gives: the front stage carries BSDF, texture, light and medium code at once and must not share
 // registers with a walk, and a round's lanes are the segments still alive.
-// One instantiation, under the all-features family's mask with FEAT_QMC cleared: the keyed PCG stream only, and an answer never depends on which
-// shading family the scene's passes use.
+// One instantiation, under direct_estimate.h's DIRECT_MASK (the all-features family's mask with FEAT_QMC cleared): the keyed PCG stream only, and an
+// answer never depends on which shading family the scene's passes use.
 #include "vertex_query.h"
-#include "pt_wavefront.h"
-
-#define VERTEX_MASK (BSDF_MASK_ALL & ~FEAT_QMC)
+#include "direct_estimate.h"
 
 namespace {
 
-// where a lane that is `alive` appends, counted in *count: one atomicAdd per wave.  Called by all 64 lanes.
-PT_DEV uint32_t appendPlace(bool alive, uint32_t *count)
-{
-    const unsigned long long on = __ballot(alive);
-    uint32_t base = 0;
-    if (on != 0ull) {
-        const uint32_t lane = laneId();
-        if (lane == 0)
-            base = atomicAdd(count, (uint32_t)__popcll(on));
-        base = __shfl(base, 0) + (uint32_t)__popcll(on & ((1ull << lane) - 1ull));
-    }
-    return base;
-}
-
-PT_DEV void appendLive(bool alive, uint32_t g, uint32_t *list, uint32_t *count)
-{
-    const uint32_t at = appendPlace(alive, count);
-    if (alive) list[at] = g;
-}
-
-PT_DEV void putSegment(const DirectState &st, uint32_t g, f3 o, float tmin, f3 d, float tmax, int medium, uint32_t bounce, int endCap, float mis,
-                       f3 c, float cw, f3 e, float ew)
-{
-    st.o[g] = mk4(o, tmin);
-    st.d[g] = mk4(d, tmax);
-    st.t[g] = mk4(splat3(1.0f), __int_as_float(medium));
-    st.b[g] = make_uint4(bounce, (uint32_t)endCap, __float_as_uint(0.0f), __float_as_uint(mis));
-    st.c[g] = mk4(c, cw);
-    st.e[g] = mk4(e, ew);
-}
-
-// The far distance the walk of a segment [tmin, tmax) starts with (radiance_query.hip: queryWalkFar): 2^-10 further than a finite tmax, so that the
-// front stage ends the segment exactly -- a hit counts when t < tmax -- whatever the walk's own arithmetic does within a few ulps of its far distance
-PT_DEV float walkFar(float tmax) { return (tmax > 0.0f && tmax < PT_INF) ? tmax*1.0009765625f : tmax; }
-
+// (the walk looks a little further than the segment reaches, query_walk.h: the front stage ends the segment exactly)
 PT_DEV void putWalkRay(float4 *walkRays, uint32_t at, float4 ro, float4 rd)
 {
-    rd.w = walkFar(rd.w);
+    rd.w = queryWalkFar(rd.w);
     walkRays[(size_t)at*2u + 0u] = ro;
     walkRays[(size_t)at*2u + 1u] = rd;
 }
@@ -80,12 +44,7 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_begin(VertexPar
         float4 *P = paths + (size_t)i*VERTEX_PATH_VECTORS;
         if (p.start) {
             ro = rays[(size_t)i*2u + 0u]; rd = rays[(size_t)i*2u + 1u];
-            int medium = p.medium;
-            if (media) {
-                medium = media[i];
-                if (medium == TGHIP_MEDIUM_OF_CAMERA) medium = p.cameraMedium;
-                if (medium < 0 || (uint32_t)medium >= numMedia) medium = -1;
-            }
+            const int medium = rayStartMedium(p, media, numMedia, i);
             const uint32_t key = p.firstIndex + i;
             Rng rng = rngStart(p.seed, key, p.sample);          // PathSampleGenerator::startPath
             for (uint32_t k = 0; k < p.firstNumber; ++k) (void)rngNextI(rng);
@@ -103,19 +62,18 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_begin(VertexPar
             if (alive) { ro = P[0]; rd = P[1]; }
         }
     }
-    const uint32_t at = appendPlace(alive, count);
-    if (alive) {
+    appendAt(alive, count, [&](uint32_t at) {
         list[at] = i;
         putWalkRay(walkRays, at, ro, rd);
-    }
+    });
 }
 
 __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceScene s, float4 *paths, const uint32_t *list, uint32_t live, const float4 *hits,
                                                                       const int *inst, DirectState st, VertexState vs, uint32_t *segList, uint32_t *segCount)
 {
-    constexpr uint32_t M = VERTEX_MASK;
+    constexpr uint32_t M = DIRECT_MASK;
     const uint32_t j = blockIdx.x*VERTEX_QUERY_THREADS + threadIdx.x;
-    bool q0 = false, q1 = false;
+    uint32_t status = 0u;
     if (j < live) {
         float4 *P = paths + (size_t)list[j]*VERTEX_PATH_VECTORS;
         const float4 c0 = P[0], c1 = P[1], c2 = P[2], c3 = P[3], c4 = P[4], c5 = P[5], c6 = P[6];
@@ -141,7 +99,7 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
         const int hitInst = inst ? inst[j] : -1;
         const int maxBounces = s.settings.max_bounces, minBounces = s.settings.min_bounces;
         const bool nee = s.settings.enable_light_sampling != 0;
-        uint32_t end = 0u, status = 0u, add = 0u;
+        uint32_t end = 0u, add = 0u;
         float lightWeight = 1.0f;
         f3 directThroughput = splat3(0.0f), pending = splat3(0.0f);
 
@@ -193,64 +151,14 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
             end = TGHIP_PATH_END_ABSORBED;
         } else if (volumeEvent) {
             // TraceBase::handleVolume (TraceBase.cpp:496-514) with volumeEstimateDirect / volumeSampleDirect / volumeLightSample / volumePhaseSample
-            // (:323-381, 402-414, 470-481): k_direct_setup<true>'s body at mediumSample.p
+            // (:323-381, 402-414, 470-481): direct_estimate.h's volume body at mediumSample.p
             const TgHipMedium &mm = s.media[med];
             const bool volumeNee = s.settings.enable_volume_light_sampling != 0;
             wasSpecular = !volumeNee;
             if (volumeNee && bounce < maxBounces - 1) {
-                const uint32_t segBounce = (uint32_t)(bounce + 1);
-                const int light = chooseLight<M>(s, rng, volP, lightWeight);
-                if (light >= 0) {
-                    status |= DIRECT_ITEM_ESTIMATE;
-                    const bool meshLight = s.objects[light].type == TGHIP_OBJ_MESH;
-                    const bool diracLight = s.objects[light].type == TGHIP_OBJ_POINT;
-                    if (diracLight) status |= DIRECT_ITEM_DIRAC;
-                    {
-                        f3 d; float dist, pdf;
-                        if (lightSampleDirect<M>(s, light, volP, rng, d, dist, pdf)) {
-                            const float f = phaseEval(mm, ray.d, d);
-                            if (f != 0.0f && meshLight) {
-                                putSegment(st, j*2u, volP, 0.0f, d, PT_INF, med, segBounce, light, powerHeuristic(pdf, f), splat3(f), dist, splat3(0.0f), pdf);
-                                q0 = true;
-                            } else if (f != 0.0f) {
-                                RayD sr; sr.o = volP; sr.d = d; sr.tmin = 0.0f; sr.tmax = PT_INF;   // parentRay.scatter(p, d, 0.0f)
-                                LightHit lh;
-                                bool reached;
-                                if (diracLight) { lh.t = dist; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f); reached = true; }
-                                else reached = lightIntersect<M>(s, light, sr, lh) && !(lh.t*(1.0f + 1e-3f) < dist);
-                                if (reached) {
-                                    const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                    if (!isZero(e)) {
-                                        putSegment(st, j*2u, volP, 0.0f, d, lh.t, med, segBounce, light, diracLight ? 1.0f : powerHeuristic(pdf, f), splat3(f), 0.0f, e, pdf);
-                                        q0 = true;
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    if (!diracLight) {
-                        f3 w; float ppdf;
-                        phaseSample<M>(mm, rng, ray.d, w, ppdf);
-                        if (meshLight) {
-                            putSegment(st, j*2u + 1u, volP, 0.0f, w, PT_INF, med, segBounce, light, 1.0f, splat3(1.0f), ppdf, splat3(0.0f), 0.0f);   // directPdf needs the hit
-                            q1 = true;
-                        } else {
-                            RayD sr; sr.o = volP; sr.d = w; sr.tmin = 0.0f; sr.tmax = PT_INF;
-                            LightHit lh;
-                            if (lightIntersect<M>(s, light, sr, lh)) {
-                                const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                if (!isZero(e)) {
-                                    const float mis1 = powerHeuristic(ppdf, lightDirectPdf<M>(s, light, w, volP, lh));
-                                    putSegment(st, j*2u + 1u, volP, 0.0f, w, lh.t, med, segBounce, light, mis1, splat3(1.0f), 0.0f, e, 0.0f);   // phaseSample.weight = 1
-                                    q1 = true;
-                                }
-                            }
-                        }
-                    }
-                    st.origin[j] = mk4(volP, 0.0f);
-                    directThroughput = throughput;
-                    if (q0 || q1) add |= VERTEX_ADD_PENDING;   // (the pending term of a volume vertex is zero)
-                }
+                status = estimateDirectVolume(s, st, j, rng, volP, ray.d, med, (uint32_t)(bounce + 1), -1, lightWeight);
+                if (status & DIRECT_ITEM_ESTIMATE) directThroughput = throughput;
+                if (status & (DIRECT_ITEM_SEG0 | DIRECT_ITEM_SEG1)) add |= VERTEX_ADD_PENDING;   // (the pending term of a volume vertex is zero)
             }
             f3 w; float ppdf;
             phaseSample<M>(mm, rng, ray.d, w, ppdf);         // the continuation; throughput *= 1
@@ -259,34 +167,14 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
             // the path escaped (the loop's condition failed, or PathTracer.cpp:59-60): the epilogue below
             end = TGHIP_PATH_END_ESCAPED;
         } else {
-            Info info;
-            intersectionInfo<M>(s, ray, hit, info, hitInst);
-            const uint32_t lobes = s.bsdfs[info.bsdf].lobes;
-            // TraceBase::makeLocalScatterEvent (TraceBase.cpp:24-51)
-            Frame frame = shadingFrame<M>(s, info);
-            const bool hitBackside = dot(frame.normal, ray.d) > 0.0f;
-            const bool flipped = s.settings.enable_two_sided_shading && hitBackside && !(lobes & LOBE_TRANSMISSIVE);
-            if (flipped) {
-                frame.normal = -frame.normal;
-                frame.tangent = -frame.tangent;
-            }
+            ScatterPoint pt;
             Event ev;
-            ev.wi = toLocal(frame, -ray.d);
-            ev.u = info.u; ev.v = info.v; ev.rng = &rng;
-            const bool consistency = s.settings.enable_consistency_checks != 0;
-            auto isConsistent = [&](f3 woLocal, f3 w) {      // TraceBase.cpp:53-60
-                if (!consistency) return true;
-                const bool geometricBackside = dot(w, info.Ng) < 0.0f;
-                const bool shadingBackside = (woLocal.z < 0.0f) != flipped;
-                return geometricBackside == shadingBackside;
-            };
-            // each shadow ray starts in the medium on its side of the surface (TraceBase.cpp:260-261, 302-303)
-            auto sideMedium = [&](f3 dir) {
-                return s.num_media ? selectMedium(s.objects[info.object], med, dot(dir, info.Ng) < 0.0f) : med;
-            };
+            makeScatterPoint(s, ray, hit, hitInst, rng, pt, ev);
+            const Info &info = pt.info;
+            const Frame &frame = pt.frame;
 
             f3 transparency = splat3(0.0f);
-            if (lobes & TGHIP_LOBE_FORWARD) {
+            if (pt.lobes & TGHIP_LOBE_FORWARD) {
                 ev.wo = -ev.wi; ev.requested = TGHIP_LOBE_FORWARD;
                 transparency = bsdfEval<M>(s, info.bsdf, ev);
             }
@@ -297,76 +185,11 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
                 wo = ray.d;
                 throughput = throughput*(transparency/transparencyScalar);
             } else {
-                // estimateDirect (TraceBase.cpp:483-494) as k_direct_setup<false> computes it, with bounce + 1, the path's medium and stream
+                // estimateDirect (TraceBase.cpp:483-494): direct_estimate.h's surface body with bounce + 1, the path's medium and stream; no visibility
+                // output here, so no segment for a light sample without emission
                 if (nee && bounce < maxBounces - 1) {
-                    const uint32_t segBounce = (uint32_t)(bounce + 1);
-                    const int light = chooseLight<M>(s, rng, info.p, lightWeight);
-                    const bool pureSpecular = lobes != 0 && (lobes & ~(uint32_t)LOBE_SPECULAR) == 0;
-                    if (light >= 0 && !pureSpecular && lobes != TGHIP_LOBE_FORWARD) {
-                        status |= DIRECT_ITEM_ESTIMATE;
-                        const bool meshLight = s.objects[light].type == TGHIP_OBJ_MESH;
-                        const bool diracLight = s.objects[light].type == TGHIP_OBJ_POINT;
-                        if (diracLight) status |= DIRECT_ITEM_DIRAC;
-                        // lightSample (TraceBase.cpp:246-285)
-                        {
-                            f3 d; float dist, pdf;
-                            if (lightSampleDirect<M>(s, light, info.p, rng, d, dist, pdf)) {
-                                ev.wo = toLocal(frame, d);
-                                ev.requested = LOBE_ALL_BUT_SPECULAR;
-                                if (isConsistent(ev.wo, d)) {
-                                    const f3 f = bsdfEval<M>(s, info.bsdf, ev);
-                                    if (!isZero(f) && meshLight) {
-                                        // whether the ray reaches a mesh emitter, and with which emission, is known after the walk: the round completes the term
-                                        putSegment(st, j*2u, info.p, 5e-4f, d, PT_INF, sideMedium(d), segBounce, light, powerHeuristic(pdf, bsdfPdf<M>(s, info.bsdf, ev)), f, dist,
-                                                   splat3(0.0f), pdf);
-                                        q0 = true;
-                                    } else if (!isZero(f)) {
-                                        RayD sr; sr.o = info.p; sr.d = d; sr.tmin = 5e-4f; sr.tmax = PT_INF;
-                                        LightHit lh;
-                                        // attenuatedEmission's own hit and distance test (TraceBase.cpp:155-162); a Dirac light's shadow ray ends at the sampled distance
-                                        bool reached;
-                                        if (diracLight) { lh.t = dist; lh.u = 0.0f; lh.v = 0.0f; lh.backSide = false; lh.n = splat3(0.0f); reached = true; }
-                                        else reached = lightIntersect<M>(s, light, sr, lh) && !(lh.t*(1.0f + 1e-3f) < dist);
-                                        if (reached) {
-                                            const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                            if (!isZero(e)) {          // (no visibility output here: a black side needs no shadow ray)
-                                                const float mis0 = diracLight ? 1.0f : powerHeuristic(pdf, bsdfPdf<M>(s, info.bsdf, ev));   // no MIS against a Dirac light (:281-282)
-                                                putSegment(st, j*2u, info.p, 5e-4f, d, lh.t, sideMedium(d), segBounce, light, mis0, f, 0.0f, e, pdf);
-                                                q0 = true;
-                                            }
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                        // bsdfSample (TraceBase.cpp:287-321); not for Dirac lights (:396-397)
-                        if (!diracLight) {
-                            ev.requested = LOBE_ALL_BUT_SPECULAR;
-                            ev.weight = splat3(1.0f); ev.pdf = 1.0f;
-                            if (bsdfSample<M>(s, info.bsdf, ev) && !isZero(ev.weight)) {
-                                const f3 wog = toGlobal(frame, ev.wo);
-                                if (isConsistent(ev.wo, wog)) {
-                                    if (meshLight) {
-                                        putSegment(st, j*2u + 1u, info.p, 5e-4f, wog, PT_INF, sideMedium(wog), segBounce, light, 1.0f, ev.weight, ev.pdf, splat3(0.0f), 0.0f);   // directPdf needs the hit
-                                        q1 = true;
-                                    } else {
-                                        RayD sr; sr.o = info.p; sr.d = wog; sr.tmin = 5e-4f; sr.tmax = PT_INF;
-                                        LightHit lh;
-                                        if (lightIntersect<M>(s, light, sr, lh)) {
-                                            const f3 e = lightEvalDirect<M>(s, light, lh.u, lh.v, lh.backSide);
-                                            if (!isZero(e)) {
-                                                const float mis1 = powerHeuristic(ev.pdf, lightDirectPdf<M>(s, light, wog, info.p, lh));
-                                                putSegment(st, j*2u + 1u, info.p, 5e-4f, wog, lh.t, sideMedium(wog), segBounce, light, mis1, ev.weight, 0.0f, e, 0.0f);
-                                                q1 = true;
-                                            }
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                        st.origin[j] = mk4(info.p, 0.0f);
-                        directThroughput = throughput;
-                    }
+                    status = estimateDirectSurface<false>(s, st, j, rng, pt, ev, med, (uint32_t)(bounce + 1), -1, lightWeight);
+                    if (status & DIRECT_ITEM_ESTIMATE) directThroughput = throughput;
                 }
                 // emission of the surface itself (TraceBase.cpp:540-543): added behind the direct term, by the back stage
                 {
@@ -383,7 +206,7 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
                     alive = false;
                 } else {
                     wo = toGlobal(frame, ev.wo);
-                    if (!isConsistent(ev.wo, wo)) {
+                    if (!isConsistent(s, pt, ev.wo, wo)) {
                         alive = false;
                     } else {
                         throughput = throughput*ev.weight;
@@ -395,9 +218,8 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
                 end = TGHIP_PATH_END_ABSORBED;
             } else {
                 const f3 hp = ray.o + ray.d*hit.x;           // ray.hitpoint()
-                if (s.num_media)                             // TraceBase.cpp:561-563
-                    med = selectMedium(s.objects[info.object], med, dot(wo, info.Ng) < 0.0f);
-                medBounce = 0;                               // state.reset()
+                med = sideMedium(s, pt, med, wo);            // TraceBase.cpp:561-563
+                medBounce = 0;                              // state.reset()
                 continuePath(hp, wo, 5e-4f);
             }
         }
@@ -437,13 +259,13 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_front(DeviceSce
         P[4] = make_float4(__uint_as_float(medBounce), __uint_as_float((uint32_t)bounce), __uint_as_float(wasSpecular ? TGHIP_PATH_WAS_SPECULAR : 0u), hit.w);
         P[5] = make_float4(didHit ? hit.x : 0.0f, __uint_as_float((uint32_t)rng.state), __uint_as_float((uint32_t)(rng.state >> 32)), c5.w);
         P[6] = make_float4(__uint_as_float(drawn), c6.y, c6.z, c6.w);
-        st.status[j] = status | (q0 ? DIRECT_ITEM_SEG0 : 0u) | (q1 ? DIRECT_ITEM_SEG1 : 0u);
+        st.status[j] = status;
         st.weight[j] = lightWeight;
         vs.w[j] = mk4(directThroughput, lightWeight);
         vs.p[j] = mk4(pending, __uint_as_float(add));
     }
-    appendLive(q0, j*2u, segList, segCount);
-    appendLive(q1, j*2u + 1u, segList, segCount);
+    appendLive((status & DIRECT_ITEM_SEG0) != 0u, j*2u, segList, segCount);
+    appendLive((status & DIRECT_ITEM_SEG1) != 0u, j*2u + 1u, segList, segCount);
 }
 
 // sampleDirect: result(0) += lightSample, += bsdfSample unless the light is a Dirac one (TraceBase.cpp:390-399), times chooseLight's weight (:493) as
@@ -465,13 +287,8 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_back(float4 *pa
         const uint32_t status = st.status[j];
         const float4 p = vs.p[j];
         if (status & (DIRECT_ITEM_SEG0 | DIRECT_ITEM_SEG1)) {
-            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            const float4 r0 = (status & DIRECT_ITEM_SEG0) ? st.res[j*2u] : zero;
-            f3 result = splat3(0.0f) + xyz(r0);
-            if (!(status & DIRECT_ITEM_DIRAC)) {
-                const float4 r1 = (status & DIRECT_ITEM_SEG1) ? st.res[j*2u + 1u] : zero;
-                result = result + xyz(r1);
-            }
+            float shadowT;                               // (no visibility output here)
+            const f3 result = directItemResult(st, j, status, shadowT);
             const float4 w = vs.w[j];
             em = em + (result*w.w)*xyz(w);               // emission += estimateDirect(...)*throughput
         }
@@ -487,11 +304,10 @@ __global__ __launch_bounds__(VERTEX_QUERY_THREADS) void k_vertex_back(float4 *pa
         P[3] = c3;
         alive = end == 0u;
     }
-    const uint32_t at = appendPlace(alive, nextCount);
-    if (alive) {
+    appendAt(alive, nextCount, [&](uint32_t at) {
         next[at] = i;
         putWalkRay(walkRays, at, P[0], P[1]);
-    }
+    });
 }
 
 hipError_t vertexQueryLaunchBegin(hipStream_t stream, const VertexParams &p, uint32_t numMedia, const float4 *rays, const int *media, float4 *paths,
