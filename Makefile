@@ -17,7 +17,10 @@ LIBNAME  := $(if $(PROFILE),libtungsten_hip_prof.so,$(if $(VARIANT),libtungsten_
 HOSTSRC  := $(wildcard tungsten_amd/csrc/host/*.cpp)
 HOSTLIB  := $(filter-out tungsten_amd/csrc/host/main.cpp,$(HOSTSRC))
 HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB))
-# the shim (tungsten_hip.hip; its context: shim_context.h, device_array.h) + reduce.hip, its RCCL reduces (host code only) + one translation unit per family of
+# the kernels' unit and the core of the shim (tungsten_hip.hip: context, options, upload, launch plan, render pass, tghip_debug_libm with its two kernels; the
+# context and what the shim's units share: shim_context.h, device_array.h) + the shim's host-only units, which hold no kernel and take no kernel's address --
+# shim_queries.hip (tghip_query_*), shim_images.hip (the transfers, tghip_develop, tghip_nlmeans), shim_debug.hip (tghip_debug_bsdf / _light / _medium), reduce.hip
+# (the RCCL reduces): a change to one of them compiles in seconds and moves no kernel + debug_units.hip, the kernels behind shim_debug.hip + one translation unit per family of
 # explicit instantiations (pt_instances.h lists each unit's; they compile in parallel under make -j) + develop.hip, the kernels of tghip_develop,
 # + denoise.hip, the NL-means kernel of tghip_nlmeans (its host comparator csrc/host/Denoise.cpp comes in through HOSTSRC)
 # + ray_query.hip, the kernels of tghip_query_rays (its argument check csrc/host/RayQuery.cpp comes in through HOSTSRC; the claim, the ray load and the
@@ -33,7 +36,7 @@ HOSTOBJ  := $(patsubst tungsten_amd/csrc/host/%.cpp,$(OBJDIR)/host_%.o,$(HOSTLIB
 HIPSRC   := $(wildcard tungsten_amd/csrc/hip/*.hip)
 HIPOBJ   := $(patsubst tungsten_amd/csrc/hip/%.hip,$(OBJDIR)/%.o,$(HIPSRC))
 # (the shim reads what csrc/host/SceneCheck.cpp decided about a scene, SceneTraits, what csrc/host/PassPlan.cpp decided about a pass, PassPlan, what
-# csrc/host/LaunchChoice.cpp decided about the pass's kernels, LaunchChoice, and calls csrc/host/RayQuery.cpp's check of a query)
+# csrc/host/LaunchChoice.cpp decided about the pass's kernels, LaunchChoice; shim_queries.hip calls the queries' checks, csrc/host/*Query.cpp)
 HIPHDR   := $(wildcard tungsten_amd/csrc/hip/*.h) include/tungsten_hip.h tungsten_amd/csrc/host/SceneCheck.hpp tungsten_amd/csrc/host/PassPlan.hpp tungsten_amd/csrc/host/RayQuery.hpp tungsten_amd/csrc/host/RadianceQuery.hpp tungsten_amd/csrc/host/SurfaceQuery.hpp tungsten_amd/csrc/host/TransmittanceQuery.hpp tungsten_amd/csrc/host/DirectQuery.hpp tungsten_amd/csrc/host/VertexQuery.hpp tungsten_amd/csrc/host/LaunchChoice.hpp
 # -ffp-contract=off: no FMA contraction, so device arithmetic rounds like the CPU reference/oracle
 # (DESIGN.md "Numerics"); TG_FAST=1 allows contraction.

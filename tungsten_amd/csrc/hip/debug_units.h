@@ -1,5 +1,5 @@
 // Launchers of debug_units.hip: the product's BSDF and light code called on caller-supplied cases (tghip_debug_bsdf, tghip_debug_light, tghip_debug_medium, include/tungsten_hip.h).  The shim in
-// tungsten_hip.hip owns the context, checks the arguments and stages the host arrays; this enqueues the kernels on `stream` and returns.
+// shim_debug.hip holds the context, checks the arguments and stages the host arrays; this enqueues the kernels on `stream` and returns.
 #ifndef TGAMD_DEBUG_UNITS_H_
 #define TGAMD_DEBUG_UNITS_H_
 

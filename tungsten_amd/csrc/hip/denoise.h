@@ -1,4 +1,4 @@
-// Launcher of denoise.hip: the denoiser's NL-means filter on the device (tghip_nlmeans, include/tungsten_hip.h).  The shim in tungsten_hip.hip owns
+// Launcher of denoise.hip: the denoiser's NL-means filter on the device (tghip_nlmeans, include/tungsten_hip.h).  The shim in shim_images.hip holds
 // the context, checks the arguments, develops an aux source's planes and stages host arrays; this enqueues the kernel on `stream` and returns.
 #ifndef TGAMD_DENOISE_H_
 #define TGAMD_DENOISE_H_

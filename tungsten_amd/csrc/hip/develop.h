@@ -1,4 +1,4 @@
-// Launchers of develop.hip: the frame developed on the device (tghip_develop, include/tungsten_hip.h).  The shim in tungsten_hip.hip owns the
+// Launchers of develop.hip: the frame developed on the device (tghip_develop, include/tungsten_hip.h).  The shim in shim_images.hip holds the
 // context, checks the arguments and stages host outputs; these enqueue the kernels on `stream` and return.
 #ifndef TGAMD_DEVELOP_H_
 #define TGAMD_DEVELOP_H_

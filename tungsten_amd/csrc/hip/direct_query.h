@@ -1,5 +1,5 @@
 // Launchers of direct_query.hip: TraceBase::estimateDirect / volumeEstimateDirect at the hit (or start) of caller rays (tghip_query_direct,
-// include/tungsten_hip.h) as a small wavefront.  The shim in tungsten_hip.hip owns the context, checks the arguments (csrc/host/DirectQuery.cpp),
+// include/tungsten_hip.h) as a small wavefront.  The shim in shim_queries.hip holds the context, checks the arguments (csrc/host/DirectQuery.cpp),
 // stages host memory, cuts a large call into chunks of items, runs the hit walk of tghip_query_surface (surface_query.h) and the shadow walks of
 // tghip_query_transmittance (transmittance_query.h) as they are, and reads the survivors' count back behind every round; these enqueue the three
 // dense stages and return.

@@ -1,7 +1,7 @@
 // Launchers of radiance_query.hip: the two small kernels tghip_query_radiance (include/tungsten_hip.h) adds to a pass of the wavefront loop -- the
-// ray source in front of every closest-hit launch, and the copy of the pass's sums and counts into the caller's arrays.  The shim in tungsten_hip.hip
-// owns the context, checks the arguments and plans the pass (csrc/host/RadianceQuery.cpp), stages host memory and drives the loop; these enqueue
-// on `stream` and return.
+// ray source in front of every closest-hit launch, and the copy of the pass's sums and counts into the caller's arrays.  The shim in shim_queries.hip
+// holds the context, checks the arguments and plans the pass (csrc/host/RadianceQuery.cpp) and stages host memory, tungsten_hip.hip drives the loop
+// (tghipRunPass; runBatch launches the ray source); these enqueue on `stream` and return.
 #ifndef TGAMD_RADIANCE_QUERY_H_
 #define TGAMD_RADIANCE_QUERY_H_
 

@@ -1,5 +1,5 @@
 // Launcher of ray_query.hip: batched closest-hit and occlusion queries on caller rays (tghip_query_rays, include/tungsten_hip.h).  The shim in
-// tungsten_hip.hip owns the context, checks the arguments (csrc/host/RayQuery.cpp), stages host memory and resets the work counter in-stream; this
+// shim_queries.hip holds the context, checks the arguments (csrc/host/RayQuery.cpp), stages host memory and resets the work counter in-stream; this
 // enqueues the kernel on `stream` and returns.
 #ifndef TGAMD_RAY_QUERY_H_
 #define TGAMD_RAY_QUERY_H_

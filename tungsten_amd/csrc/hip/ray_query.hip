@@ -2,7 +2,7 @@
 // query of this ray has a hit" (TraceBase.cpp:79, 114-115: the closest-hit formulation of the path tracer's shadow rays; geometry only, no light to
 // leave out).  Persistent workgroups claim rays from ONE global counter: the idle lanes of a wave are counted with a ballot, one lane adds the count and
 // broadcasts the base, each idle lane takes base + its rank.  Nothing waits for another workgroup and nothing spins: a wave leaves once it holds no
-// ray and the counter has passed n.  The shim resets the counter in-stream before every launch (tungsten_hip.hip: tghip_query_rays).
+// ray and the counter has passed n.  The shim resets the counter in-stream before every launch (shim_queries.hip: tghip_query_rays).
 // The closest-hit kernels answer tghip_query_surface's walk on scenes without instances as well (surface_query.hip).  The claim, the ray load and the
 // 8-wide loop are query_walk.h's, shared with transmittance_query.hip; the per-ray loop below exists there once more over its list of rays
 // (k_transmittance_walk<WALK>), and its instanced form in surface_query.hip with the instance record kept (k_surface_walk<RAY_QUERY_INST>).

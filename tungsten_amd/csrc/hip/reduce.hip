@@ -1,5 +1,5 @@
 // The reduces of the extern "C" shim (include/tungsten_hip.h): the framebuffers of several contexts of one process, or of one context per process,
-// summed into the root's by RCCL.  Host code only: the contexts' kernels are tungsten_hip.hip's.
+// summed into the root's by RCCL.  Host code only, like the shim's other units beside tungsten_hip.hip (shim_context.h lists them).
 #include "shim_context.h"
 
 #include <cstring>
@@ -69,8 +69,8 @@ int tghip_reduce_framebuffers(tghip_ctx *const *ctxs, int n, int root, float *rg
         for (int d : devices)
             if (d == c->device) { rc->error = "tghip_reduce_framebuffers: two contexts on one device (RCCL wants one rank per device; sum on the host instead)"; return TGHIP_E_UNSUPPORTED; }
         devices.push_back(c->device);
-        int w = tghip_wait(c);
-        if (w != TGHIP_OK && w != TGHIP_E_ABORTED) return w;
+        const int w = runOutPass(c);
+        if (w != TGHIP_OK) return w;
     }
     if (npixels != size_t(rc->width)*rc->height) { rc->error = "pixel count mismatch"; return TGHIP_E_INVALID; }
     HIP_TRY(rc, hipSetDevice(rc->device));
@@ -145,8 +145,8 @@ int tghip_reduce_framebuffer_rank(tghip_ctx *ctx, int root, float *rgb_sum, uint
     if (!ctx->rankComm) { ctx->error = "tghip_reduce_framebuffer_rank: no communicator (tghip_comm_init_rank)"; return TGHIP_E_INVALID; }
     if (root < 0 || root >= ctx->rankCount || npixels != size_t(ctx->width)*ctx->height) { ctx->error = "tghip_reduce_framebuffer_rank: root / pixel count mismatch"; return TGHIP_E_INVALID; }
     if (ctx->failReduce) { ctx->error = "tghip_reduce_framebuffer_rank: forced failure (the \"fail_reduce\" option)"; return TGHIP_E_HIP; }
-    int w = tghip_wait(ctx);
-    if (w != TGHIP_OK && w != TGHIP_E_ABORTED) return w;
+    const int w = runOutPass(ctx);
+    if (w != TGHIP_OK) return w;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool isRoot = ctx->rankIndex == root;
     int grc;

@@ -1,5 +1,7 @@
-// The shim's private header: the context behind the tghip_ctx handle of include/tungsten_hip.h and the small types it is made of.  Shared by the
-// translation units that implement the extern "C" entry points: tungsten_hip.hip (everything that launches a kernel) and reduce.hip (the RCCL reduces).
+// The shim's private header: the context behind the tghip_ctx handle of include/tungsten_hip.h, the small types it is made of and the helpers more
+// than one unit of the shim uses.  Shared by the translation units that implement the extern "C" entry points: tungsten_hip.hip (the kernels' unit:
+// context, options, upload, launch plan, render pass, tghip_trace_rays, tghip_debug_libm, counters) and the host-only ones -- shim_queries.hip
+// (tghip_query_*), shim_images.hip (the transfers, tghip_develop, tghip_nlmeans), shim_debug.hip (tghip_debug_bsdf / _light / _medium), reduce.hip (the RCCL reduces).
 #pragma once
 #include "pt_kernels.h"
 #include "device_array.h"
@@ -7,6 +9,7 @@
 #include "../host/LaunchChoice.hpp"
 #include "../host/PassPlan.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -232,6 +235,37 @@ struct tghip_ctx {
 
 // reduce.hip: destroys the communicator of tghip_comm_init_rank (tghip_destroy)
 void tghipDestroyRankComm(void *comm);
+// tungsten_hip.hip: the planned pass `plan` of `pass` over a w x h image, into `target` (tghip_wait's render pass, tghip_query_radiance's query)
+int tghipRunPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t h, PassPlan &plan, const PassTarget &target);
+
+// What planPass reads of the context's options, for work items of `chunkSamples` samples ("chunk_samples"; tghip_query_radiance: always 1)
+inline PassPlanOptions passPlanOptions(const tghip_ctx *ctx, int chunkSamples) { return {uint64_t(std::max<long long>(ctx->maxItems, 256)), uint64_t(ctx->maxSlots), uint32_t(std::max(chunkSamples, 0))}; }
+// The pass under way run out, before a call reads or writes what it renders into: one that was aborted is no error of that call's
+inline int runOutPass(tghip_ctx *ctx) { const int rc = tghip_wait(ctx); return rc == TGHIP_E_ABORTED ? TGHIP_OK : rc; }
+
+// The launches of `launch` between the context's two timing events, `after` -- the copies back into host memory -- behind them and, once the stream
+// has run dry, the launches' milliseconds in `ms`.
+template<typename Launch, typename After>
+static int timedLaunches(tghip_ctx *ctx, double &ms, Launch launch, After after)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->evA, ctx->stream));
+    int rc = launch();
+    if (rc != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->evB, ctx->stream));
+    if ((rc = after()) != TGHIP_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float elapsed = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&elapsed, ctx->evA, ctx->evB));
+    ms = elapsed;
+    return TGHIP_OK;
+}
+// ... and what the tghip_*_kernel_time functions answer: the milliseconds the last such call stored
+inline int kernelTime(const tghip_ctx *ctx, double tghip_ctx::*stored, double *ms)
+{
+    if (!ctx || !ms) return TGHIP_E_INVALID;
+    *ms = ctx->*stored;
+    return TGHIP_OK;
+}
 
 // ---- "The caller's pointer, host or device" as a device pointer, with an array of the context as the scratch of host memory ----
 // An input of `bytes` bytes: the caller's device memory itself, or `scratch` -- grown to hold them -- behind a copy queued on the context's stream.

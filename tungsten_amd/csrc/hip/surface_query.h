@@ -1,5 +1,5 @@
 // Launchers of surface_query.hip: what is at the closest hit of caller rays (tghip_query_surface, include/tungsten_hip.h).  The shim in
-// tungsten_hip.hip owns the context, checks the arguments (csrc/host/SurfaceQuery.cpp), stages host memory and resets the work counter in-stream; these
+// shim_queries.hip holds the context, checks the arguments (csrc/host/SurfaceQuery.cpp), stages host memory and resets the work counter in-stream; these
 // enqueue the two stages on `stream` and return.
 #ifndef TGAMD_SURFACE_QUERY_H_
 #define TGAMD_SURFACE_QUERY_H_

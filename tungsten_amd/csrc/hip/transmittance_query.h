@@ -1,5 +1,5 @@
 // Launchers of transmittance_query.hip: TraceBase::generalizedShadowRay on caller rays (tghip_query_transmittance, include/tungsten_hip.h) as a small
-// wavefront.  The shim in tungsten_hip.hip owns the context, checks the arguments (csrc/host/TransmittanceQuery.cpp), stages host memory, resets the
+// wavefront.  The shim in shim_queries.hip holds the context, checks the arguments (csrc/host/TransmittanceQuery.cpp), stages host memory, resets the
 // two counter words in-stream before every round and reads the survivors' count back behind it; these enqueue one round's two stages and return.
 #ifndef TGAMD_TRANSMITTANCE_QUERY_H_
 #define TGAMD_TRANSMITTANCE_QUERY_H_

@@ -1,5 +1,5 @@
 // Launchers of vertex_query.hip: one turn of PathTracer::traceSample's loop (integrators/path_tracer/PathTracer.cpp:50-131) on paths whose state the
-// caller holds (tghip_query_vertex, include/tungsten_hip.h) as a small wavefront.  The shim in tungsten_hip.hip owns the context, checks the arguments
+// caller holds (tghip_query_vertex, include/tungsten_hip.h) as a small wavefront.  The shim in shim_queries.hip holds the context, checks the arguments
 // (csrc/host/VertexQuery.cpp), stages host memory, cuts a large call into parts, runs the closest-hit walk of tghip_query_surface (surface_query.h)
 // over the live paths' rays and the shadow walks and rounds of tghip_query_direct (transmittance_query.h, direct_query.h) as they are, and reads the
 // one-word counts back; these enqueue the three dense stages and return.
