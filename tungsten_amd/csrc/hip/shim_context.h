@@ -22,8 +22,9 @@
 // created after another one was destroyed came out with a binding on which the four parts of the wavefront loop no longer ran side by
 // side (materialtest 1280x720x256: 840 Msamples/s in a process's first context, 675 in every later one; the 16-spp passes of the
 // as-shipped scene 24 ms against 35 ms).  A renderer that is opened once per frame or per scene keeps its first context's streams this way.
+constexpr int TGHIP_MAX_PARTS = 8;        // parts of the pool the wavefront loop may run as ("streams" option, LaunchChoice::parts)
 struct StreamSet {
-    hipStream_t main = nullptr, part[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, abort = nullptr;
+    hipStream_t main = nullptr, part[TGHIP_MAX_PARTS - 1] = {}, abort = nullptr;
 };
 
 // The arrays of one upload -- the scene's, the pool's, the per-resolution pass arrays --, freed together
@@ -58,11 +59,11 @@ struct PassTarget {
 struct tghip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t partStream[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // streams of parts 1..3 of the split wavefront loop ("streams" option)
-    hipStream_t classStream[8][2] = {};   // per part: the streams of the shading classes that run beside the part's own ("class_streams" option)
-    hipEvent_t evFork[8] = {}, evJoin[8][2] = {};
-    hipStream_t launchStream = nullptr;   // where the launch helpers put their kernels (stream, or the stream of the part being launched)
-    hipEvent_t evPart[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, evMain = nullptr;
+    hipStream_t partStream[TGHIP_MAX_PARTS - 1] = {};   // streams of parts 1 .. 7 of the split wavefront loop ("streams" option); part 0 runs on `stream`
+    hipStream_t streamOfPart(int k) const { return k ? partStream[k - 1] : stream; }
+    hipStream_t classStream[TGHIP_MAX_PARTS][2] = {};   // per part: the streams of the shading classes that run beside the part's own ("class_streams" option)
+    hipEvent_t evFork[TGHIP_MAX_PARTS] = {}, evJoin[TGHIP_MAX_PARTS][2] = {};
+    hipEvent_t evPart[TGHIP_MAX_PARTS - 1] = {}, evMain = nullptr;
     hipDeviceProp_t prop;
     std::string error = "no error";
 
@@ -209,7 +210,7 @@ struct tghip_ctx {
     int leafBatchBvh2 = 0;                // "leaf_batch_bvh2" (PathState::leaf_batch_bvh2); 0 = leaf_batch, or the measured value for two-level scenes
     long long poolPad = 9472;             // bytes between the per-slot arrays of the pool (multiple of 16)
     bool timeKernels = false;             // HIP events around every launch of the wavefront loop (bench.py roofline)
-    std::vector<hipEvent_t> evPool;
+    std::vector<hipEvent_t> evPool;       // ... in pairs, a run of pairs per class of launches (tungsten_hip.hip: Batch::timed)
 
     // abort (PathTraceIntegrator::abortRender): a host-side request flag, mirrored into one device word the kernels poll.
     // The word is allocated once per context (never with the reallocatable pool), so tghip_abort may write it from any

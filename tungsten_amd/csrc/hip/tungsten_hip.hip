@@ -438,35 +438,34 @@ tghip_ctx *tghip_create(int device_ordinal)
         if (!reused) {
             // TGHIP_STREAM_PRIORITIES="p0,p1,..." (an experiment's hook, profiles/r6_ab_stream_priorities.txt): HIP stream priorities of the main stream and the part
             // streams, in creation order (lower = served first; the device's range is clamped by HIP); unset: plain streams
-            int prio[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            int prio[TGHIP_MAX_PARTS] = {};
             bool withPrio = false;
             if (const char *env = std::getenv("TGHIP_STREAM_PRIORITIES")) {
                 withPrio = true;
                 int k = 0;
-                for (const char *c = env; *c && k < 8; ) {
+                for (const char *c = env; *c && k < TGHIP_MAX_PARTS; ) {
                     prio[k++] = int(std::strtol(c, const_cast<char **>(&c), 10));
                     while (*c == ',' || *c == ' ') ++c;
                 }
             }
             auto create = [&](hipStream_t *st, int p) { return withPrio ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, p) : hipStreamCreateWithFlags(st, hipStreamNonBlocking); };
             if (e == hipSuccess) e = create(&set.main, prio[0]);
-            for (int k = 0; k < 7; ++k)
+            for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k)
                 if (e == hipSuccess) e = create(&set.part[k], prio[k + 1]);
             if (e == hipSuccess) e = hipStreamCreateWithFlags(&set.abort, hipStreamNonBlocking);
         }
         ctx->stream = set.main;
-        for (int k = 0; k < 7; ++k) ctx->partStream[k] = set.part[k];
+        for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k) ctx->partStream[k] = set.part[k];
         ctx->abortStream = set.abort;
     }
-    for (int k = 0; k < 7; ++k)
+    for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evPart[k], hipEventDisableTiming);
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < TGHIP_MAX_PARTS; ++k) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evFork[k], hipEventDisableTiming);
         for (int a = 0; a < 2; ++a)
             if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evJoin[k][a], hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evMain, hipEventDisableTiming);
-    ctx->launchStream = ctx->stream;
     if (e == hipSuccess) e = hipEventCreate(&ctx->evA);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evB);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evSurfMid);
@@ -491,8 +490,8 @@ void tghip_destroy(tghip_ctx *ctx)
     // every stream idle before the first buffer goes -- with the context, at the end: its arrays free themselves (device_array.h) -- (the part /
     // class streams join the main one at the end of a pass, an aborted or failed pass may have left them behind)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (int k = 0; k < 7; ++k) if (ctx->partStream[k]) (void)hipStreamSynchronize(ctx->partStream[k]);
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k) if (ctx->partStream[k]) (void)hipStreamSynchronize(ctx->partStream[k]);
+    for (int k = 0; k < TGHIP_MAX_PARTS; ++k)
         for (int a = 0; a < 2; ++a) if (ctx->classStream[k][a]) (void)hipStreamSynchronize(ctx->classStream[k][a]);
     if (ctx->abortStream) (void)hipStreamSynchronize(ctx->abortStream);
     if (ctx->rankComm) tghipDestroyRankComm(ctx->rankComm);
@@ -500,9 +499,9 @@ void tghip_destroy(tghip_ctx *ctx)
     if (ctx->evB) (void)hipEventDestroy(ctx->evB);
     if (ctx->evSurfMid) (void)hipEventDestroy(ctx->evSurfMid);
     for (hipEvent_t e : ctx->evPool) (void)hipEventDestroy(e);
-    for (int k = 0; k < 7; ++k) if (ctx->evPart[k]) (void)hipEventDestroy(ctx->evPart[k]);
+    for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k) if (ctx->evPart[k]) (void)hipEventDestroy(ctx->evPart[k]);
     if (ctx->evMain) (void)hipEventDestroy(ctx->evMain);
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < TGHIP_MAX_PARTS; ++k) {
         if (ctx->evFork[k]) (void)hipEventDestroy(ctx->evFork[k]);
         for (int a = 0; a < 2; ++a) {
             if (ctx->evJoin[k][a]) (void)hipEventDestroy(ctx->evJoin[k][a]);
@@ -514,14 +513,14 @@ void tghip_destroy(tghip_ctx *ctx)
         StreamSet set;
         set.main = ctx->stream; set.abort = ctx->abortStream;
         bool complete = set.main != nullptr && set.abort != nullptr;
-        for (int k = 0; k < 7; ++k) { set.part[k] = ctx->partStream[k]; complete = complete && set.part[k] != nullptr; }
+        for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k) { set.part[k] = ctx->partStream[k]; complete = complete && set.part[k] != nullptr; }
         if (complete) {
             std::lock_guard<std::mutex> lock(g_streamMutex);
             g_freeStreams[ctx->device].push_back(set);
         } else {                                 // (a context whose creation failed half way)
             if (set.main) (void)hipStreamDestroy(set.main);
             if (set.abort) (void)hipStreamDestroy(set.abort);
-            for (int k = 0; k < 7; ++k) if (set.part[k]) (void)hipStreamDestroy(set.part[k]);
+            for (int k = 0; k < TGHIP_MAX_PARTS - 1; ++k) if (set.part[k]) (void)hipStreamDestroy(set.part[k]);
         }
     }
     delete ctx;                                  // (and with it every device array it holds: the device is current, the streams are idle)
@@ -546,7 +545,7 @@ int tghip_set_option(tghip_ctx *ctx, const char *key, long long value)
     if (k == "count_traversal" || setLaunchOption(ctx->opt, k, value)) {
         if (k == "count_traversal") ctx->countTraversal = value != 0;
         if (k == "slots_per_block") dropPool(ctx);
-        for (int kk = 0; kk < 8 && k == "class_streams" && value != 0; ++kk)     // (created when the option is first switched on: an experiment's streams)
+        for (int kk = 0; kk < TGHIP_MAX_PARTS && k == "class_streams" && value != 0; ++kk)     // (created when the option is first switched on: an experiment's streams)
             for (int a = 0; a < 2; ++a)
                 if (!ctx->classStream[kk][a]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->classStream[kk][a], hipStreamNonBlocking));
         return ctx->haveScene ? replan(ctx) : TGHIP_OK;
@@ -732,248 +731,6 @@ int tghip_bind_framebuffer(tghip_ctx *ctx, float *dev_rgb_sum, uint32_t *dev_cou
 }
 
 
-// Runs the wavefront loop for one batch of work items until every slot is drained.
-static int runBatch(tghip_ctx *ctx, const PassParams &pp, const PassTarget &target)
-{
-    if (ctx->abortRequested.load(std::memory_order_acquire))
-        return TGHIP_E_ABORTED;                  // aborted before this batch started: nothing to drain
-    PathState st = ctx->pool;
-    st.partial = ctx->partial.get();
-    st.abort_flag = ctx->abortFlagDev.get();
-    st.leaf_batch = uint32_t(ctx->leafBatch);
-    const LaunchPlan &lp = ctx->lp;              // (tghip_wait planned the pass's kind)
-    const LaunchChoice &choice = lp.choice;
-    st.inst_tree_depth = uint32_t(choice.instTreeDepth);
-    st.inst_phase_min = uint32_t(ctx->instPhaseMin);
-    st.inst_refill_at = uint32_t(ctx->instRefillAt);
-    st.nee_factors = choice.neeFactors ? 1u : 0u;   // the closest-hit shadow walk, k_trace_shadow<., FORWARD>
-    st.suspend_lanes = ctx->poolWalkArrays ? uint32_t(ctx->suspendLanes) : 0u;
-    st.suspend_turns = uint32_t(std::max(ctx->suspendTurns, 1));
-    st.suspend_min_queue = uint32_t(ctx->suspendMinQueue);
-    st.leaf_batch_bvh2 = uint32_t(ctx->leafBatchBvh2 > 0 ? ctx->leafBatchBvh2 : ctx->sc.haveInstances ? 16 : ctx->leafBatch);
-    const DeviceScene &s = ctx->scene;
-    const int grid = int(ctx->poolGrid);
-    const bool fused = choice.fusedFlat;
-    const bool runToCompletion = choice.oneLaunch;   // one launch renders the whole batch
-
-    // optional per-launch timing: one event pair per kernel launch of a check interval, read back at the
-    // interval's host sync (events live on ctx->stream, the stream the kernels are launched on)
-    const bool timing = ctx->timeKernels;
-    // (short batches: 8 -- every check drains all streams, ~0.2 ms in which nothing runs, and most of a short pass is its drain: 27 near-empty
-    // iterations of ~150 us each for the 16-spp passes of the as-shipped materialtest, profiles/README.md; the price is <= 7 empty iterations
-    // of ~55 us after the last path has ended)
-    const int checkInterval = ctx->checkInterval > 0 ? ctx->checkInterval : (uint64_t(pp.total_items) >= 4ull*st.num_slots ? 16 : 8);
-    const size_t evNeeded = size_t(checkInterval)*3*2*8;          // (every part's launches are timed: up to eight parts)
-    if (timing) {
-        while (ctx->evPool.size() < evNeeded) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            ctx->evPool.push_back(e);
-        }
-    }
-    size_t evUsed = 0;
-    // (on the stream the launch goes to: ctx->launchStream is the part's own stream inside the split loop)
-    auto ticMain = [&]() { if (timing) (void)hipEventRecord(ctx->evPool[evUsed++], ctx->launchStream); };
-    auto tic = ticMain;
-
-    // "streams" = N > 1: the workgroups (and with them the slots, queues and work items) are split into N parts that run the same
-    // wavefront loop on N streams: kernels of different parts share the CUs (csrc/host/LaunchChoice.cpp), and the drain tail of one part's kernel
-    // overlaps the other parts' kernels
-    int parts = choice.parts;
-    if (grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
-        parts = 1;
-    const bool split = parts > 1;
-    PathState stPart[8] = {st, st, st, st, st, st, st, st};
-    PassParams ppPart[8] = {pp, pp, pp, pp, pp, pp, pp, pp};
-    hipStream_t streamOf[8] = {ctx->stream, ctx->partStream[0], ctx->partStream[1], ctx->partStream[2], ctx->partStream[3], ctx->partStream[4], ctx->partStream[5], ctx->partStream[6]};
-    if (split) {
-        const uint32_t groups = (pp.total_items + PT_ITEM_GROUP - 1)/PT_ITEM_GROUP;
-        uint32_t itemBegin = 0;
-        for (int k = 0; k < parts; ++k) {
-            const uint32_t off = uint32_t(grid/parts)*uint32_t(k);
-            for (uint32_t g = 0; g < PT_POOL_GROUPS; ++g)
-                stPart[k].poolg[g] = st.poolg[g] + size_t(off)*st.slots_per_block*16u;
-            stPart[k].bm = st.bm + size_t(off)*(st.slots_per_block >> 5);
-            stPart[k].ctl = st.ctl + off;
-            stPart[k].stats = st.stats + off;
-            stPart[k].num_slots = st.num_slots/uint32_t(parts);
-            const uint32_t itemEnd = k + 1 == parts ? pp.total_items : std::min(pp.total_items, uint32_t((uint64_t(groups)*(k + 1) + parts - 1)/parts)*PT_ITEM_GROUP);
-            ppPart[k].item_begin = pp.item_begin + itemBegin;
-            ppPart[k].total_items = itemEnd - itemBegin;
-            itemBegin = itemEnd;
-        }
-    }
-    HIP_TRY(ctx, hipMemsetAsync(st.partial, 0, size_t(pp.total_items)*sizeof(float4), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(st.live, 0, 4*sizeof(uint32_t), ctx->stream));
-    if (split) {
-        HIP_TRY(ctx, hipEventRecord(ctx->evMain, ctx->stream));            // (the memsets above come first for the other streams as well)
-        for (int k = 0; k < parts; ++k) {
-            if (k) HIP_TRY(ctx, hipStreamWaitEvent(streamOf[k], ctx->evMain, 0));
-            hipLaunchKernelGGL(k_start, dim3(grid/parts), dim3(256), 0, streamOf[k], s, stPart[k], ppPart[k]);
-        }
-    } else {
-        hipLaunchKernelGGL(k_start, dim3(grid), dim3(256), 0, ctx->stream, s, st, pp);
-    }
-    // k_tail: per-launch timing does not see it (the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
-    const bool tailEligible = choice.tailEligible && st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
-    const bool tailFits = tailEligible && lp.tailFits;
-    const uint64_t tailThreshold = uint64_t(std::max<long long>(ctx->tailThreshold, 0));
-    const bool foldFinish = choice.foldFinish;   // k_finish rides in front of the next iteration's closest-hit launch
-    const int shadeLaunches = choice.shadeLaunches;
-    uint32_t iterTag = 1;                        // k_start publishes tag 1 when it queued anything
-    bool first = true;
-    int roundIters = checkInterval;              // launches of the wavefront loop between two host checks
-        // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
-        // The shading launches of an iteration, in the choice's order.  The classes (the escaped paths, Q_MISS; 0; the classes 1 .. 3 that occur) consume queues
-        // of their own and OR what they append into the workgroup's bitmaps (k_shade: CONCURRENT), so their launches MAY run side by side on three
-        // streams: the "class_streams" option gives launches a lane beside the part's stream.  Measured slower than one after the other (materialtest
-        // 735-800 against 825-830 Msamples/s, mesh1m 409 against 508, for 2 to 24 hardware queues): with four parts in flight the chip is not short of
-        // independent launches.
-        auto launchShading = [&](const PathState &st, const PassParams &pp, int grid, int part) {
-            const hipStream_t mainStream = ctx->launchStream;
-            bool forked = false, lanes[3] = {false, false, false};
-            for (int i = 0; i < choice.numShade; ++i) {
-                const int lane = choice.shade[i].lane;
-                hipStream_t stream = mainStream;
-                if (lane) {
-                    stream = ctx->classStream[part][lane - 1];
-                    if (!forked) (void)hipEventRecord(ctx->evFork[part], mainStream);
-                    (void)hipStreamWaitEvent(stream, ctx->evFork[part], 0);
-                    forked = lanes[lane] = true;
-                }
-                launchKernel(lp.shade[i], grid, stream, s, st, pp, choice.shade[i].cls);
-                if (lane) (void)hipEventRecord(ctx->evJoin[part][lane - 1], stream);
-            }
-            for (int lane = 1; lane < 3; ++lane)
-                if (lanes[lane]) (void)hipStreamWaitEvent(mainStream, ctx->evJoin[part][lane - 1], 0);
-        };
-        // the launches of one wavefront iteration over the workgroups [0, grid) of `st` (the whole pool, or one part of it)
-        auto launchIteration = [&](const PathState &st, const PassParams &pp, int grid, uint32_t iterTag, bool timed, int part) {
-            auto tic = [&]() { if (timed) ticMain(); };
-            if (choice.queryPaths)                  // (the fresh paths of the previous iteration's finish / of k_start get the caller's rays before they are traced)
-                radianceQueryLaunchPaths(ctx->launchStream, grid, st, target.rays, target.numRays);
-            else if (choice.cameraRays)             // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
-                hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp);
-            tic();
-            if (choice.closest.kernel.family == K_FINISH_CLOSEST_WIDE)   // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
-                launchKernel(lp.closest, grid, ctx->launchStream, s, st, pp);
-            else
-                launchKernel(lp.closest, grid, ctx->launchStream, s, st);
-            tic();
-            // (the end of a query's first segment, before the hits are shaded.  Launched whether or not a ray of the batch has a finite tmax: the rays
-            // may be device memory, which the host could only know that of after a reduction over them -- about 10 us per launch, profiles/radiance_query/bench.txt)
-            if (choice.queryPaths)
-                radianceQueryLaunchClip(ctx->launchStream, grid, st, target.rays, target.numRays);
-            tic();
-            launchShading(st, pp, grid, part);
-            tic(); tic();
-            launchKernel(lp.shadow, grid, ctx->launchStream, s, st, pp, iterTag);
-            tic();
-            if (!foldFinish)                     // (always: the shading launches leave their finished paths to k_finish as well; folded: the next iteration's
-                                                 // closest-hit launch, or finishParts before a host check)
-                hipLaunchKernelGGL(k_finish, dim3(grid), dim3(256), 0, ctx->launchStream, s, st, pp, iterTag);
-        };
-        // folded k_finish: the last iteration's finish as a launch of its own -- before the host reads the liveness word, before k_tail
-        auto finishParts = [&](uint32_t tag) {
-            for (int k = 0; k < parts; ++k)
-                hipLaunchKernelGGL(k_finish, dim3(grid/parts), dim3(256), 0, split ? streamOf[k] : ctx->stream, s, split ? stPart[k] : st, split ? ppPart[k] : pp, tag);
-        };
-    for (;;) {
-        evUsed = 0;
-        {
-            // an abort request that arrived since the last check (or before the pass's first launch): make sure the device
-            // word is set -- in stream order, so the launches below see it and drain their slots
-            for (int k = 1; k < parts; ++k) {   // the main stream waits for the other parts before it reads the flag
-                HIP_TRY(ctx, hipEventRecord(ctx->evPart[k - 1], streamOf[k]));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->evPart[k - 1], 0));
-            }
-            if (ctx->abortRequested.load(std::memory_order_acquire))
-                HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev.get(), 0xFF, sizeof(uint32_t), ctx->stream));
-            if (tailEligible) hipLaunchKernelGGL(k_live_slots, dim3(1), dim3(256), 0, ctx->stream, st, uint32_t(grid));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->hostLive, st.live, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (timing && !first) {
-                double *acc[3] = {&ctx->counters.ms_trace_closest, &ctx->counters.ms_shade, &ctx->counters.ms_trace_shadow};
-                // (split loop: EVERY part's launches are bracketed, each on its own stream -- three pairs per part and iteration, in launch
-                // order.  Rounds 2-4 timed part 0 only and counted the others "as long on average": they are not -- the parts whose
-                // streams the hardware queues serve later run ~45 % longer launches (rocprofv3's kernel trace, profiles/README.md) --, so the
-                // per-kernel averages were part 0's, a fifth below the mean)
-                size_t pairs = size_t(roundIters)*3*size_t(parts);
-                for (size_t k = 0; k < pairs; ++k) {
-                    float ms = 0.0f;
-                    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->evPool[2*k], ctx->evPool[2*k + 1]));
-                    *acc[k % 3] += double(ms);
-                }
-                const int perIter = parts;
-                ctx->counters.launches_trace_closest += roundIters*perIter;
-                ctx->counters.launches_trace_shadow += roundIters*perIter;
-                ctx->counters.launches_shade += roundIters*perIter*shadeLaunches;   // (one event pair brackets them: ms_shade is their sum)
-            }
-            if (ctx->hostLive[0] != iterTag)
-                break;                           // the last iteration left every extension queue empty
-            if (tailFits && uint64_t(ctx->hostLive[1]) <= tailThreshold) {
-                // few paths left: each part of the pool finishes in one launch of k_tail (its workgroups iterate on their own)
-                uint32_t classes = 1u;
-                for (int c = 1; c < PT_NUM_CLASSES; ++c)
-                    if (ctx->sc.classPresent[c]) classes |= 1u << c;
-                for (int k = 0; k < parts; ++k) {
-                    const hipStream_t stream = split ? streamOf[k] : ctx->stream;
-                    if (k) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->evMain, 0));   // (after the main stream's check above)
-                    else if (split) HIP_TRY(ctx, hipEventRecord(ctx->evMain, ctx->stream));
-                    launchKernel(lp.tail, grid/parts, stream, s, split ? stPart[k] : st, split ? ppPart[k] : pp, classes);
-                }
-                for (int k = 1; k < parts; ++k) {
-                    HIP_TRY(ctx, hipEventRecord(ctx->evPart[k - 1], streamOf[k]));
-                    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->evPart[k - 1], 0));
-                }
-                ctx->counters.tail_launches++;
-                if (std::getenv("TGHIP_VERBOSE")) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    std::fprintf(stderr, "[tghip]   tail kernel after %llu iterations with %u paths alive: %.2f ms\n", (unsigned long long)(iterTag - 1), ctx->hostLive[1],
-                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-                }
-                break;
-            }
-        }
-        first = false;
-        roundIters = runToCompletion ? 1 : checkInterval;
-        for (int it = 0; it < roundIters; ++it) {
-            ++iterTag;
-            if (fused) {
-                // flat-list scene: intersection and shadow tests happen inside the shading launches
-                PassParams ppi = pp;
-                ppi.iter_tag = iterTag;
-                tic(); tic(); tic();
-                launchShading(st, ppi, grid, 0);
-                tic(); tic(); tic();
-                ctx->counters.iterations++;
-                continue;
-            }
-            if (split) {
-                // (rejected, round 5: part k's iteration i on stream (k + i) mod parts, so that every part spends the same time on every hardware
-                // queue: profiles/r5_sweep_rotate_streams.jsonl)
-                for (int k = 0; k < parts; ++k) {
-                    ctx->launchStream = streamOf[k];
-                    launchIteration(stPart[k], ppPart[k], grid/parts, iterTag, true, k);
-                }
-                ctx->launchStream = ctx->stream;
-            } else {
-                launchIteration(st, pp, grid, iterTag, true, 0);
-            }
-            ctx->counters.iterations++;
-        }
-        if (foldFinish && !fused)
-            finishParts(iterTag);
-    }
-    float *sum = target.sum;
-    uint32_t *cnt = target.count;
-    if (pp.rec_sorted) hipLaunchKernelGGL(k_resolve_records, dim3((pp.num_sorted*16u + 255)/256), dim3(256), 0, ctx->stream, st, pp, sum, cnt);
-    else               hipLaunchKernelGGL(k_resolve, dim3((pp.pix_slots + 255)/256), dim3(256), 0, ctx->stream, st, pp, sum, cnt);
-    HIP_TRY(ctx, hipGetLastError());
-    return ctx->abortRequested.load(std::memory_order_acquire) ? TGHIP_E_ABORTED : TGHIP_OK;
-}
-
 // PassParams::rec_hint of a record pass: hint[g] = the chunk item 64 g lies in -- the last c < chunks with start[c] <= 64 g (the chunk starts never
 // decrease; nextPath walks on from there while its item is >= start[c + 1], which ends at the sentinel behind the last chunk at the latest)
 __global__ void k_record_hints(const uint32_t *start, uint32_t chunks, uint32_t *hint, uint32_t n)
@@ -1006,23 +763,271 @@ int tghip_render_pass(tghip_ctx *ctx, const TgHipPassDesc *pass)
 
 } // extern "C"
 
-// The planned pass `plan` of `pass` over a w x h image, into `target`: the launch plan of its kind, the device arrays the plan names, the pool, the
-// wavefront loop batch by batch.  What tghip_wait runs for a render pass (w x h the scene's image, the target the context's framebuffer) and
-// tghip_query_radiance (shim_queries.hip) for a query (the virtual image of the rays, a framebuffer of its own).  Synchronous.
-int tghipRunPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t h, PassPlan &plan, const PassTarget &target)
+// ---- One batch of the wavefront loop (runBatch): its path state, its parts, start, host check, k_tail, a round of iterations, resolve ----
+namespace {
+// A part of a batch: a run of the pool's workgroups with their slots, queues and work items, and the stream its launches go to
+struct BatchPart { PathState st; PassParams pp; hipStream_t stream; int grid; int index; };
+// what a timing bracket measures: TgHipCounters has milliseconds and launches of each
+enum TimedClass { TIMED_CLOSEST, TIMED_SHADE, TIMED_SHADOW, TIMED_CLASSES };
+// The batch's path state: the pool, with what the context's options and the pass's launch choice say about the walks
+PathState batchState(const tghip_ctx *ctx)
 {
-    const bool verbose = std::getenv("TGHIP_VERBOSE") != nullptr;
-    const auto tWait0 = std::chrono::steady_clock::now();
-    auto msSince = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    int rc = TGHIP_OK;
-    // the kernels of a pass of this kind -- a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch) --: planned again only
-    // when the kind differs from the last pass's
-    PassKind kind = passKindOf(ctx->sc, pass.flags, plan.shortBatch, ctx->countTraversal);
-    kind.rayPaths = target.rayPaths;
-    if (!(kind == ctx->lp.kind) && (rc = planLaunches(ctx, kind, ctx->lp)) != TGHIP_OK)
-        return rc;
+    const LaunchChoice &choice = ctx->lp.choice;
+    PathState st = ctx->pool;
+    st.partial = ctx->partial.get();
+    st.abort_flag = ctx->abortFlagDev.get();
+    st.leaf_batch = uint32_t(ctx->leafBatch);
+    st.inst_tree_depth = uint32_t(choice.instTreeDepth);
+    st.inst_phase_min = uint32_t(ctx->instPhaseMin);
+    st.inst_refill_at = uint32_t(ctx->instRefillAt);
+    st.nee_factors = choice.neeFactors ? 1u : 0u;   // the closest-hit shadow walk, k_trace_shadow<., FORWARD>
+    st.suspend_lanes = ctx->poolWalkArrays ? uint32_t(ctx->suspendLanes) : 0u;
+    st.suspend_turns = uint32_t(std::max(ctx->suspendTurns, 1));
+    st.suspend_min_queue = uint32_t(ctx->suspendMinQueue);
+    st.leaf_batch_bvh2 = uint32_t(ctx->leafBatchBvh2 > 0 ? ctx->leafBatchBvh2 : ctx->sc.haveInstances ? 16 : ctx->leafBatch);
+    return st;
+}
 
-    // the device arrays the plan names
+// "streams" = N > 1: the workgroups (and with them the slots, queues and work items) are split into N parts that run the same
+// wavefront loop on N streams: kernels of different parts share the CUs (csrc/host/LaunchChoice.cpp), and the drain tail of one part's kernel
+// overlaps the other parts' kernels.  A grid or a batch too small for the parts wanted is ONE part: the whole pool on the context's stream.
+std::vector<BatchPart> splitBatch(const tghip_ctx *ctx, const PathState &st, const PassParams &pp)
+{
+    const int grid = int(ctx->poolGrid);
+    int parts = ctx->lp.choice.parts;
+    if (grid < 2*parts || grid % parts != 0 || pp.total_items < uint32_t(2*parts)*PT_ITEM_GROUP)
+        parts = 1;
+    const uint32_t groups = (pp.total_items + PT_ITEM_GROUP - 1)/PT_ITEM_GROUP;
+    uint32_t itemBegin = 0;
+    std::vector<BatchPart> part;
+    part.reserve(size_t(parts));
+    for (int k = 0; k < parts; ++k) {
+        BatchPart p{st, pp, ctx->streamOfPart(k), grid/parts, k};
+        const uint32_t off = uint32_t(p.grid)*uint32_t(k);
+        for (uint32_t g = 0; g < PT_POOL_GROUPS; ++g)
+            p.st.poolg[g] = st.poolg[g] + size_t(off)*st.slots_per_block*16u;
+        p.st.bm = st.bm + size_t(off)*(st.slots_per_block >> 5);
+        p.st.ctl = st.ctl + off;
+        p.st.stats = st.stats + off;
+        p.st.num_slots = st.num_slots/uint32_t(parts);
+        const uint32_t itemEnd = k + 1 == parts ? pp.total_items : std::min(pp.total_items, uint32_t((uint64_t(groups)*(k + 1) + parts - 1)/parts)*PT_ITEM_GROUP);
+        p.pp.item_begin = pp.item_begin + itemBegin;
+        p.pp.total_items = itemEnd - itemBegin;
+        itemBegin = itemEnd;
+        part.push_back(p);
+    }
+    return part;
+}
+
+struct Batch {
+    enum Outcome { DONE, TAIL, GO_ON };          // what a host check finds: every queue empty, few enough paths for k_tail, neither
+    tghip_ctx *const ctx;
+    const PassParams &pp;                        // the whole batch's (the parts hold their shares)
+    const PassTarget &target;
+    const LaunchPlan &lp;                        // (tghipRunPass planned the pass's kind)
+    const LaunchChoice &choice;
+    const DeviceScene &s;
+    const PathState st;                          // the whole pool
+    const int checkInterval;                     // iterations between two host checks
+    std::vector<BatchPart> part;                 // at most TGHIP_MAX_PARTS
+    const int parts;
+    uint32_t iterTag = 1;                        // k_start publishes tag 1 when it queued anything
+    size_t brackets[TIMED_CLASSES] = {0, 0, 0};  // timing brackets of each class since the last host check
+    // (short batches: 8 -- every check drains all streams, ~0.2 ms in which nothing runs, and most of a short pass is its drain: 27 near-empty
+    // iterations of ~150 us each for the 16-spp passes of the as-shipped materialtest, profiles/README.md; the price is <= 7 empty iterations
+    // of ~55 us after the last path has ended)
+    Batch(tghip_ctx *c, const PassParams &p, const PassTarget &t)
+        : ctx(c), pp(p), target(t), lp(c->lp), choice(c->lp.choice), s(c->scene), st(batchState(c)),
+          checkInterval(c->checkInterval > 0 ? c->checkInterval : (uint64_t(p.total_items) >= 4ull*st.num_slots ? 16 : 8)),
+          part(splitBatch(c, st, p)), parts(int(part.size())) {}
+    // Fork: what the main stream holds so far comes first for the other parts' streams.  Join: the main stream waits for them.  (One part: no call.)
+    int forkParts() {
+        if (parts > 1) HIP_TRY(ctx, hipEventRecord(ctx->evMain, ctx->stream));
+        for (int k = 1; k < parts; ++k)
+            HIP_TRY(ctx, hipStreamWaitEvent(part[k].stream, ctx->evMain, 0));
+        return TGHIP_OK;
+    }
+    int joinParts() {
+        for (int k = 1; k < parts; ++k) {
+            HIP_TRY(ctx, hipEventRecord(ctx->evPart[k - 1], part[k].stream));
+            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->evPart[k - 1], 0));
+        }
+        return TGHIP_OK;
+    }
+    // Per-launch timing ("time_kernels"): `launches` between two events of the pool on the part's stream, read back class by class at the next host
+    // check.  A round brackets each class once per part and iteration: a class's brackets are a run of the pool's pairs, sized for the most parts.
+    size_t bracketEvent(int cls, size_t n) const { return 2*((size_t(cls)*checkInterval)*TGHIP_MAX_PARTS + n); }
+    template<typename Launches>
+    void timed(TimedClass cls, const BatchPart &p, Launches launches) {
+        const size_t e = bracketEvent(cls, brackets[cls]);
+        if (ctx->timeKernels) (void)hipEventRecord(ctx->evPool[e], p.stream);
+        launches();
+        if (ctx->timeKernels) { (void)hipEventRecord(ctx->evPool[e + 1], p.stream); brackets[cls]++; }
+    }
+    // The event pool grown to a round's brackets, the two memsets, the fork (the memsets come first for the other streams as well), k_start
+    int start() {
+        while (ctx->timeKernels && ctx->evPool.size() < bracketEvent(TIMED_CLASSES, 0)) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(ctx, hipEventCreate(&e));
+            ctx->evPool.push_back(e);
+        }
+        HIP_TRY(ctx, hipMemsetAsync(st.partial, 0, size_t(pp.total_items)*sizeof(float4), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(st.live, 0, 4*sizeof(uint32_t), ctx->stream));
+        const int rc = forkParts();
+        for (int k = 0; k < parts && rc == TGHIP_OK; ++k)
+            hipLaunchKernelGGL(k_start, dim3(part[k].grid), dim3(256), 0, part[k].stream, s, part[k].st, part[k].pp);
+        return rc;
+    }
+    // The host check: the parts joined, the liveness word (and, where k_tail may follow, the live paths) read back on a dry main stream, the
+    // round's brackets added to the counters
+    int check(Outcome &outcome) {
+        // k_tail: per-launch timing does not see it (the few thousand rays it traces are in the counters, its one launch is in none of the three kernel classes)
+        const bool tailEligible = choice.tailEligible && st.slots_per_block <= PT_MAX_SLOTS_PER_BLOCK;
+        const int rc = joinParts();              // the main stream waits for the other parts before it reads the flag
+        if (rc != TGHIP_OK) return rc;
+        // an abort request that arrived since the last check (or before the pass's first launch): make sure the device
+        // word is set -- in stream order, so the launches below see it and drain their slots
+        if (ctx->abortRequested.load(std::memory_order_acquire))
+            HIP_TRY(ctx, hipMemsetAsync(ctx->abortFlagDev.get(), 0xFF, sizeof(uint32_t), ctx->stream));
+        if (tailEligible) hipLaunchKernelGGL(k_live_slots, dim3(1), dim3(256), 0, ctx->stream, st, ctx->poolGrid);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hostLive, st.live, 2*sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        // (split loop: EVERY part's launches are bracketed, each on its own stream -- three pairs per part and iteration, in launch
+        // order.  Rounds 2-4 timed part 0 only and counted the others "as long on average": they are not -- the parts whose
+        // streams the hardware queues serve later run ~45 % longer launches (rocprofv3's kernel trace, profiles/README.md) --, so the
+        // per-kernel averages were part 0's, a fifth below the mean)
+        TgHipCounters &c = ctx->counters;
+        double *ms[TIMED_CLASSES] = {&c.ms_trace_closest, &c.ms_shade, &c.ms_trace_shadow};
+        for (int cls = 0; cls < TIMED_CLASSES; ++cls)
+            for (size_t k = 0; k < brackets[cls]; ++k) {
+                float elapsed = 0.0f;
+                HIP_TRY(ctx, hipEventElapsedTime(&elapsed, ctx->evPool[bracketEvent(cls, k)], ctx->evPool[bracketEvent(cls, k) + 1]));
+                *ms[cls] += double(elapsed);
+            }
+        c.launches_trace_closest += brackets[TIMED_CLOSEST];
+        c.launches_trace_shadow += brackets[TIMED_SHADOW];
+        c.launches_shade += brackets[TIMED_SHADE]*size_t(choice.shadeLaunches);   // (one bracket around them: ms_shade is their sum)
+        brackets[TIMED_CLOSEST] = brackets[TIMED_SHADE] = brackets[TIMED_SHADOW] = 0;
+        if (ctx->hostLive[0] != iterTag) outcome = DONE;   // the last iteration left every extension queue empty
+        else if (tailEligible && lp.tailFits && uint64_t(ctx->hostLive[1]) <= uint64_t(std::max<long long>(ctx->tailThreshold, 0))) outcome = TAIL;
+        else outcome = GO_ON;
+        return TGHIP_OK;
+    }
+    // Few paths left: each part of the pool finishes in one launch of k_tail (its workgroups iterate on their own), forked behind the main stream's check
+    int tail() {
+        uint32_t classes = 1u;
+        for (int c = 1; c < PT_NUM_CLASSES; ++c)
+            if (ctx->sc.classPresent[c]) classes |= 1u << c;
+        int rc = forkParts();
+        for (int k = 0; k < parts && rc == TGHIP_OK; ++k)
+            launchKernel(lp.tail, part[k].grid, part[k].stream, s, part[k].st, part[k].pp, classes);
+        if (rc != TGHIP_OK || (rc = joinParts()) != TGHIP_OK) return rc;
+        ctx->counters.tail_launches++;
+        if (std::getenv("TGHIP_VERBOSE")) {
+            const auto t0 = std::chrono::steady_clock::now();
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            std::fprintf(stderr, "[tghip]   tail kernel after %llu iterations with %u paths alive: %.2f ms\n", (unsigned long long)(iterTag - 1), ctx->hostLive[1],
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        }
+        return TGHIP_OK;
+    }
+    // The shading launches of an iteration, in the choice's order.  The classes (the escaped paths, Q_MISS; 0; the classes 1 .. 3 that occur) consume queues
+    // of their own and OR what they append into the workgroup's bitmaps (k_shade: CONCURRENT), so their launches MAY run side by side on three
+    // streams: the "class_streams" option gives launches a lane beside the part's stream.  Measured slower than one after the other (materialtest
+    // 735-800 against 825-830 Msamples/s, mesh1m 409 against 508, for 2 to 24 hardware queues): with four parts in flight the chip is not short of
+    // independent launches.
+    void launchShading(const BatchPart &p) {
+        bool forked = false, lanes[3] = {false, false, false};
+        for (int i = 0; i < choice.numShade; ++i) {
+            const int lane = choice.shade[i].lane;
+            hipStream_t stream = p.stream;
+            if (lane) {
+                stream = ctx->classStream[p.index][lane - 1];
+                if (!forked) (void)hipEventRecord(ctx->evFork[p.index], p.stream);
+                (void)hipStreamWaitEvent(stream, ctx->evFork[p.index], 0);
+                forked = lanes[lane] = true;
+            }
+            launchKernel(lp.shade[i], p.grid, stream, s, p.st, p.pp, choice.shade[i].cls);
+            if (lane) (void)hipEventRecord(ctx->evJoin[p.index][lane - 1], stream);
+        }
+        for (int lane = 1; lane < 3; ++lane)
+            if (lanes[lane]) (void)hipStreamWaitEvent(p.stream, ctx->evJoin[p.index][lane - 1], 0);
+    }
+    void launchFinish(const BatchPart &p) { hipLaunchKernelGGL(k_finish, dim3(p.grid), dim3(256), 0, p.stream, s, p.st, p.pp, iterTag); }
+    // the launches of one wavefront iteration over a part
+    void launchIteration(const BatchPart &p) {
+        if (choice.queryPaths)                   // (the fresh paths of the previous iteration's finish / of k_start get the caller's rays before they are traced)
+            radianceQueryLaunchPaths(p.stream, p.grid, p.st, target.rays, target.numRays);
+        else if (choice.cameraRays)              // (the fresh camera rays of the previous iteration's finish / of k_start, before they are traced)
+            hipLaunchKernelGGL(k_camera_rays, dim3(p.grid), dim3(256), 0, p.stream, s, p.st, p.pp);
+        timed(TIMED_CLOSEST, p, [&] {
+            if (choice.closest.kernel.family == K_FINISH_CLOSEST_WIDE)   // (k_finish's work of the previous iteration in front of the walk, pt_wavefront.h)
+                launchKernel(lp.closest, p.grid, p.stream, s, p.st, p.pp);
+            else
+                launchKernel(lp.closest, p.grid, p.stream, s, p.st);
+        });
+        // (the end of a query's first segment, before the hits are shaded.  Launched whether or not a ray of the batch has a finite tmax: the rays
+        // may be device memory, which the host could only know that of after a reduction over them -- about 10 us per launch, profiles/radiance_query/bench.txt)
+        if (choice.queryPaths)
+            radianceQueryLaunchClip(p.stream, p.grid, p.st, target.rays, target.numRays);
+        timed(TIMED_SHADE, p, [&] { launchShading(p); });
+        timed(TIMED_SHADOW, p, [&] { launchKernel(lp.shadow, p.grid, p.stream, s, p.st, p.pp, iterTag); });
+        if (!choice.foldFinish)                  // (always: the shading launches leave their finished paths to k_finish as well; folded: the next iteration's
+            launchFinish(p);                     // closest-hit launch, or the end of the round)
+    }
+    // One round: the iterations between two host checks -- one where a single launch renders the whole batch
+    void iterate() {
+        const int roundIters = choice.oneLaunch ? 1 : checkInterval;
+        for (int it = 0; it < roundIters; ++it, ctx->counters.iterations++) {
+            ++iterTag;
+            if (choice.fusedFlat) {
+                // flat-list scene: intersection and shadow tests happen inside the shading launches, over the whole pool -- flat scenes are never
+                // split (chooseLaunches, LaunchChoice.cpp) -- and the two walks' brackets stay empty
+                part[0].pp.iter_tag = iterTag;
+                timed(TIMED_CLOSEST, part[0], [] {});
+                timed(TIMED_SHADE, part[0], [&] { launchShading(part[0]); });
+                timed(TIMED_SHADOW, part[0], [] {});
+            } else {
+                // (rejected, round 5: part k's iteration i on stream (k + i) mod parts, so that every part spends the same time on every hardware
+                // queue: profiles/r5_sweep_rotate_streams.jsonl)
+                for (int k = 0; k < parts; ++k)
+                    launchIteration(part[k]);
+            }
+        }
+        // folded k_finish: the last iteration's finish as a launch of its own -- before the host reads the liveness word, before k_tail
+        for (int k = 0; k < parts && choice.foldFinish && !choice.fusedFlat; ++k)
+            launchFinish(part[k]);
+    }
+    int resolve() {
+        if (pp.rec_sorted) hipLaunchKernelGGL(k_resolve_records, dim3((pp.num_sorted*16u + 255)/256), dim3(256), 0, ctx->stream, st, pp, target.sum, target.count);
+        else               hipLaunchKernelGGL(k_resolve, dim3((pp.pix_slots + 255)/256), dim3(256), 0, ctx->stream, st, pp, target.sum, target.count);
+        HIP_TRY(ctx, hipGetLastError());
+        return ctx->abortRequested.load(std::memory_order_acquire) ? TGHIP_E_ABORTED : TGHIP_OK;
+    }
+};
+} // namespace
+
+// Runs the wavefront loop for one batch of work items until every slot is drained.
+static int runBatch(tghip_ctx *ctx, const PassParams &pp, const PassTarget &target)
+{
+    if (ctx->abortRequested.load(std::memory_order_acquire))
+        return TGHIP_E_ABORTED;                  // aborted before this batch started: nothing to drain
+    Batch batch(ctx, pp, target);
+    Batch::Outcome found = Batch::GO_ON;
+    int rc = batch.start();
+    while (rc == TGHIP_OK) {
+        if ((rc = batch.check(found)) != TGHIP_OK || found == Batch::DONE) break;
+        if (found == Batch::TAIL) { rc = batch.tail(); break; }
+        batch.iterate();
+    }
+    return rc == TGHIP_OK ? batch.resolve() : rc;
+}
+
+// The device arrays the plan of a pass names -- the shard's tiles, the tile seeds, a record pass's six arrays and its hint table, the auxiliary
+// pixels, the per-sample radiance --, grown, filled on the context's stream and named in `base`, the pass's parameters every batch starts from
+static int placePassArrays(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t h, PassPlan &plan, const PassTarget &target, PassParams &base)
+{
+    int rc = TGHIP_OK;
     auto upload = [&](DeviceArray<uint32_t> &dev, const std::vector<uint32_t> &src) -> int {
         const int grc = dev.grow(ctx, src.size());
         if (grc != TGHIP_OK) return grc;
@@ -1030,7 +1035,6 @@ int tghipRunPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t
             HIP_TRY(ctx, hipMemcpyAsync(dev.get(), src.data(), src.size()*sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         return TGHIP_OK;
     };
-    PassParams base{};
     base.shard_index = pass.shard_index; base.shard_count = plan.shardCount;
     base.shard_skew = plan.shardSkew;
     base.tiles_x = plan.tilesX; base.num_tiles = plan.numTiles;
@@ -1083,6 +1087,27 @@ int tghipRunPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t
         ctx->samplesFloats = need;
         base.samples = ctx->dSamples.get(); base.samples_begin = plan.sppBegin; base.samples_spp = plan.spp;
     }
+    return TGHIP_OK;
+}
+
+// The planned pass `plan` of `pass` over a w x h image, into `target`: the launch plan of its kind, the device arrays the plan names, the pool, the
+// wavefront loop batch by batch.  What tghip_wait runs for a render pass (w x h the scene's image, the target the context's framebuffer) and
+// tghip_query_radiance (shim_queries.hip) for a query (the virtual image of the rays, a framebuffer of its own).  Synchronous.
+int tghipRunPass(tghip_ctx *ctx, const TgHipPassDesc &pass, uint32_t w, uint32_t h, PassPlan &plan, const PassTarget &target)
+{
+    const bool verbose = std::getenv("TGHIP_VERBOSE") != nullptr;
+    const auto tWait0 = std::chrono::steady_clock::now();
+    auto msSince = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    int rc = TGHIP_OK;
+    // the kernels of a pass of this kind -- a short batch runs on ONE stream with 4 workgroups per CU (PassPlan.cpp: shortBatch) --: planned again only
+    // when the kind differs from the last pass's
+    PassKind kind = passKindOf(ctx->sc, pass.flags, plan.shortBatch, ctx->countTraversal);
+    kind.rayPaths = target.rayPaths;
+    if (!(kind == ctx->lp.kind) && (rc = planLaunches(ctx, kind, ctx->lp)) != TGHIP_OK)
+        return rc;
+    PassParams base{};
+    if ((rc = placePassArrays(ctx, pass, w, h, plan, target, base)) != TGHIP_OK)
+        return rc;
 
     uint64_t wantSlots = std::min<uint64_t>(uint64_t(ctx->maxSlots), plan.batchItems);
     // the run-to-completion kernel (runBatch) gives every thread its own slots for the whole launch: one slot per
